@@ -12,7 +12,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/${R}_profiles; mkdir -p $OUT
 HEAD=$(cat $ROOT/build/HEAD_STAMP 2>/dev/null | head -1); HEAD=${HEAD:-unknown}
 export TMPDIR=/tmp AVRF_BLOCKING=1
-SINGLE="python3 $ROOT/bench.py --gpus 1 --slots 1 --lanes 1 --host-threads 1 --hash-group 1 --steps 20 --warmup 5 --min-seconds 0.5 --no-ring --no-cpu-baseline --no-projection"
+SINGLE="python3 $ROOT/bench.py --gpus 1 --slots 1 --lanes 1 --host-threads 1 --hash-group 1 --steps 20 --warmup 5 --min-seconds 0.5 --full --no-ring --no-cpu-baseline --no-projection"
 PASSES=("FETCH_SIZE" "WRITE_SIZE" "VALUBusy" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64")
 stats() {   # name, command...: rocprofv3 --kernel-trace --stats, keep the kernel_stats csv
   name=$1; shift; d=$(mktemp -d /tmp/kt.XXXX)
@@ -38,8 +38,8 @@ for w in $WHAT; do case $w in
   gather) /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -o /tmp/gather_probe $ROOT/tools/gather_probe.hip && /tmp/gather_probe 200 > $OUT/${R}_gather_probe.txt 2>&1; stamp_txt $OUT/${R}_gather_probe.txt "tools/gather_probe.hip 200";;
   pmc_peritem) python3 $ROOT/tools/pmc.py $OUT/${R}_pmc_per_item.json "SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64" "VALUBusy" -- python3 $ROOT/tools/ped_bench.py 65536; stamp_json $OUT/${R}_pmc_per_item.json "tools/pmc.py <passes> -- python3 tools/ped_bench.py 65536"; cp $OUT/${R}_pmc_per_item.json $ROOT/profiles/;;
   single) stats single_context $SINGLE;;
-  default) stats bench_default python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-ring --no-projection --no-cpu-baseline;;
-  benchline) python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err; stamp_json $OUT/${R}_bench_default.json "python bench.py --gpus 1 --steps 20 --warmup 5";;
+  default) stats bench_default python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --min-seconds 2 --full --no-ring --no-projection --no-cpu-baseline;;
+  benchline) python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --min-seconds 2 --full > $OUT/${R}_bench_default.json 2> $OUT/${R}_bench_default.err; stamp_json $OUT/${R}_bench_default.json "python bench.py --gpus 1 --steps 20 --warmup 5 --min-seconds 2 --full";;
   ring) stats ring_prove_2048 python3 $ROOT/tools/ring_bench.py 1024 2048 1;;
   ring_bn254) stats ring_bn254_prove_1024 python3 $ROOT/tools/ring_bench.py 4096 1024 1 1;;
   peritem) stats per_item python3 $ROOT/tools/ped_bench.py 65536;;
