@@ -1162,6 +1162,20 @@ k_g1_table(const uint32_t *__restrict__ bases, uint32_t n, int c, int nwin, uint
   }
 }
 
+// transient device scratch of a table build, freed on every path out (the stream is waited for before a normal free; on a throw the
+// hipFree of the destructor waits for the device itself)
+namespace {
+struct ScratchBuf {
+  void *p = nullptr;
+  ScratchBuf() = default;
+  ScratchBuf(const ScratchBuf &) = delete;
+  ScratchBuf &operator=(const ScratchBuf &) = delete;
+  ~ScratchBuf() { if (p) (void)hipFree(p); }
+  uint32_t *u32() const { return (uint32_t *)p; }
+  hipError_t release() { hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; return e; }
+};
+}  // namespace
+
 void build_g1_table(int curve, const uint32_t *d_bases, size_t n, int c, int nwin, uint32_t *d_table, hipStream_t stream) {
   if (!n) return;
   const size_t fqn = curve == 0 ? G1Bls12381::Fq::N : G1Bn254::Fq::N;
@@ -1170,13 +1184,14 @@ void build_g1_table(int curve, const uint32_t *d_bases, size_t n, int c, int nwi
   // workspaces that was a race: after two setups on two streams the first batched commitment of avrf_ring_srs_generate returned the
   // point at infinity for its first vector, every time, and not with HIP_LAUNCH_BLOCKING=1 or a device synchronisation in between
   // (tests/test_gpu_ring.py::test_srs_generate caught it once an unrelated null-stream hipMemset, which had been hiding it, went away).)
-  uint32_t *tmp = nullptr;
-  HIP_CHECK(hipMalloc((void **)&tmp, (size_t)nwin * n * 3 * fqn * 4));
+  // (held in ScratchBuf: a throw between the allocation and the free -- a launch or the wait failing -- does not leak it)
+  ScratchBuf tmp;
+  HIP_CHECK(hipMalloc(&tmp.p, (size_t)nwin * n * 3 * fqn * 4));
   dim3 g((unsigned)((n + 63) / 64)), b(64);
-  if (curve == 0) hipLaunchKernelGGL(k_g1_table<G1Bls12381>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp);
-  else hipLaunchKernelGGL(k_g1_table<G1Bn254>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp);
+  if (curve == 0) hipLaunchKernelGGL(k_g1_table<G1Bls12381>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp.u32());
+  else hipLaunchKernelGGL(k_g1_table<G1Bn254>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp.u32());
   HIP_CHECK(hipStreamSynchronize(stream));
-  HIP_CHECK(hipFree(tmp));
+  HIP_CHECK(tmp.release());
 }
 
 template <class C>
@@ -1437,19 +1452,22 @@ template <class C> static void build_direct_impl(const uint32_t *d_bases, G1Dire
   const size_t n = t->n; const uint32_t rows = (uint32_t)t->rows;
   if (t->points >= 0x7fffffffull) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};     // 31-bit entry indices
   HIP_CHECK(hipMalloc(&t->d, t->bytes));
-  uint32_t *rowbase = nullptr, *tmp = nullptr;
-  HIP_CHECK(hipMalloc(&rowbase, (size_t)rows * n * 2 * N * 4));
-  build_g1_table(t->curve, d_bases, n, t->c, (int)rows, rowbase, stream);
+  // transient scratch (include/avrf.h, resource contract): the window rows of the bases (2 Fq per lane), then K multiples' ZZ / ZZZ /
+  // running products per lane (3 Fq each) -- 386 Fq per (row, base) at the peak; build_g1_table's own scratch is gone by then
+  ScratchBuf rowbase, tmp;
+  HIP_CHECK(hipMalloc(&rowbase.p, (size_t)rows * n * 2 * N * 4));
+  build_g1_table(t->curve, d_bases, n, t->c, (int)rows, rowbase.u32(), stream);
   const uint32_t lanes = (uint32_t)(rows * n), K = 128;
-  HIP_CHECK(hipMalloc(&tmp, (size_t)K * lanes * 3 * N * 4));
+  HIP_CHECK(hipMalloc(&tmp.p, (size_t)K * lanes * 3 * N * 4));
   uint32_t mmax = 0; for (uint32_t w = 0; w < rows; w++) mmax = t->mult[w] > mmax ? t->mult[w] : mmax;
   for (uint32_t m0 = 0; m0 < mmax; m0 += K)
-    hipLaunchKernelGGL(k_g1_multiples<C>, dim3((lanes + 63) / 64), dim3(64), 0, stream, (const uint32_t *)rowbase, (uint32_t)n, rows, *t, m0, K, t->d, tmp, lanes);
+    hipLaunchKernelGGL(k_g1_multiples<C>, dim3((lanes + 63) / 64), dim3(64), 0, stream, (const uint32_t *)rowbase.u32(), (uint32_t)n, rows, *t, m0, K, t->d, tmp.u32(), lanes);
   HIP_CHECK(hipStreamSynchronize(stream));
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipFree(tmp)); HIP_CHECK(hipFree(rowbase));
+  HIP_CHECK(tmp.release()); HIP_CHECK(rowbase.release());
 }
 void build_g1_direct_table(int curve, const uint32_t *d_bases, size_t n, int c, G1DirectTable *t, hipStream_t stream) {
+  free_g1_direct_table(t);                           // (a table this struct held before is not leaked by a rebuild into it)
   g1_direct_table_shape(curve, n, c, t);
   if (curve == 0) build_direct_impl<G1Bls12381>(d_bases, t, stream); else build_direct_impl<G1Bn254>(d_bases, t, stream);
 }

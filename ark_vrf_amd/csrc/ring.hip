@@ -546,6 +546,11 @@ struct avrf_ring_setup {
   uint32_t *d_srs = nullptr;                          // n_srs Montgomery affine points
   uint32_t *d_srs_table = nullptr; int table_c = 0, table_nwin = 0;   // fixed-base window table over the SRS (batched commits)
   std::shared_ptr<DirectEntry> direct, direct_wit; bool direct_tried = false;   // the tables of all multiples (SRS powers; witness bases), built on first use
+  uint64_t table_budget = UINT64_MAX;                 // HBM the two tables may take (avrf_ring_setup_set_table_budget; UINT64_MAX: the process default)
+  uint64_t planned_budget = UINT64_MAX;               // the budget the tables held now were planned under
+  bool table_missed = false;                          // a planned table was not built (did not fit, allocation or build failed): bucket form for it
+  std::shared_ptr<std::atomic<uint64_t>> table_batches = std::make_shared<std::atomic<uint64_t>>(0);   // commitment batches served from the
+                                                      // tables (shared with the second lane, whose shallow copy holds the same counter)
   uint32_t *d_wit_bases = nullptr;                    // the 2N + 1 witness bases the tables are built over
   int wit_c = 0, wit_nwin = 0;                        // window width of the witness table (sparse MSMs: few entries, small buckets)
   uint32_t *d_wit_table = nullptr;                    // same over [L_i(tau) G, i < N | prefix sums PS_k = sum_{i<k} L_i(tau) G, k <= N] (witness commits)
@@ -1081,7 +1086,7 @@ template <class S, class G> struct Ring {
     static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
     struct timespec t0; if (trace) { HIP_CHECK(hipStreamSynchronize(su->stream)); clock_gettime(CLOCK_MONOTONIC, &t0); }
     // many vectors at once and the table of all multiples is there: one gathered point per (coefficient, row), no buckets (msm.hip)
-    if (su->direct && batch >= 32) msm_g1_direct_device(su->direct->t, d_coeffs_mont, n, stride, su->ws, su->stream, xy.data(), batch, mont_id);
+    if (su->direct && batch >= 32) { msm_g1_direct_device(su->direct->t, d_coeffs_mont, n, stride, su->ws, su->stream, xy.data(), batch, mont_id); ++*su->table_batches; }
     else msm_g1_fixed_device(su->curve, su->d_srs_table, su->table_c, su->n_srs, d_coeffs_mont, n, stride, su->ws, su->stream, xy.data(), batch, nullptr, mont_id);
     if (trace) { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
       fprintf(stderr, "    commit n=%zu batch=%zu: %.3f ms wall, accumulate %.3f ms (c=%d seg=%d)\n", n, batch,
@@ -1139,7 +1144,7 @@ template <class S, class G> struct Ring {
   // `batch` sparse commits over the witness table: vector b = m (base index, plain scalar) pairs
   static void commit_sparse(avrf_ring_setup *su, const uint32_t *d_scalars_plain, const uint32_t *d_base_idx, size_t m, size_t batch, std::vector<G1Aff> &out) {
     std::vector<uint8_t> xy(batch * 2 * FQB);
-    if (su->direct_wit && batch >= 32) msm_g1_direct_device(su->direct_wit->t, d_scalars_plain, m, m, su->ws, su->stream, xy.data(), batch, 0, d_base_idx);
+    if (su->direct_wit && batch >= 32) { msm_g1_direct_device(su->direct_wit->t, d_scalars_plain, m, m, su->ws, su->stream, xy.data(), batch, 0, d_base_idx); ++*su->table_batches; }
     else msm_g1_fixed_device(su->curve, su->d_wit_table, su->wit_c, 2 * su->N + 1, d_scalars_plain, m, m, su->ws, su->stream, xy.data(), batch, d_base_idx);
     out.resize(batch);
     for (size_t b = 0; b < batch; b++) {
@@ -1786,6 +1791,111 @@ template <class F> static int guarded(F f) {
   catch (const std::bad_alloc &) { return AVRF_ERR_NO_DEVICE; }
 }
 
+// The tables of all multiples of this setup's SRS powers (kind 0) and witness bases (kind 1): found in the registry or built (once
+// per device and SRS, ~2 s).
+//  - no explicit budget (the process default): sized to the HBM that is free -- the widest window c <= 16 whose table fits
+//    min(what is left of AVRF_RING_TABLE_GB (default 232, both tables together), free - 40 GB), any registry table of the SRS adopted;
+//    no table when even the bucket form's own width does not fit, when AVRF_RING_DIRECT=0, or when the allocation fails (the bucket form
+//    then runs as before).
+//  - an explicit budget (avrf_ring_setup_set_table_budget): the widths are a pure function of it (plan_direct); free memory only
+//    decides whether a planned table is built, and a registry table is adopted only at exactly the planned width.
+// Either way table_missed records a planned table that is not held.  Called under no lock; takes g_direct_mu.
+static bool direct_env_off() { const char *e = getenv("AVRF_RING_DIRECT"); return e && atoi(e) == 0; }
+static double direct_env_budget_gb() { const char *e = getenv("AVRF_RING_TABLE_GB"); return e ? atof(e) : 232.0; }
+static bool tables_disabled(const avrf_ring_setup *su) { return su->table_budget != UINT64_MAX ? su->table_budget == 0 : direct_env_off(); }
+static size_t direct_bases(const avrf_ring_setup *su, int kind) { return kind ? 2 * su->N + 1 : su->n_srs; }
+// bytes of the table of `nb` bases at width c, 0 when it would hold 2^31 - 1 points or more (31-bit entry indices of k_direct_index)
+static uint64_t direct_bytes(int curve, size_t nb, int c) {
+  G1DirectTable shape;
+  const uint64_t b = g1_direct_table_shape(curve, nb, c, &shape);
+  return shape.points < 0x7fffffffull ? b : 0;
+}
+// the explicit-budget plan: the SRS table the widest c in [bucket width, 16] that fits the budget, then the witness table the widest
+// c in [8, 16] that fits what is left (c = 0: no table of that kind)
+static void plan_direct(const avrf_ring_setup *su, uint64_t budget, int c_out[2], uint64_t bytes_out[2]) {
+  for (int kind = 0; kind < 2; kind++) {
+    c_out[kind] = 0; bytes_out[kind] = 0;
+    const int c_lo = kind ? 8 : std::max(su->table_c, 8);
+    for (int c = 16; c >= c_lo; c--) {
+      const uint64_t b = direct_bytes(su->curve, direct_bases(su, kind), c);
+      if (b && b <= budget) { c_out[kind] = c; bytes_out[kind] = b; budget -= b; break; }
+    }
+  }
+}
+static void sync_lane_tables(avrf_ring_setup *su) {
+  if (avrf_ring_setup *l = su->lane1) { l->direct = su->direct; l->direct_wit = su->direct_wit; l->direct_tried = su->direct_tried; l->d_wit_bases = su->d_wit_bases; }
+}
+static void drop_tables_locked(avrf_ring_setup *su) {                 // (g_direct_mu held: the registry frees a table with its last holder)
+  su->direct.reset(); su->direct_wit.reset();
+  sync_lane_tables(su);
+}
+static std::shared_ptr<DirectEntry> find_direct_locked(const avrf_ring_setup *su, int kind, int c_exact) {
+  const size_t nb = direct_bases(su, kind);
+  for (auto it = g_direct.begin(); it != g_direct.end();) {
+    std::shared_ptr<DirectEntry> e = it->lock();
+    if (!e) { it = g_direct.erase(it); continue; }
+    if (e->device == su->device && e->kind == kind && e->t.curve == su->curve && e->t.n == nb && e->srs_key == su->g1_raw && (!c_exact || e->t.c == c_exact)) return e;
+    ++it;
+  }
+  return nullptr;
+}
+static uint64_t held_bytes_locked(int device) {
+  uint64_t sum = 0;
+  for (auto &w : g_direct) if (std::shared_ptr<DirectEntry> e = w.lock()) if (e->device == device && e->t.d) sum += e->t.bytes;
+  return sum;
+}
+static void ensure_direct(avrf_ring_setup *su) {
+  if (su->direct_tried || !su->n_srs) return;
+  su->direct_tried = true;
+  su->table_missed = false;
+  su->planned_budget = su->table_budget;
+  const bool expl = su->table_budget != UINT64_MAX;
+  if (tables_disabled(su)) { std::lock_guard<std::mutex> lk(g_direct_mu); drop_tables_locked(su); return; }
+  with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; R_::ensure_lagrange(su); return 0; });   // the witness bases
+  std::lock_guard<std::mutex> lk(g_direct_mu);
+  double budget_gb = direct_env_budget_gb();
+  int plan_c[2] = {0, 0}; uint64_t plan_b[2] = {0, 0};
+  if (expl) plan_direct(su, su->table_budget, plan_c, plan_b);
+  // kind 0 over the SRS powers, then kind 1 over the witness bases with what is left of the budget
+  for (int kind = 0; kind < 2; kind++) {
+    std::shared_ptr<DirectEntry> &slot = kind ? su->direct_wit : su->direct;
+    const size_t nb = direct_bases(su, kind);
+    const uint32_t *bases = kind ? su->d_wit_bases : su->d_srs;
+    if (!bases) continue;
+    int c = 0;
+    if (expl) {
+      if (slot && slot->t.c != plan_c[kind]) slot.reset();               // (held at another width: released before anything is built)
+      if (!plan_c[kind] || slot) continue;                               // nothing planned, or held at the planned width already
+      if ((slot = find_direct_locked(su, kind, plan_c[kind]))) continue;
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); su->table_missed = true; continue; }
+      if ((double)plan_b[kind] > (double)free_b - 40e9) { su->table_missed = true; continue; }
+      c = plan_c[kind];
+    } else {
+      const int c_min = kind ? su->wit_c : su->table_c;
+      if (kind) if (const char *e = getenv("AVRF_RING_DIRECT_WIT")) if (atoi(e) == 0) continue;   // (A/B knob: the witness commits stay on the bucket form)
+      if (!slot) slot = find_direct_locked(su, kind, 0);
+      if (slot) { budget_gb -= slot->t.bytes * 1e-9; continue; }
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); break; }
+      double usable = (double)free_b - 40e9; if (usable > budget_gb * 1e9) usable = budget_gb * 1e9;
+      for (int cc = 16; cc >= c_min && cc >= 8; cc--) {
+        const uint64_t b = direct_bytes(su->curve, nb, cc);
+        if (b && (double)b <= usable) { c = cc; break; }
+      }
+      if (!c) continue;
+    }
+    auto e = std::make_shared<DirectEntry>();
+    e->device = su->device; e->kind = kind; e->srs_key = su->g1_raw;
+    try { build_g1_direct_table(su->curve, bases, nb, c, &e->t, su->stream); }
+    catch (const HipFailure &) { (void)hipGetLastError(); su->table_missed = true; continue; }   // (the entry's destructor frees what was allocated)
+    g_direct.push_back(e);
+    slot = e;
+    budget_gb -= e->t.bytes * 1e-9;
+  }
+  sync_lane_tables(su);
+}
+
 extern "C" {
 
 int avrf_ring_setup_load(avrf_ctx *ctx, const uint8_t *srs, size_t srs_len, size_t ring_size, avrf_ring_setup **out) {
@@ -1820,6 +1930,7 @@ void avrf_ring_setup_free(avrf_ring_setup *su) {
   su->ws.release();
   su->ptab.release();
   if (su->host_lines && su->host_lines_free) su->host_lines_free(su->host_lines);
+  { std::lock_guard<std::mutex> lk(g_direct_mu); drop_tables_locked(su); }
   if (avrf_ring_setup *l = su->lane1) {                                // only what the lane owns
     void *o[] = {l->d_buf, l->d_scr[0], l->d_scr[1], l->d_scr[2], l->d_scr[3], l->d_scr[4], l->d_scr[5]};
     for (void *p : o) if (p) (void)hipFree(p);
@@ -1841,6 +1952,56 @@ int avrf_ring_setup_plan(const avrf_ring_setup *su, int32_t out[4]) {
   // once a batched prove call has built the tables of all multiples, those are what the commitments of a batch run over
   if (su->direct) { out[0] = su->direct->t.c; out[1] = su->direct->t.rows; }
   if (su->direct_wit) { out[2] = su->direct_wit->t.c; out[3] = su->direct_wit->t.rows; }
+  return AVRF_OK;
+}
+uint64_t avrf_ring_table_bytes(int suite, size_t ring_size, int kind, int c) {
+  if (!ring_suite(suite) || ring_size == 0 || ring_size > ((size_t)1 << 40) || (kind != 0 && kind != 1) || c < 8 || c > 16) return 0;
+  const size_t pcs = avrf_ring_pcs_domain_size(suite, ring_size), N = (pcs - 1) / 3;
+  return direct_bytes(pairing_curve_of(suite), kind ? 2 * N + 1 : pcs, c);
+}
+int avrf_ring_setup_set_table_budget(avrf_ring_setup *su, uint64_t bytes) {
+  if (!su) return AVRF_ERR_BAD_ARG;
+  if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
+  if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
+  su->table_budget = bytes;                                            // (read at the next build; the tables held stay)
+  return AVRF_OK;
+}
+int avrf_ring_setup_build_tables(avrf_ring_setup *su) {
+  if (!su) return AVRF_ERR_BAD_ARG;
+  if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
+  if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
+  if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
+  // a new budget: the tables of the old plan are released first, so that the new ones can take their memory; the same plan: the held
+  // tables stay (a no-op, or a retry of the tables that were not built)
+  if (su->planned_budget != su->table_budget) { std::lock_guard<std::mutex> lk(g_direct_mu); drop_tables_locked(su); }
+  su->direct_tried = false;
+  if (int st = guarded([&] { ensure_direct(su); return (int)AVRF_OK; })) return st;
+  return su->table_missed ? AVRF_ERR_NO_DEVICE : AVRF_OK;
+}
+int avrf_ring_setup_release_tables(avrf_ring_setup *su) {
+  if (!su) return AVRF_ERR_BAD_ARG;
+  if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
+  if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
+  (void)hipSetDevice(su->device);                                      // (the entry's destructor frees on its own device)
+  std::lock_guard<std::mutex> lk(g_direct_mu);
+  su->direct_tried = true;                                             // no lazy build again until avrf_ring_setup_build_tables
+  su->table_missed = false;
+  drop_tables_locked(su);
+  return AVRF_OK;
+}
+int avrf_ring_setup_tables(const avrf_ring_setup *su, uint64_t out[10]) {
+  if (!su || !out) return AVRF_ERR_BAD_ARG;
+  if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
+  if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
+  const bool expl = su->table_budget != UINT64_MAX, off = tables_disabled(su);
+  std::lock_guard<std::mutex> lk(g_direct_mu);
+  for (int i = 0; i < 10; i++) out[i] = 0;
+  out[0] = (su->direct ? 1u : 0u) | (su->direct_wit ? 2u : 0u) | (expl ? 4u : 0u) | (su->table_missed ? 8u : 0u) | (off ? 16u : 0u);
+  out[1] = expl ? su->table_budget : off ? 0 : (uint64_t)(direct_env_budget_gb() * 1e9);
+  if (su->direct) { out[2] = (uint64_t)su->direct->t.c; out[3] = (uint64_t)su->direct->t.rows; out[4] = su->direct->t.bytes; }
+  if (su->direct_wit) { out[5] = (uint64_t)su->direct_wit->t.c; out[6] = (uint64_t)su->direct_wit->t.rows; out[7] = su->direct_wit->t.bytes; }
+  out[8] = su->table_batches->load();
+  out[9] = held_bytes_locked(su->device);
   return AVRF_OK;
 }
 
@@ -1882,52 +2043,6 @@ int avrf_ring_vk_builder_finalize(const avrf_ring_vk_builder *b, uint8_t *commit
   for (int i = 0; i < 3; i++) { if (b->setup->curve == 0) g1_encode<G1Bls12381>(b->C[i], true, o); else g1_encode<G1Bn254>(b->C[i], true, o); }
   memcpy(commitment_out, o.data(), o.size());
   return AVRF_OK;
-}
-
-// The table of all multiples of this setup's SRS: found in the registry or built (once per device and SRS, ~2 s), sized to the HBM that
-// is free -- the widest window c <= 16 whose table fits min(what is left of AVRF_RING_TABLE_GB (default 232, both tables together), free - 40 GB); no table when even the
-// bucket form's own width does not fit, when AVRF_RING_DIRECT=0, or when the allocation fails (the bucket form then runs as before).
-static void ensure_direct(avrf_ring_setup *su) {
-  if (su->direct_tried || !su->n_srs) return;
-  su->direct_tried = true;
-  if (const char *e = getenv("AVRF_RING_DIRECT")) if (atoi(e) == 0) return;
-  with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; R_::ensure_lagrange(su); return 0; });   // the witness bases
-  std::lock_guard<std::mutex> lk(g_direct_mu);
-  double budget_gb = 232.0;
-  if (const char *e = getenv("AVRF_RING_TABLE_GB")) budget_gb = atof(e);
-  // kind 0 over the SRS powers, then kind 1 over the witness bases with what is left of the budget
-  for (int kind = 0; kind < 2; kind++) {
-    std::shared_ptr<DirectEntry> &slot = kind ? su->direct_wit : su->direct;
-    const size_t nb = kind ? 2 * su->N + 1 : su->n_srs;
-    const uint32_t *bases = kind ? su->d_wit_bases : su->d_srs;
-    const int c_min = kind ? su->wit_c : su->table_c;
-    if (!bases) continue;
-    if (kind) if (const char *e = getenv("AVRF_RING_DIRECT_WIT")) if (atoi(e) == 0) continue;   // (A/B knob: the witness commits stay on the bucket form)
-    for (auto it = g_direct.begin(); it != g_direct.end();) {
-      std::shared_ptr<DirectEntry> e = it->lock();
-      if (!e) { it = g_direct.erase(it); continue; }
-      if (e->device == su->device && e->kind == kind && e->t.curve == su->curve && e->t.n == nb && e->srs_key == su->g1_raw) { slot = e; break; }
-      ++it;
-    }
-    if (slot) { budget_gb -= slot->t.bytes * 1e-9; continue; }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return; }
-    double usable = (double)free_b - 40e9; if (usable > budget_gb * 1e9) usable = budget_gb * 1e9;
-    int c = 0;
-    for (int cc = 16; cc >= c_min && cc >= 8; cc--) {
-      G1DirectTable shape;
-      if ((double)g1_direct_table_shape(su->curve, nb, cc, &shape) <= usable && shape.points < 0x7fffffffull) { c = cc; break; }
-    }
-    if (!c) continue;
-    auto e = std::make_shared<DirectEntry>();
-    e->device = su->device; e->kind = kind; e->srs_key = su->g1_raw;
-    try { build_g1_direct_table(su->curve, bases, nb, c, &e->t, su->stream); }
-    catch (const HipFailure &) { (void)hipGetLastError(); continue; }       // (the entry's destructor frees what was allocated)
-    g_direct.push_back(e);
-    slot = e;
-    budget_gb -= e->t.bytes * 1e-9;
-  }
-  if (su->lane1) { su->lane1->direct = su->direct; su->lane1->direct_wit = su->direct_wit; su->lane1->direct_tried = true; su->lane1->d_wit_bases = su->d_wit_bases; }
 }
 
 int avrf_ring_prove(avrf_ring_key *k, size_t n, const uint32_t *key_index, const uint8_t *blindings, int blinding_mode, uint8_t *proofs_out) {

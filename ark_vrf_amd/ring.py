@@ -96,6 +96,41 @@ class RingSetup:
             raise nat.AvrfError(f"avrf_ring_index -> {st}")
         return RingKey(self, h, bytes(com))
 
+    # ---- tables of all multiples (include/avrf.h: avrf_ring_setup_set_table_budget / build_tables / release_tables / tables)
+    TABLE_BUDGET_DEFAULT = (1 << 64) - 1
+
+    def set_table_budget(self, nbytes):
+        """HBM this setup's two tables may take together (None = the process default, 0 = bucket form only); takes effect at the
+        next build."""
+        b = self.TABLE_BUDGET_DEFAULT if nbytes is None else int(nbytes)
+        st = nat.lib().avrf_ring_setup_set_table_budget(self._h, C.c_uint64(b))
+        if st != nat.OK:
+            raise nat.AvrfError(f"avrf_ring_setup_set_table_budget -> {st}")
+
+    def build_tables(self):
+        """Builds (or adopts) the planned tables now.  Returns the status: 0, or ERR_NO_DEVICE (-1) when a planned table could
+        not be held -- the setup stays usable on the bucket form.  Other failures raise."""
+        st = nat.lib().avrf_ring_setup_build_tables(self._h)
+        if st not in (nat.OK, nat.ERR_NO_DEVICE):
+            raise nat.AvrfError(f"avrf_ring_setup_build_tables -> {st}")
+        return st
+
+    def release_tables(self):
+        st = nat.lib().avrf_ring_setup_release_tables(self._h)
+        if st != nat.OK:
+            raise nat.AvrfError(f"avrf_ring_setup_release_tables -> {st}")
+
+    def tables(self):
+        """avrf_ring_setup_tables as a dict."""
+        out = (C.c_uint64 * 10)()
+        st = nat.lib().avrf_ring_setup_tables(self._h, out)
+        if st != nat.OK:
+            raise nat.AvrfError(f"avrf_ring_setup_tables -> {st}")
+        o = list(out)
+        return {"state": o[0], "srs_held": bool(o[0] & 1), "wit_held": bool(o[0] & 2), "explicit": bool(o[0] & 4),
+                "missed": bool(o[0] & 8), "disabled": bool(o[0] & 16), "budget": o[1],
+                "srs": (o[2], o[3], o[4]), "wit": (o[5], o[6], o[7]), "served": o[8], "process_bytes": o[9]}
+
     def close(self):
         if self._h:
             nat.lib().avrf_ring_setup_free(self._h)
@@ -145,6 +180,18 @@ class VerifierKeyBuilder:
             self.close()
         except Exception:
             pass
+
+
+TABLE_STATE_SRS, TABLE_STATE_WIT, TABLE_STATE_EXPLICIT, TABLE_STATE_MISSED, TABLE_STATE_DISABLED = 1, 2, 4, 8, 16
+
+
+def table_bytes(suite, ring_size, kind, c):
+    """avrf_ring_table_bytes: bytes of the table of all multiples (kind 0: the 3N+1 SRS powers, 1: the 2N+1 witness bases) at
+    window c for a ring of `ring_size`; 0 outside 8..16, for a suite without ring, or at 2^31 - 1 points or more.  No device needed."""
+    f = nat.lib().avrf_ring_table_bytes
+    f.restype = C.c_uint64
+    f.argtypes = [C.c_int, C.c_size_t, C.c_int, C.c_int]
+    return f(int(suite), int(ring_size), int(kind), int(c))
 
 
 def ring_batch_verify(setup, ring_commitments, ring_of_item, instances_xy, ring_proofs):

@@ -356,6 +356,39 @@ avrf_ring_setup *avrf_ring_key_setup(const avrf_ring_key *key);
  * 64 or more proofs builds, once per device and SRS, the tables of ALL multiples of both base sets in the HBM that is free (DESIGN.md;
  * AVRF_RING_TABLE_GB, default 232, AVRF_RING_DIRECT=0 to keep the bucket form); from then on the figures are those tables'. */
 int avrf_ring_setup_plan(const avrf_ring_setup *setup, int32_t out[4]);
+/* ---- Tables of all multiples: per-setup HBM budget, explicit build and release.
+ * Without these calls nothing changes: the first prove call of 64 or more proofs builds (or adopts from the per-device registry)
+ * both tables within the process default (AVRF_RING_TABLE_GB, AVRF_RING_DIRECT, adapted to the HBM that is free at that moment).
+ * Resource contract: a build takes the table's bytes (avrf_ring_table_bytes) plus transient scratch that is freed before the call
+ * returns, 386 x rows x bases x 4 x (32-bit words of an Fq element: 12, 8) bytes -- 2.05 GB for the SRS table of a BLS12-381 ring of 1024 at c = 15 (18 rows),
+ * 6.07 GB for that of a BN254 ring of 4096 at c = 13 (20 rows) -- and blocks the calling thread while it builds.
+ * A table is shared by every setup over the same SRS on a device that plans the same width; the registry frees it with its last holder.
+ *
+ * Bytes of the table of all multiples for a ring of `ring_size` on a ring suite: kind 0 = the 3N+1 SRS powers, kind 1 = the 2N+1
+ * witness bases; 0 when c is outside 8..16, the suite has no ring, or the table would hold 2^31 - 1 points or more (entry indices
+ * are 31-bit).  Host arithmetic only: no device needed. */
+uint64_t avrf_ring_table_bytes(int suite, size_t ring_size, int kind, int c);
+/* HBM this setup's two tables may take together.  UINT64_MAX (the initial value) = the process default (the rule above); 0 = bucket
+ * form only.  With an explicit budget the plan is a pure function of it: the SRS table gets the widest c in [the bucket width
+ * (avrf_ring_setup_plan out[0] before any table), 16] whose bytes fit, the witness table the widest c in [8, 16] that fits what is
+ * left.  Free memory does not change the widths: a planned table that does not fit in free HBM - 40 GB, or whose allocation or build
+ * fails, is not built (state bit 8) and the bucket form runs for it; no narrower table is substituted.  A registry table is adopted
+ * only at exactly the planned width.  Takes effect at the next build; tables already held stay until released. */
+int avrf_ring_setup_set_table_budget(avrf_ring_setup *setup, uint64_t bytes);
+/* Build (or adopt from the per-device registry) the tables the plan calls for, now -- e.g. inside a service's prover_key path.
+ * Again with the same plan: a no-op (tables not built before are tried again); after a budget change: releases, then rebuilds.
+ * AVRF_ERR_NO_DEVICE when a planned table could not be held (state bit 8); the setup stays fully usable on the bucket form. */
+int avrf_ring_setup_build_tables(avrf_ring_setup *setup);
+/* Drop this setup's (and its second lane's) references; the registry frees a table when its last holder goes.  A released setup
+ * proves on the bucket form and does not build lazily again until avrf_ring_setup_build_tables is called. */
+int avrf_ring_setup_release_tables(avrf_ring_setup *setup);
+/* out = { state bits, budget in force (bytes), SRS table c, rows, bytes, witness table c, rows, bytes (0 when not held),
+ *         commitment batches served from tables so far, bytes of all tables this process holds on the setup's device }.
+ * State bits: 1 SRS table held, 2 witness table held, 4 an explicit budget is set, 8 a planned table was not built (bucket form
+ * for it), 16 tables disabled (budget 0, or AVRF_RING_DIRECT=0 with no explicit budget).  The budget in force without an explicit
+ * one is AVRF_RING_TABLE_GB x 10^9 (0 when disabled); free memory further limits it at a build.
+ * All four setup calls: AVRF_SRS_LOOKUP_FAILED on a verifier-only setup, AVRF_ERR_BAD_ARG on a busy context. */
+int avrf_ring_setup_tables(const avrf_ring_setup *setup, uint64_t out[10]);
 
 /* RingSetup::prover_key / verifier_key -> ring_proof::index (src/ring.rs:399-417): fixed columns of the
  * ring `pks_xy` (n_keys x 64) and their three KZG commitments.  commitment_out (may be NULL) receives the

@@ -288,6 +288,24 @@ class RingSetup {
   size_t max_ring_size() const { return avrf_ring_max_ring_size(h_); }       // src/ring.rs:298-300
   size_t proof_len() const { return avrf_ring_proof_len(h_); }
   avrf_ring_setup *handle() const { return h_; }
+  // tables of all multiples (avrf_ring_setup_set_table_budget / build_tables / release_tables / tables, include/avrf.h): a service
+  // sets the HBM one setup may pin and pays the build inside its prover_key path instead of in the first batched prove call
+  static constexpr uint64_t kDefaultTableBudget = UINT64_MAX;
+  struct Tables {
+    uint64_t state = 0, budget = 0;
+    uint64_t srs_c = 0, srs_rows = 0, srs_bytes = 0, wit_c = 0, wit_rows = 0, wit_bytes = 0;
+    uint64_t served_batches = 0, process_bytes = 0;
+  };
+  static uint64_t table_bytes(int suite_id, size_t ring_size, int kind, int c) { return avrf_ring_table_bytes(suite_id, ring_size, kind, c); }
+  int set_table_budget(uint64_t bytes) { return avrf_ring_setup_set_table_budget(h_, bytes); }
+  int build_tables() { return avrf_ring_setup_build_tables(h_); }
+  int release_tables() { return avrf_ring_setup_release_tables(h_); }
+  int tables(Tables *out) const {
+    uint64_t o[10] = {};
+    const int st = avrf_ring_setup_tables(h_, o);
+    *out = Tables{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9]};
+    return st;
+  }
 
  private:
   void reset() { if (h_) avrf_ring_setup_free(h_); h_ = nullptr; }
