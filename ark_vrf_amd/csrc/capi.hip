@@ -17,6 +17,7 @@
 #include "vrf_batch.h"
 #include "suite_dispatch.h"
 #include <chrono>
+#include <optional>
 #include <stdlib.h>
 #include <string.h>
 
@@ -36,7 +37,7 @@ static inline bool ctx_busy(const avrf_ctx *c) { return c->run_phase != 0; }
 static int ensure_fixed(avrf_ctx *c) {
   if (c->fixed_ready) return AVRF_OK;
   if (c->d_fixed.ensure((size_t)2 * 32 * 256 * sizeof(te_pre_raw)) != hipSuccess) return AVRF_ERR_NO_DEVICE;
-  launch_fixed_table(c->suite, c->d_fixed.as<te_pre_raw>(), c->stream);
+  AVRF_SINGLE(c->suite, fixed_table(c->d_fixed.as<te_pre_raw>(), c->stream));
   c->fixed_ready = true;
   return AVRF_OK;
 }
@@ -76,18 +77,18 @@ static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status) {
   if (c->validate <= 0 || !c->n) return;
   uint32_t *fl = c->d_flags.as<uint32_t>();
   const uint32_t n = (uint32_t)c->n;
-  if (kind != 2 && c->d_pks.p) launch_validate_xy(c->suite, c->d_pks.as<uint8_t>(), 64, 1, n, c->validate, fl, d_rec_status, c->stream);
-  if (kind == 1) launch_validate_xy(c->suite, c->d_proofs.as<uint8_t>(), 96, 1, n, c->validate, fl, d_rec_status, c->stream);
-  else if (kind == 2) launch_validate_xy(c->suite, c->d_proofs.as<uint8_t>(), 256, 3, n, c->validate, fl, d_rec_status, c->stream);
+  if (kind != 2 && c->d_pks.p) AVRF_SINGLE(c->suite, validate_xy(c->d_pks.as<uint8_t>(), 64, 1, n, c->validate, fl, d_rec_status, c->stream));
+  if (kind == 1) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), 96, 1, n, c->validate, fl, d_rec_status, c->stream));
+  else if (kind == 2) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), 256, 3, n, c->validate, fl, d_rec_status, c->stream));
   if (c->tot_io) {
-    if (!d_rec_status) launch_validate_xy(c->suite, c->d_ios.as<uint8_t>(), 128, 2, (uint32_t)c->tot_io, c->validate, fl, nullptr, c->stream);
+    if (!d_rec_status) AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>(), 128, 2, (uint32_t)c->tot_io, c->validate, fl, nullptr, c->stream));
     else {   // per-item status: the I/O pairs of item j are records io_off[j] .. io_off[j+1]; uniform M = 1 is the common case
       const uint32_t *io_off = c->h_io.as<uint32_t>();
       bool uniform = c->tot_io == c->n;
       for (size_t j = 0; uniform && j < c->n; j++) uniform = io_off[j] == j;
-      if (uniform) launch_validate_xy(c->suite, c->d_ios.as<uint8_t>(), 128, 2, n, c->validate, fl, d_rec_status, c->stream);
-      else launch_validate_xy(c->suite, c->d_ios.as<uint8_t>(), 128, 2, (uint32_t)c->tot_io, c->validate, fl, d_rec_status, c->stream,
-                              c->d_io_off.as<uint32_t>(), n);     // one launch: every lane looks its item up in the staged offsets
+      if (uniform) AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>(), 128, 2, n, c->validate, fl, d_rec_status, c->stream));
+      else AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>(), 128, 2, (uint32_t)c->tot_io, c->validate, fl, d_rec_status, c->stream,
+                                             c->d_io_off.as<uint32_t>(), n));     // one launch: every lane looks its item up in the staged offsets
     }
   }
 }
@@ -331,11 +332,11 @@ int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const ui
   HIP_TRY(hipMemcpyAsync(dw + w_pks + w_ios, proofs, w_pr, hipMemcpyHostToDevice, c->stream));
   uint32_t *d_flag = c->d_status.as<uint32_t>(), *h_flag = c->h_flags.as<uint32_t>() + 2;
   HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
-  if (kind == 1) launch_decompress_strided(c->suite, dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, validate, d_flag, c->stream);
-  launch_decompress_strided(c->suite, dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>(), 64, validate, d_flag, c->stream);
+  if (kind == 1) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, validate, d_flag, c->stream));
+  AVRF_SINGLE(c->suite, decompress_strided(dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>(), 64, validate, d_flag, c->stream));
   const uint8_t *dpr = dw + w_pks + w_ios;
   for (size_t p = 0; p < ppts; p++)
-    launch_decompress_strided(c->suite, dpr + L * p, (uint32_t)plen, (uint32_t)n, c->d_proofs.as<uint8_t>() + 64 * p, (uint32_t)psz, validate, d_flag, c->stream);
+    AVRF_SINGLE(c->suite, decompress_strided(dpr + L * p, (uint32_t)plen, (uint32_t)n, c->d_proofs.as<uint8_t>() + 64 * p, (uint32_t)psz, validate, d_flag, c->stream));
   HIP_TRY(hipMemcpy2DAsync(c->d_proofs.as<uint8_t>() + 64 * ppts, psz, dpr + L * ppts, plen, tail, n, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   if (suite_host_weights(c->suite)) {
@@ -365,25 +366,16 @@ int avrf_pedersen_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *ios, co
   if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   return avrf::ctx_stage_wire(c, 2, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, true);
 }
-static int stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
-                 const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
-  return ctx_stage(c, kind, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, true);
-}
-// the per-item entry points wait for the stream before they return: their staging copies need no wait of their own
-static int stage_nowait(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
-                        const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
-  return ctx_stage(c, kind, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, false);
-}
 
 int avrf_thin_batch_stage(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && (!pks_xy || !proofs)) return AVRF_ERR_BAD_ARG;
-  return stage(c, 1, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs);
+  return ctx_stage(c, 1, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, true);
 }
 int avrf_pedersen_batch_stage(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts,
                               const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && !proofs) return AVRF_ERR_BAD_ARG;
-  return stage(c, 2, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs);
+  return ctx_stage(c, 2, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs, true);
 }
 
 // ---- the weight transcripts of the contexts in flight, hashed together (host_sha512_mb.h)
@@ -482,8 +474,8 @@ int batch_begin(avrf_ctx *c, int kind) {
     HIP_TRY(c->d_rec.ensure(n * recsz)); HIP_TRY(c->h_msg.ensure(pl + n * recsz));
     b.records = c->d_rec.as<uint8_t>();
   }
-  if (kind == 1) launch_thin_prepare(c->suite, b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream);
-  else launch_ped_prepare(c->suite, b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream);
+  if (kind == 1) AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
+  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
   if (!host_stream) {
     memcpy(c->h_msg.p, prefix, pl);
     HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl, c->d_rec.p, n * recsz, hipMemcpyDeviceToHost, c->stream));
@@ -564,10 +556,10 @@ int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]) {
   for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, digest + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
   HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((n + 127) / 128) * 64 + 64));
   const double t2 = now_us();
-  if (kind == 1) launch_thin_terms(c->suite, b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
-                                   c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream);
-  else launch_ped_terms(c->suite, b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
-                        c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream);
+  if (kind == 1) AVRF_BATCH(c->suite, thin_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
+                                                 c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
+  else AVRF_BATCH(c->suite, ped_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
+                                      c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
   const double t3 = now_us();
   if (int e = guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->stream, c->pend) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   c->timing[3] = t3 - t2;
@@ -721,7 +713,7 @@ int avrf_thin_batch_challenges(avrf_ctx *c, uint8_t *c_out) {
   BatchDev b = batch_of(c);
   HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
   validate_staged(c, 1, nullptr);
-  launch_thin_prepare(c->suite, b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream);
+  AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
   HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -745,8 +737,8 @@ int avrf_thin_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t firs
   Seed64 seed;
   for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, seed64 + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
   BatchDev b = batch_of(c);
-  launch_thin_terms(c->suite, b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
-                    c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream);
+  AVRF_BATCH(c->suite, thin_terms(b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
+                                  c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
   if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   return finish_point(c, r, out_xy);
 }
@@ -761,7 +753,7 @@ int avrf_pedersen_batch_challenges(avrf_ctx *c, uint8_t *c_out) {
   BatchDev b = batch_of(c);
   HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
   validate_staged(c, 2, nullptr);
-  launch_ped_prepare(c->suite, b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream);
+  AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
   HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -781,8 +773,8 @@ int avrf_pedersen_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t 
   Seed64 seed;
   for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, seed64 + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
   BatchDev b = batch_of(c);
-  launch_ped_terms(c->suite, b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
-                   c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream);
+  AVRF_BATCH(c->suite, ped_terms(b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
+                                 c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
   if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   return finish_point(c, r, out_xy);
 }
@@ -830,14 +822,22 @@ int avrf_kernel_stats(avrf_ctx *c, int reset, double *accum_ms_total, uint64_t *
   return AVRF_OK;
 }
 
+}  // extern "C"
 // ---------------------------------------------------------------- independent per-item calls
 
+// the input flags, read once the stream has drained: AVRF_INVALID_DATA when a check refused an input
 static int read_flags(avrf_ctx *c) {
-  if (hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return -1;
+  if (hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return AVRF_ERR_NO_DEVICE;
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return AVRF_ERR_NO_DEVICE;
   static const bool trace = getenv("AVRF_TRACE_FLAGS") != nullptr;   // which check refused the input: 1 range, 2 identity, 4 scalar, 8 curve
   if (trace && *c->h_flags.as<uint32_t>()) fprintf(stderr, "avrf: input flags 0x%x (suite %d)\n", *c->h_flags.as<uint32_t>(), c->suite);
-  return (int)*c->h_flags.as<uint32_t>();
+  return *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : AVRF_OK;
+}
+
+// the context's stream has drained: AVRF_OK, or AVRF_ERR_NO_DEVICE when it (or anything before it) failed
+static int sync_stream(avrf_ctx *c) {
+  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
+  return AVRF_OK;
 }
 
 // few items with one I/O pair each: the kernels that spread an item over 32 lanes (vrf_single.hip "few items")
@@ -849,34 +849,41 @@ static bool wave_shape(const avrf_ctx *c, size_t n, const uint32_t *io_counts) {
   return true;
 }
 
-// ONE thin / tiny proof through the MSM engine (vrf_single.hip k_thin_prove_begin / _end): the terms of R = k G + sum (k z_i) I_i,
+// The one-item routes below take a call of ONE item through the MSM engine instead of a kernel per item.  Each answers the call's
+// status, or nothing when the item is too large for it (the call then goes on to the kernels).
+using Route = std::optional<int>;
+static bool one_as_msm() { static const bool on = getenv("AVRF_NO_ONE_AS_MSM") == nullptr; return on; }   // (A/B hook)
+
+// ONE thin / tiny proof with fewer than 1000 I/O pairs (vrf_single.hip k_thin_prove_begin / _end): the terms of R = k G + sum (k z_i) I_i,
 // the single-launch MSM with the host's Horner, R back as canonical x || y, challenge and response.  0.71 -> ~0.3 ms
 // for one proof; same bytes (any evaluation of R gives the same group element).  The nonce never leaves device memory.
-static bool one_as_msm() { static const bool on = getenv("AVRF_NO_ONE_AS_MSM") == nullptr; return on; }   // (A/B hook)
-static int prove_one_as_msm(avrf_ctx *c, bool have_pk, bool tiny, uint8_t *proofs_out) {
-  const size_t nt = 1 + c->tot_io, plen = tiny ? 48 : 96, sb = thin_prove_state_bytes(c->suite);
+static Route prove_one_as_msm(avrf_ctx *c, bool have_pk, bool tiny, uint8_t *proofs_out) {
+  if (c->tot_io >= 1000) return {};
+  const size_t nt = 1 + c->tot_io, plen = tiny ? 48 : 96, sb = AVRF_SINGLE(c->suite, prove_state_bytes());
+  HIP_TRY(c->h_c.ensure(64));
   if (!have_pk) { if (int fs = ensure_fixed(c)) return fs; }
   HIP_TRY(c->L->d_scalars.ensure(nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw))); HIP_TRY(c->d_misc.ensure(sb + 64)); HIP_TRY(c->d_out.ensure(plen));
   BatchDev b = batch_of(c);
   if (!have_pk) b.pks_xy = nullptr;
   uint8_t *d_state = c->d_misc.as<uint8_t>();
-  launch_thin_prove_begin(c->suite, b, c->L->d_scalars.as<uint32_t>(), c->L->d_pre.as<te_pre_raw>(), d_state, c->stream, tiny);
+  AVRF_SINGLE(c->suite, thin_prove_begin(b, c->L->d_scalars.as<uint32_t>(), c->L->d_pre.as<te_pre_raw>(), d_state, c->stream, tiny));
   HostExt r;
   if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), nt, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   uint8_t *rxy = c->h_c.as<uint8_t>();                                  // (pinned; the challenges are not in use by a prover)
   finish_point(c, r, rxy);
   HIP_TRY(hipMemcpyAsync(d_state + sb, rxy, 64, hipMemcpyHostToDevice, c->stream));
-  launch_thin_prove_end(c->suite, b, d_state, d_state + sb, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream, tiny);
+  AVRF_SINGLE(c->suite, thin_prove_end(b, d_state, d_state + sb, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream, tiny));
   HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, plen, hipMemcpyDeviceToHost, c->stream));
-  const int f = read_flags(c);
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  return f ? AVRF_INVALID_DATA : AVRF_OK;
+  return read_flags(c);
 }
 
-// ONE Pedersen proof the same way (vrf_single.hip k_ped_prove_begin / _mid / _end): Yb = pk + bl B as a two-term MSM, then R = k G + kb B
-// and Ok = k I_m as two scalar vectors over {G, B, I_0, ..} in one launch; every doubling chain is the host's.  1.03 -> ~0.5 ms.
-static int prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out, uint8_t *blindings_out) {
-  const size_t m = c->tot_io, nt = 2 + m, sb = ped_prove_state_bytes(c->suite), wb = (m * 32 + 63) / 64 * 64 + 64;
+// ONE Pedersen proof with up to 1000 I/O pairs the same way (vrf_single.hip k_ped_prove_begin / _mid / _end): Yb = pk + bl B as a
+// two-term MSM, then R = k G + kb B and Ok = k I_m as two scalar vectors over {G, B, I_0, ..} in one launch; every doubling chain is
+// the host's.  1.03 -> ~0.5 ms.
+static Route prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out, uint8_t *blindings_out) {
+  if (c->tot_io > 1000) return {};
+  if (!have_pk) { if (int fs = ensure_fixed(c)) return fs; }
+  const size_t m = c->tot_io, nt = 2 + m, sb = AVRF_SINGLE(c->suite, ped_state_bytes()), wb = (m * 32 + 63) / 64 * 64 + 64;
   HIP_TRY(c->L->d_scalars.ensure(2 * nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw)));
   HIP_TRY(c->d_misc.ensure(sb + wb + 192 + 32)); HIP_TRY(c->d_out.ensure(256)); HIP_TRY(c->h_c.ensure(192));
   BatchDev b = batch_of(c);
@@ -884,280 +891,229 @@ static int prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out, 
   uint8_t *d_state = c->d_misc.as<uint8_t>(), *d_pts = d_state + sb + wb, *d_blind = d_pts + 192;
   uint32_t *d_wts = reinterpret_cast<uint32_t *>(d_state + sb);
   uint32_t *d_sc = c->L->d_scalars.as<uint32_t>(); te_pre_raw *d_pre = c->L->d_pre.as<te_pre_raw>();
-  launch_ped_prove_begin(c->suite, b, d_sc, d_pre, d_state, d_wts, c->stream);
+  AVRF_SINGLE(c->suite, ped_prove_begin(b, d_sc, d_pre, d_state, d_wts, c->stream));
   HostExt r[2];
   if (int e = guarded([&] { return msm_te_device(c->suite, d_pre, d_sc, 2, c->L->ws, c->stream, &r[0]) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   uint8_t *pts = c->h_c.as<uint8_t>();                                  // pinned: Yb | R | Ok
   finish_point(c, r[0], pts);
   HIP_TRY(hipMemcpyAsync(d_pts, pts, 64, hipMemcpyHostToDevice, c->stream));
-  launch_ped_prove_mid(c->suite, b, d_sc, d_pre, d_state, d_wts, d_pts, c->stream);
+  AVRF_SINGLE(c->suite, ped_prove_mid(b, d_sc, d_pre, d_state, d_wts, d_pts, c->stream));
   if (int e = guarded([&] { return msm_te_small_vectors(c->suite, d_pre, d_sc, nt, 2, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   finish_point(c, r[0], pts + 64); finish_point(c, r[1], pts + 128);
   HIP_TRY(hipMemcpyAsync(d_pts + 64, pts + 64, 128, hipMemcpyHostToDevice, c->stream));
-  launch_ped_prove_end(c->suite, b, d_state, d_pts, c->d_out.as<uint8_t>(), blindings_out ? d_blind : nullptr, c->d_flags.as<uint32_t>(), c->stream);
+  AVRF_SINGLE(c->suite, ped_prove_end(b, d_state, d_pts, c->d_out.as<uint8_t>(), blindings_out ? d_blind : nullptr, c->d_flags.as<uint32_t>(), c->stream));
   HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, 256, hipMemcpyDeviceToHost, c->stream));
   if (blindings_out) HIP_TRY(hipMemcpyAsync(blindings_out, d_blind, 32, hipMemcpyDeviceToHost, c->stream));
-  const int f = read_flags(c);
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  return f ? AVRF_INVALID_DATA : AVRF_OK;
+  return read_flags(c);
+}
+
+// ONE Thin item of up to 2048 MSM terms: its equation  R + c z0 pk + sum_i c z_i O_i - s z0 G - sum_i s z_i I_i == 0  (src/thin.rs:158-161
+// expanded, the BatchVerifier's sum with the weight w = 1) through the prepare / terms kernels and the single-launch MSM
+// (msm.hip k_msm_tiny_bits): the doubling chain runs on the host's Horner instead of a lone wave -- 0.54 -> 0.28 ms.  Same
+// statuses as the per-item kernels: the flags of the prepare kernel and of the validation are InvalidData, a non-zero sum is
+// VerificationFailure.  Everything is enqueued back to back; the one wait is in batch_end.
+static Route verify_one_as_msm(avrf_ctx *c, int32_t *status_out) {
+  if (!c->n_terms || c->n_terms > 2048) return {};
+  uint8_t zero[64] = {0};
+  c->unit_weights = true;
+  int st = batch_begin(c, 1);
+  if (st == AVRF_OK) st = batch_launch(c, 1, zero);
+  if (st == AVRF_OK) st = batch_end(c, 1);
+  c->unit_weights = false;
+  if (st != AVRF_OK && st != AVRF_VERIFICATION_FAILURE) { c->run_phase = 0; return st; }
+  status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : st;
+  return AVRF_OK;
+}
+
+// ONE Pedersen item of up to 2048 terms: its two equations (src/pedersen.rs:229-245) as two scalar vectors over the item's seven
+// bases -- the terms kernel run with the weights (t, u) = (1, 0) and (0, 1) -- through the single-launch MSM with the host's two
+// Horners side by side (see verify_one_as_msm): both sums must be the identity, exactly the reference's two checks.  0.52 -> ~0.33 ms.
+static Route verify_ped_one_as_msm(avrf_ctx *c, int32_t *status_out) {
+  if (!c->n_terms || c->n_terms > 2048) return {};
+  int st = batch_begin(c, 2);                                          // validation + prepare kernel (challenge, merged pair) + flags copy
+  c->run_phase = 0;
+  if (st != AVRF_OK) return st;
+  const size_t nt = c->n_terms;
+  HIP_TRY(c->L->d_scalars.ensure(2 * nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(2 * 64 + 64));
+  c->h_weights.assign(64, 0); c->h_weights[0] = 1; c->h_weights[32 + 16] = 1;                     // (t, u) = (1, 0) | (0, 1)
+  HIP_TRY(c->d_weights.ensure(64));
+  HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), 64, hipMemcpyHostToDevice, c->stream));
+  BatchDev b = batch_of(c);
+  Seed64 seed; for (int i = 0; i < 8; i++) seed.w[i] = 0;
+  for (int v = 0; v < 2; v++) {
+    b.weights = c->d_weights.as<uint8_t>() + 32 * v;
+    AVRF_BATCH(c->suite, ped_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>() + (size_t)v * nt * 8,
+                                   c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)nt, c->stream));
+  }
+  HostExt r[2];
+  if (int e = guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), nt, 2, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : (point_is_identity(c, r[0]) && point_is_identity(c, r[1])) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
+  return AVRF_OK;
+}
+
+// What a per-item entry point hands the route driver besides its inputs
+struct ItemCall {
+  int kind;                  // 1 thin, 2 pedersen, 3 tiny (ctx_stage)
+  bool prover;
+  size_t psz;                // proof bytes: 96 / 256 / 48
+  uint8_t *proofs_out;       // provers: n proofs
+  uint8_t *blindings_out;    // the Pedersen prover: n blindings, or NULL
+  int32_t *status_out;       // verifiers: n statuses
+};
+
+// The one body of avrf_{thin,tiny,pedersen}_{prove,verify}: stage the inputs, then the first route that takes the call --
+// `one` (one item through the MSM engine), `wave` (few items with one I/O pair each, 32 lanes per item; false: the suite has no
+// such kernel) unless an item comes back AVRF_WAVE_FALLBACK (a degenerate point), else `lane` (a lane per item, in ITEM_CHUNK
+// chunks) -- then the proofs (and blindings) back and the input flags read, or the statuses back.
+template <class One, class Wave, class Lane>
+static int item_call(avrf_ctx *c, const ItemCall &k, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
+                     const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, One one, Wave wave, Lane lane) {
+  // Tiny waits for its staging copies; Thin and Pedersen leave them in flight (the call waits for the stream before it returns)
+  int st = ctx_stage(c, k.kind, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, k.kind == 3);
+  if (st || !n) return st;
+  if (k.prover) {
+    c->staged_kind = 0;       // (a Thin / Pedersen verifier leaves its batch staged: avrf_batch_last_terms and avrf_*_batch_run see it)
+    HIP_TRY(c->d_out.ensure(n * k.psz));
+    if (k.kind == 2) HIP_TRY(c->d_misc.ensure(n * 32));                // the blindings
+  } else HIP_TRY(c->d_status.ensure(n * 4));
+  // the provers read the input flags back; the Tiny verifier has always cleared them too, the Thin / Pedersen verifiers never have
+  if (k.prover || k.kind == 3) HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+  auto finish = [&](bool wave_statuses) -> int {
+    if (!k.prover) {
+      validate_staged(c, k.kind, c->d_status.as<int32_t>());           // Validate::Yes failures overwrite the item's status with InvalidData
+      HIP_TRY(hipMemcpyAsync(k.status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+      return sync_stream(c);
+    }
+    HIP_TRY(hipMemcpyAsync(k.proofs_out, c->d_out.p, n * k.psz, hipMemcpyDeviceToHost, c->stream));
+    if (k.blindings_out) HIP_TRY(hipMemcpyAsync(k.blindings_out, c->d_misc.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+    if (wave_statuses) HIP_TRY(hipMemcpyAsync(c->h_c.p, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    return read_flags(c);
+  };
+  auto routes = [&]() -> int {
+    if (n == 1 && one_as_msm()) { if (Route r = one()) return *r; }
+    if ((!k.prover || pks_xy) && wave_shape(c, n, io_counts)) {      // (the wave provers take the public keys as given)
+      if (k.prover && k.kind == 2) { if (int fs = ensure_fixed(c)) return fs; }   // (the Pedersen one reads the fixed-base tables)
+      if (k.prover) { HIP_TRY(c->d_status.ensure(n * 4)); HIP_TRY(c->h_c.ensure(n * 4)); }
+      if (wave(batch_of(c))) {
+        const int ws = finish(true);
+        if (ws < 0) return ws;
+        const int32_t *h_status = k.prover ? c->h_c.as<int32_t>() : k.status_out;
+        bool fallback = false;
+        for (size_t j = 0; j < n; j++) fallback |= h_status[j] == AVRF_WAVE_FALLBACK;
+        if (!fallback) return ws;
+        if (k.prover) HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));   // (the lane-per-item kernel takes the call)
+      }
+    }
+    if (int e = per_item_chunks(c, !k.prover || pks_xy, lane)) return e;
+    return finish(false);
+  };
+  const double t0 = now_us();
+  st = routes();
+  c->timing[0] = now_us() - t0;               // avrf_last_timing: the routes' wall time, for every kind and on every return
+  if (k.kind == 3 && st == AVRF_OK) c->staged_kind = 0;                 // Tiny has no batch verifier: nothing stays staged
+  return st;
+}
+
+// The opening of the point-wise calls below: AVRF_ERR_BAD_ARG for a missing argument (`args_ok` false), a busy context or more than
+// 2^31 - 1 items, AVRF_OK for none; else `body` runs with the context's device selected and whatever was staged dropped.
+template <class F> static int pointwise(avrf_ctx *c, size_t n, bool args_ok, F body) {
+  if (!c || (n && !args_ok) || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
+  if (!n) return AVRF_OK;
+  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  c->staged_kind = 0;
+  return body();
+}
+extern "C" {
+
+// thin::Prover::prove and tiny::Prover::prove (src/thin.rs:111-129, src/tiny.rs:163-176): the same kernels, told apart by `tiny`
+static int thin_or_tiny_prove(avrf_ctx *c, bool tiny, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
+                              const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, uint8_t *proofs_out) {
+  if (n && (!sks || !proofs_out)) return AVRF_ERR_BAD_ARG;
+  return item_call(c, {tiny ? 3 : 1, true, size_t(tiny ? 48 : 96), proofs_out, nullptr, nullptr}, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr,
+      [&] { return prove_one_as_msm(c, pks_xy != nullptr, tiny, proofs_out); },
+      [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, thin_prove_wave(b, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream, tiny)); },
+      [&](const BatchDev &b) { AVRF_SINGLE(c->suite, thin_prove(b, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream, tiny)); });
 }
 
 int avrf_thin_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                     const uint8_t *ads, const uint32_t *ad_lens, uint8_t *proofs_out) {
-  if (n && (!sks || !proofs_out)) return AVRF_ERR_BAD_ARG;
-  int st = stage_nowait(c, 1, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr);
-  if (st || !n) return st;
-  c->staged_kind = 0;
-  HIP_TRY(c->d_out.ensure(n * 96));
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  double t0 = now_us();
-  if (n == 1 && c->tot_io < 1000 && one_as_msm()) {
-    HIP_TRY(c->h_c.ensure(64));
-    const int st1 = prove_one_as_msm(c, pks_xy != nullptr, false, proofs_out);
-    c->timing[0] = now_us() - t0;
-    return st1;
-  }
-  if (pks_xy && wave_shape(c, n, io_counts)) {
-    HIP_TRY(c->d_status.ensure(n * 4)); HIP_TRY(c->h_c.ensure(n * 4));
-    if (launch_thin_prove_wave(c->suite, batch_of(c), c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream)) {
-      HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, n * 96, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_c.p, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-      int f = read_flags(c);
-      if (f < 0) return AVRF_ERR_NO_DEVICE;
-      bool fallback = false;
-      for (size_t j = 0; j < n; j++) fallback |= c->h_c.as<int32_t>()[j] == AVRF_WAVE_FALLBACK;
-      if (!fallback) { c->timing[0] = now_us() - t0; return f ? AVRF_INVALID_DATA : AVRF_OK; }
-      HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));          // a degenerate point somewhere: the lane-per-item kernel takes the call
-    }
-  }
-  if (int e = per_item_chunks(c, pks_xy != nullptr, [&](const BatchDev &b) { launch_thin_prove(c->suite, b, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream); })) return e;
-  HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, n * 96, hipMemcpyDeviceToHost, c->stream));
-  int f = read_flags(c);
-  c->timing[0] = now_us() - t0;
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  return f ? AVRF_INVALID_DATA : AVRF_OK;
+  return thin_or_tiny_prove(c, false, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs_out);
 }
 
 int avrf_thin_verify(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                      const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int32_t *status_out) {
   if (n && (!pks_xy || !proofs || !status_out)) return AVRF_ERR_BAD_ARG;
-  int st = stage_nowait(c, 1, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs);
-  if (st || !n) return st;
-  HIP_TRY(c->d_status.ensure(n * 4));
-  double t0 = now_us();
-  // ONE item: its equation  R + c z0 pk + sum_i c z_i O_i - s z0 G - sum_i s z_i I_i == 0  (src/thin.rs:158-161 expanded, the
-  // BatchVerifier's sum with the weight w = 1) through the prepare / terms kernels and the single-launch MSM
-  // (msm.hip k_msm_tiny_bits): the doubling chain runs on the host's Horner instead of a lone wave -- 0.54 -> 0.28 ms.  Same
-  // statuses as the per-item kernels: the flags of the prepare kernel and of the validation are InvalidData, a non-zero sum is
-  // VerificationFailure.  Everything is enqueued back to back; the one wait is in batch_end.
-  if (n == 1 && one_as_msm() && c->n_terms && c->n_terms <= 2048) {
-    uint8_t zero[64] = {0};
-    c->unit_weights = true;
-    int st = batch_begin(c, 1);
-    if (st == AVRF_OK) st = batch_launch(c, 1, zero);
-    if (st == AVRF_OK) st = batch_end(c, 1);
-    c->unit_weights = false;
-    if (st == AVRF_OK || st == AVRF_VERIFICATION_FAILURE) {
-      if (*c->h_flags.as<uint32_t>()) st = AVRF_INVALID_DATA;
-      status_out[0] = st; c->timing[0] = now_us() - t0;
-      return AVRF_OK;
-    }
-    c->run_phase = 0;
-    return st;
-  }
-  if (wave_shape(c, n, io_counts) && launch_thin_verify_wave(c->suite, batch_of(c), c->d_status.as<int32_t>(), c->stream)) {
-    validate_staged(c, 1, c->d_status.as<int32_t>());
-    HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-    bool fallback = false;
-    for (size_t j = 0; j < n; j++) fallback |= status_out[j] == AVRF_WAVE_FALLBACK;
-    if (!fallback) { c->timing[0] = now_us() - t0; return AVRF_OK; }     // (else a degenerate point somewhere: the lane-per-item kernel takes the call)
-  }
-  if (int e = per_item_chunks(c, true, [&](const BatchDev &b) { launch_thin_verify(c->suite, b, c->d_status.as<int32_t>(), c->stream); })) return e;
-  validate_staged(c, 1, c->d_status.as<int32_t>());                   // Validate::Yes failures overwrite the item's status with InvalidData
-  HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  c->timing[0] = now_us() - t0;
-  return AVRF_OK;
+  return item_call(c, {1, false, 96, nullptr, nullptr, status_out}, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs,
+      [&] { return verify_one_as_msm(c, status_out); },
+      [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, thin_verify_wave(b, c->d_status.as<int32_t>(), c->stream)); },
+      [&](const BatchDev &b) { AVRF_SINGLE(c->suite, thin_verify(b, c->d_status.as<int32_t>(), c->stream)); });
 }
 
 // tiny::Prover::prove / tiny::Verifier::verify (src/tiny.rs:163-214) for batches of independent items
 int avrf_tiny_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                     const uint8_t *ads, const uint32_t *ad_lens, uint8_t *proofs_out) {
-  if (n && (!sks || !proofs_out)) return AVRF_ERR_BAD_ARG;
-  int st = stage(c, 3, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr);
-  if (st || !n) return st;
-  c->staged_kind = 0;
-  HIP_TRY(c->d_out.ensure(n * 48));
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  if (n == 1 && c->tot_io < 1000 && one_as_msm()) { HIP_TRY(c->h_c.ensure(64)); return prove_one_as_msm(c, pks_xy != nullptr, true, proofs_out); }
-  if (pks_xy && wave_shape(c, n, io_counts)) {                         // few items: 32 lanes per item (vrf_single.hip)
-    HIP_TRY(c->d_status.ensure(n * 4)); HIP_TRY(c->h_c.ensure(n * 4));
-    if (launch_thin_prove_wave(c->suite, batch_of(c), c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream, true)) {
-      HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, n * 48, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_c.p, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-      int f = read_flags(c);
-      if (f < 0) return AVRF_ERR_NO_DEVICE;
-      bool fallback = false;
-      for (size_t j = 0; j < n; j++) fallback |= c->h_c.as<int32_t>()[j] == AVRF_WAVE_FALLBACK;
-      if (!fallback) return f ? AVRF_INVALID_DATA : AVRF_OK;
-      HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-    }
-  }
-  if (int e = per_item_chunks(c, pks_xy != nullptr, [&](const BatchDev &b) { launch_thin_prove(c->suite, b, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream, true); })) return e;
-  HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, n * 48, hipMemcpyDeviceToHost, c->stream));
-  int f = read_flags(c);
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  return f ? AVRF_INVALID_DATA : AVRF_OK;
+  return thin_or_tiny_prove(c, true, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs_out);
 }
 int avrf_tiny_verify(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                      const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int32_t *status_out) {
   if (n && (!pks_xy || !proofs || !status_out)) return AVRF_ERR_BAD_ARG;
-  int st = stage(c, 3, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs);
-  if (st || !n) return st;
-  HIP_TRY(c->d_status.ensure(n * 4));
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  if (wave_shape(c, n, io_counts) && launch_tiny_verify_wave(c->suite, batch_of(c), c->d_status.as<int32_t>(), c->stream)) {
-    validate_staged(c, 3, c->d_status.as<int32_t>());
-    HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-    bool fallback = false;
-    for (size_t j = 0; j < n; j++) fallback |= status_out[j] == AVRF_WAVE_FALLBACK;
-    if (!fallback) { c->staged_kind = 0; return AVRF_OK; }
-  }
-  if (int e = per_item_chunks(c, true, [&](const BatchDev &b) { launch_tiny_verify(c->suite, b, c->d_status.as<int32_t>(), c->stream); })) return e;
-  validate_staged(c, 3, c->d_status.as<int32_t>());
-  HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  c->staged_kind = 0;
-  return AVRF_OK;
+  return item_call(c, {3, false, 48, nullptr, nullptr, status_out}, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs,
+      [] { return Route(); },                                          // (no one-item route)
+      [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, tiny_verify_wave(b, c->d_status.as<int32_t>(), c->stream)); },
+      [&](const BatchDev &b) { AVRF_SINGLE(c->suite, tiny_verify(b, c->d_status.as<int32_t>(), c->stream)); });
 }
 
 int avrf_pedersen_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                         const uint8_t *ads, const uint32_t *ad_lens, uint8_t *proofs_out, uint8_t *blindings_out) {
   if (n && (!sks || !proofs_out)) return AVRF_ERR_BAD_ARG;
-  int st = stage_nowait(c, 2, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr);
-  if (st || !n) return st;
-  c->staged_kind = 0;
-  HIP_TRY(c->d_out.ensure(n * 256)); HIP_TRY(c->d_misc.ensure(n * 32));
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  double t0 = now_us();
-  if (n == 1 && c->tot_io <= 1000 && one_as_msm()) {
-    if (!pks_xy) { if (int fs = ensure_fixed(c)) return fs; }
-    const int st1 = prove_ped_one_as_msm(c, pks_xy != nullptr, proofs_out, blindings_out);
-    c->timing[0] = now_us() - t0;
-    return st1;
-  }
-  if (pks_xy && wave_shape(c, n, io_counts)) {                         // few items: 32 lanes per item (vrf_single.hip)
-    if (int fs = ensure_fixed(c)) return fs;
-    HIP_TRY(c->d_status.ensure(n * 4)); HIP_TRY(c->h_c.ensure(n * 4));
-    if (launch_ped_prove_wave(c->suite, batch_of(c), c->d_out.as<uint8_t>(), c->d_misc.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream)) {
-      HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, n * 256, hipMemcpyDeviceToHost, c->stream));
-      if (blindings_out) HIP_TRY(hipMemcpyAsync(blindings_out, c->d_misc.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_c.p, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-      int f = read_flags(c);
-      if (f < 0) return AVRF_ERR_NO_DEVICE;
-      bool fallback = false;
-      for (size_t j = 0; j < n; j++) fallback |= c->h_c.as<int32_t>()[j] == AVRF_WAVE_FALLBACK;
-      if (!fallback) { c->timing[0] = now_us() - t0; return f ? AVRF_INVALID_DATA : AVRF_OK; }
-      HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-    }
-  }
-  if (int e = per_item_chunks(c, pks_xy != nullptr, [&](const BatchDev &b) { launch_ped_prove(c->suite, b, c->d_out.as<uint8_t>(), c->d_misc.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream); })) return e;
-  HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, n * 256, hipMemcpyDeviceToHost, c->stream));
-  if (blindings_out) HIP_TRY(hipMemcpyAsync(blindings_out, c->d_misc.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  int f = read_flags(c);
-  c->timing[0] = now_us() - t0;
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  return f ? AVRF_INVALID_DATA : AVRF_OK;
+  return item_call(c, {2, true, 256, proofs_out, blindings_out, nullptr}, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr,
+      [&] { return prove_ped_one_as_msm(c, pks_xy != nullptr, proofs_out, blindings_out); },
+      [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, ped_prove_wave(b, c->d_out.as<uint8_t>(), c->d_misc.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream)); },
+      [&](const BatchDev &b) { AVRF_SINGLE(c->suite, ped_prove(b, c->d_out.as<uint8_t>(), c->d_misc.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream)); });
 }
 
 int avrf_pedersen_verify(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts,
                          const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int32_t *status_out) {
   if (n && (!proofs || !status_out)) return AVRF_ERR_BAD_ARG;
-  int st = stage_nowait(c, 2, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs);
-  if (st || !n) return st;
-  HIP_TRY(c->d_status.ensure(n * 4));
-  double t0 = now_us();
-  // ONE item: its two equations (src/pedersen.rs:229-245) as two scalar vectors over the item's seven bases -- the terms kernel run with
-  // the weights (t, u) = (1, 0) and (0, 1) -- through the single-launch MSM with the host's two Horners side by side (see
-  // avrf_thin_verify): both sums must be the identity, exactly the reference's two checks.  0.52 -> ~0.33 ms.
-  if (n == 1 && one_as_msm() && c->n_terms && c->n_terms <= 2048) {
-    int st = batch_begin(c, 2);                                        // validation + prepare kernel (challenge, merged pair) + flags copy
-    c->run_phase = 0;
-    if (st != AVRF_OK) return st;
-    const size_t nt = c->n_terms;
-    HIP_TRY(c->L->d_scalars.ensure(2 * nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(2 * 64 + 64));
-    c->h_weights.assign(64, 0); c->h_weights[0] = 1; c->h_weights[32 + 16] = 1;                   // (t, u) = (1, 0) | (0, 1)
-    HIP_TRY(c->d_weights.ensure(64));
-    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), 64, hipMemcpyHostToDevice, c->stream));
-    BatchDev b = batch_of(c);
-    Seed64 seed; for (int i = 0; i < 8; i++) seed.w[i] = 0;
-    for (int v = 0; v < 2; v++) {
-      b.weights = c->d_weights.as<uint8_t>() + 32 * v;
-      launch_ped_terms(c->suite, b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>() + (size_t)v * nt * 8,
-                       c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)nt, c->stream);
-    }
-    HostExt r[2];
-    if (int e = guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), nt, 2, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
-    status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : (point_is_identity(c, r[0]) && point_is_identity(c, r[1])) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
-    c->timing[0] = now_us() - t0;
-    return AVRF_OK;
-  }
-  if (wave_shape(c, n, io_counts) && launch_ped_verify_wave(c->suite, batch_of(c), c->d_status.as<int32_t>(), c->stream)) {
-    validate_staged(c, 2, c->d_status.as<int32_t>());
-    HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-    bool fallback = false;
-    for (size_t j = 0; j < n; j++) fallback |= status_out[j] == AVRF_WAVE_FALLBACK;
-    if (!fallback) { c->timing[0] = now_us() - t0; return AVRF_OK; }
-  }
-  if (int e = per_item_chunks(c, true, [&](const BatchDev &b) { launch_ped_verify(c->suite, b, c->d_status.as<int32_t>(), c->stream); })) return e;
-  validate_staged(c, 2, c->d_status.as<int32_t>());
-  HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  c->timing[0] = now_us() - t0;
-  return AVRF_OK;
+  return item_call(c, {2, false, 256, nullptr, nullptr, status_out}, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs,
+      [&] { return verify_ped_one_as_msm(c, status_out); },
+      [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, ped_verify_wave(b, c->d_status.as<int32_t>(), c->stream)); },
+      [&](const BatchDev &b) { AVRF_SINGLE(c->suite, ped_verify(b, c->d_status.as<int32_t>(), c->stream)); });
 }
 
 static int smul_common(avrf_ctx *c, size_t n, const uint8_t *scalars, const uint8_t *points_xy, uint8_t *out_xy) {
-  if (!c || (n && (!scalars || !out_xy))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (!n) return AVRF_OK;
-  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0;
-  // A handful of variable-base products (Secret::output = sk * input, src/lib.rs:391-393: 80 us on a CPU core): a lane walks 253
-  // doublings in 1.9 ms however few items there are.  Up to 32 go through the single-launch MSM instead, as n scalar vectors over
-  // the n bases with the scalars on the diagonal (a zero scalar has no bit sums), the doubling chains folded side by side on the host pool: 0.15 ms for one, ~0.4 ms for 32.
-  // The bit sums are the literal product for ANY curve point, like the lane kernel's window form (no endomorphism split).
-  if (points_xy && n <= 32 && one_as_msm()) {
-    for (size_t i = 0; i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
-    HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->L->d_scalars.ensure(n * n * 32)); HIP_TRY(c->L->d_pre.ensure(n * sizeof(te_pre_raw)));
-    std::vector<uint8_t> diag(n * n * 32, 0);
-    for (size_t i = 0; i < n; i++) memcpy(&diag[(i * n + i) * 32], scalars + 32 * i, 32);
-    HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, diag.data(), diag.size(), hipMemcpyHostToDevice, c->stream));
+  return pointwise(c, n, scalars && out_xy, [&]() -> int {
+    // A handful of variable-base products (Secret::output = sk * input, src/lib.rs:391-393: 80 us on a CPU core): a lane walks 253
+    // doublings in 1.9 ms however few items there are.  Up to 32 go through the single-launch MSM instead, as n scalar vectors over
+    // the n bases with the scalars on the diagonal (a zero scalar has no bit sums), the doubling chains folded side by side on the host pool: 0.15 ms for one, ~0.4 ms for 32.
+    // The bit sums are the literal product for ANY curve point, like the lane kernel's window form (no endomorphism split).
+    if (points_xy && n <= 32 && one_as_msm()) {
+      for (size_t i = 0; i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
+      HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->L->d_scalars.ensure(n * n * 32)); HIP_TRY(c->L->d_pre.ensure(n * sizeof(te_pre_raw)));
+      std::vector<uint8_t> diag(n * n * 32, 0);
+      for (size_t i = 0; i < n; i++) memcpy(&diag[(i * n + i) * 32], scalars + 32 * i, 32);
+      HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, diag.data(), diag.size(), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+      launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
+      HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+      HostExt r[32];
+      if (int e = guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, n, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+      if (*c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
+      for (size_t i = 0; i < n; i++) finish_point(c, r[i], out_xy + 64 * i);
+      return AVRF_OK;
+    }
+    HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(c->d_out.ensure(n * 64));
+    HIP_TRY(hipMemcpyAsync(c->d_sks.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+    if (points_xy) { HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream)); }
     HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-    launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
-    HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HostExt r[32];
-    if (int e = guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, n, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
-    if (*c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
-    for (size_t i = 0; i < n; i++) finish_point(c, r[i], out_xy + 64 * i);
-    return AVRF_OK;
-  }
-  HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(c->d_out.ensure(n * 64));
-  HIP_TRY(hipMemcpyAsync(c->d_sks.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-  if (points_xy) { HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream)); }
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  if (!points_xy) { if (int fs = ensure_fixed(c)) return fs; }
-  launch_smul(c->suite, c->d_sks.as<uint8_t>(), points_xy ? c->d_misc.as<uint8_t>() : nullptr, (uint32_t)n, c->d_out.as<uint8_t>(),
-              c->d_flags.as<uint32_t>(), c->d_fixed.as<te_pre_raw>(), c->stream);
-  HIP_TRY(hipMemcpyAsync(out_xy, c->d_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
-  int f = read_flags(c);
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  return f ? AVRF_INVALID_DATA : AVRF_OK;
+    if (!points_xy) { if (int fs = ensure_fixed(c)) return fs; }
+    AVRF_SINGLE(c->suite, smul(c->d_sks.as<uint8_t>(), points_xy ? c->d_misc.as<uint8_t>() : nullptr, (uint32_t)n, c->d_out.as<uint8_t>(),
+                               c->d_flags.as<uint32_t>(), c->d_fixed.as<te_pre_raw>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out_xy, c->d_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
+    return read_flags(c);
+  });
 }
 int avrf_scalar_mul_base(avrf_ctx *c, size_t n, const uint8_t *sks, uint8_t *out_xy) { return smul_common(c, n, sks, nullptr, out_xy); }
 int avrf_scalar_mul(avrf_ctx *c, size_t n, const uint8_t *scalars, const uint8_t *points_xy, uint8_t *out_xy) {
@@ -1168,96 +1124,74 @@ int avrf_scalar_mul(avrf_ctx *c, size_t n, const uint8_t *scalars, const uint8_t
 size_t avrf_point_len(int suite) { return (suite < 0 || suite >= AVRF_N_SUITES) ? 0 : (size_t)point_len_of(suite); }
 
 int avrf_points_decompress(avrf_ctx *c, size_t n, const uint8_t *in, uint8_t *out_xy, int validate, int32_t *status_out) {
-  if (!c || (n && (!in || !out_xy || !status_out))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (!n) return AVRF_OK;
-  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0;
-  const size_t pl = (size_t)point_len_of(c->suite);
-  HIP_TRY(c->d_misc.ensure(n * pl)); HIP_TRY(c->d_out.ensure(n * 64)); HIP_TRY(c->d_status.ensure(n * 4));
-  HIP_TRY(hipMemcpyAsync(c->d_misc.p, in, n * pl, hipMemcpyHostToDevice, c->stream));
-  launch_decompress(c->suite, c->d_misc.as<uint8_t>(), (uint32_t)n, c->d_out.as<uint8_t>(), validate, c->d_status.as<int32_t>(), c->stream);
-  HIP_TRY(hipMemcpyAsync(out_xy, c->d_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  return AVRF_OK;
+  return pointwise(c, n, in && out_xy && status_out, [&]() -> int {
+    const size_t pl = (size_t)point_len_of(c->suite);
+    HIP_TRY(c->d_misc.ensure(n * pl)); HIP_TRY(c->d_out.ensure(n * 64)); HIP_TRY(c->d_status.ensure(n * 4));
+    HIP_TRY(hipMemcpyAsync(c->d_misc.p, in, n * pl, hipMemcpyHostToDevice, c->stream));
+    AVRF_SINGLE(c->suite, decompress(c->d_misc.as<uint8_t>(), (uint32_t)n, c->d_out.as<uint8_t>(), validate, c->d_status.as<int32_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out_xy, c->d_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+  });
 }
 int avrf_hash_to_curve(avrf_ctx *c, size_t n, const uint8_t *data, const uint32_t *data_lens, uint8_t *out_xy, int32_t *status_out) {
-  if (!c || (n && (!data_lens || !out_xy || !status_out))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (!n) return AVRF_OK;
-  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  std::vector<uint32_t> off(n + 1); uint64_t tot = 0;
-  for (size_t i = 0; i < n; i++) { off[i] = (uint32_t)tot; tot += data_lens[i]; if (tot > 0xffffffffULL) return AVRF_ERR_BAD_ARG; }
-  off[n] = (uint32_t)tot;
-  if (tot && !data) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0;
-  HIP_TRY(c->d_ads.ensure(tot + 16)); HIP_TRY(c->d_ad_off.ensure((n + 1) * 4)); HIP_TRY(c->d_out.ensure(n * 64)); HIP_TRY(c->d_status.ensure(n * 4));
-  if (tot) HIP_TRY(hipMemcpyAsync(c->d_ads.p, data, tot, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_ad_off.p, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  launch_hash_to_curve(c->suite, c->d_ads.as<uint8_t>(), c->d_ad_off.as<uint32_t>(), (uint32_t)n, c->d_out.as<uint8_t>(), c->d_status.as<int32_t>(), c->stream);
-  HIP_TRY(hipMemcpyAsync(out_xy, c->d_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  return AVRF_OK;
+  // the messages' offsets are checked with the arguments, before the device is selected: lengths that sum to 2^32 or more, or no
+  // data for messages that are not all empty, are AVRF_ERR_BAD_ARG (a call pointwise() refuses anyway is refused before the walk)
+  if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
+  bool ok = data_lens && out_xy && status_out && n <= 0x7fffffffULL;
+  std::vector<uint32_t> off(ok ? n + 1 : 0); uint64_t tot = 0;
+  for (size_t i = 0; ok && i < n; i++) { off[i] = (uint32_t)tot; tot += data_lens[i]; ok = tot <= 0xffffffffULL; }
+  if (ok) { off[n] = (uint32_t)tot; ok = !tot || data; }
+  return pointwise(c, n, ok, [&]() -> int {
+    HIP_TRY(c->d_ads.ensure(tot + 16)); HIP_TRY(c->d_ad_off.ensure((n + 1) * 4)); HIP_TRY(c->d_out.ensure(n * 64)); HIP_TRY(c->d_status.ensure(n * 4));
+    if (tot) HIP_TRY(hipMemcpyAsync(c->d_ads.p, data, tot, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_ad_off.p, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    AVRF_SINGLE(c->suite, hash_to_curve(c->d_ads.as<uint8_t>(), c->d_ad_off.as<uint32_t>(), (uint32_t)n, c->d_out.as<uint8_t>(), c->d_status.as<int32_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out_xy, c->d_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+  });
 }
 // Output::hash::<N> of n output points (x || y in, N = hash_len <= 64 bytes each out)
 int avrf_output_hash(avrf_ctx *c, size_t n, const uint8_t *points_xy, size_t hash_len, uint8_t *out) {
-  if (!c || hash_len < 1 || hash_len > 64 || (n && (!points_xy || !out))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (!n) return AVRF_OK;
-  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0;
-  HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->d_out.ensure(n * 64));
-  HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream));
-  launch_output_hash(c->suite, c->d_misc.as<uint8_t>(), (uint32_t)n, (uint32_t)hash_len, c->d_out.as<uint8_t>(), c->stream);
-  HIP_TRY(hipMemcpyAsync(out, c->d_out.p, n * hash_len, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  return AVRF_OK;
+  if (hash_len < 1 || hash_len > 64) return AVRF_ERR_BAD_ARG;
+  return pointwise(c, n, points_xy && out, [&]() -> int {
+    HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->d_out.ensure(n * 64));
+    HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream));
+    AVRF_SINGLE(c->suite, output_hash(c->d_misc.as<uint8_t>(), (uint32_t)n, (uint32_t)hash_len, c->d_out.as<uint8_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_out.p, n * hash_len, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+  });
 }
 // Secret::from_seed for n 32-byte seeds: the secret scalars (LE32, canonical) and, when pks_xy_out is given, the public keys
 int avrf_secret_from_seed(avrf_ctx *c, size_t n, const uint8_t *seeds, uint8_t *sks_out, uint8_t *pks_xy_out) {
-  if (!c || (n && (!seeds || !sks_out))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (!n) return AVRF_OK;
-  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0;
-  HIP_TRY(c->d_misc.ensure(n * 32)); HIP_TRY(c->d_sks.ensure(n * 32));
-  HIP_TRY(hipMemcpyAsync(c->d_misc.p, seeds, n * 32, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  launch_secret_from_seed(c->suite, c->d_misc.as<uint8_t>(), (uint32_t)n, c->d_sks.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream);
-  HIP_TRY(hipMemcpyAsync(sks_out, c->d_sks.p, n * 32, hipMemcpyDeviceToHost, c->stream));
-  // the reference zeroizes the seed and the intermediate scalar (src/lib.rs:367-368): the seeds are scrubbed from the scratch buffer
-  // behind the kernel, the scalars behind the copy back (d_misc / d_sks are general scratch that later, non-secret calls reuse and
-  // copy from).  sks_out is the caller's to scrub, as `Secret` is the caller's in the reference.
-  HIP_TRY(hipMemsetAsync(c->d_misc.p, 0, n * 32, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_sks.p, 0, n * 32, c->stream));
-  int f = read_flags(c);
-  if (f < 0) return AVRF_ERR_NO_DEVICE;
-  if (f) return AVRF_INVALID_DATA;
-  if (!pks_xy_out) return AVRF_OK;
-  const int st = smul_common(c, n, sks_out, nullptr, pks_xy_out);          // (uploads the scalars into d_sks again for the base multiplication)
-  if (hipMemsetAsync(c->d_sks.p, 0, n * 32, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return st ? st : (int)AVRF_ERR_NO_DEVICE; }
-  return st;
+  return pointwise(c, n, seeds && sks_out, [&]() -> int {
+    HIP_TRY(c->d_misc.ensure(n * 32)); HIP_TRY(c->d_sks.ensure(n * 32));
+    HIP_TRY(hipMemcpyAsync(c->d_misc.p, seeds, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+    AVRF_SINGLE(c->suite, secret_from_seed(c->d_misc.as<uint8_t>(), (uint32_t)n, c->d_sks.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(sks_out, c->d_sks.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+    // the reference zeroizes the seed and the intermediate scalar (src/lib.rs:367-368): the seeds are scrubbed from the scratch buffer
+    // behind the kernel, the scalars behind the copy back (d_misc / d_sks are general scratch that later, non-secret calls reuse and
+    // copy from).  sks_out is the caller's to scrub, as `Secret` is the caller's in the reference.
+    HIP_TRY(hipMemsetAsync(c->d_misc.p, 0, n * 32, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_sks.p, 0, n * 32, c->stream));
+    if (int st = read_flags(c)) return st;
+    if (!pks_xy_out) return AVRF_OK;
+    const int st = smul_common(c, n, sks_out, nullptr, pks_xy_out);        // (uploads the scalars into d_sks again for the base multiplication)
+    if (hipMemsetAsync(c->d_sks.p, 0, n * 32, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return st ? st : (int)AVRF_ERR_NO_DEVICE; }
+    return st;
+  });
 }
 int avrf_points_compress(avrf_ctx *c, size_t n, const uint8_t *in_xy, uint8_t *out) {
-  if (!c || (n && (!in_xy || !out))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (!n) return AVRF_OK;
-  if (n > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0;
-  HIP_TRY(c->d_misc.ensure(n * 64)); const size_t pl = (size_t)point_len_of(c->suite);
-  HIP_TRY(c->d_out.ensure(n * pl));
-  HIP_TRY(hipMemcpyAsync(c->d_misc.p, in_xy, n * 64, hipMemcpyHostToDevice, c->stream));
-  launch_compress(c->suite, c->d_misc.as<uint8_t>(), (uint32_t)n, c->d_out.as<uint8_t>(), c->stream);
-  HIP_TRY(hipMemcpyAsync(out, c->d_out.p, n * pl, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  return AVRF_OK;
+  return pointwise(c, n, in_xy && out, [&]() -> int {
+    const size_t pl = (size_t)point_len_of(c->suite);
+    HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->d_out.ensure(n * pl));
+    HIP_TRY(hipMemcpyAsync(c->d_misc.p, in_xy, n * 64, hipMemcpyHostToDevice, c->stream));
+    AVRF_SINGLE(c->suite, compress(c->d_misc.as<uint8_t>(), (uint32_t)n, c->d_out.as<uint8_t>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_out.p, n * pl, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+  });
 }
 
 }  // extern "C"

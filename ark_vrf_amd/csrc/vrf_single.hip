@@ -17,10 +17,12 @@
 #include "fpu_sqrt.h"
 #include "suite_dispatch.h"
 
-// Built once per suite (-DAVRF_TU_SUITE=<id>: the kernels of that suite and the explicit instantiation of SingleOps<S>) and
-// once without it (the run-time dispatch below); csrc/Makefile.  One translation unit for all suites took eight minutes.
+// Built once per suite (-DAVRF_TU_SUITE=<id>: the kernels of that suite and the explicit instantiation of SingleOps<S>, which
+// capi.hip reaches through AVRF_SINGLE); csrc/Makefile.  One translation unit for all suites took eight minutes.
+#ifndef AVRF_TU_SUITE
+#error "vrf_single.hip is built once per suite: -DAVRF_TU_SUITE=<id> (csrc/Makefile)"
+#endif
 namespace avrf {
-#ifdef AVRF_TU_SUITE
 // waves per SIMD the register allocator must leave room for in the per-item protocol kernels (1: the whole register file)
 #ifndef AVRF_ITEM_WAVES
 #define AVRF_ITEM_WAVES 1
@@ -1148,9 +1150,11 @@ template <class S> void SingleOps<S>::fixed_table(struct te_pre_raw *d_tab, hipS
 }
 template <class S> void SingleOps<S>::smul(const uint8_t *d_scalars, const uint8_t *d_points_xy, uint32_t n, uint8_t *d_out, uint32_t *d_flags,
                                            const struct te_pre_raw *d_fixed, hipStream_t st) {
+  if (!n) return;
   hipLaunchKernelGGL(k_smul<S>, dim3((n + 127) / 128), dim3(128), 0, st, d_scalars, d_points_xy, n, d_out, d_flags, (const te_pre *)d_fixed);
 }
 template <class S> void SingleOps<S>::thin_prove(const BatchDev &b, uint8_t *d_proofs_out, uint32_t *d_flags, hipStream_t st, bool tiny) {
+  if (!b.n) return;
   const dim3 g((b.n - b.first + 127) / 128), bl(128);
   if (tiny) hipLaunchKernelGGL((k_thin_prove<S, true>), g, bl, 0, st, b, d_proofs_out, d_flags);
   else hipLaunchKernelGGL((k_thin_prove<S, false>), g, bl, 0, st, b, d_proofs_out, d_flags);
@@ -1175,16 +1179,20 @@ template <class S> void SingleOps<S>::ped_prove_end(const BatchDev &b, const uin
   hipLaunchKernelGGL(k_ped_prove_end<S>, dim3(1), dim3(64), 0, st, b, d_state, d_pts, d_proofs_out, d_blind, d_flags);
 }
 template <class S> void SingleOps<S>::tiny_verify(const BatchDev &b, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return;
   hipLaunchKernelGGL(k_tiny_verify<S>, dim3((b.n - b.first + 127) / 128), dim3(128), 0, st, b, d_status);
 }
 template <class S> void SingleOps<S>::thin_verify(const BatchDev &b, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return;
   hipLaunchKernelGGL(k_thin_verify<S>, dim3((b.n - b.first + 127) / 128), dim3(128), 0, st, b, d_status);
 }
 template <class S> bool SingleOps<S>::thin_verify_wave(const BatchDev &b, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return false;
   if constexpr (S::SW_NATIVE) return false;
   else { hipLaunchKernelGGL(k_thin_verify_wave<S>, dim3((b.n - b.first + 1) / 2), dim3(64), 0, st, b, d_status); return true; }
 }
 template <class S> bool SingleOps<S>::thin_prove_wave(const BatchDev &b, uint8_t *d_proofs_out, uint32_t *d_flags, int32_t *d_status, hipStream_t st, bool tiny) {
+  if (!b.n) return false;
   if constexpr (S::SW_NATIVE) return false;
   else {
     if (tiny) hipLaunchKernelGGL((k_thin_prove_wave<S, true>), dim3((b.n - b.first + 1) / 2), dim3(64), 0, st, b, d_proofs_out, d_flags, d_status);
@@ -1193,27 +1201,34 @@ template <class S> bool SingleOps<S>::thin_prove_wave(const BatchDev &b, uint8_t
   }
 }
 template <class S> bool SingleOps<S>::tiny_verify_wave(const BatchDev &b, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return false;
   if constexpr (S::SW_NATIVE) return false;
   else { hipLaunchKernelGGL(k_tiny_verify_wave<S>, dim3((b.n - b.first + 1) / 2), dim3(64), 0, st, b, d_status); return true; }
 }
 template <class S> bool SingleOps<S>::ped_verify_wave(const BatchDev &b, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return false;
   if constexpr (S::SW_NATIVE) return false;
   else { hipLaunchKernelGGL(k_ped_verify_wave<S>, dim3(b.n - b.first), dim3(64), 0, st, b, d_status); return true; }
 }
 template <class S> bool SingleOps<S>::ped_prove_wave(const BatchDev &b, uint8_t *d_proofs_out, uint8_t *d_blind, uint32_t *d_flags, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return false;
   if constexpr (S::SW_NATIVE) return false;
   else { hipLaunchKernelGGL(k_ped_prove_wave<S>, dim3((b.n - b.first + 1) / 2), dim3(64), 0, st, b, d_proofs_out, d_blind, d_flags, d_status); return true; }
 }
 template <class S> void SingleOps<S>::ped_prove(const BatchDev &b, uint8_t *d_proofs_out, uint8_t *d_blind, uint32_t *d_flags, hipStream_t st) {
+  if (!b.n) return;
   hipLaunchKernelGGL(k_ped_prove<S>, dim3((b.n - b.first + 127) / 128), dim3(128), 0, st, b, d_proofs_out, d_blind, d_flags);
 }
 template <class S> void SingleOps<S>::ped_verify(const BatchDev &b, int32_t *d_status, hipStream_t st) {
+  if (!b.n) return;
   hipLaunchKernelGGL(k_ped_verify<S>, dim3((b.n - b.first + 127) / 128), dim3(128), 0, st, b, d_status);
 }
 template <class S> void SingleOps<S>::hash_to_curve(const uint8_t *d_data, const uint32_t *d_off, uint32_t n, uint8_t *d_out, int32_t *d_status, hipStream_t st) {
+  if (!n) return;
   hipLaunchKernelGGL(k_hash_to_curve<S>, dim3((n + 127) / 128), dim3(128), 0, st, d_data, d_off, n, d_out, d_status);
 }
 template <class S> void SingleOps<S>::decompress(const uint8_t *d_in, uint32_t n, uint8_t *d_out, int validate, int32_t *d_status, hipStream_t st) {
+  if (!n) return;
   // few points: four lanes per point for the subgroup test r P (where the test is two Jacobi symbols the lane-per-point kernel is the fast one at every n)
   if constexpr (!S::SW_NATIVE && !S::HAS_2DESCENT) if (validate && n <= 4096) {
     hipLaunchKernelGGL(k_decompress_wave<S>, dim3(((S::HAS_GLV ? 8 : 4) * n + 63) / 64), dim3(64), 0, st, d_in, n, d_out, d_status);   // (two quads per point with the endomorphism)
@@ -1223,125 +1238,26 @@ template <class S> void SingleOps<S>::decompress(const uint8_t *d_in, uint32_t n
 }
 template <class S> void SingleOps<S>::validate_xy(const uint8_t *d_base, uint32_t stride, uint32_t ppr, uint32_t nrec, int level, uint32_t *d_flags,
                                                   int32_t *d_rec_status, hipStream_t st, const uint32_t *d_item_off, uint32_t n_items) {
+  if (!nrec || !ppr || level <= 0) return;
   const uint32_t tot = nrec * ppr;
   hipLaunchKernelGGL(k_validate_xy<S>, dim3((tot + 127) / 128), dim3(128), 0, st, d_base, stride, ppr, nrec, level, d_flags, d_rec_status, d_item_off, n_items);
 }
 template <class S> void SingleOps<S>::decompress_strided(const uint8_t *d_in, uint32_t in_stride, uint32_t n, uint8_t *d_out, uint32_t out_stride, int validate, uint32_t *d_flags, hipStream_t st) {
+  if (!n) return;
   hipLaunchKernelGGL(k_decompress_strided<S>, dim3((n + 127) / 128), dim3(128), 0, st, d_in, in_stride, n, d_out, out_stride, validate, d_flags);
 }
 template <class S> void SingleOps<S>::compress(const uint8_t *d_in, uint32_t n, uint8_t *d_out, hipStream_t st) {
+  if (!n) return;
   hipLaunchKernelGGL(k_compress<S>, dim3((n + 255) / 256), dim3(256), 0, st, d_in, n, d_out);
 }
 template <class S> void SingleOps<S>::output_hash(const uint8_t *d_in, uint32_t n, uint32_t len, uint8_t *d_out, hipStream_t st) {
+  if (!n) return;
   hipLaunchKernelGGL(k_output_hash<S>, dim3((n + 127) / 128), dim3(128), 0, st, d_in, n, len, d_out);
 }
 template <class S> void SingleOps<S>::secret_from_seed(const uint8_t *d_seeds, uint32_t n, uint8_t *d_sk, uint32_t *d_flags, hipStream_t st) {
+  if (!n) return;
   hipLaunchKernelGGL(k_secret_from_seed<S>, dim3((n + 127) / 128), dim3(128), 0, st, d_seeds, n, d_sk, d_flags);
 }
 template struct SingleOps<suite_by_id<AVRF_TU_SUITE>::type>;
 
 }  // namespace avrf
-
-#else   // ---------------------------------------------------------------- run-time dispatch unit
-
-#define AVRF_SINGLE(suite, CALL) with_suite((suite), [&](auto tag_) { using S_ = typename decltype(tag_)::type; SingleOps<S_>::CALL; })
-
-void launch_fixed_table(int suite, struct te_pre_raw *d_tab, hipStream_t st) { AVRF_SINGLE(suite, fixed_table(d_tab, st)); }
-void launch_smul(int suite, const uint8_t *d_scalars, const uint8_t *d_points_xy, uint32_t n, uint8_t *d_out, uint32_t *d_flags,
-                 const struct te_pre_raw *d_fixed, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, smul(d_scalars, d_points_xy, n, d_out, d_flags, d_fixed, st));
-}
-size_t thin_prove_state_bytes(int suite) {
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::prove_state_bytes(); });
-}
-void launch_thin_prove_begin(int suite, const BatchDev &b, uint32_t *d_scalars, struct te_pre_raw *d_pre, uint8_t *d_state, hipStream_t st, bool tiny) {
-  AVRF_SINGLE(suite, thin_prove_begin(b, d_scalars, d_pre, d_state, st, tiny));
-}
-void launch_thin_prove_end(int suite, const BatchDev &b, const uint8_t *d_state, const uint8_t *d_rxy, uint8_t *d_proofs_out, uint32_t *d_flags, hipStream_t st, bool tiny) {
-  AVRF_SINGLE(suite, thin_prove_end(b, d_state, d_rxy, d_proofs_out, d_flags, st, tiny));
-}
-size_t ped_prove_state_bytes(int suite) {
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::ped_state_bytes(); });
-}
-void launch_ped_prove_begin(int suite, const BatchDev &b, uint32_t *d_scalars, struct te_pre_raw *d_pre, uint8_t *d_state, uint32_t *d_wts, hipStream_t st) {
-  AVRF_SINGLE(suite, ped_prove_begin(b, d_scalars, d_pre, d_state, d_wts, st));
-}
-void launch_ped_prove_mid(int suite, const BatchDev &b, uint32_t *d_scalars, struct te_pre_raw *d_pre, uint8_t *d_state, const uint32_t *d_wts, const uint8_t *d_yb, hipStream_t st) {
-  AVRF_SINGLE(suite, ped_prove_mid(b, d_scalars, d_pre, d_state, d_wts, d_yb, st));
-}
-void launch_ped_prove_end(int suite, const BatchDev &b, const uint8_t *d_state, const uint8_t *d_pts, uint8_t *d_proofs_out, uint8_t *d_blind, uint32_t *d_flags, hipStream_t st) {
-  AVRF_SINGLE(suite, ped_prove_end(b, d_state, d_pts, d_proofs_out, d_blind, d_flags, st));
-}
-void launch_thin_prove(int suite, const BatchDev &b, uint8_t *d_proofs_out, uint32_t *d_flags, hipStream_t st, bool tiny) {
-  if (!b.n) return;
-  AVRF_SINGLE(suite, thin_prove(b, d_proofs_out, d_flags, st, tiny));
-}
-void launch_tiny_verify(int suite, const BatchDev &b, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return;
-  AVRF_SINGLE(suite, tiny_verify(b, d_status, st));
-}
-void launch_thin_verify(int suite, const BatchDev &b, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return;
-  AVRF_SINGLE(suite, thin_verify(b, d_status, st));
-}
-bool launch_thin_verify_wave(int suite, const BatchDev &b, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return false;
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::thin_verify_wave(b, d_status, st); });
-}
-bool launch_thin_prove_wave(int suite, const BatchDev &b, uint8_t *d_proofs_out, uint32_t *d_flags, int32_t *d_status, hipStream_t st, bool tiny) {
-  if (!b.n) return false;
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::thin_prove_wave(b, d_proofs_out, d_flags, d_status, st, tiny); });
-}
-bool launch_tiny_verify_wave(int suite, const BatchDev &b, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return false;
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::tiny_verify_wave(b, d_status, st); });
-}
-bool launch_ped_verify_wave(int suite, const BatchDev &b, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return false;
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::ped_verify_wave(b, d_status, st); });
-}
-bool launch_ped_prove_wave(int suite, const BatchDev &b, uint8_t *d_proofs_out, uint8_t *d_blind, uint32_t *d_flags, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return false;
-  return with_suite(suite, [&](auto tag_) { using S_ = typename decltype(tag_)::type; return SingleOps<S_>::ped_prove_wave(b, d_proofs_out, d_blind, d_flags, d_status, st); });
-}
-void launch_ped_prove(int suite, const BatchDev &b, uint8_t *d_proofs_out, uint8_t *d_blind, uint32_t *d_flags, hipStream_t st) {
-  if (!b.n) return;
-  AVRF_SINGLE(suite, ped_prove(b, d_proofs_out, d_blind, d_flags, st));
-}
-void launch_ped_verify(int suite, const BatchDev &b, int32_t *d_status, hipStream_t st) {
-  if (!b.n) return;
-  AVRF_SINGLE(suite, ped_verify(b, d_status, st));
-}
-void launch_hash_to_curve(int suite, const uint8_t *d_data, const uint32_t *d_off, uint32_t n, uint8_t *d_out, int32_t *d_status, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, hash_to_curve(d_data, d_off, n, d_out, d_status, st));
-}
-void launch_decompress(int suite, const uint8_t *d_in, uint32_t n, uint8_t *d_out, int validate, int32_t *d_status, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, decompress(d_in, n, d_out, validate, d_status, st));
-}
-void launch_validate_xy(int suite, const uint8_t *d_base, uint32_t stride, uint32_t ppr, uint32_t nrec, int level, uint32_t *d_flags,
-                        int32_t *d_rec_status, hipStream_t st, const uint32_t *d_item_off, uint32_t n_items) {
-  if (!nrec || !ppr || level <= 0) return;
-  AVRF_SINGLE(suite, validate_xy(d_base, stride, ppr, nrec, level, d_flags, d_rec_status, st, d_item_off, n_items));
-}
-void launch_decompress_strided(int suite, const uint8_t *d_in, uint32_t in_stride, uint32_t n, uint8_t *d_out, uint32_t out_stride, int validate, uint32_t *d_flags, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, decompress_strided(d_in, in_stride, n, d_out, out_stride, validate, d_flags, st));
-}
-void launch_compress(int suite, const uint8_t *d_in, uint32_t n, uint8_t *d_out, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, compress(d_in, n, d_out, st));
-}
-void launch_output_hash(int suite, const uint8_t *d_in, uint32_t n, uint32_t len, uint8_t *d_out, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, output_hash(d_in, n, len, d_out, st));
-}
-void launch_secret_from_seed(int suite, const uint8_t *d_seeds, uint32_t n, uint8_t *d_sk, uint32_t *d_flags, hipStream_t st) {
-  if (!n) return;
-  AVRF_SINGLE(suite, secret_from_seed(d_seeds, n, d_sk, d_flags, st));
-}
-
-}  // namespace avrf
-#endif
