@@ -15,6 +15,31 @@ struct te_ext_raw { uint32_t w[32]; };   // x | y | t | z
 // thrown by the device engines on a failed HIP call; every extern "C" entry point catches it and returns AVRF_ERR_NO_DEVICE
 struct HipFailure { hipError_t err; const char *file; int line; };
 
+// One owned device allocation of exactly the bytes asked for: freed by its destructor on every path out, a throw included (hipFree
+// waits for the device itself, so work in flight on a stream is over before the memory goes).  Movable, not copyable: a struct that
+// holds one cannot be copied by accident.  (capi_internal.h DevBuf is the other kind: staging buffers that round their size up so that
+// batches of slowly growing size do not reallocate, released by hand with their context.)
+struct DevMem {
+  void *p = nullptr; size_t cap = 0;
+  DevMem() = default;
+  explicit DevMem(size_t bytes) { ensure(bytes); }
+  DevMem(const DevMem &) = delete;
+  DevMem &operator=(const DevMem &) = delete;
+  DevMem(DevMem &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevMem &operator=(DevMem &&o) noexcept { if (this != &o) { (void)release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  ~DevMem() { (void)release(); }
+  // grow-only: at least `bytes` afterwards, the contents are NOT kept across a growth.  Throws HipFailure (the buffer is then empty).
+  void ensure(size_t bytes) {
+    if (bytes <= cap) return;
+    if (hipError_t e = release()) throw HipFailure{e, __FILE__, __LINE__};
+    if (hipError_t e = hipMalloc(&p, bytes)) { p = nullptr; throw HipFailure{e, __FILE__, __LINE__}; }
+    cap = bytes;
+  }
+  hipError_t release() { hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; cap = 0; return e; }
+  template <class T = uint32_t> T *as() const { return (T *)p; }
+  explicit operator bool() const { return p != nullptr; }
+};
+
 struct MsmPlan {
   int c;         // window bits
   int nwin;      // number of windows: nwin * c >= scalar bits + 1

@@ -1162,20 +1162,6 @@ k_g1_table(const uint32_t *__restrict__ bases, uint32_t n, int c, int nwin, uint
   }
 }
 
-// transient device scratch of a table build, freed on every path out (the stream is waited for before a normal free; on a throw the
-// hipFree of the destructor waits for the device itself)
-namespace {
-struct ScratchBuf {
-  void *p = nullptr;
-  ScratchBuf() = default;
-  ScratchBuf(const ScratchBuf &) = delete;
-  ScratchBuf &operator=(const ScratchBuf &) = delete;
-  ~ScratchBuf() { if (p) (void)hipFree(p); }
-  uint32_t *u32() const { return (uint32_t *)p; }
-  hipError_t release() { hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; return e; }
-};
-}  // namespace
-
 void build_g1_table(int curve, const uint32_t *d_bases, size_t n, int c, int nwin, uint32_t *d_table, hipStream_t stream) {
   if (!n) return;
   const size_t fqn = curve == 0 ? G1Bls12381::Fq::N : G1Bn254::Fq::N;
@@ -1184,12 +1170,11 @@ void build_g1_table(int curve, const uint32_t *d_bases, size_t n, int c, int nwi
   // workspaces that was a race: after two setups on two streams the first batched commitment of avrf_ring_srs_generate returned the
   // point at infinity for its first vector, every time, and not with HIP_LAUNCH_BLOCKING=1 or a device synchronisation in between
   // (tests/test_gpu_ring.py::test_srs_generate caught it once an unrelated null-stream hipMemset, which had been hiding it, went away).)
-  // (held in ScratchBuf: a throw between the allocation and the free -- a launch or the wait failing -- does not leak it)
-  ScratchBuf tmp;
-  HIP_CHECK(hipMalloc(&tmp.p, (size_t)nwin * n * 3 * fqn * 4));
+  // (owned: a throw between the allocation and the free -- a launch or the wait failing -- does not leak it)
+  DevMem tmp((size_t)nwin * n * 3 * fqn * 4);
   dim3 g((unsigned)((n + 63) / 64)), b(64);
-  if (curve == 0) hipLaunchKernelGGL(k_g1_table<G1Bls12381>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp.u32());
-  else hipLaunchKernelGGL(k_g1_table<G1Bn254>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp.u32());
+  if (curve == 0) hipLaunchKernelGGL(k_g1_table<G1Bls12381>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp.as());
+  else hipLaunchKernelGGL(k_g1_table<G1Bn254>, g, b, 0, stream, d_bases, (uint32_t)n, c, nwin, d_table, tmp.as());
   HIP_CHECK(hipStreamSynchronize(stream));
   HIP_CHECK(tmp.release());
 }
@@ -1454,14 +1439,13 @@ template <class C> static void build_direct_impl(const uint32_t *d_bases, G1Dire
   HIP_CHECK(hipMalloc(&t->d, t->bytes));
   // transient scratch (include/avrf.h, resource contract): the window rows of the bases (2 Fq per lane), then K multiples' ZZ / ZZZ /
   // running products per lane (3 Fq each) -- 386 Fq per (row, base) at the peak; build_g1_table's own scratch is gone by then
-  ScratchBuf rowbase, tmp;
-  HIP_CHECK(hipMalloc(&rowbase.p, (size_t)rows * n * 2 * N * 4));
-  build_g1_table(t->curve, d_bases, n, t->c, (int)rows, rowbase.u32(), stream);
+  DevMem rowbase((size_t)rows * n * 2 * N * 4);
+  build_g1_table(t->curve, d_bases, n, t->c, (int)rows, rowbase.as(), stream);
   const uint32_t lanes = (uint32_t)(rows * n), K = 128;
-  HIP_CHECK(hipMalloc(&tmp.p, (size_t)K * lanes * 3 * N * 4));
+  DevMem tmp((size_t)K * lanes * 3 * N * 4);
   uint32_t mmax = 0; for (uint32_t w = 0; w < rows; w++) mmax = t->mult[w] > mmax ? t->mult[w] : mmax;
   for (uint32_t m0 = 0; m0 < mmax; m0 += K)
-    hipLaunchKernelGGL(k_g1_multiples<C>, dim3((lanes + 63) / 64), dim3(64), 0, stream, (const uint32_t *)rowbase.u32(), (uint32_t)n, rows, *t, m0, K, t->d, tmp.u32(), lanes);
+    hipLaunchKernelGGL(k_g1_multiples<C>, dim3((lanes + 63) / 64), dim3(64), 0, stream, (const uint32_t *)rowbase.as(), (uint32_t)n, rows, *t, m0, K, t->d, tmp.as(), lanes);
   HIP_CHECK(hipStreamSynchronize(stream));
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(tmp.release()); HIP_CHECK(rowbase.release());

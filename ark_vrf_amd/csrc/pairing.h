@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "msm.h"
 
 namespace avrf {
 
@@ -21,8 +22,8 @@ enum : int {
 struct PairingTables {
   int curve = 0;                 // 0 BLS12-381, 1 BN254
   uint32_t steps = 0, nq = 0, words = 0;
-  uint32_t *d_cst = nullptr;     // PC_COUNT x N words
-  uint32_t *d_tab = nullptr;     // nq x steps x 36 x N words: {T0[12], TX[12], TY[12]} per step
+  DevMem d_cst;                  // PC_COUNT x N words
+  DevMem d_tab;                  // nq x steps x 36 x N words: {T0[12], TX[12], TY[12]} per step
   // g2_raw: nq `powers_in_g2` entries exactly as in an arkworks URS file (src/ring.rs:380-393).  Throws HipFailure.
   void build(int curve, const uint8_t *g2_raw, size_t nq, hipStream_t stream);
   void release();

@@ -413,18 +413,16 @@ template <class C> static void build_impl(PairingTables &pt, const uint8_t *g2_r
     memcpy(&qw[(i * 4 + 2) * N], q.y.a.l, 4 * N); memcpy(&qw[(i * 4 + 3) * N], q.y.b.l, 4 * N);
   }
   pt.steps = (uint32_t)ate_steps<C>(); pt.nq = (uint32_t)nq; pt.words = N;
-  uint32_t *d_q = nullptr, *d_flag = nullptr;
-  HIP_CHECK(hipMalloc(&pt.d_cst, csw.size() * 4)); HIP_CHECK(hipMalloc(&pt.d_tab, (size_t)nq * pt.steps * 36 * N * 4));
-  HIP_CHECK(hipMalloc(&d_q, qw.size() * 4)); HIP_CHECK(hipMalloc(&d_flag, 4));
-  HIP_CHECK(hipMemcpyAsync(pt.d_cst, csw.data(), csw.size() * 4, hipMemcpyHostToDevice, stream));
-  HIP_CHECK(hipMemcpyAsync(d_q, qw.data(), qw.size() * 4, hipMemcpyHostToDevice, stream));
-  HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, stream));
-  hipLaunchKernelGGL(k_g2_lines<C>, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, stream, (const uint32_t *)d_q, (uint32_t)nq, pt.steps,
-                     (const uint32_t *)pt.d_cst, pt.d_tab, d_flag);
+  pt.d_cst.ensure(csw.size() * 4); pt.d_tab.ensure((size_t)nq * pt.steps * 36 * N * 4);
+  DevMem d_q(qw.size() * 4), d_flag(4);
+  HIP_CHECK(hipMemcpyAsync(pt.d_cst.p, csw.data(), csw.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(d_q.p, qw.data(), qw.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, stream));
+  hipLaunchKernelGGL(k_g2_lines<C>, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, stream, (const uint32_t *)d_q.as(), (uint32_t)nq, pt.steps,
+                     (const uint32_t *)pt.d_cst.as(), pt.d_tab.as(), d_flag.as());
   uint32_t flag = 0;
-  HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream)); HIP_CHECK(hipGetLastError());
-  (void)hipFree(d_q); (void)hipFree(d_flag);
   if (flag) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};
 }
 
@@ -433,18 +431,14 @@ void PairingTables::build(int curve, const uint8_t *g2_raw, size_t nq, hipStream
   if (curve == 0) build_impl<G1Bls12381>(*this, g2_raw, nq, stream); else build_impl<G1Bn254>(*this, g2_raw, nq, stream);
   this->curve = curve;
 }
-void PairingTables::release() {
-  if (d_cst) (void)hipFree(d_cst);
-  if (d_tab) (void)hipFree(d_tab);
-  d_cst = d_tab = nullptr; steps = nq = 0;
-}
+void PairingTables::release() { (void)d_cst.release(); (void)d_tab.release(); steps = nq = 0; }
 
 void launch_pairing_check(const PairingTables &pt, const uint32_t *d_pts, size_t n, int32_t *d_ok, hipStream_t stream) {
   if (!n) return;
   const dim3 grid((unsigned)((n * 16 + 63) / 64)), block(64);
-  if (pt.curve == 0) hipLaunchKernelGGL(k_pairing_check<G1Bls12381>, grid, block, 0, stream, d_pts, (const uint32_t *)pt.d_tab, (const uint32_t *)pt.d_cst,
+  if (pt.curve == 0) hipLaunchKernelGGL(k_pairing_check<G1Bls12381>, grid, block, 0, stream, d_pts, (const uint32_t *)pt.d_tab.as(), (const uint32_t *)pt.d_cst.as(),
                                         (uint32_t)n, pt.nq, pt.steps, d_ok);
-  else hipLaunchKernelGGL(k_pairing_check<G1Bn254>, grid, block, 0, stream, d_pts, (const uint32_t *)pt.d_tab, (const uint32_t *)pt.d_cst, (uint32_t)n,
+  else hipLaunchKernelGGL(k_pairing_check<G1Bn254>, grid, block, 0, stream, d_pts, (const uint32_t *)pt.d_tab.as(), (const uint32_t *)pt.d_cst.as(), (uint32_t)n,
                           pt.nq, pt.steps, d_ok);
 }
 

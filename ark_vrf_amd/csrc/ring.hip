@@ -23,6 +23,7 @@
 #include "host_sha512.h"
 #include "host_sha256.h"
 #include "host_pool.h"
+#include "capi_internal.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -33,11 +34,12 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace avrf {
 
-// a failed HIP call unwinds to the extern "C" entry point (guarded() below), which returns AVRF_ERR_NO_DEVICE
+// a failed HIP call unwinds to the extern "C" entry point (guarded(), capi_internal.h), which returns AVRF_ERR_NO_DEVICE
 #define HIP_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw avrf::HipFailure{e_, __FILE__, __LINE__}; } while (0)
 
 // ------------------------------------------------------------------------------------------------
@@ -500,6 +502,17 @@ template <class F> static H256 fr_pow(H256 a, uint64_t e) {
 template <class F> static H256 fr_small(uint64_t v) { return HostField<F>::to_mont(H256{{v, 0, 0, 0}}); }
 
 struct G1Aff { uint8_t xy[96]; bool inf; };           // canonical LE x || y (FQB bytes each)
+// a result of the MSM engine or of HostG1::to_affine_bytes (x || y, fqb bytes each): the point at infinity iff all zero
+static G1Aff g1_from_xy(const uint8_t *xy, int fqb) {
+  G1Aff r; memset(&r, 0, sizeof r); memcpy(r.xy, xy, 2 * fqb);
+  r.inf = true; for (int i = 0; i < 2 * fqb; i++) if (r.xy[i]) r.inf = false;
+  return r;
+}
+// PIOP domain size of a ring (src/ring.rs:810-821): the keys, 4 more rows and the bits of the blinding, up to a power of two
+static size_t ring_domain_size(size_t ring_size, size_t scalar_bits) {
+  size_t need = ring_size + 4 + scalar_bits, N = 1; while (N < need) N <<= 1;
+  return N;
+}
 
 // ark-serialize G1 encodings: BLS12-381 zcash big-endian; BN254 arkworks little-endian
 template <class G> static void g1_encode(const G1Aff &p, bool compressed, std::vector<uint8_t> &out) {
@@ -540,41 +553,62 @@ struct DirectEntry {
 static std::mutex g_direct_mu;
 static std::vector<std::weak_ptr<DirectEntry>> g_direct;
 
+struct OwnedWorkspace : MsmWorkspace {               // an MSM workspace released on every path out
+  OwnedWorkspace() = default;
+  OwnedWorkspace(const OwnedWorkspace &) = delete;
+  OwnedWorkspace &operator=(const OwnedWorkspace &) = delete;
+  ~OwnedWorkspace() { release(); }
+};
+
+// What ONE chunk of proofs in flight mutates: a stream, staging, the per-chunk scratch and an MSM workspace.  A setup has two, so
+// that two chunks are in flight and one hides the other's host rounds.  Lane 0 runs on the context's stream and serves every
+// other call on the setup; lane 1 gets a non-blocking stream of its own on the first two-lane prove call and allocates nothing
+// before it is used.
+struct RingLane {
+  hipStream_t stream = nullptr; bool owns_stream = false;
+  DevMem buf;                                         // staging for NTT batches / MSM scalars
+  // per-chunk scratch: 0 witness evaluations (4 x 4N; later the opening quotients), 1 aggregated constraints (4N; later
+  // the aggregated opening polynomial), 2 coefficients (4 x N), 3 parameter block, 4 quotient, 5 linearisation
+  DevMem scr[6];
+  OwnedWorkspace ws;
+  uint32_t *scratch(int which, size_t bytes) { scr[which].ensure(bytes); return scr[which].as(); }
+  RingLane() = default;
+  RingLane(const RingLane &) = delete;
+  RingLane &operator=(const RingLane &) = delete;
+  ~RingLane() { ws.release(); if (owns_stream) (void)hipStreamDestroy(stream); }   // (the workspace before the stream it ran on)
+};
+
+// Everything outside the two lanes is SHARED by the chunks in flight and read-only while they are: whatever a chunk needs built on
+// first use (the witness table, the tables of all multiples) is built by avrf_ring_prove before its threads start, on lane 0.
+// `delete` releases everything but the registry references, which avrf_ring_setup_free drops under g_direct_mu first.
 struct avrf_ring_setup {
-  avrf_ctx *ctx; int suite; int curve; hipStream_t stream; int device;   // curve: pairing curve of the suite (0 BLS12-381, 1 BN254)
+  avrf_ctx *ctx; int suite; int curve; int device;    // curve: pairing curve of the suite (0 BLS12-381, 1 BN254)
   size_t N, cap, keyset, L, n_srs;                    // n_srs = 0: verifier-only setup (PcsVerifierParams), no SRS on the device
-  uint32_t *d_srs = nullptr;                          // n_srs Montgomery affine points
-  uint32_t *d_srs_table = nullptr; int table_c = 0, table_nwin = 0;   // fixed-base window table over the SRS (batched commits)
+  DevMem d_srs;                                       // n_srs Montgomery affine points
+  DevMem d_srs_table; int table_c = 0, table_nwin = 0;   // fixed-base window table over the SRS (batched commits)
   std::shared_ptr<DirectEntry> direct, direct_wit; bool direct_tried = false;   // the tables of all multiples (SRS powers; witness bases), built on first use
   uint64_t table_budget = UINT64_MAX;                 // HBM the two tables may take (avrf_ring_setup_set_table_budget; UINT64_MAX: the process default)
   uint64_t planned_budget = UINT64_MAX;               // the budget the tables held now were planned under
   bool table_missed = false;                          // a planned table was not built (did not fit, allocation or build failed): bucket form for it
-  std::shared_ptr<std::atomic<uint64_t>> table_batches = std::make_shared<std::atomic<uint64_t>>(0);   // commitment batches served from the
-                                                      // tables (shared with the second lane, whose shallow copy holds the same counter)
-  uint32_t *d_wit_bases = nullptr;                    // the 2N + 1 witness bases the tables are built over
+  std::atomic<uint64_t> table_batches{0};             // commitment batches served from the tables (both lanes count)
+  DevMem d_wit_bases;                                 // the 2N + 1 witness bases the tables are built over
   int wit_c = 0, wit_nwin = 0;                        // window width of the witness table (sparse MSMs: few entries, small buckets)
-  uint32_t *d_wit_table = nullptr;                    // same over [L_i(tau) G, i < N | prefix sums PS_k = sum_{i<k} L_i(tau) G, k <= N] (witness commits)
-  void *host_lines = nullptr; void (*host_lines_free)(void *) = nullptr;   // host Miller-loop line tables of (g2, tau g2), built on first use
+  DevMem d_wit_table;                                 // same over [L_i(tau) G, i < N | prefix sums PS_k = sum_{i<k} L_i(tau) G, k <= N] (witness commits)
+  std::unique_ptr<void, void (*)(void *)> host_lines{nullptr, nullptr};   // host Miller-loop line tables of (g2, tau g2), built on first use
   G1Aff g1_0;                                         // powers_in_g1[0]
   std::vector<uint8_t> g2_raw;                        // powers_in_g2[0..2] exactly as in the SRS file
   std::vector<uint8_t> g1_raw;                        // the n_srs powers_in_g1 this setup keeps, serialize_uncompressed encoding
   std::vector<uint8_t> lag_raw;                       // L_i(tau) G, i < N (RingBuilderPcsParams), same encoding; filled by ensure_lagrange
   H256 w, w4;                                         // domain generators (Montgomery)
-  uint32_t *d_tw_n = nullptr, *d_tw_n_inv = nullptr, *d_tw_4n = nullptr, *d_tw_4n_inv = nullptr;
+  DevMem d_tw_n, d_tw_n_inv, d_tw_4n, d_tw_4n_inv;
   H256 ninv, n4inv;
   std::vector<std::pair<H256, H256>> h_pows;          // 2^i * BLINDING_BASE, affine Montgomery
-  uint32_t *d_buf = nullptr; size_t buf_cap = 0;      // scratch for NTT batches / MSM scalars
-  uint32_t *d_l4 = nullptr;                           // L_first | L_last evaluated on the 4N domain (2 x 4N)
-  // per-chunk scratch: 0 witness evaluations (4 x 4N; later the opening quotients), 1 aggregated constraints (4N; later
-  // the aggregated opening polynomial), 2 coefficients (4 x N), 3 parameter block, 4 quotient, 5 linearisation
-  uint32_t *d_scr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t scr_cap[6] = {0, 0, 0, 0, 0, 0};
-  MsmWorkspace ws;
+  DevMem d_l4;                                        // L_first | L_last evaluated on the 4N domain (2 x 4N)
   PairingTables ptab; bool ptab_ready = false;        // line tables of (g2, tau g2) for the device pairing checks (built on first use)
-  // second lane for avrf_ring_prove: a shallow copy (same SRS tables, twiddles, constants) with its own stream, scratch
-  // and MSM workspace, so two chunks of proofs are in flight and one hides the other's host rounds
-  avrf_ring_setup *lane1 = nullptr;
+  RingLane lane[2];
 };
+static_assert(!std::is_copy_constructible<avrf_ring_setup>::value && !std::is_copy_assignable<avrf_ring_setup>::value,
+              "a setup owns device memory and its lanes: a lane is a member, never a copy");
 struct avrf_ring_key {
   avrf_ring_setup *setup;
   size_t n_keys;
@@ -583,9 +617,9 @@ struct avrf_ring_key {
   std::vector<H256> px_poly, py_poly, sel_poly;       // coefficients
   std::vector<H256> px4, py4, sel4;                   // evaluations on the 4N domain
   G1Aff C[3];
-  uint32_t *d_fixed4 = nullptr;                       // px4 | py4 | sel4 on the device (3 x 4N)
-  uint32_t *d_fixed_coef = nullptr;                   // px | py | sel coefficients on the device (3 x N)
-  void *d_points_pre = nullptr;                       // the ring's points (keys, padding, blinding-base powers) as te_pre {x, y, d x y}: k_ring_witness_acc
+  DevMem d_fixed4;                                    // px4 | py4 | sel4 on the device (3 x 4N)
+  DevMem d_fixed_coef;                                // px | py | sel coefficients on the device (3 x N)
+  DevMem d_points_pre;                                // the ring's points (keys, padding, blinding-base powers) as te_pre {x, y, d x y}: k_ring_witness_acc
 };
 
 // VerifierKeyBuilder (src/ring.rs:539-637): the ring commitment under construction
@@ -608,70 +642,62 @@ template <class S, class G> struct Ring {
   using F = typename S::Fq;
   static constexpr int FQB = T::FQB;
 
-  static void ensure_buf(avrf_ring_setup *su, size_t bytes) {
-    if (bytes <= su->buf_cap) return;
-    if (su->d_buf) HIP_CHECK(hipFree(su->d_buf));
-    HIP_CHECK(hipMalloc(&su->d_buf, bytes)); su->buf_cap = bytes;
-  }
-  static uint32_t *make_twiddles(H256 w, size_t n) {
+  static DevMem make_twiddles(H256 w, size_t n) {
     std::vector<H256> tw(n / 2);
     H256 x = Fr::one();
     for (size_t i = 0; i < n / 2; i++) { tw[i] = x; x = Fr::mul(x, w); }
-    uint32_t *d; HIP_CHECK(hipMalloc(&d, (n / 2) * 32)); HIP_CHECK(hipMemcpy(d, tw.data(), (n / 2) * 32, hipMemcpyHostToDevice));
+    DevMem d((n / 2) * 32); HIP_CHECK(hipMemcpy(d.p, tw.data(), (n / 2) * 32, hipMemcpyHostToDevice));
     return d;
   }
-  // in-place (i)NTT of `batch` vectors of size n held on the host, via the device
-  static void ntt(avrf_ring_setup *su, std::vector<H256> &v, size_t n, size_t batch, bool inverse) {
-    ensure_buf(su, n * batch * 32);
-    HIP_CHECK(hipMemcpyAsync(su->d_buf, v.data(), n * batch * 32, hipMemcpyHostToDevice, su->stream));
-    const uint32_t *tw = n == su->N ? (inverse ? su->d_tw_n_inv : su->d_tw_n) : (inverse ? su->d_tw_4n_inv : su->d_tw_4n);
-    fp sc; H256 k = n == su->N ? su->ninv : su->n4inv; memcpy(sc.v, k.l, 32);
-    ntt_launch<F>(su->d_buf, (uint32_t)n, tw, (uint32_t)batch, inverse ? &sc : nullptr, su->stream);
-    HIP_CHECK(hipMemcpyAsync(v.data(), su->d_buf, n * batch * 32, hipMemcpyDeviceToHost, su->stream));
-    HIP_CHECK(hipStreamSynchronize(su->stream));
+  // host coordinates of an affine point (HostG1's XYZZ form)
+  static typename T::HG::Pt g1_lift(const G1Aff &p) {
+    using HG = typename T::HG; using FqN = typename T::FqN;
+    typename HG::Pt q = HG::identity();
+    if (!p.inf) { typename FqN::El x, y; memcpy(x.l, p.xy, FQB); memcpy(y.l, p.xy + FQB, FQB); q.x = FqN::to_mont(x); q.y = FqN::to_mont(y); q.zz = FqN::one(); q.zzz = FqN::one(); }
+    return q;
   }
-  // KZG commit: sum coeffs[i] * powers_in_g1[i] on the device
-  static G1Aff commit(avrf_ring_setup *su, const H256 *coeffs_mont, size_t n) {
-    std::vector<H256> plain(n);
-    for (size_t i = 0; i < n; i++) plain[i] = Fr::from_mont(coeffs_mont[i]);
-    ensure_buf(su, n * 32);
-    HIP_CHECK(hipMemcpyAsync(su->d_buf, plain.data(), n * 32, hipMemcpyHostToDevice, su->stream));
-    G1Aff r; memset(&r, 0, sizeof r);
-    msm_g1_device(su->curve, su->d_srs, su->d_buf, n, su->ws, su->stream, r.xy);
-    r.inf = true; for (int i = 0; i < 2 * FQB; i++) if (r.xy[i]) r.inf = false;
-    return r;
+  static void g1_from_xy_batch(const std::vector<uint8_t> &xy, size_t batch, G1Aff *out) {
+    for (size_t b = 0; b < batch; b++) out[b] = g1_from_xy(&xy[b * 2 * FQB], FQB);
+  }
+  // in-place (i)NTT of `batch` vectors of size n held on the host, via the device
+  static void ntt(avrf_ring_setup *su, RingLane &ln, std::vector<H256> &v, size_t n, size_t batch, bool inverse) {
+    ln.buf.ensure(n * batch * 32);
+    HIP_CHECK(hipMemcpyAsync(ln.buf.p, v.data(), n * batch * 32, hipMemcpyHostToDevice, ln.stream));
+    const DevMem &tw = n == su->N ? (inverse ? su->d_tw_n_inv : su->d_tw_n) : (inverse ? su->d_tw_4n_inv : su->d_tw_4n);
+    fp sc; H256 k = n == su->N ? su->ninv : su->n4inv; memcpy(sc.v, k.l, 32);
+    ntt_launch<F>(ln.buf.as(), (uint32_t)n, tw.as(), (uint32_t)batch, inverse ? &sc : nullptr, ln.stream);
+    HIP_CHECK(hipMemcpyAsync(v.data(), ln.buf.p, n * batch * 32, hipMemcpyDeviceToHost, ln.stream));
+    HIP_CHECK(hipStreamSynchronize(ln.stream));
   }
   // `batch` KZG commits in one launch chain: coeffs = batch vectors of length n (Montgomery; pad with zeros)
-  static void commit_batch(avrf_ring_setup *su, const H256 *coeffs_mont, size_t n, size_t batch, G1Aff *out) {
+  static void commit_batch(avrf_ring_setup *su, RingLane &ln, const H256 *coeffs_mont, size_t n, size_t batch, G1Aff *out) {
     std::vector<H256> plain(n * batch);
     for (size_t i = 0; i < n * batch; i++) plain[i] = Fr::from_mont(coeffs_mont[i]);
-    ensure_buf(su, n * batch * 32);
-    HIP_CHECK(hipMemcpyAsync(su->d_buf, plain.data(), n * batch * 32, hipMemcpyHostToDevice, su->stream));
+    ln.buf.ensure(n * batch * 32);
+    HIP_CHECK(hipMemcpyAsync(ln.buf.p, plain.data(), n * batch * 32, hipMemcpyHostToDevice, ln.stream));
     std::vector<uint8_t> xy(batch * 2 * FQB);
-    msm_g1_device(su->curve, su->d_srs, su->d_buf, n, su->ws, su->stream, xy.data(), batch);
-    for (size_t b = 0; b < batch; b++) {
-      memset(&out[b], 0, sizeof(G1Aff)); memcpy(out[b].xy, &xy[b * 2 * FQB], 2 * FQB);
-      out[b].inf = true; for (int i = 0; i < 2 * FQB; i++) if (out[b].xy[i]) out[b].inf = false;
-    }
-  }
-  static H256 poly_eval(const std::vector<H256> &c, const H256 &x) {
-    H256 acc = {{0, 0, 0, 0}};
-    for (size_t i = c.size(); i-- > 0;) acc = Fr::add(Fr::mul(acc, x), c[i]);
-    return acc;
-  }
-  static std::vector<H256> div_linear(const std::vector<H256> &c, const H256 &z) {   // (c(X) - c(z)) / (X - z)
-    std::vector<H256> out(c.size() - 1); H256 acc = {{0, 0, 0, 0}};
-    for (size_t i = c.size() - 1; i >= 1; i--) { acc = Fr::add(c[i], Fr::mul(acc, z)); out[i - 1] = acc; }
-    return out;
+    msm_g1_device(su->curve, su->d_srs.as(), ln.buf.as(), n, ln.ws, ln.stream, xy.data(), batch);
+    g1_from_xy_batch(xy, batch, out);
   }
   static H256 challenge(ArkTranscript &t, const char *l) { uint8_t b[48]; t.challenge48(l, b); return fr_from_be48<F>(b); }
   static void push_le32(std::vector<uint8_t> &o, const H256 &mont) { H256 p = Fr::from_mont(mont); size_t k = o.size(); o.resize(k + 32); memcpy(&o[k], p.l, 32); }
 
+  // a handle with what both loaders fill alike: identity, lane 0 on the context's stream, sizes and the domain constants
+  static std::unique_ptr<avrf_ring_setup> new_setup(avrf_ctx *ctx, size_t N, size_t n_srs) {
+    auto su = std::make_unique<avrf_ring_setup>();
+    su->ctx = ctx; su->suite = S::ID; su->curve = pairing_curve_of(S::ID); su->lane[0].stream = avrf_ctx_stream_(ctx); su->device = avrf_ctx_device_(ctx);
+    su->N = N; su->cap = N - 3; su->L = S::Fr::BITS; su->keyset = su->cap - su->L - 1; su->n_srs = n_srs;
+    H256 root = Fr::from32(G::ROOT_OF_UNITY);
+    int lg = 0; while (((size_t)1 << lg) < N) lg++;
+    H256 w4 = root; for (int i = 0; i < G::TWO_ADICITY - (lg + 2); i++) w4 = Fr::sqr(w4);
+    su->w4 = w4; su->w = Fr::sqr(Fr::sqr(w4));
+    su->ninv = Fr::inv(fr_small<F>(N)); su->n4inv = Fr::inv(fr_small<F>(4 * N));
+    return su;
+  }
+
   // ---- setup: parse `URS { powers_in_g1, powers_in_g2 }` (serialize_uncompressed), src/ring.rs:380-393,1412-1421
   static int setup_load(avrf_ctx *ctx, const uint8_t *srs, size_t len, size_t ring_size, avrf_ring_setup **out) {
-    const size_t L = S::Fr::BITS;
-    size_t need = ring_size + 4 + L, N = 1; while (N < need) N <<= 1;      // src/ring.rs:810-821
-    const size_t pcs = 3 * N + 1;
+    const size_t L = S::Fr::BITS, N = ring_domain_size(ring_size, L), pcs = 3 * N + 1;
     if (len < 8) return AVRF_INVALID_DATA;
     uint64_t cnt; memcpy(&cnt, srs, 8);
     const size_t e1 = 2 * FQB, e2 = 4 * FQB;
@@ -703,9 +729,8 @@ template <class S, class G> struct Ring {
     uint64_t cnt2; memcpy(&cnt2, srs + 8 + cnt * e1, 8);
     if (len != 8 + cnt * e1 + 8 + cnt2 * e2) return AVRF_INVALID_DATA;
     if (cnt < pcs || cnt2 < 2) return AVRF_RING_CAPACITY_EXCEEDED;      // src/ring.rs:382-384
-    avrf_ring_setup *su = new avrf_ring_setup();
-    su->ctx = ctx; su->suite = S::ID; su->curve = pairing_curve_of(S::ID); su->stream = avrf_ctx_stream_(ctx); su->device = avrf_ctx_device_(ctx);
-    su->N = N; su->cap = N - 3; su->L = L; su->keyset = su->cap - L - 1; su->n_srs = pcs;
+    std::unique_ptr<avrf_ring_setup> owner = new_setup(ctx, N, pcs);
+    avrf_ring_setup *su = owner.get(); RingLane &ln = su->lane[0];
     std::vector<uint8_t> le(pcs * e1);
     for (size_t i = 0; i < pcs; i++) {
       const uint8_t *p = srs + 8 + i * e1; uint8_t *q = &le[i * e1];
@@ -716,13 +741,14 @@ template <class S, class G> struct Ring {
     su->g2_raw.assign(srs + 8 + cnt * e1 + 8, srs + 8 + cnt * e1 + 8 + 2 * e2);
     su->g1_raw.assign(srs + 8, srs + 8 + pcs * e1);
     HIP_CHECK(hipSetDevice(su->device));
-    uint8_t *d_le; uint32_t *d_flag; uint32_t flag = 0;
-    HIP_CHECK(hipMalloc(&d_le, le.size())); HIP_CHECK(hipMalloc(&d_flag, 4)); HIP_CHECK(hipMalloc(&su->d_srs, pcs * e1));
-    HIP_CHECK(hipMemcpy(d_le, le.data(), le.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, su->stream));   // (the flag reset in stream order with the kernel: the null stream does not order with a non-blocking one)
-    launch_g1_bases(su->curve, d_le, pcs, su->d_srs, d_flag, su->stream);
-    HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, su->stream)); HIP_CHECK(hipStreamSynchronize(su->stream));
-    HIP_CHECK(hipFree(d_le)); HIP_CHECK(hipFree(d_flag));
-    if (flag) { HIP_CHECK(hipFree(su->d_srs)); delete su; return AVRF_INVALID_DATA; }
+    {
+      DevMem d_le(le.size()), d_flag(4); uint32_t flag = 0;
+      su->d_srs.ensure(pcs * e1);
+      HIP_CHECK(hipMemcpy(d_le.p, le.data(), le.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, ln.stream));   // (the flag reset in stream order with the kernel: the null stream does not order with a non-blocking one)
+      launch_g1_bases(su->curve, d_le.as<uint8_t>(), pcs, su->d_srs.as(), d_flag.as(), ln.stream);
+      HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, ln.stream)); HIP_CHECK(hipStreamSynchronize(ln.stream));
+      if (flag) return AVRF_INVALID_DATA;
+    }
     {  // fixed-base window table: T[w][i] = 2^(c w) * tau^i G, all windows of a commit then share one bucket set
       // window width from the size of the commitments (3N + 1 coefficients): wider windows save bucket additions (k_accumulate:
       // one per table row and coefficient), narrower ones save bucket REDUCTION (k_bucket_sum + k_wsum: 2^(c-1) buckets per set).
@@ -738,28 +764,21 @@ template <class S, class G> struct Ring {
       if (const char *e = getenv("AVRF_RING_TABLE_C")) { int v = atoi(e); if (v >= 4 && v <= 14) su->table_c = v; }
       {
         su->table_nwin = (G::Fr::BITS + 1 + su->table_c - 1) / su->table_c;
-        HIP_CHECK(hipMalloc(&su->d_srs_table, (size_t)su->table_nwin * pcs * e1));
-        build_g1_table(su->curve, su->d_srs, pcs, su->table_c, su->table_nwin, su->d_srs_table, su->stream);
-        HIP_CHECK(hipStreamSynchronize(su->stream));
+        su->d_srs_table.ensure((size_t)su->table_nwin * pcs * e1);
+        build_g1_table(su->curve, su->d_srs.as(), pcs, su->table_c, su->table_nwin, su->d_srs_table.as(), ln.stream);
+        HIP_CHECK(hipStreamSynchronize(ln.stream));
       }
     }
-    // domain
-    H256 root = Fr::from32(G::ROOT_OF_UNITY);
-    int lg = 0; while (((size_t)1 << lg) < N) lg++;
-    H256 w4 = root; for (int i = 0; i < G::TWO_ADICITY - (lg + 2); i++) w4 = Fr::sqr(w4);
-    su->w4 = w4; su->w = Fr::sqr(Fr::sqr(w4));
     su->d_tw_n = make_twiddles(su->w, N); su->d_tw_n_inv = make_twiddles(Fr::inv(su->w), N);
     su->d_tw_4n = make_twiddles(su->w4, 4 * N); su->d_tw_4n_inv = make_twiddles(Fr::inv(su->w4), 4 * N);
-    su->ninv = Fr::inv(fr_small<F>(N)); su->n4inv = Fr::inv(fr_small<F>(4 * N));
     {  // Lagrange basis polynomials of rows 0 and cap-1, evaluated on the 4N domain (shared by every proof)
       const H256 zero = {{0, 0, 0, 0}};
       std::vector<H256> lfl(2 * N, zero); lfl[0] = Fr::one(); lfl[N + su->cap - 1] = Fr::one();
-      ntt(su, lfl, N, 2, true);
+      ntt(su, ln, lfl, N, 2, true);
       std::vector<H256> l4(2 * 4 * N, zero);
       for (size_t i = 0; i < N; i++) { l4[i] = lfl[i]; l4[4 * N + i] = lfl[N + i]; }
-      ntt(su, l4, 4 * N, 2, false);
-      HIP_CHECK(hipMalloc(&su->d_l4, l4.size() * 32)); HIP_CHECK(hipMemcpy(su->d_l4, l4.data(), l4.size() * 32, hipMemcpyHostToDevice));
-
+      ntt(su, ln, l4, 4 * N, 2, false);
+      su->d_l4.ensure(l4.size() * 32); HIP_CHECK(hipMemcpy(su->d_l4.p, l4.data(), l4.size() * 32, hipMemcpyHostToDevice));
     }
     // 2^i * H  (A.5)
     HostExt h; h.x = Fr::from32(S::B_X); h.y = Fr::from32(S::B_Y); h.t = Fr::mul(h.x, h.y); h.z = Fr::one();
@@ -767,7 +786,7 @@ template <class S, class G> struct Ring {
       H256 zi = Fr::inv(h.z); su->h_pows.push_back({Fr::mul(h.x, zi), Fr::mul(h.y, zi)});
       h = Te::dbl(h);
     }
-    *out = su;
+    *out = owner.release();
     return AVRF_OK;
   }
 
@@ -777,8 +796,7 @@ template <class S, class G> struct Ring {
   // builder / serialisation of the full setup answer AVRF_SRS_LOOKUP_FAILED on such a handle.
   static int verifier_setup_load(avrf_ctx *ctx, const uint8_t *vp, size_t len, size_t ring_size, avrf_ring_setup **out) {
     using HP = HostPairing<G>;
-    const size_t L = S::Fr::BITS, e1 = 2 * FQB, e2 = 4 * FQB;
-    size_t need = ring_size + 4 + L, N = 1; while (N < need) N <<= 1;
+    const size_t e1 = 2 * FQB, e2 = 4 * FQB;
     G1Aff g1; std::vector<uint8_t> g2(2 * e2);
     if (len == e1 + 2 * e2) {
       g1 = g1_from_raw(vp);
@@ -798,16 +816,9 @@ template <class S, class G> struct Ring {
     // lie on the twist; like the reference's RingSetup deserialisation they get no G2 subgroup test -- PcsVerifierParams are
     // trusted-setup material published with the ring parameters, not per-proof input (src/ring.rs:466-474).
     if (g1.inf || !g1_on_curve_host(g1) || !g1_in_subgroup_host(g1)) return AVRF_INVALID_DATA;
-    avrf_ring_setup *su = new avrf_ring_setup();
-    su->ctx = ctx; su->suite = S::ID; su->curve = pairing_curve_of(S::ID); su->stream = avrf_ctx_stream_(ctx); su->device = avrf_ctx_device_(ctx);
-    su->N = N; su->cap = N - 3; su->L = L; su->keyset = su->cap - L - 1; su->n_srs = 0;
+    std::unique_ptr<avrf_ring_setup> su = new_setup(ctx, ring_domain_size(ring_size, S::Fr::BITS), 0);
     su->g1_0 = g1; su->g2_raw = g2;
-    H256 root = Fr::from32(G::ROOT_OF_UNITY);
-    int lg = 0; while (((size_t)1 << lg) < N) lg++;
-    H256 w4 = root; for (int i = 0; i < G::TWO_ADICITY - (lg + 2); i++) w4 = Fr::sqr(w4);
-    su->w4 = w4; su->w = Fr::sqr(Fr::sqr(w4));
-    su->ninv = Fr::inv(fr_small<F>(N)); su->n4inv = Fr::inv(fr_small<F>(4 * N));
-    *out = su;
+    *out = su.release();
     return AVRF_OK;
   }
   static int verifier_params_serialize(avrf_ring_setup *su, bool compress, std::vector<uint8_t> &o) {
@@ -928,32 +939,22 @@ template <class S, class G> struct Ring {
     std::vector<H256> pw(n_g1);                                        // tau^i, plain
     { H256 tm = Fr::to_mont(tau), run = Fr::one(); for (size_t i = 0; i < n_g1; i++) { pw[i] = Fr::from_mont(run); run = Fr::mul(run, tm); } }
     const int c = 4, nwin = (G::Fr::BITS + 1 + c - 1) / c;
-    uint8_t *d_le; uint32_t *d_flag, *d_base, *d_table, *d_sc; uint32_t flag = 0;
-    HIP_CHECK(hipMalloc(&d_le, e1)); HIP_CHECK(hipMalloc(&d_flag, 4)); HIP_CHECK(hipMalloc(&d_base, e1));
-    HIP_CHECK(hipMalloc(&d_table, (size_t)nwin * e1)); HIP_CHECK(hipMalloc(&d_sc, n_g1 * 32));
-    HIP_CHECK(hipMemcpy(d_le, le, e1, hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, stream));   // (the flag reset in stream order with the kernel that sets it)
-    HIP_CHECK(hipMemcpy(d_sc, pw.data(), n_g1 * 32, hipMemcpyHostToDevice));
-    launch_g1_bases(pairing_curve_of(S::ID), d_le, 1, d_base, d_flag, stream);
-    HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, stream)); HIP_CHECK(hipStreamSynchronize(stream));
-    int st = AVRF_OK;
     std::vector<uint8_t> xy(n_g1 * e1);
-    if (flag) st = AVRF_INVALID_DATA;
-    else {
-      build_g1_table(pairing_curve_of(S::ID), d_base, 1, c, nwin, d_table, stream);
-      MsmWorkspace ws;
-      msm_g1_fixed_device(pairing_curve_of(S::ID), d_table, c, 1, d_sc, 1, 1, ws, stream, xy.data(), n_g1);
-      ws.release();
+    {
+      OwnedWorkspace ws;
+      DevMem d_le(e1), d_flag(4), d_base(e1), d_table((size_t)nwin * e1), d_sc(n_g1 * 32); uint32_t flag = 0;
+      HIP_CHECK(hipMemcpy(d_le.p, le, e1, hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, stream));   // (the flag reset in stream order with the kernel that sets it)
+      HIP_CHECK(hipMemcpy(d_sc.p, pw.data(), n_g1 * 32, hipMemcpyHostToDevice));
+      launch_g1_bases(pairing_curve_of(S::ID), d_le.as<uint8_t>(), 1, d_base.as(), d_flag.as(), stream);
+      HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, stream)); HIP_CHECK(hipStreamSynchronize(stream));
+      if (flag) return AVRF_INVALID_DATA;
+      build_g1_table(pairing_curve_of(S::ID), d_base.as(), 1, c, nwin, d_table.as(), stream);
+      msm_g1_fixed_device(pairing_curve_of(S::ID), d_table.as(), c, 1, d_sc.as(), 1, 1, ws, stream, xy.data(), n_g1);
     }
-    HIP_CHECK(hipFree(d_le)); HIP_CHECK(hipFree(d_flag)); HIP_CHECK(hipFree(d_base)); HIP_CHECK(hipFree(d_table)); HIP_CHECK(hipFree(d_sc));
-    if (st) return st;
     uint64_t cnt = n_g1; memcpy(out, &cnt, 8);
     {
       std::vector<uint8_t> enc; enc.reserve(n_g1 * e1);
-      for (size_t i = 0; i < n_g1; i++) {
-        G1Aff a; memset(&a, 0, sizeof a); memcpy(a.xy, &xy[i * e1], e1);
-        a.inf = true; for (size_t k = 0; k < e1; k++) if (a.xy[k]) a.inf = false;
-        g1_encode<G>(a, false, enc);                                   // serialize_uncompressed (with arkworks' y flag on BN254)
-      }
+      for (size_t i = 0; i < n_g1; i++) g1_encode<G>(g1_from_xy(&xy[i * e1], FQB), false, enc);   // serialize_uncompressed (with arkworks' y flag on BN254)
       memcpy(out + 8, enc.data(), n_g1 * e1);
     }
     using HP = HostPairing<G>;
@@ -965,14 +966,14 @@ template <class S, class G> struct Ring {
   }
 
   // ---- ring_proof::index (A.5): fixed columns and their commitments
-  static int index(avrf_ring_setup *su, const uint8_t *pks_xy, size_t n_keys, avrf_ring_key **out) {
+  static int index(avrf_ring_setup *su, const uint8_t *pks_xy, size_t n_keys, std::unique_ptr<avrf_ring_key> &out) {
     if (n_keys > su->keyset) return AVRF_RING_CAPACITY_EXCEEDED;       // src/ring.rs:400-402
-    const size_t N = su->N;
-    avrf_ring_key *k = new avrf_ring_key(); k->setup = su; k->n_keys = n_keys;
+    const size_t N = su->N; RingLane &ln = su->lane[0];
+    auto k = std::make_unique<avrf_ring_key>(); k->setup = su; k->n_keys = n_keys;
     H256 padx = Fr::from32(S::PAD_X), pady = Fr::from32(S::PAD_Y);
     for (size_t i = 0; i < n_keys; i++) {
       H256 x = Fr::load_le(pks_xy + 64 * i), y = Fr::load_le(pks_xy + 64 * i + 32);
-      if (Fr::geq_p(x) || Fr::geq_p(y)) { delete k; return AVRF_INVALID_DATA; }
+      if (Fr::geq_p(x) || Fr::geq_p(y)) return AVRF_INVALID_DATA;
       k->points.push_back({Fr::to_mont(x), Fr::to_mont(y)});
     }
     for (size_t i = n_keys; i < su->keyset; i++) k->points.push_back({padx, pady});
@@ -982,27 +983,27 @@ template <class S, class G> struct Ring {
     for (size_t i = 0; i < k->points.size(); i++) { cols[i] = k->points[i].first; cols[N + i] = k->points[i].second; }
     for (size_t i = 0; i < su->keyset; i++) cols[2 * N + i] = Fr::one();
     k->px.assign(cols.begin(), cols.begin() + N); k->py.assign(cols.begin() + N, cols.begin() + 2 * N); k->sel.assign(cols.begin() + 2 * N, cols.end());
-    ntt(su, cols, N, 3, true);
+    ntt(su, ln, cols, N, 3, true);
     k->px_poly.assign(cols.begin(), cols.begin() + N); k->py_poly.assign(cols.begin() + N, cols.begin() + 2 * N); k->sel_poly.assign(cols.begin() + 2 * N, cols.end());
-    commit_batch(su, cols.data(), N, 3, k->C);
-    HIP_CHECK(hipMalloc(&k->d_fixed_coef, 3 * N * 32)); HIP_CHECK(hipMemcpy(k->d_fixed_coef, cols.data(), 3 * N * 32, hipMemcpyHostToDevice));
+    commit_batch(su, ln, cols.data(), N, 3, k->C);
+    k->d_fixed_coef.ensure(3 * N * 32); HIP_CHECK(hipMemcpy(k->d_fixed_coef.p, cols.data(), 3 * N * 32, hipMemcpyHostToDevice));
     // evaluations of the fixed columns on the 4N domain (shared by every proof over this ring)
     std::vector<H256> e4(3 * 4 * N, zero);
     for (size_t i = 0; i < N; i++) { e4[i] = k->px_poly[i]; e4[4 * N + i] = k->py_poly[i]; e4[8 * N + i] = k->sel_poly[i]; }
-    ntt(su, e4, 4 * N, 3, false);
+    ntt(su, ln, e4, 4 * N, 3, false);
     k->px4.assign(e4.begin(), e4.begin() + 4 * N); k->py4.assign(e4.begin() + 4 * N, e4.begin() + 8 * N); k->sel4.assign(e4.begin() + 8 * N, e4.end());
-    HIP_CHECK(hipMalloc(&k->d_fixed4, e4.size() * 32)); HIP_CHECK(hipMemcpy(k->d_fixed4, e4.data(), e4.size() * 32, hipMemcpyHostToDevice));
+    k->d_fixed4.ensure(e4.size() * 32); HIP_CHECK(hipMemcpy(k->d_fixed4.p, e4.data(), e4.size() * 32, hipMemcpyHostToDevice));
     {  // the same points as te_pre for the device witness accumulation (k_ring_witness_acc)
       const size_t np = k->points.size();
       std::vector<H256> xy(2 * np);
       for (size_t i = 0; i < np; i++) { xy[2 * i] = k->points[i].first; xy[2 * i + 1] = k->points[i].second; }
-      ensure_buf(su, np * 64);
-      HIP_CHECK(hipMalloc(&k->d_points_pre, np * sizeof(te_pre)));
-      HIP_CHECK(hipMemcpyAsync(su->d_buf, xy.data(), np * 64, hipMemcpyHostToDevice, su->stream));
-      hipLaunchKernelGGL(k_ring_points_pre<S>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, su->stream, (const uint32_t *)su->d_buf, (uint32_t)np, (te_pre *)k->d_points_pre);
-      HIP_CHECK(hipStreamSynchronize(su->stream));
+      ln.buf.ensure(np * 64);
+      k->d_points_pre.ensure(np * sizeof(te_pre));
+      HIP_CHECK(hipMemcpyAsync(ln.buf.p, xy.data(), np * 64, hipMemcpyHostToDevice, ln.stream));
+      hipLaunchKernelGGL(k_ring_points_pre<S>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ln.stream, (const uint32_t *)ln.buf.as(), (uint32_t)np, k->d_points_pre.as<te_pre>());
+      HIP_CHECK(hipStreamSynchronize(ln.stream));
     }
-    *out = k;
+    out = std::move(k);
     return AVRF_OK;
   }
 
@@ -1019,28 +1020,21 @@ template <class S, class G> struct Ring {
   // ---- VerifierKeyBuilder (src/ring.rs:539-637): start from the all-padding ring, then every appended key replaces a
   // padding point: C_x += (x - x_pad) L_i(tau) G, C_y likewise -- two sparse MSMs over the Lagrange-basis table per append
   static G1Aff g1_add_aff(const G1Aff &a, const G1Aff &b) {
-    using HG = typename T::HG; using FqN = typename T::FqN;
-    auto lift = [](const G1Aff &p) { typename HG::Pt q = HG::identity();
-      if (!p.inf) { typename FqN::El x, y; memcpy(x.l, p.xy, FQB); memcpy(y.l, p.xy + FQB, FQB); q.x = FqN::to_mont(x); q.y = FqN::to_mont(y); q.zz = FqN::one(); q.zzz = FqN::one(); }
-      return q; };
-    typename HG::Pt r = HG::add(lift(a), lift(b));
-    G1Aff o; memset(&o, 0, sizeof o); HG::to_affine_bytes(r, o.xy);
-    o.inf = true; for (int i = 0; i < 2 * FQB; i++) if (o.xy[i]) o.inf = false;
-    return o;
+    using HG = typename T::HG;
+    uint8_t xy[2 * FQB]; HG::to_affine_bytes(HG::add(g1_lift(a), g1_lift(b)), xy);
+    return g1_from_xy(xy, FQB);
   }
   static int builder_new(avrf_ring_setup *su, avrf_ring_vk_builder **out) {
-    avrf_ring_key *k = nullptr;
-    int st = index(su, nullptr, 0, &k);                                // the ring of padding points only
-    if (st) return st;
-    avrf_ring_vk_builder *b = new avrf_ring_vk_builder(); b->setup = su;
+    std::unique_ptr<avrf_ring_key> k;
+    if (int st = index(su, nullptr, 0, k)) return st;                  // the ring of padding points only
+    auto b = std::make_unique<avrf_ring_vk_builder>(); b->setup = su;
     for (int i = 0; i < 3; i++) b->C[i] = k->C[i];
-    if (k->d_fixed4) (void)hipFree(k->d_fixed4); if (k->d_fixed_coef) (void)hipFree(k->d_fixed_coef); delete k;
     ensure_lagrange(su);
-    *out = b;
+    *out = b.release();
     return AVRF_OK;
   }
   static int builder_append(avrf_ring_vk_builder *b, const uint8_t *pks_xy, size_t n) {
-    avrf_ring_setup *su = b->setup;
+    avrf_ring_setup *su = b->setup; RingLane &ln = su->lane[0];
     if (n > su->keyset - b->curr) return AVRF_RING_CAPACITY_EXCEEDED;   // src/ring.rs:606-608; nothing appended
     if (!n) return AVRF_OK;
     const H256 padx = Fr::from32(S::PAD_X), pady = Fr::from32(S::PAD_Y);
@@ -1051,11 +1045,11 @@ template <class S, class G> struct Ring {
       sc[i] = Fr::from_mont(Fr::sub(Fr::to_mont(x), padx)); sc[n + i] = Fr::from_mont(Fr::sub(Fr::to_mont(y), pady));
       bi[i] = bi[n + i] = (uint32_t)(b->curr + i);
     }
-    uint32_t *d = dev_scratch(su, 1, 2 * n * 36);
+    uint32_t *d = ln.scratch(1, 2 * n * 36);
     uint32_t *d_sc = d, *d_bi = d + 2 * n * 8;
-    HIP_CHECK(hipMemcpyAsync(d_sc, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemcpyAsync(d_bi, bi.data(), 2 * n * 4, hipMemcpyHostToDevice, su->stream));
-    std::vector<G1Aff> D; commit_sparse(su, d_sc, d_bi, n, 2, D);
+    HIP_CHECK(hipMemcpyAsync(d_sc, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemcpyAsync(d_bi, bi.data(), 2 * n * 4, hipMemcpyHostToDevice, ln.stream));
+    std::vector<G1Aff> D; commit_sparse(su, ln, d_sc, d_bi, n, 2, D);
     b->C[0] = g1_add_aff(b->C[0], D[0]); b->C[1] = g1_add_aff(b->C[1], D[1]);
     b->curr += n;
     return AVRF_OK;
@@ -1071,100 +1065,72 @@ template <class S, class G> struct Ring {
     G1Aff C[4], Cq, pi[2];
     ArkTranscript t;
   };
-  static uint32_t *dev_scratch(avrf_ring_setup *su, int which, size_t bytes) {
-    uint32_t **p = &su->d_scr[which]; size_t *cap = &su->scr_cap[which];
-    if (bytes > *cap) { if (*p) HIP_CHECK(hipFree(*p)); HIP_CHECK(hipMalloc(p, bytes)); *cap = bytes; }
-    return *p;
-  }
   // batched commit of `batch` coefficient vectors on the device in Montgomery form: vector b starts at
   // d_coeffs_mont + b * stride elements, its first n coefficients are committed (the source is left untouched)
-  static void commit_device(avrf_ring_setup *su, const uint32_t *d_coeffs_mont, size_t stride, size_t n, size_t batch, std::vector<G1Aff> &out) {
+  static void commit_device(avrf_ring_setup *su, RingLane &ln, const uint32_t *d_coeffs_mont, size_t stride, size_t n, size_t batch, std::vector<G1Aff> &out) {
     // (the digit kernel of the MSM takes the Montgomery limbs as they are: no plain copy of the coefficient vectors)
     constexpr int mont_id = std::is_same<F, FqBandersnatch>::value ? 1 : 2;
     static_assert(std::is_same<F, FqBandersnatch>::value || std::is_same<F, FqBabyJubJub>::value, "scalar field of the KZG commitments");
     std::vector<uint8_t> xy(batch * 2 * FQB);
     static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
-    struct timespec t0; if (trace) { HIP_CHECK(hipStreamSynchronize(su->stream)); clock_gettime(CLOCK_MONOTONIC, &t0); }
+    struct timespec t0; if (trace) { HIP_CHECK(hipStreamSynchronize(ln.stream)); clock_gettime(CLOCK_MONOTONIC, &t0); }
     // many vectors at once and the table of all multiples is there: one gathered point per (coefficient, row), no buckets (msm.hip)
-    if (su->direct && batch >= 32) { msm_g1_direct_device(su->direct->t, d_coeffs_mont, n, stride, su->ws, su->stream, xy.data(), batch, mont_id); ++*su->table_batches; }
-    else msm_g1_fixed_device(su->curve, su->d_srs_table, su->table_c, su->n_srs, d_coeffs_mont, n, stride, su->ws, su->stream, xy.data(), batch, nullptr, mont_id);
+    if (su->direct && batch >= 32) { msm_g1_direct_device(su->direct->t, d_coeffs_mont, n, stride, ln.ws, ln.stream, xy.data(), batch, mont_id); ++su->table_batches; }
+    else msm_g1_fixed_device(su->curve, su->d_srs_table.as(), su->table_c, su->n_srs, d_coeffs_mont, n, stride, ln.ws, ln.stream, xy.data(), batch, nullptr, mont_id);
     if (trace) { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
       fprintf(stderr, "    commit n=%zu batch=%zu: %.3f ms wall, accumulate %.3f ms (c=%d seg=%d)\n", n, batch,
-              (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6, su->ws.accum_ms_last, su->ws.last_plan.c, su->ws.last_plan.lpb); }
-    out.resize(batch);
-    for (size_t b = 0; b < batch; b++) {
-      memset(&out[b], 0, sizeof(G1Aff)); memcpy(out[b].xy, &xy[b * 2 * FQB], 2 * FQB);
-      out[b].inf = true; for (int i = 0; i < 2 * FQB; i++) if (out[b].xy[i]) out[b].inf = false;
-    }
+              (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6, ln.ws.accum_ms_last, ln.ws.last_plan.c, ln.ws.last_plan.lpb); }
+    out.resize(batch); g1_from_xy_batch(xy, batch, out.data());
   }
   // Lagrange-basis SRS for the witness columns, built on first use: L_i(tau) G = commit(iNTT(e_i)) (N commits in one
   // batched MSM), then the prefix sums PS_k on the host and a window table over [L_0 .. L_{N-1} | PS_0 .. PS_N].
+  // (lane 0, and never with a chunk in flight: the chunks read what this writes)
   static void ensure_lagrange(avrf_ring_setup *su) {
     if (su->d_wit_table) return;
-    const size_t N = su->N, nb = 2 * N + 1;
+    const size_t N = su->N, nb = 2 * N + 1; RingLane &ln = su->lane[0];
     // in tiles of 256 unit vectors: scratch is O(256 N) instead of the N x N matrix (2 GiB at N = 8192, 137 GB at 2^16)
     const size_t TILE = N < 256 ? N : 256;
-    uint32_t *d_mat = dev_scratch(su, 0, TILE * N * 32);
+    uint32_t *d_mat = ln.scratch(0, TILE * N * 32);
     std::vector<G1Aff> lag; lag.reserve(N);
     for (size_t i0 = 0; i0 < N; i0 += TILE) {
       const size_t rows = N - i0 < TILE ? N - i0 : TILE;
-      HIP_CHECK(hipMemsetAsync(d_mat, 0, rows * N * 32, su->stream));
-      hipLaunchKernelGGL(k_set_diag<F>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, su->stream, d_mat, (uint32_t)N, (uint32_t)rows, (uint32_t)i0);
-      { fp sc; memcpy(sc.v, su->ninv.l, 32); ntt_launch<F>(d_mat, (uint32_t)N, su->d_tw_n_inv, (uint32_t)rows, &sc, su->stream); }
-      std::vector<G1Aff> part; commit_device(su, d_mat, N, N, rows, part);
+      HIP_CHECK(hipMemsetAsync(d_mat, 0, rows * N * 32, ln.stream));
+      hipLaunchKernelGGL(k_set_diag<F>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ln.stream, d_mat, (uint32_t)N, (uint32_t)rows, (uint32_t)i0);
+      { fp sc; memcpy(sc.v, su->ninv.l, 32); ntt_launch<F>(d_mat, (uint32_t)N, su->d_tw_n_inv.as(), (uint32_t)rows, &sc, ln.stream); }
+      std::vector<G1Aff> part; commit_device(su, ln, d_mat, N, N, rows, part);
       lag.insert(lag.end(), part.begin(), part.end());
     }
     su->lag_raw.clear();
     for (size_t i = 0; i < N; i++) g1_encode<G>(lag[i], false, su->lag_raw);
-    using HG = typename T::HG; using FqN = typename T::FqN;
+    using HG = typename T::HG;
     std::vector<typename HG::Pt> ps(N + 1);
     ps[0] = HG::identity();
-    for (size_t i = 0; i < N; i++) {
-      typename HG::Pt q = HG::identity();
-      if (!lag[i].inf) { typename FqN::El x, y; memcpy(x.l, lag[i].xy, FQB); memcpy(y.l, lag[i].xy + FQB, FQB);
-        q.x = FqN::to_mont(x); q.y = FqN::to_mont(y); q.zz = FqN::one(); q.zzz = FqN::one(); }
-      ps[i + 1] = HG::add(ps[i], q);
-    }
+    for (size_t i = 0; i < N; i++) ps[i + 1] = HG::add(ps[i], g1_lift(lag[i]));
     std::vector<uint8_t> le(nb * 2 * FQB);
     for (size_t i = 0; i < N; i++) memcpy(&le[i * 2 * FQB], lag[i].xy, 2 * FQB);
     HG::to_affine_bytes_batch(ps.data(), N + 1, &le[N * 2 * FQB]);
-    uint8_t *d_le; uint32_t *d_flag, *d_bases;
-    HIP_CHECK(hipMalloc(&d_le, le.size())); HIP_CHECK(hipMalloc(&d_flag, 4)); HIP_CHECK(hipMalloc(&d_bases, nb * 2 * FQB));
-    HIP_CHECK(hipMemcpy(d_le, le.data(), le.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, su->stream));
-    launch_g1_bases(su->curve, d_le, nb, d_bases, d_flag, su->stream);
+    DevMem d_le(le.size()), d_flag(4), d_bases(nb * 2 * FQB);
+    HIP_CHECK(hipMemcpy(d_le.p, le.data(), le.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, ln.stream));
+    launch_g1_bases(su->curve, d_le.as<uint8_t>(), nb, d_bases.as(), d_flag.as(), ln.stream);
     su->wit_c = 7;
     if (const char *e = getenv("AVRF_RING_WIT_C")) { int v = atoi(e); if (v >= 4 && v <= 14) su->wit_c = v; }
     su->wit_nwin = (G::Fr::BITS + 1 + su->wit_c - 1) / su->wit_c;
-    HIP_CHECK(hipMalloc(&su->d_wit_table, (size_t)su->wit_nwin * nb * 2 * FQB));
-    build_g1_table(su->curve, d_bases, nb, su->wit_c, su->wit_nwin, su->d_wit_table, su->stream);
-    HIP_CHECK(hipStreamSynchronize(su->stream));
-    HIP_CHECK(hipFree(d_le)); HIP_CHECK(hipFree(d_flag));
-    su->d_wit_bases = d_bases;
+    DevMem d_table((size_t)su->wit_nwin * nb * 2 * FQB);
+    build_g1_table(su->curve, d_bases.as(), nb, su->wit_c, su->wit_nwin, d_table.as(), ln.stream);
+    HIP_CHECK(hipStreamSynchronize(ln.stream));
+    su->d_wit_bases = std::move(d_bases); su->d_wit_table = std::move(d_table);   // (only a finished table is seen)
   }
   // `batch` sparse commits over the witness table: vector b = m (base index, plain scalar) pairs
-  static void commit_sparse(avrf_ring_setup *su, const uint32_t *d_scalars_plain, const uint32_t *d_base_idx, size_t m, size_t batch, std::vector<G1Aff> &out) {
+  static void commit_sparse(avrf_ring_setup *su, RingLane &ln, const uint32_t *d_scalars_plain, const uint32_t *d_base_idx, size_t m, size_t batch, std::vector<G1Aff> &out) {
     std::vector<uint8_t> xy(batch * 2 * FQB);
-    if (su->direct_wit && batch >= 32) { msm_g1_direct_device(su->direct_wit->t, d_scalars_plain, m, m, su->ws, su->stream, xy.data(), batch, 0, d_base_idx); ++*su->table_batches; }
-    else msm_g1_fixed_device(su->curve, su->d_wit_table, su->wit_c, 2 * su->N + 1, d_scalars_plain, m, m, su->ws, su->stream, xy.data(), batch, d_base_idx);
-    out.resize(batch);
-    for (size_t b = 0; b < batch; b++) {
-      memset(&out[b], 0, sizeof(G1Aff)); memcpy(out[b].xy, &xy[b * 2 * FQB], 2 * FQB);
-      out[b].inf = true; for (int i = 0; i < 2 * FQB; i++) if (out[b].xy[i]) out[b].inf = false;
-    }
+    if (su->direct_wit && batch >= 32) { msm_g1_direct_device(su->direct_wit->t, d_scalars_plain, m, m, ln.ws, ln.stream, xy.data(), batch, 0, d_base_idx); ++su->table_batches; }
+    else msm_g1_fixed_device(su->curve, su->d_wit_table.as(), su->wit_c, 2 * su->N + 1, d_scalars_plain, m, m, ln.ws, ln.stream, xy.data(), batch, d_base_idx);
+    out.resize(batch); g1_from_xy_batch(xy, batch, out.data());
   }
-  static fp fp_zero_host() { fp r; memset(&r, 0, sizeof r); return r; }
 
-  static avrf_ring_setup *second_lane(avrf_ring_setup *su) {
-    if (su->lane1) return su->lane1;
-    ensure_lagrange(su);                                               // so that the copy sees the witness table
-    avrf_ring_setup *l = new avrf_ring_setup(*su);
-    l->lane1 = nullptr; l->d_buf = nullptr; l->buf_cap = 0; l->ws = MsmWorkspace(); l->host_lines = nullptr; l->host_lines_free = nullptr;
-    for (int i = 0; i < 6; i++) { l->d_scr[i] = nullptr; l->scr_cap[i] = 0; }
-    HIP_CHECK(hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
-    su->lane1 = l;
-    return l;
-  }
-  static int prove_chunk(avrf_ring_key *k, avrf_ring_setup *su, size_t n, const uint32_t *key_index, const uint8_t *blindings, bool hiding, uint8_t *out) {
+  // (the witness table is there: avrf_ring_prove builds it before the first chunk -- two chunks run this at once)
+  static int prove_chunk(avrf_ring_key *k, RingLane &ln, size_t n, const uint32_t *key_index, const uint8_t *blindings, bool hiding, uint8_t *out) {
+    avrf_ring_setup *su = k->setup;
     const size_t N = su->N, cap = su->cap, M = 4 * N, plen = 4 * FQB + 7 * 32 + FQB + 32 + 2 * FQB;
     const H256 one = Fr::one();
     static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
@@ -1172,13 +1138,11 @@ template <class S, class G> struct Ring {
     auto cpu_now = [] { struct timespec ts; clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     double t_prev = now(), c_prev = cpu_now();                         // (trace: wall time and the PROCESS's CPU time of every phase, workers included)
     auto lap = [&](const char *what) { if (trace) { double t = now(), c = cpu_now(); fprintf(stderr, "  ring_prove[%zu] %-32s %8.3f ms wall %8.3f ms cpu\n", n, what, t - t_prev, c - c_prev); t_prev = t; c_prev = c; } };
-    for (size_t i = 0; i < n; i++) if (key_index[i] >= k->n_keys) return AVRF_ERR_BAD_ARG;
     std::vector<ProofState> st(n);
     const H256 w_last = fr_pow<F>(su->w, cap - 1);
     // ---- round 0: the witness in sparse form (A.7 step 1).  Rows with bit 1: the signer's key and the set bits
     // of the blinding; the accumulator column only changes there, so it is cnt+1 points; the four KZG commits are
     // sparse MSMs over the Lagrange-basis SRS and its prefix sums (same group elements as the coefficient-form commits).
-    ensure_lagrange(su);
     constexpr size_t MP = 264;                                         // padded entries per sparse vector (L + 2 + 3 zk rows <= 264)
     // hiding (RingContext with blinding, src/ring.rs:277-295): the last 3 rows of every witness column are uniformly
     // random field elements (w3f-ring-proof `private_column`); they only add 3 sparse terms to each commitment
@@ -1191,28 +1155,28 @@ template <class S, class G> struct Ring {
     }
     // ---- round 0 + 1 (device): witness accumulation (k_ring_witness_acc), columns, coefficients, their 4N evaluations, 4n sparse
     // commits in one MSM chain.  Back to the host: result and instance of every proof (for the transcript and the constraints).
-    uint32_t *d_coef = dev_scratch(su, 2, n * 4 * N * 32), *d_e4 = dev_scratch(su, 0, std::max(n * 4 * M * 32, n * 257 * 128));
+    uint32_t *d_coef = ln.scratch(2, n * 4 * N * 32), *d_e4 = ln.scratch(0, std::max(n * 4 * M * 32, n * 257 * 128));
     std::vector<H256> wout(n * 4);
     {
       const size_t b_pos = n * 256 * 4, b_cnt = n * 4, b_val = n * 257 * 64, b_sc = n * 4 * MP * 32, b_bi = n * 4 * MP * 4, b_zk = n * 12 * 32, b_bl = n * 32, b_out = n * 128;
-      uint32_t *d_w = dev_scratch(su, 1, b_sc + b_val + b_zk + b_pos + b_bi + 2 * b_cnt + b_bl + b_out);
+      uint32_t *d_w = ln.scratch(1, b_sc + b_val + b_zk + b_pos + b_bi + 2 * b_cnt + b_bl + b_out);
       uint32_t *d_sc = d_w, *d_val = d_sc + b_sc / 4, *d_zk = d_val + b_val / 4, *d_pos = d_zk + b_zk / 4, *d_bi = d_pos + b_pos / 4, *d_cnt = d_bi + b_bi / 4,
                *d_ki = d_cnt + n, *d_bl = d_ki + n, *d_out = d_bl + b_bl / 4;
-      if (hiding) HIP_CHECK(hipMemcpyAsync(d_zk, zk.data(), b_zk, hipMemcpyHostToDevice, su->stream));
-      HIP_CHECK(hipMemcpyAsync(d_ki, key_index, b_cnt, hipMemcpyHostToDevice, su->stream));
-      HIP_CHECK(hipMemcpyAsync(d_bl, blindings, b_bl, hipMemcpyHostToDevice, su->stream));
-      HIP_CHECK(hipMemsetAsync(d_sc, 0, b_sc, su->stream));
-      HIP_CHECK(hipMemsetAsync(d_bi, 0, b_bi, su->stream));
+      if (hiding) HIP_CHECK(hipMemcpyAsync(d_zk, zk.data(), b_zk, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(d_ki, key_index, b_cnt, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(d_bl, blindings, b_bl, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipMemsetAsync(d_sc, 0, b_sc, ln.stream));
+      HIP_CHECK(hipMemsetAsync(d_bi, 0, b_bi, ln.stream));
       fp sx, sy; { const H256 ax = Fr::from32(S::ACC_X), ay = Fr::from32(S::ACC_Y); memcpy(sx.v, ax.l, 32); memcpy(sy.v, ay.l, 32); }
-      hipLaunchKernelGGL(k_ring_witness_acc<S>, dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, su->stream, (const te_pre *)k->d_points_pre, (const uint32_t *)d_ki,
+      hipLaunchKernelGGL(k_ring_witness_acc<S>, dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, ln.stream, k->d_points_pre.as<const te_pre>(), (const uint32_t *)d_ki,
                          (const uint8_t *)d_bl, (uint32_t)n, (uint32_t)su->keyset, (uint32_t)su->L, (uint32_t)N, (uint32_t)cap, sx, sy,
                          hiding ? (const uint32_t *)d_zk : nullptr, d_e4, d_pos, d_cnt, d_val, d_sc, d_bi, d_out);
-      HIP_CHECK(hipMemcpyAsync(wout.data(), d_out, b_out, hipMemcpyDeviceToHost, su->stream));
-      hipLaunchKernelGGL(k_ring_witness_cols<F>, dim3((unsigned)((N + 255) / 256), (unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_pos,
+      HIP_CHECK(hipMemcpyAsync(wout.data(), d_out, b_out, hipMemcpyDeviceToHost, ln.stream));
+      hipLaunchKernelGGL(k_ring_witness_cols<F>, dim3((unsigned)((N + 255) / 256), (unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_pos,
                          (const uint32_t *)d_cnt, (const uint32_t *)d_ki, (const uint32_t *)d_val, hiding ? (const uint32_t *)d_zk : nullptr, (uint32_t)N, (uint32_t)cap, d_coef);
-      { fp sc; memcpy(sc.v, su->ninv.l, 32); ntt_launch<F>(d_coef, (uint32_t)N, su->d_tw_n_inv, (uint32_t)(4 * n), &sc, su->stream); }
-      ntt_launch2<F>(d_coef, (uint32_t)N, d_e4, (uint32_t)M, su->d_tw_4n, (uint32_t)(4 * n), nullptr, su->stream);   // zero-extended to 4N
-      std::vector<G1Aff> C; commit_sparse(su, d_sc, d_bi, MP, 4 * n, C);                                         // (waits for the stream)
+      { fp sc; memcpy(sc.v, su->ninv.l, 32); ntt_launch<F>(d_coef, (uint32_t)N, su->d_tw_n_inv.as(), (uint32_t)(4 * n), &sc, ln.stream); }
+      ntt_launch2<F>(d_coef, (uint32_t)N, d_e4, (uint32_t)M, su->d_tw_4n.as(), (uint32_t)(4 * n), nullptr, ln.stream);   // zero-extended to 4N
+      std::vector<G1Aff> C; commit_sparse(su, ln, d_sc, d_bi, MP, 4 * n, C);                                         // (waits for the stream)
       const H256 ax = Fr::from32(S::ACC_X), ay = Fr::from32(S::ACC_Y);
       for (size_t p = 0; p < n; p++) {
         for (int i = 0; i < 4; i++) st[p].C[i] = C[4 * p + i];
@@ -1232,11 +1196,11 @@ template <class S, class G> struct Ring {
     // per-chunk parameter block on the device: RingConsts[n] | zeta[n] | nu[8n] | ev[7n] | lin_zw[n]
     const size_t qlen = 3 * N + 1, olen = 3 * N;
     const size_t rc_bytes = (n * sizeof(RingConsts) + 31) / 32 * 32;
-    uint32_t *d_par = dev_scratch(su, 3, rc_bytes + n * (1 + 8 + 7 + 1) * 32);
+    uint32_t *d_par = ln.scratch(3, rc_bytes + n * (1 + 8 + 7 + 1) * 32);
     RingConsts *d_rc = (RingConsts *)d_par;
     uint32_t *d_zeta = d_par + rc_bytes / 4, *d_nu = d_zeta + n * 8, *d_ev = d_nu + n * 64, *d_linzw = d_ev + n * 56;
     // ---- round 2 (device): constraint aggregation on the 4N domain, iNTT(4N), * Z_zk / (X^N - 1), n quotient commits
-    uint32_t *d_agg = dev_scratch(su, 1, n * M * 32), *d_q = dev_scratch(su, 4, n * qlen * 32);
+    uint32_t *d_agg = ln.scratch(1, n * M * 32), *d_q = ln.scratch(4, n * qlen * 32);
     {
       std::vector<RingConsts> rc(n);
       auto setfp = [](fp &d, const H256 &v) { memcpy(d.v, v.l, 32); };
@@ -1244,19 +1208,19 @@ template <class S, class G> struct Ring {
         for (int i = 0; i < 7; i++) setfp(rc[p].alpha[i], st[p].al[i]);
         setfp(rc[p].w_last, w_last); setfp(rc[p].seedx, st[p].seedx); setfp(rc[p].seedy, st[p].seedy); setfp(rc[p].resx, st[p].resx); setfp(rc[p].resy, st[p].resy);
       }
-      HIP_CHECK(hipMemcpyAsync(d_rc, rc.data(), n * sizeof(RingConsts), hipMemcpyHostToDevice, su->stream));
-      hipLaunchKernelGGL(k_ring_constraints<S>, dim3((M + 255) / 256, (unsigned)n), dim3(256), 0, su->stream, d_e4, k->d_fixed4, su->d_l4, su->d_tw_4n,
+      HIP_CHECK(hipMemcpyAsync(d_rc, rc.data(), n * sizeof(RingConsts), hipMemcpyHostToDevice, ln.stream));
+      hipLaunchKernelGGL(k_ring_constraints<S>, dim3((M + 255) / 256, (unsigned)n), dim3(256), 0, ln.stream, d_e4, k->d_fixed4.as(), su->d_l4.as(), su->d_tw_4n.as(),
                          (const RingConsts *)d_rc, (uint32_t)M, d_agg);
       fp sc; memcpy(sc.v, su->n4inv.l, 32);
-      ntt_launch<F>(d_agg, (uint32_t)M, su->d_tw_4n_inv, (uint32_t)n, &sc, su->stream);
+      ntt_launch<F>(d_agg, (uint32_t)M, su->d_tw_4n_inv.as(), (uint32_t)n, &sc, ln.stream);
       Fp3 z;                                                           // Z(X) = prod_j (X - w^(N-3+j)) = X^3 + z2 X^2 + z1 X + z0
       { H256 r0 = fr_pow<F>(su->w, N - 3), r1 = Fr::mul(r0, su->w), r2 = Fr::mul(r1, su->w);
         H256 z2 = Fr::neg(Fr::add(Fr::add(r0, r1), r2)), z1 = Fr::add(Fr::add(Fr::mul(r0, r1), Fr::mul(r0, r2)), Fr::mul(r1, r2)), z0 = Fr::neg(Fr::mul(Fr::mul(r0, r1), r2));
         setfp(z.v[0], z0); setfp(z.v[1], z1); setfp(z.v[2], z2); }
-      hipLaunchKernelGGL(k_ring_quotient<F>, dim3((unsigned)((qlen + 255) / 256), (unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_agg, (uint32_t)N,
+      hipLaunchKernelGGL(k_ring_quotient<F>, dim3((unsigned)((qlen + 255) / 256), (unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_agg, (uint32_t)N,
                          (uint32_t)qlen, z, d_q);
       lap("constraints + quotient (launch)");
-      std::vector<G1Aff> C; commit_device(su, d_q, qlen, qlen, n, C);
+      std::vector<G1Aff> C; commit_device(su, ln, d_q, qlen, qlen, n, C);
       for (size_t p = 0; p < n; p++) st[p].Cq = C[p];
     }
     lap("n quotient commits");
@@ -1268,18 +1232,18 @@ template <class S, class G> struct Ring {
         std::vector<uint8_t> b; g1_encode<G>(ps.Cq, false, b); ps.t.label("quotient"); ps.t.append(b);
         ps.zeta = challenge(ps.t, "evaluation_point"); zs[p] = ps.zeta;
       }, 256);
-      HIP_CHECK(hipMemcpyAsync(d_zeta, zs.data(), n * 32, hipMemcpyHostToDevice, su->stream));
+      HIP_CHECK(hipMemcpyAsync(d_zeta, zs.data(), n * 32, hipMemcpyHostToDevice, ln.stream));
     }
-    uint32_t *d_lin = dev_scratch(su, 5, n * N * 32);
+    uint32_t *d_lin = ln.scratch(5, n * N * 32);
     fp w_dev; memcpy(w_dev.v, su->w.l, 32);
-    hipLaunchKernelGGL(k_ring_evals<F>, dim3(7, (unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_coef, (const uint32_t *)k->d_fixed_coef,
+    hipLaunchKernelGGL(k_ring_evals<F>, dim3(7, (unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_coef, (const uint32_t *)k->d_fixed_coef.as(),
                        (const uint32_t *)d_zeta, (uint32_t)N, d_ev);
-    hipLaunchKernelGGL(k_ring_lin<S>, dim3((unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_coef, (const RingConsts *)d_rc, (const uint32_t *)d_zeta,
+    hipLaunchKernelGGL(k_ring_lin<S>, dim3((unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_coef, (const RingConsts *)d_rc, (const uint32_t *)d_zeta,
                        (const uint32_t *)d_ev, w_dev, (uint32_t)N, d_lin, d_linzw);
     {
       std::vector<H256> evh(n * 8);                                    // ev[7n] | lin_zw[n] are contiguous on the device
-      HIP_CHECK(hipMemcpyAsync(evh.data(), d_ev, n * 8 * 32, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipStreamSynchronize(su->stream));
+      HIP_CHECK(hipMemcpyAsync(evh.data(), d_ev, n * 8 * 32, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipStreamSynchronize(ln.stream));
       std::vector<H256> nus(n * 8);
       parallel_for(n, [&](size_t p) {
         ProofState &ps = st[p];
@@ -1289,35 +1253,35 @@ template <class S, class G> struct Ring {
         { std::vector<uint8_t> bb; push_le32(bb, ps.lin_zw); ps.t.label("shifted_linearization_evaluation"); ps.t.append(bb); }
         for (int i = 0; i < 8; i++) { ps.nu[i] = challenge(ps.t, "kzg_aggregation"); nus[p * 8 + i] = ps.nu[i]; }
       }, 64);
-      HIP_CHECK(hipMemcpyAsync(d_nu, nus.data(), n * 8 * 32, hipMemcpyHostToDevice, su->stream));
-      HIP_CHECK(hipStreamSynchronize(su->stream));                     // nus goes out of scope
+      HIP_CHECK(hipMemcpyAsync(d_nu, nus.data(), n * 8 * 32, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipStreamSynchronize(ln.stream));                     // nus goes out of scope
     }
     lap("evals + linearisation");
     // ---- round 4 (device): aggregated opening at zeta, opening of lin at zeta*w, 2n opening commits
     {
       uint32_t *d_aggz = d_agg;                                        // the 4N aggregate is dead: reuse (qlen <= 4N)
-      uint32_t *d_open = dev_scratch(su, 0, n * 4 * M * 32);           // = d_e4 (dead): q1 (n x olen) | q2 (n x N)
+      uint32_t *d_open = ln.scratch(0, n * 4 * M * 32);           // = d_e4 (dead): q1 (n x olen) | q2 (n x N)
       uint32_t *d_q1 = d_open, *d_q2 = d_open + n * olen * 8;
-      hipLaunchKernelGGL(k_ring_aggz<F>, dim3((unsigned)((qlen + 255) / 256), (unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_coef,
-                         (const uint32_t *)k->d_fixed_coef, (const uint32_t *)d_q, (const uint32_t *)d_nu, (uint32_t)N, (uint32_t)qlen, d_aggz);
+      hipLaunchKernelGGL(k_ring_aggz<F>, dim3((unsigned)((qlen + 255) / 256), (unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_coef,
+                         (const uint32_t *)k->d_fixed_coef.as(), (const uint32_t *)d_q, (const uint32_t *)d_nu, (uint32_t)N, (uint32_t)qlen, d_aggz);
       fp one_m; memcpy(one_m.v, one.l, 32);
-      hipLaunchKernelGGL(k_ring_divlin<F>, dim3((unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_aggz, (uint32_t)qlen, (uint32_t)qlen,
+      hipLaunchKernelGGL(k_ring_divlin<F>, dim3((unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_aggz, (uint32_t)qlen, (uint32_t)qlen,
                          (const uint32_t *)d_zeta, one_m, d_q1, (uint32_t)olen);
       // small chunks: BOTH openings in one MSM chain (2n vectors of stride 3N, the short one zero-padded: zero digits are dropped
       // by the sort) -- a chain of 32-128 proofs is latency-bound (k_wsum_blk: ~50 sequential G1 additions per bucket set, 0.85 ms
       // whatever the number of sets), so the second chain cost as much as the first; large chunks keep two exact-length chains
       const bool merged = n <= 128;
       const size_t q2_stride = merged ? olen : N;
-      if (merged) HIP_CHECK(hipMemsetAsync(d_q2, 0, n * olen * 32, su->stream));
-      hipLaunchKernelGGL(k_ring_divlin<F>, dim3((unsigned)n), dim3(256), 0, su->stream, (const uint32_t *)d_lin, (uint32_t)N, (uint32_t)N,
+      if (merged) HIP_CHECK(hipMemsetAsync(d_q2, 0, n * olen * 32, ln.stream));
+      hipLaunchKernelGGL(k_ring_divlin<F>, dim3((unsigned)n), dim3(256), 0, ln.stream, (const uint32_t *)d_lin, (uint32_t)N, (uint32_t)N,
                          (const uint32_t *)d_zeta, w_dev, d_q2, (uint32_t)q2_stride);
       std::vector<G1Aff> C1, C2;
       if (merged) {
-        commit_device(su, d_q1, olen, olen, 2 * n, C1);
+        commit_device(su, ln, d_q1, olen, olen, 2 * n, C1);
         for (size_t p = 0; p < n; p++) { st[p].pi[0] = C1[p]; st[p].pi[1] = C1[n + p]; }
       } else {
-        commit_device(su, d_q1, olen, olen, n, C1);
-        commit_device(su, d_q2, N, N - 1, n, C2);
+        commit_device(su, ln, d_q1, olen, olen, n, C1);
+        commit_device(su, ln, d_q2, N, N - 1, n, C2);
         for (size_t p = 0; p < n; p++) { st[p].pi[0] = C1[p]; st[p].pi[1] = C2[p]; }
       }
     }
@@ -1392,52 +1356,28 @@ template <class S, class G> struct Ring {
     return FqN::eq(FqN::sqr(ym), FqN::add(FqN::mul(FqN::sqr(xm), xm), FqN::from32(G::B)));
   }
 
-  static G1Aff g1_msm(avrf_ring_setup *su, const std::vector<uint8_t> &bases_xy, const std::vector<H256> &scalars_plain,
-                      bool check_subgroup = false, bool *bad_points = nullptr) {
-    const size_t n = scalars_plain.size();
-    G1Aff r; memset(&r, 0, sizeof r); r.inf = true;
-    if (!n) return r;
-    // staging in the setup's grow-only scratch (no allocation on the verification path)
-    const size_t pb = (n * 2 * FQB + 255) / 256 * 256, sb = (n * 32 + 255) / 256 * 256;
-    uint8_t *base = (uint8_t *)dev_scratch(su, 1, 2 * pb + sb + 256);
-    uint8_t *d_xy = base; uint32_t *d_b = (uint32_t *)(base + pb), *d_s = (uint32_t *)(base + 2 * pb), *d_flag = (uint32_t *)(base + 2 * pb + sb);
-    HIP_CHECK(hipMemcpyAsync(d_xy, bases_xy.data(), n * 2 * FQB, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemcpyAsync(d_s, scalars_plain.data(), n * 32, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, su->stream));
-    launch_g1_bases(su->curve, d_xy, n, d_b, d_flag, su->stream);
-    if (check_subgroup) launch_g1_subgroup_check(su->curve, d_b, n, d_flag, su->stream);   // Validate::Yes of the deserialised points
-    msm_g1_device(su->curve, d_b, d_s, n, su->ws, su->stream, r.xy);       // (synchronises the stream)
-    if (bad_points) { uint32_t f = 0; HIP_CHECK(hipMemcpy(&f, d_flag, 4, hipMemcpyDeviceToHost)); *bad_points = f != 0; }
-    r.inf = true; for (int i = 0; i < 2 * FQB; i++) if (r.xy[i]) r.inf = false;
-    return r;
-  }
-
   // the verifier's two sums over one launch chain: vector 0 = scalars_a over bases_a, vector 1 = scalars_b over bases_b, as two
   // scalar vectors over the concatenated bases (a zero scalar has no digits and costs nothing downstream).  One chain instead
   // of two is 0.25 ms of launch latency less per verification call, and the host's two bit-sum Horners run side by side.
-  static void g1_msm2(avrf_ring_setup *su, const std::vector<uint8_t> &bases_a, const std::vector<H256> &scalars_a,
+  static void g1_msm2(avrf_ring_setup *su, RingLane &ln, const std::vector<uint8_t> &bases_a, const std::vector<H256> &scalars_a,
                       const std::vector<uint8_t> &bases_b, const std::vector<H256> &scalars_b, bool check_subgroup_a, bool *bad_points,
                       G1Aff *out_a, G1Aff *out_b) {
     const size_t na = scalars_a.size(), nbv = scalars_b.size(), n = na + nbv;
     const size_t pb = (n * 2 * FQB + 255) / 256 * 256, sb = (2 * n * 32 + 255) / 256 * 256;
-    uint8_t *base = (uint8_t *)dev_scratch(su, 1, 2 * pb + sb + 256);
+    uint8_t *base = (uint8_t *)ln.scratch(1, 2 * pb + sb + 256);
     uint8_t *d_xy = base; uint32_t *d_b = (uint32_t *)(base + pb), *d_s = (uint32_t *)(base + 2 * pb), *d_flag = (uint32_t *)(base + 2 * pb + sb);
-    HIP_CHECK(hipMemcpyAsync(d_xy, bases_a.data(), na * 2 * FQB, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemcpyAsync(d_xy + na * 2 * FQB, bases_b.data(), nbv * 2 * FQB, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemsetAsync(d_s, 0, 2 * n * 32, su->stream));
-    HIP_CHECK(hipMemcpyAsync(d_s, scalars_a.data(), na * 32, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemcpyAsync(d_s + (n + na) * 8, scalars_b.data(), nbv * 32, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, su->stream));
-    launch_g1_bases(su->curve, d_xy, n, d_b, d_flag, su->stream);
-    if (check_subgroup_a) launch_g1_subgroup_check(su->curve, d_b, na, d_flag, su->stream);   // Validate::Yes of the deserialised points
+    HIP_CHECK(hipMemcpyAsync(d_xy, bases_a.data(), na * 2 * FQB, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemcpyAsync(d_xy + na * 2 * FQB, bases_b.data(), nbv * 2 * FQB, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemsetAsync(d_s, 0, 2 * n * 32, ln.stream));
+    HIP_CHECK(hipMemcpyAsync(d_s, scalars_a.data(), na * 32, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemcpyAsync(d_s + (n + na) * 8, scalars_b.data(), nbv * 32, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream));
+    launch_g1_bases(su->curve, d_xy, n, d_b, d_flag, ln.stream);
+    if (check_subgroup_a) launch_g1_subgroup_check(su->curve, d_b, na, d_flag, ln.stream);   // Validate::Yes of the deserialised points
     uint8_t xy[2][2 * FQB];
-    msm_g1_device(su->curve, d_b, d_s, n, su->ws, su->stream, &xy[0][0], 2, n);            // (synchronises the stream)
+    msm_g1_device(su->curve, d_b, d_s, n, ln.ws, ln.stream, &xy[0][0], 2, n);            // (synchronises the stream)
     if (bad_points) { uint32_t f = 0; HIP_CHECK(hipMemcpy(&f, d_flag, 4, hipMemcpyDeviceToHost)); *bad_points = f != 0; }
-    G1Aff *outs[2] = {out_a, out_b};
-    for (int v = 0; v < 2; v++) {
-      memset(outs[v], 0, sizeof(G1Aff)); memcpy(outs[v]->xy, xy[v], 2 * FQB);
-      outs[v]->inf = true; for (int i = 0; i < 2 * FQB; i++) if (xy[v][i]) outs[v]->inf = false;
-    }
+    *out_a = g1_from_xy(xy[0], FQB); *out_b = g1_from_xy(xy[1], FQB);
   }
 
   // ---- CanonicalSerialize of the setup objects (src/ring.rs:484-542): RingSetup = its PcsParams (URS { powers_in_g1,
@@ -1473,7 +1413,7 @@ template <class S, class G> struct Ring {
   // ---- n independent KZG pairing checks on the device: ok[i] = [ e(A_i, g2) * e(B_i, tau g2) == 1 ]   (pairing.hip)
   static void ensure_pairing(avrf_ring_setup *su) {
     if (su->ptab_ready) return;
-    su->ptab.build(su->curve, su->g2_raw.data(), 2, su->stream);
+    su->ptab.build(su->curve, su->g2_raw.data(), 2, su->lane[0].stream);
     su->ptab_ready = true;
   }
   // the Miller-loop lines of the setup's two fixed G2 arguments, tabulated once for the host pairing (host_pairing.h G2Lines)
@@ -1485,12 +1425,12 @@ template <class S, class G> struct Ring {
       typename HP::G2 q[2];
       const size_t g2len = su->g2_raw.size() / 2;
       HP::g2_decode(su->g2_raw.data(), &q[0]); HP::g2_decode(su->g2_raw.data() + g2len, &q[1]);
-      auto *t = new typename HP::G2Lines[2];
+      std::unique_ptr<typename HP::G2Lines[]> t(new typename HP::G2Lines[2]);
       t[0] = HP::g2_lines(q[0]); t[1] = HP::g2_lines(q[1]);
-      su->host_lines = t;
-      su->host_lines_free = [](void *p) { delete[] static_cast<typename HP::G2Lines *>(p); };
+      // (published only when both tables are complete: a throw above leaves host_lines null and the next call builds again)
+      su->host_lines = std::unique_ptr<void, void (*)(void *)>(t.release(), [](void *p) { delete[] static_cast<typename HP::G2Lines *>(p); });
     }
-    return static_cast<const typename HP::G2Lines *>(su->host_lines);
+    return static_cast<const typename HP::G2Lines *>(su->host_lines.get());
   }
   // Few independent checks: ONE wave of the device pairing kernel needs 11.7 ms whatever it carries, a host core 1.0 ms per check
   // (line tables), so up to two checks per pool thread (at most 16) are finished on the host pool from the device's G1 sums.
@@ -1513,30 +1453,30 @@ template <class S, class G> struct Ring {
   }
   static int pairing_check(avrf_ring_setup *su, size_t n, const uint8_t *a_xy, const uint8_t *b_xy, int32_t *ok_out) {
     if (!n) return AVRF_OK;
-    const size_t e1 = 2 * FQB;
+    const size_t e1 = 2 * FQB; RingLane &ln = su->lane[0];
     std::vector<uint8_t> le(2 * n * e1);
     for (size_t i = 0; i < n; i++) { memcpy(&le[(2 * i) * e1], a_xy + i * e1, e1); memcpy(&le[(2 * i + 1) * e1], b_xy + i * e1, e1); }
     const size_t pb = (2 * n * e1 + 255) / 256 * 256, ob = (n * 4 + 255) / 256 * 256;
-    uint8_t *base = (uint8_t *)dev_scratch(su, 1, 2 * pb + ob + 256);
+    uint8_t *base = (uint8_t *)ln.scratch(1, 2 * pb + ob + 256);
     uint8_t *d_le = base; uint32_t *d_pts = (uint32_t *)(base + pb); int32_t *d_ok = (int32_t *)(base + 2 * pb); uint32_t *d_flag = (uint32_t *)(base + 2 * pb + ob);
-    HIP_CHECK(hipMemcpyAsync(d_le, le.data(), 2 * n * e1, hipMemcpyHostToDevice, su->stream));
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, su->stream));
-    launch_g1_bases(su->curve, d_le, 2 * n, d_pts, d_flag, su->stream);
+    HIP_CHECK(hipMemcpyAsync(d_le, le.data(), 2 * n * e1, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream));
+    launch_g1_bases(su->curve, d_le, 2 * n, d_pts, d_flag, ln.stream);
     uint32_t flag = 0;
     if (few_checks(n)) {
       std::vector<uint32_t> pts(2 * n * e1 / 4);
-      HIP_CHECK(hipMemcpyAsync(pts.data(), d_pts, 2 * n * e1, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipStreamSynchronize(su->stream)); HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(pts.data(), d_pts, 2 * n * e1, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
       if (flag) return AVRF_INVALID_DATA;
       host_pair_checks(su, pts.data(), n, ok_out);
       return AVRF_OK;
     }
     ensure_pairing(su);
-    launch_pairing_check(su->ptab, d_pts, n, d_ok, su->stream);
-    HIP_CHECK(hipMemcpyAsync(ok_out, d_ok, n * 4, hipMemcpyDeviceToHost, su->stream));
-    HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, su->stream));
-    HIP_CHECK(hipStreamSynchronize(su->stream)); HIP_CHECK(hipGetLastError());
+    launch_pairing_check(su->ptab, d_pts, n, d_ok, ln.stream);
+    HIP_CHECK(hipMemcpyAsync(ok_out, d_ok, n * 4, hipMemcpyDeviceToHost, ln.stream));
+    HIP_CHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, ln.stream));
+    HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
     return flag ? AVRF_INVALID_DATA : AVRF_OK;
   }
 
@@ -1550,6 +1490,7 @@ template <class S, class G> struct Ring {
   static int verify_batch(avrf_ring_setup *su, size_t n, const uint8_t *commitments, const uint32_t *ring_of_item, size_t n_rings,
                           const uint8_t *instances_xy, const uint8_t *proofs, int32_t *each_status = nullptr) {
     if (n == 0) return AVRF_OK;
+    RingLane &ln = su->lane[0];
     static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
     auto now = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     double t_prev = now();
@@ -1596,12 +1537,12 @@ template <class S, class G> struct Ring {
       const size_t np = 7 * n, cb = (np * FQB + 255) / 256 * 256, xb = (np * 2 * FQB + 255) / 256 * 256;
       std::vector<uint8_t> comp(np * FQB), xy(np * 2 * FQB);
       for (size_t k = 0; k < np; k++) memcpy(&comp[k * FQB], proofs + plen * (k / 7) + g1_off[k % 7], FQB);
-      uint8_t *base = (uint8_t *)dev_scratch(su, 1, cb + xb + np + 256);
-      HIP_CHECK(hipMemcpyAsync(base, comp.data(), np * FQB, hipMemcpyHostToDevice, su->stream));
-      launch_g1_decompress(su->curve, base, np, base + cb, base + cb + xb, su->stream);
-      HIP_CHECK(hipMemcpyAsync(xy.data(), base + cb, np * 2 * FQB, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipMemcpyAsync(dec_ok.data(), base + cb + xb, np, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipStreamSynchronize(su->stream)); HIP_CHECK(hipGetLastError());
+      uint8_t *base = (uint8_t *)ln.scratch(1, cb + xb + np + 256);
+      HIP_CHECK(hipMemcpyAsync(base, comp.data(), np * FQB, hipMemcpyHostToDevice, ln.stream));
+      launch_g1_decompress(su->curve, base, np, base + cb, base + cb + xb, ln.stream);
+      HIP_CHECK(hipMemcpyAsync(xy.data(), base + cb, np * 2 * FQB, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(dec_ok.data(), base + cb + xb, np, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
       for (size_t k = 0; k < np; k++) {
         memset(&dec[k], 0, sizeof dec[k]);
         if (dec_ok[k] == 2) dec[k].inf = true; else memcpy(dec[k].xy, &xy[k * 2 * FQB], 2 * FQB);
@@ -1724,27 +1665,27 @@ template <class S, class G> struct Ring {
       if (!host_pair) ensure_pairing(su);
       const size_t nb = n * TPI;
       const size_t pb = (nb * e1 + 255) / 256 * 256, sb = (nb * 32 + 255) / 256 * 256, ob = (n * 2 * e1 + 255) / 256 * 256, kb = (n * 4 + 255) / 256 * 256;
-      uint8_t *base = (uint8_t *)dev_scratch(su, 1, 2 * pb + sb + ob + 2 * kb + 256);
+      uint8_t *base = (uint8_t *)ln.scratch(1, 2 * pb + sb + ob + 2 * kb + 256);
       uint8_t *d_xy = base; uint32_t *d_b = (uint32_t *)(base + pb), *d_s = (uint32_t *)(base + 2 * pb), *d_pts = (uint32_t *)(base + 2 * pb + sb);
       int32_t *d_ok = (int32_t *)(base + 2 * pb + sb + ob), *d_rec = (int32_t *)(base + 2 * pb + sb + ob + kb);
       uint32_t *d_flag = (uint32_t *)(base + 2 * pb + sb + ob + 2 * kb);
-      HIP_CHECK(hipMemcpyAsync(d_xy, bb.data(), nb * e1, hipMemcpyHostToDevice, su->stream));
+      HIP_CHECK(hipMemcpyAsync(d_xy, bb.data(), nb * e1, hipMemcpyHostToDevice, ln.stream));
       if (su->curve == 0) parallel_for(n, [&](size_t it) { for (size_t j = 0; j < TPI; j++) g1_glv_split_bls(ss[it * TPI + j].l); });   // k -> (k mod z^2, k div z^2)
-      HIP_CHECK(hipMemcpyAsync(d_s, ss.data(), nb * 32, hipMemcpyHostToDevice, su->stream));
-      HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, su->stream)); HIP_CHECK(hipMemsetAsync(d_rec, 0, n * 4, su->stream));
-      launch_g1_bases(su->curve, d_xy, nb, d_b, d_flag, su->stream);
-      if (!host_subgroup) launch_g1_subgroup_check(su->curve, d_b, nb, d_flag, su->stream, d_rec, (uint32_t)TPI);
-      launch_g1_lincomb(su->curve, d_b, d_s, n, (uint32_t)TPI, 11, d_pts, su->stream, su->curve == 0);
+      HIP_CHECK(hipMemcpyAsync(d_s, ss.data(), nb * 32, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream)); HIP_CHECK(hipMemsetAsync(d_rec, 0, n * 4, ln.stream));
+      launch_g1_bases(su->curve, d_xy, nb, d_b, d_flag, ln.stream);
+      if (!host_subgroup) launch_g1_subgroup_check(su->curve, d_b, nb, d_flag, ln.stream, d_rec, (uint32_t)TPI);
+      launch_g1_lincomb(su->curve, d_b, d_s, n, (uint32_t)TPI, 11, d_pts, ln.stream, su->curve == 0);
       std::vector<int32_t> okv(n), rec(n); uint32_t range_flag = 0;
       std::vector<uint32_t> pts(host_pair ? n * 2 * e1 / 4 : 0);
-      if (host_pair) HIP_CHECK(hipMemcpyAsync(pts.data(), d_pts, n * 2 * e1, hipMemcpyDeviceToHost, su->stream));
+      if (host_pair) HIP_CHECK(hipMemcpyAsync(pts.data(), d_pts, n * 2 * e1, hipMemcpyDeviceToHost, ln.stream));
       else {
-        launch_pairing_check(su->ptab, d_pts, n, d_ok, su->stream);
-        HIP_CHECK(hipMemcpyAsync(okv.data(), d_ok, n * 4, hipMemcpyDeviceToHost, su->stream));
+        launch_pairing_check(su->ptab, d_pts, n, d_ok, ln.stream);
+        HIP_CHECK(hipMemcpyAsync(okv.data(), d_ok, n * 4, hipMemcpyDeviceToHost, ln.stream));
       }
-      HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec, n * 4, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipMemcpyAsync(&range_flag, d_flag, 4, hipMemcpyDeviceToHost, su->stream));
-      HIP_CHECK(hipStreamSynchronize(su->stream)); HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec, n * 4, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(&range_flag, d_flag, 4, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
       lap(host_pair ? "per-item G1 sums (device)" : "per-item G1 sums + pairing checks (device)");
       if (range_flag & 1) return AVRF_INVALID_DATA;      // a base with a coordinate >= p (launch_g1_bases): no item to pin it on
       if (host_pair) { host_pair_checks(su, pts.data(), n, okv.data()); lap("pairing checks (host pool)"); }
@@ -1759,7 +1700,7 @@ template <class S, class G> struct Ring {
     // subgroup-checked on the device before they are used (ark-serialize Validate::Yes; BLS12-381 G1 has a large cofactor)
     bool bad = false;
     G1Aff acc1, acc2;
-    g1_msm2(su, b1, s1, b2, s2, !host_subgroup, &bad, &acc1, &acc2);
+    g1_msm2(su, ln, b1, s1, b2, s2, !host_subgroup, &bad, &acc1, &acc2);
     if (bad) { if (each_status) { each_status[0] = AVRF_INVALID_DATA; return AVRF_OK; } return AVRF_INVALID_DATA; }
     lap("two G1 MSMs (device, one chain)");
     const typename HP::G2Lines *lines = host_lines(su);
@@ -1778,18 +1719,18 @@ using RingJ = Ring<SuiteBabyJubJub, G1Bn254>;
 using RingK = Ring<SuiteJubJub, G1Bls12381>;        // JubJub-SHA512-TAI over BLS12-381 (src/suites/jubjub.rs:76-95)
 using RingX = Ring<SuiteBandersnatchShake, G1Bls12381>;   // Bandersnatch with the SHAKE128 transcript (src/suites/bandersnatch_shake128.rs)
 using RingW = Ring<SuiteBandersnatchSW, G1Bls12381>;   // Bandersnatch-SW: the ring proof runs on the TEMapping of the keys (src/ring.rs:75-81)
-template <class R> struct RingTag { using type = R; };
+// f(r) with r a value of the suite's Ring: it has only static members, so r.f(...) names them
 template <class F> static auto with_ring(int suite, F &&f) {
-  switch (suite) { case 1: return f(RingTag<RingJ>{}); case 2: return f(RingTag<RingK>{}); case 4: return f(RingTag<RingW>{}); case 5: return f(RingTag<RingX>{}); default: return f(RingTag<RingB>{}); }
+  switch (suite) { case 1: return f(RingJ{}); case 2: return f(RingK{}); case 4: return f(RingW{}); case 5: return f(RingX{}); default: return f(RingB{}); }
+}
+// the compressed RingCommitment: the three column commitments in the pairing curve's encoding
+static void encode_commitment(int curve, const G1Aff C[3], uint8_t *out) {
+  std::vector<uint8_t> b;
+  for (int i = 0; i < 3; i++) { if (curve == 0) g1_encode<G1Bls12381>(C[i], true, b); else g1_encode<G1Bn254>(C[i], true, b); }
+  memcpy(out, b.data(), b.size());
 }
 
 }  // namespace
-
-template <class F> static int guarded(F f) {
-  try { return f(); }
-  catch (const avrf::HipFailure &e) { fprintf(stderr, "avrf: HIP error %s at %s:%d\n", hipGetErrorString(e.err), e.file, e.line); return AVRF_ERR_NO_DEVICE; }
-  catch (const std::bad_alloc &) { return AVRF_ERR_NO_DEVICE; }
-}
 
 // The tables of all multiples of this setup's SRS powers (kind 0) and witness bases (kind 1): found in the registry or built (once
 // per device and SRS, ~2 s).
@@ -1822,12 +1763,8 @@ static void plan_direct(const avrf_ring_setup *su, uint64_t budget, int c_out[2]
     }
   }
 }
-static void sync_lane_tables(avrf_ring_setup *su) {
-  if (avrf_ring_setup *l = su->lane1) { l->direct = su->direct; l->direct_wit = su->direct_wit; l->direct_tried = su->direct_tried; l->d_wit_bases = su->d_wit_bases; }
-}
 static void drop_tables_locked(avrf_ring_setup *su) {                 // (g_direct_mu held: the registry frees a table with its last holder)
   su->direct.reset(); su->direct_wit.reset();
-  sync_lane_tables(su);
 }
 static std::shared_ptr<DirectEntry> find_direct_locked(const avrf_ring_setup *su, int kind, int c_exact) {
   const size_t nb = direct_bases(su, kind);
@@ -1851,7 +1788,7 @@ static void ensure_direct(avrf_ring_setup *su) {
   su->planned_budget = su->table_budget;
   const bool expl = su->table_budget != UINT64_MAX;
   if (tables_disabled(su)) { std::lock_guard<std::mutex> lk(g_direct_mu); drop_tables_locked(su); return; }
-  with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; R_::ensure_lagrange(su); return 0; });   // the witness bases
+  with_ring(su->suite, [&](auto r) { r.ensure_lagrange(su); return 0; });   // the witness bases
   std::lock_guard<std::mutex> lk(g_direct_mu);
   double budget_gb = direct_env_budget_gb();
   int plan_c[2] = {0, 0}; uint64_t plan_b[2] = {0, 0};
@@ -1860,7 +1797,7 @@ static void ensure_direct(avrf_ring_setup *su) {
   for (int kind = 0; kind < 2; kind++) {
     std::shared_ptr<DirectEntry> &slot = kind ? su->direct_wit : su->direct;
     const size_t nb = direct_bases(su, kind);
-    const uint32_t *bases = kind ? su->d_wit_bases : su->d_srs;
+    const uint32_t *bases = (kind ? su->d_wit_bases : su->d_srs).as();
     if (!bases) continue;
     int c = 0;
     if (expl) {
@@ -1887,13 +1824,12 @@ static void ensure_direct(avrf_ring_setup *su) {
     }
     auto e = std::make_shared<DirectEntry>();
     e->device = su->device; e->kind = kind; e->srs_key = su->g1_raw;
-    try { build_g1_direct_table(su->curve, bases, nb, c, &e->t, su->stream); }
+    try { build_g1_direct_table(su->curve, bases, nb, c, &e->t, su->lane[0].stream); }
     catch (const HipFailure &) { (void)hipGetLastError(); su->table_missed = true; continue; }   // (the entry's destructor frees what was allocated)
     g_direct.push_back(e);
     slot = e;
     budget_gb -= e->t.bytes * 1e-9;
   }
-  sync_lane_tables(su);
 }
 
 extern "C" {
@@ -1903,41 +1839,27 @@ int avrf_ring_setup_load(avrf_ctx *ctx, const uint8_t *srs, size_t srs_len, size
   if (avrf_ctx_busy_(ctx)) return AVRF_ERR_BAD_ARG;
   *out = nullptr;
   if (!ring_suite(avrf_ctx_suite_(ctx))) return AVRF_ERR_BAD_ARG;      // not a RingSuite (Ed25519)
-  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::setup_load(ctx, srs, srs_len, ring_size, out); }); });
+  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r) { return r.setup_load(ctx, srs, srs_len, ring_size, out); }); });
 }
 int avrf_ring_srs_generate(avrf_ctx *ctx, const uint8_t *tau, const uint8_t *g1, const uint8_t *g2, size_t n_g1, uint8_t *out, size_t out_cap, size_t *out_len) {
   if (!ctx || !tau || !g1 || !g2 || !ring_suite(avrf_ctx_suite_(ctx))) return AVRF_ERR_BAD_ARG;
   if (avrf_ctx_busy_(ctx)) return AVRF_ERR_BAD_ARG;
-  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::srs_generate(ctx, tau, g1, g2, n_g1, out, out_cap, out_len); }); });
+  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r) { return r.srs_generate(ctx, tau, g1, g2, n_g1, out, out_cap, out_len); }); });
 }
 int avrf_ring_setup_from_seed(avrf_ctx *ctx, const uint8_t *seed, size_t ring_size, avrf_ring_setup **out) {
   if (!ctx || !seed || !out || !ring_suite(avrf_ctx_suite_(ctx))) return AVRF_ERR_BAD_ARG;
   if (avrf_ctx_busy_(ctx)) return AVRF_ERR_BAD_ARG;
   *out = nullptr;
-  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::setup_from_seed(ctx, seed, ring_size, out); }); });
+  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r) { return r.setup_from_seed(ctx, seed, ring_size, out); }); });
 }
 size_t avrf_ring_pcs_domain_size(int suite, size_t ring_size) {       /* pcs_domain_size, src/ring.rs:810-817: 3 * piop_domain + 1 */
   const size_t L = with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (size_t)S::Fr::BITS; });
-  size_t need = ring_size + 4 + L, N = 1; while (N < need) N <<= 1;
-  return 3 * N + 1;
+  return 3 * ring_domain_size(ring_size, L) + 1;
 }
 void avrf_ring_setup_free(avrf_ring_setup *su) {
   if (!su) return;
   (void)hipSetDevice(su->device);
-  void *d[] = {su->d_srs, su->d_tw_n, su->d_tw_n_inv, su->d_tw_4n, su->d_tw_4n_inv, su->d_buf, su->d_l4, su->d_srs_table, su->d_wit_table, su->d_wit_bases,
-               su->d_scr[0], su->d_scr[1], su->d_scr[2], su->d_scr[3], su->d_scr[4], su->d_scr[5]};
-  for (void *p : d) if (p) (void)hipFree(p);
-  su->ws.release();
-  su->ptab.release();
-  if (su->host_lines && su->host_lines_free) su->host_lines_free(su->host_lines);
   { std::lock_guard<std::mutex> lk(g_direct_mu); drop_tables_locked(su); }
-  if (avrf_ring_setup *l = su->lane1) {                                // only what the lane owns
-    void *o[] = {l->d_buf, l->d_scr[0], l->d_scr[1], l->d_scr[2], l->d_scr[3], l->d_scr[4], l->d_scr[5]};
-    for (void *p : o) if (p) (void)hipFree(p);
-    l->ws.release();
-    (void)hipStreamDestroy(l->stream);
-    delete l;
-  }
   delete su;
 }
 size_t avrf_ring_max_ring_size(const avrf_ring_setup *su) { return su ? su->keyset : 0; }
@@ -2000,7 +1922,7 @@ int avrf_ring_setup_tables(const avrf_ring_setup *su, uint64_t out[10]) {
   out[1] = expl ? su->table_budget : off ? 0 : (uint64_t)(direct_env_budget_gb() * 1e9);
   if (su->direct) { out[2] = (uint64_t)su->direct->t.c; out[3] = (uint64_t)su->direct->t.rows; out[4] = su->direct->t.bytes; }
   if (su->direct_wit) { out[5] = (uint64_t)su->direct_wit->t.c; out[6] = (uint64_t)su->direct_wit->t.rows; out[7] = su->direct_wit->t.bytes; }
-  out[8] = su->table_batches->load();
+  out[8] = su->table_batches.load();
   out[9] = held_bytes_locked(su->device);
   return AVRF_OK;
 }
@@ -2011,15 +1933,13 @@ int avrf_ring_index(avrf_ring_setup *su, const uint8_t *pks_xy, size_t n_keys, a
   *out = nullptr;
   if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;                       // verifier-only setup
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
-  int st = guarded([&] { return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::index(su, pks_xy, n_keys, out); }); });
-  if (st == AVRF_OK && commitment_out) {
-    std::vector<uint8_t> b;
-    for (int i = 0; i < 3; i++) { if (su->curve == 0) g1_encode<G1Bls12381>((*out)->C[i], true, b); else g1_encode<G1Bn254>((*out)->C[i], true, b); }
-    memcpy(commitment_out, b.data(), b.size());
-  }
-  return st;
+  std::unique_ptr<avrf_ring_key> k;
+  if (int st = guarded([&] { return with_ring(su->suite, [&](auto r) { return r.index(su, pks_xy, n_keys, k); }); })) return st;
+  if (commitment_out) encode_commitment(su->curve, k->C, commitment_out);
+  *out = k.release();
+  return AVRF_OK;
 }
-void avrf_ring_key_free(avrf_ring_key *k) { if (!k) return; if (k->d_fixed4) (void)hipFree(k->d_fixed4); if (k->d_fixed_coef) (void)hipFree(k->d_fixed_coef); if (k->d_points_pre) (void)hipFree(k->d_points_pre); delete k; }
+void avrf_ring_key_free(avrf_ring_key *k) { delete k; }
 
 int avrf_ring_vk_builder_new(avrf_ring_setup *su, avrf_ring_vk_builder **out) {
   if (!su || !out) return AVRF_ERR_BAD_ARG;
@@ -2027,7 +1947,7 @@ int avrf_ring_vk_builder_new(avrf_ring_setup *su, avrf_ring_vk_builder **out) {
   *out = nullptr;
   if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
-  return guarded([&] { return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::builder_new(su, out); }); });
+  return guarded([&] { return with_ring(su->suite, [&](auto r) { return r.builder_new(su, out); }); });
 }
 void avrf_ring_vk_builder_free(avrf_ring_vk_builder *b) { delete b; }
 size_t avrf_ring_vk_builder_free_slots(const avrf_ring_vk_builder *b) { return b ? b->setup->keyset - b->curr : 0; }
@@ -2035,13 +1955,11 @@ int avrf_ring_vk_builder_append(avrf_ring_vk_builder *b, const uint8_t *pks_xy, 
   if (!b || (n && !pks_xy)) return AVRF_ERR_BAD_ARG;
   if (avrf_ctx_busy_(b->setup->ctx)) return AVRF_ERR_BAD_ARG;
   if (hipSetDevice(b->setup->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
-  return guarded([&] { return with_ring(b->setup->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::builder_append(b, pks_xy, n); }); });
+  return guarded([&] { return with_ring(b->setup->suite, [&](auto r) { return r.builder_append(b, pks_xy, n); }); });
 }
 int avrf_ring_vk_builder_finalize(const avrf_ring_vk_builder *b, uint8_t *commitment_out) {
   if (!b || !commitment_out) return AVRF_ERR_BAD_ARG;
-  std::vector<uint8_t> o;
-  for (int i = 0; i < 3; i++) { if (b->setup->curve == 0) g1_encode<G1Bls12381>(b->C[i], true, o); else g1_encode<G1Bn254>(b->C[i], true, o); }
-  memcpy(commitment_out, o.data(), o.size());
+  encode_commitment(b->setup->curve, b->C, commitment_out);
   return AVRF_OK;
 }
 
@@ -2059,25 +1977,32 @@ int avrf_ring_prove(avrf_ring_key *k, size_t n, const uint32_t *key_index, const
   if (n >= 32 && n <= 1024) chunk = (n + 1) / 2;
   if (const char *e = getenv("AVRF_RING_CHUNK")) { long v = atol(e); if (v >= 1 && v <= 4096) chunk = (size_t)v; }   // (test hook: re-read per call)
   avrf_ring_setup *su = k->setup;
+  if (!n) return AVRF_OK;
+  for (size_t i = 0; i < n; i++) if (key_index[i] >= k->n_keys) return AVRF_ERR_BAD_ARG;   // (a refused call builds nothing)
+  // everything the chunks share is built here, before a chunk is in flight: the tables of all multiples and the witness table
   if (n >= 64) if (int st = guarded([&] { ensure_direct(su); return (int)AVRF_OK; })) return st;
-  auto run = [&](avrf_ring_setup *lane, size_t i) {
+  if (int st = guarded([&] { return with_ring(su->suite, [&](auto r) { r.ensure_lagrange(su); return (int)AVRF_OK; }); })) return st;
+  auto run = [&](RingLane &lane, size_t i) {
     const size_t m = n - i < chunk ? n - i : chunk;
     return guarded([&] {
-      return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::prove_chunk(k, lane, m, key_index + i, blindings + 32 * i, blinding_mode == 1, proofs_out + plen * i); }); });
+      return with_ring(su->suite, [&](auto r) { return r.prove_chunk(k, lane, m, key_index + i, blindings + 32 * i, blinding_mode == 1, proofs_out + plen * i); }); });
   };
   const char *le = getenv("AVRF_RING_LANES"); const bool one_lane = le && atoi(le) == 1;
   if (n <= chunk || one_lane) {
-    for (size_t i = 0; i < n; i += chunk) if (int st = run(su, i)) return st;
+    for (size_t i = 0; i < n; i += chunk) if (int st = run(su->lane[0], i)) return st;
     return AVRF_OK;
   }
-  // two chunks in flight: chunks alternate between the setup's own stream/scratch and its second lane
-  avrf_ring_setup *lanes[2] = {su, nullptr};
-  if (int st = guarded([&] { lanes[1] = with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::second_lane(su); }); return (int)AVRF_OK; })) return st;
+  // two chunks in flight: chunks alternate between the two lanes
+  RingLane *lanes[2] = {&su->lane[0], &su->lane[1]};
+  if (int st = guarded([&] {                                           // the second lane's stream, on the first two-lane call
+        RingLane &l = su->lane[1];
+        if (!l.owns_stream) { HIP_CHECK(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking)); l.owns_stream = true; }
+        return (int)AVRF_OK; })) return st;
   std::atomic<int> status{AVRF_OK};
   std::thread th[2];
   for (int t = 0; t < 2; t++) th[t] = std::thread([&, t] {
     if (hipSetDevice(su->device) != hipSuccess) { status = AVRF_ERR_NO_DEVICE; return; }
-    for (size_t i = (size_t)t * chunk; i < n && status == AVRF_OK; i += 2 * chunk) if (int st = run(lanes[t], i)) status = st;
+    for (size_t i = (size_t)t * chunk; i < n && status == AVRF_OK; i += 2 * chunk) if (int st = run(*lanes[t], i)) status = st;
   });
   for (auto &x : th) x.join();
   return status;
@@ -2094,19 +2019,19 @@ int avrf_ring_verifier_setup_load(avrf_ctx *ctx, const uint8_t *params, size_t p
   if (avrf_ctx_busy_(ctx)) return AVRF_ERR_BAD_ARG;
   *out = nullptr;
   if (!ring_suite(avrf_ctx_suite_(ctx))) return AVRF_ERR_BAD_ARG;
-  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::verifier_setup_load(ctx, params, params_len, ring_size, out); }); });
+  return guarded([&] { return with_ring(avrf_ctx_suite_(ctx), [&](auto r) { return r.verifier_setup_load(ctx, params, params_len, ring_size, out); }); });
 }
 int avrf_ring_pcs_verifier_params_serialize(avrf_ring_setup *su, int compress, uint8_t *out, size_t out_cap, size_t *out_len) {
   if (!su) return AVRF_ERR_BAD_ARG;
   std::vector<uint8_t> v;
-  int st = guarded([&] { return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::verifier_params_serialize(su, compress != 0, v); }); });
+  int st = guarded([&] { return with_ring(su->suite, [&](auto r) { return r.verifier_params_serialize(su, compress != 0, v); }); });
   return st ? st : copy_out(v, out, out_cap, out_len);
 }
 int avrf_ring_setup_serialize(avrf_ring_setup *su, int compress, uint8_t *out, size_t out_cap, size_t *out_len) {
   if (!su) return AVRF_ERR_BAD_ARG;
   if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
   std::vector<uint8_t> v;
-  int st = guarded([&] { return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::setup_serialize(su, compress != 0, v); }); });
+  int st = guarded([&] { return with_ring(su->suite, [&](auto r) { return r.setup_serialize(su, compress != 0, v); }); });
   return st ? st : copy_out(v, out, out_cap, out_len);
 }
 int avrf_ring_builder_params_serialize(avrf_ring_setup *su, int compress, uint8_t *out, size_t out_cap, size_t *out_len) {
@@ -2115,7 +2040,7 @@ int avrf_ring_builder_params_serialize(avrf_ring_setup *su, int compress, uint8_
   if (!su->n_srs) return AVRF_SRS_LOOKUP_FAILED;
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
   std::vector<uint8_t> v;
-  int st = guarded([&] { return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::builder_params_serialize(su, compress != 0, v); }); });
+  int st = guarded([&] { return with_ring(su->suite, [&](auto r) { return r.builder_params_serialize(su, compress != 0, v); }); });
   return st ? st : copy_out(v, out, out_cap, out_len);
 }
 
@@ -2125,14 +2050,14 @@ int avrf_ring_verify_each(avrf_ring_setup *su, size_t n, const uint8_t *ring_com
   if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
   return guarded([&] {
-    return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::verify_batch(su, n, ring_commitments, ring_of_item, n_rings, instances_xy, ring_proofs, status_out); }); });
+    return with_ring(su->suite, [&](auto r) { return r.verify_batch(su, n, ring_commitments, ring_of_item, n_rings, instances_xy, ring_proofs, status_out); }); });
 }
 
 int avrf_ring_pairing_check(avrf_ring_setup *su, size_t n, const uint8_t *a_xy, const uint8_t *b_xy, int32_t *ok_out) {
   if (!su || (n && (!a_xy || !b_xy || !ok_out))) return AVRF_ERR_BAD_ARG;
   if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
-  return guarded([&] { return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::pairing_check(su, n, a_xy, b_xy, ok_out); }); });
+  return guarded([&] { return with_ring(su->suite, [&](auto r) { return r.pairing_check(su, n, a_xy, b_xy, ok_out); }); });
 }
 
 int avrf_ring_batch_verify(avrf_ring_setup *su, size_t n, const uint8_t *ring_commitments, size_t n_rings, const uint32_t *ring_of_item,
@@ -2141,7 +2066,7 @@ int avrf_ring_batch_verify(avrf_ring_setup *su, size_t n, const uint8_t *ring_co
   if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
   return guarded([&] {
-    return with_ring(su->suite, [&](auto r_) { using R_ = typename decltype(r_)::type; return R_::verify_batch(su, n, ring_commitments, ring_of_item, n_rings, instances_xy, ring_proofs); }); });
+    return with_ring(su->suite, [&](auto r) { return r.verify_batch(su, n, ring_commitments, ring_of_item, n_rings, instances_xy, ring_proofs); }); });
 }
 
 }  // extern "C"
