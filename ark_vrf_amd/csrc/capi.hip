@@ -147,14 +147,17 @@ int avrf_ctx_create(int suite, int device, avrf_ctx **out) { return ctx_create(s
 
 void avrf_ctx_destroy(avrf_ctx *c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->lane_owner) (void)hipStreamSynchronize(c->own.stream);
-  DevBuf *bufs[] = {&c->d_pks, &c->d_ios, &c->d_io_off, &c->d_ads, &c->d_ad_off, &c->d_proofs, &c->d_sks, &c->d_c, &c->d_z,
-                    &c->d_flags, &c->d_misc, &c->d_out, &c->d_status, &c->d_fixed, &c->d_weights, &c->d_rec, &c->d_tabs};
-  for (DevBuf *b : bufs) b->release();
-  c->h_c.release(); c->h_flags.release(); c->h_io.release(); c->h_msg.release();
-  c->own.release();                                                    // stream + workspace (nothing for a pool slot)
-  delete c;
+  delete c;                                                            // (~avrf_ctx, capi_internal.h: the order things go in)
+}
+
+// MSM over the first n terms of the context's lane (c->L->d_pre, c->L->d_scalars) on its stream, waited for.  What the engine
+// refuses is AVRF_ERR_BAD_ARG, a failed HIP call or allocation AVRF_ERR_NO_DEVICE (guarded).
+static int lane_msm(avrf_ctx *c, size_t n, HostExt *r) {
+  return guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; });
+}
+// the same for nv scalar vectors over the lane's first n bases through the single-launch form (msm.h msm_te_small_vectors): r[v]
+static int lane_msm_vectors(avrf_ctx *c, size_t n, size_t nv, HostExt *r) {
+  return guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, nv, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; });
 }
 
 static int finish_point(avrf_ctx *c, const HostExt &r, uint8_t out_xy[64]) {
@@ -184,7 +187,7 @@ int avrf_msm_te(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *s
     HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
   c->staged_kind = 0;
-  if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm(c, n, &r)) return e;
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   return finish_point(c, r, out_xy);
 }
@@ -209,7 +212,7 @@ int avrf_msm_te_mont(avrf_ctx *c, size_t n, const uint8_t *bases_mont_xy, const 
     HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
   c->staged_kind = 0;
-  if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm(c, n, &r)) return e;
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   uint8_t canon[64];
   finish_point(c, r, canon);
@@ -561,7 +564,7 @@ int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]) {
   else AVRF_BATCH(c->suite, ped_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
                                       c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
   const double t3 = now_us();
-  if (int e = guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->stream, c->pend) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->chain(), c->stream) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   c->timing[3] = t3 - t2;
   c->run_msm_us = now_us() - t3;
   c->run_phase = 2;
@@ -575,7 +578,7 @@ int batch_end(avrf_ctx *c, int kind) {
   HIP_TRY(hipSetDevice(c->device));
   const double t3 = now_us();
   HostExt r;
-  if (int e = guarded([&] { return msm_te_finish(c->suite, c->L->ws, c->stream, &r, c->pend) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = guarded([&] { return msm_te_finish(c->suite, c->L->ws, c->chain(), c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   double t4 = now_us();
   int st = point_is_identity(c, r) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
   double t5 = now_us();
@@ -615,7 +618,7 @@ int avrf_pedersen_batch_run(avrf_ctx *c) { return batch_run(c, 2); }
 static int run_call(avrf_ctx *c, int (*phase)(avrf_ctx *, int)) {
   if (!c) return AVRF_ERR_BAD_ARG;
   if (!c->staged_kind) {
-    if (c->run_phase) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); c->run_phase = 0; c->L->ws.pending_armed = false; }
+    if (c->run_phase) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); c->run_phase = 0; c->chain().disarm(); }
     return AVRF_ERR_BAD_ARG;
   }
   return phase(c, c->staged_kind);
@@ -739,7 +742,7 @@ int avrf_thin_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t firs
   BatchDev b = batch_of(c);
   AVRF_BATCH(c->suite, thin_terms(b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
                                   c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
-  if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm(c, c->n_terms, &r)) return e;
   return finish_point(c, r, out_xy);
 }
 
@@ -775,7 +778,7 @@ int avrf_pedersen_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t 
   BatchDev b = batch_of(c);
   AVRF_BATCH(c->suite, ped_terms(b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
                                  c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
-  if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm(c, c->n_terms, &r)) return e;
   return finish_point(c, r, out_xy);
 }
 
@@ -868,7 +871,7 @@ static Route prove_one_as_msm(avrf_ctx *c, bool have_pk, bool tiny, uint8_t *pro
   uint8_t *d_state = c->d_misc.as<uint8_t>();
   AVRF_SINGLE(c->suite, thin_prove_begin(b, c->L->d_scalars.as<uint32_t>(), c->L->d_pre.as<te_pre_raw>(), d_state, c->stream, tiny));
   HostExt r;
-  if (int e = guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), nt, c->L->ws, c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm(c, nt, &r)) return e;
   uint8_t *rxy = c->h_c.as<uint8_t>();                                  // (pinned; the challenges are not in use by a prover)
   finish_point(c, r, rxy);
   HIP_TRY(hipMemcpyAsync(d_state + sb, rxy, 64, hipMemcpyHostToDevice, c->stream));
@@ -893,12 +896,12 @@ static Route prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out
   uint32_t *d_sc = c->L->d_scalars.as<uint32_t>(); te_pre_raw *d_pre = c->L->d_pre.as<te_pre_raw>();
   AVRF_SINGLE(c->suite, ped_prove_begin(b, d_sc, d_pre, d_state, d_wts, c->stream));
   HostExt r[2];
-  if (int e = guarded([&] { return msm_te_device(c->suite, d_pre, d_sc, 2, c->L->ws, c->stream, &r[0]) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm(c, 2, &r[0])) return e;
   uint8_t *pts = c->h_c.as<uint8_t>();                                  // pinned: Yb | R | Ok
   finish_point(c, r[0], pts);
   HIP_TRY(hipMemcpyAsync(d_pts, pts, 64, hipMemcpyHostToDevice, c->stream));
   AVRF_SINGLE(c->suite, ped_prove_mid(b, d_sc, d_pre, d_state, d_wts, d_pts, c->stream));
-  if (int e = guarded([&] { return msm_te_small_vectors(c->suite, d_pre, d_sc, nt, 2, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm_vectors(c, nt, 2, r)) return e;
   finish_point(c, r[0], pts + 64); finish_point(c, r[1], pts + 128);
   HIP_TRY(hipMemcpyAsync(d_pts + 64, pts + 64, 128, hipMemcpyHostToDevice, c->stream));
   AVRF_SINGLE(c->suite, ped_prove_end(b, d_state, d_pts, c->d_out.as<uint8_t>(), blindings_out ? d_blind : nullptr, c->d_flags.as<uint32_t>(), c->stream));
@@ -946,7 +949,7 @@ static Route verify_ped_one_as_msm(avrf_ctx *c, int32_t *status_out) {
                                    c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)nt, c->stream));
   }
   HostExt r[2];
-  if (int e = guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), nt, 2, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm_vectors(c, nt, 2, r)) return e;
   status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : (point_is_identity(c, r[0]) && point_is_identity(c, r[1])) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
   return AVRF_OK;
 }
@@ -1099,7 +1102,7 @@ static int smul_common(avrf_ctx *c, size_t n, const uint8_t *scalars, const uint
       launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
       HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
       HostExt r[32];
-      if (int e = guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, n, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+      if (int e = lane_msm_vectors(c, n, n, r)) return e;
       if (*c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
       for (size_t i = 0; i < n; i++) finish_point(c, r[i], out_xy + 64 * i);
       return AVRF_OK;

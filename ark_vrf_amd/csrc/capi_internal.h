@@ -14,33 +14,16 @@
 
 namespace avrf {
 
-struct DevBuf {
-  void *p = nullptr; size_t cap = 0;
+// Staging buffers of a context: msm.h's owned storage under another size rule -- rounded up, so that batches of slowly growing
+// size do not reallocate -- and with an error code instead of a throw, for HIP_TRY.  Freed with whatever holds them.
+template <bool PINNED> struct StageBuf : OwnedMem<PINNED> {
   hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
+    if (bytes <= this->cap && this->p) return hipSuccess;
+    return this->reset(PINNED ? bytes + 256 : bytes + bytes / 8 + 256);
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T *as() const { return (T *)p; }
 };
-struct PinBuf {
-  void *p = nullptr; size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    hipError_t e = hipHostMalloc(&p, bytes + 256);
-    if (e == hipSuccess) cap = bytes + 256;
-    return e;
-  }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-  template <class T> T *as() const { return (T *)p; }
-};
+using DevBuf = StageBuf<false>;
+using PinBuf = StageBuf<true>;
 
 template <class F> int guarded(F f) {
   try { return f(); }
@@ -51,12 +34,18 @@ template <class F> int guarded(F f) {
 // An execution lane: the stream an MSM chain runs on, its workspace and the term arrays the chain reads.  A context owns one;
 // the slots of a pool (pool.hip) borrow the pool's lanes for the MSM phase of their batches, so that many staged batches can
 // wait for their weight transcript without each holding a stream and ~150 MB of workspace.  One chain in flight per lane.
-struct Lane {
+// (the stream is a base so that it outlives every member: workspace and term arrays are freed before the stream they ran on goes)
+struct LaneStream {
   hipStream_t stream = nullptr;
+  LaneStream() = default;
+  LaneStream(const LaneStream &) = delete;
+  LaneStream &operator=(const LaneStream &) = delete;
+  ~LaneStream() { if (stream) (void)hipStreamDestroy(stream); }
+};
+struct Lane : LaneStream {
   int queued = 0;                 // chains enqueued and not yet collected (pool.hip)
   MsmWorkspace ws;
   DevBuf d_scalars, d_pre, d_gpart;
-  void release() { ws.release(); d_scalars.release(); d_pre.release(); d_gpart.release(); if (stream) (void)hipStreamDestroy(stream); stream = nullptr; }
 };
 
 }  // namespace avrf
@@ -65,7 +54,8 @@ struct avrf_ctx {
   int suite = 0, device = 0;
   hipStream_t stream = nullptr;   // where the next piece of work is enqueued: the own lane's stream, or what a pool points it at
   avrf::Lane own; avrf::Lane *L = &own;
-  avrf::MsmPending *pend = nullptr;   // pool slots: where the MSM chain's results land (several chains queue on one lane); else the lane's workspace
+  avrf::MsmChain *pend = nullptr;   // pool slots: the record of the slot's MSM chain (several chains queue on one lane); else the lane's own
+  avrf::MsmChain &chain() const { return pend ? *pend : L->ws.own; }
   bool lane_owner = true;         // false: a pool slot -- no stream or workspace of its own (L and stream are set by the pool)
   // staged batch
   int validate = 0;               // avrf_ctx_set_validation: 0 unchecked (typed-point callers), 1 on-curve, 2 + subgroup
@@ -86,6 +76,10 @@ struct avrf_ctx {
   int run_phase = 0;              // batch_begin / batch_hash / batch_end
   bool unit_weights = false;      // batch_launch: every item's weight is 1 (avrf_thin_verify runs ONE item as its own equation through the MSM path)
   double run_t0 = 0, run_begin_us = 0, run_msm_us = 0;
+  // The order a context goes in: its device made current and its own stream drained; then the members, last first -- the staging
+  // buffers, then `own`: workspace and term arrays, the stream last.  (A pool slot's context has no stream or workspace of its own; the
+  // pool detaches it from the lane it borrowed before it dies, pool.hip ~Slot.)
+  ~avrf_ctx() { (void)hipSetDevice(device); if (own.stream) (void)hipStreamSynchronize(own.stream); }
 };
 
 namespace avrf {

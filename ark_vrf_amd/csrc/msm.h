@@ -15,29 +15,46 @@ struct te_ext_raw { uint32_t w[32]; };   // x | y | t | z
 // thrown by the device engines on a failed HIP call; every extern "C" entry point catches it and returns AVRF_ERR_NO_DEVICE
 struct HipFailure { hipError_t err; const char *file; int line; };
 
-// One owned device allocation of exactly the bytes asked for: freed by its destructor on every path out, a throw included (hipFree
-// waits for the device itself, so work in flight on a stream is over before the memory goes).  Movable, not copyable: a struct that
-// holds one cannot be copied by accident.  (capi_internal.h DevBuf is the other kind: staging buffers that round their size up so that
-// batches of slowly growing size do not reallocate, released by hand with their context.)
-struct DevMem {
+// One owned allocation of exactly the bytes asked for, device memory (DevMem) or page-locked host memory (PinMem): freed by its
+// destructor on every path out, a throw included (hipFree waits for the device itself, so work in flight on a stream is over before
+// the memory goes).  Movable, not copyable: a struct that holds one cannot be copied by accident.  (capi_internal.h DevBuf / PinBuf are
+// the same storage under another size rule: staging buffers that round up so that batches of slowly growing size do not reallocate.)
+template <bool PINNED> struct OwnedMem {
   void *p = nullptr; size_t cap = 0;
-  DevMem() = default;
-  explicit DevMem(size_t bytes) { ensure(bytes); }
-  DevMem(const DevMem &) = delete;
-  DevMem &operator=(const DevMem &) = delete;
-  DevMem(DevMem &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-  DevMem &operator=(DevMem &&o) noexcept { if (this != &o) { (void)release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
-  ~DevMem() { (void)release(); }
-  // grow-only: at least `bytes` afterwards, the contents are NOT kept across a growth.  Throws HipFailure (the buffer is then empty).
-  void ensure(size_t bytes) {
-    if (bytes <= cap) return;
-    if (hipError_t e = release()) throw HipFailure{e, __FILE__, __LINE__};
-    if (hipError_t e = hipMalloc(&p, bytes)) { p = nullptr; throw HipFailure{e, __FILE__, __LINE__}; }
+  OwnedMem() = default;
+  explicit OwnedMem(size_t bytes) { ensure(bytes); }
+  OwnedMem(const OwnedMem &) = delete;
+  OwnedMem &operator=(const OwnedMem &) = delete;
+  OwnedMem(OwnedMem &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  OwnedMem &operator=(OwnedMem &&o) noexcept { if (this != &o) { (void)release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  ~OwnedMem() { (void)release(); }
+  // frees what it holds and allocates exactly `bytes`; the buffer is empty after a failure
+  hipError_t reset(size_t bytes) {
+    if (hipError_t e = release()) return e;
+    if (hipError_t e = PINNED ? hipHostMalloc(&p, bytes) : hipMalloc(&p, bytes)) { p = nullptr; return e; }
     cap = bytes;
+    return hipSuccess;
   }
-  hipError_t release() { hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; cap = 0; return e; }
+  // grow-only: at least `bytes` afterwards, the contents are NOT kept across a growth.  Throws HipFailure (the buffer is then empty).
+  void ensure(size_t bytes) { if (bytes > cap) if (hipError_t e = reset(bytes)) throw HipFailure{e, __FILE__, __LINE__}; }
+  hipError_t release() { hipError_t e = !p ? hipSuccess : PINNED ? hipHostFree(p) : hipFree(p); p = nullptr; cap = 0; return e; }
   template <class T = uint32_t> T *as() const { return (T *)p; }
   explicit operator bool() const { return p != nullptr; }
+};
+using DevMem = OwnedMem<false>;
+using PinMem = OwnedMem<true>;
+// an owned HIP event, under the same rules
+struct DevEvent {
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(const DevEvent &) = delete;
+  DevEvent &operator=(const DevEvent &) = delete;
+  DevEvent(DevEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+  DevEvent &operator=(DevEvent &&o) noexcept { if (this != &o) { destroy(); e = o.e; o.e = nullptr; } return *this; }
+  ~DevEvent() { destroy(); }
+  hipError_t create(unsigned flags = hipEventDefault) { destroy(); return hipEventCreateWithFlags(&e, flags); }
+  void destroy() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  operator hipEvent_t() const { return e; }
 };
 
 struct MsmPlan {
@@ -48,45 +65,45 @@ struct MsmPlan {
 };
 MsmPlan msm_plan(size_t n, int scalar_bits);
 
-// Device workspace owned by a context; grows on demand, never shrinks.
-struct MsmWorkspace {
-  uint16_t *keys = nullptr;      // nwin * n      bucket | sign << 15
-  uint32_t *sorted = nullptr;    // nwin * n      term index | sign << 31, grouped by (window, bucket)
-  uint32_t *hist = nullptr;      // nwin * ntiles * nb   per-tile histograms -> per-tile prefixes
-  uint32_t *cnts = nullptr;      // nwin * nb     entries per bucket
-  uint32_t *offsets = nullptr;   // nwin * nb     first entry of the bucket in sorted[]
-  uint32_t *win_tot = nullptr;   // nwin          entries per window
-  uint32_t *lane_base = nullptr; // nwin + 1      first k_accumulate lane of every window
-  uint32_t *heavy = nullptr;     // nwin * nb     buckets fed by many lanes (summed by k_heavy_sum)
-  uint32_t *plan_dev = nullptr;  // {entries per lane, lanes used, heavy buckets}
-  uint32_t *plan_host = nullptr; // pinned copy of plan_dev
-  // accumulator arrays (layout of the curve policy: te_ext 128 B, G1 XYZZ 4 * Fq)
-  uint32_t *buckets = nullptr;   // nwin * nb
-  uint32_t *rc = nullptr;        // nwin * (rows + cols) partial sums of the bucket reduction
-  uint32_t *part = nullptr;      // lanes + buckets slots: partial sum of lane t for bucket g at slot t + g
-  uint32_t *bits = nullptr;      // nwin * c
-  uint32_t *bits_host = nullptr; // pinned
-  size_t cap_n = 0, cap_slots = 0, cap_buckets = 0, cap_bits = 0, cap_part = 0, cap_hist = 0, cap_vwin = 0;   // cap_buckets.. in bytes
-  // HIP events bracketing the dominant kernel (k_accumulate) on the launch stream
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double accum_ms_total = 0; uint64_t accum_launches = 0; float accum_ms_last = 0;
-  MsmPlan last_plan = {0, 0, 0, 0};
+// What ONE enqueued launch chain sends back to the host: the results (bit sums, window triples or finished points, in the accumulator
+// layout of the curve policy), the device's plan and the timing events of the dominant kernel.  Every workspace has one of its own,
+// which serves a lane that runs one chain at a time.  A caller that queues several chains behind each other on one lane (stream +
+// workspace; the device-side workspace is reused in stream order) hands in a record per chain instead: pool.hip gives every slot one.
+struct MsmChain {
+  PinMem bits_host, plan_host;   // results | 64 bytes: copy of the workspace's plan_dev
+  DevEvent ev0, ev1;             // bracket the dominant kernel (k_accumulate) on the launch stream
+  MsmPlan plan = {0, 0, 0, 0}; int ret = 0;
   int wsum_lg = 4;               // scale 2^lg of the third point of a window triple (TE window sums)
-  // an enqueued launch chain whose results have not been collected yet (msm_te_enqueue / msm_te_finish)
-  MsmPlan pending_plan = {0, 0, 0, 0}; int pending_ret = 0; size_t pending_n = 0; bool pending_armed = false;
-  void ensure(size_t n, const MsmPlan &p, size_t acc_bytes, size_t batch, size_t lanes_max, size_t part_bytes = 0);   // part_bytes: one slot of `part` (0: acc_bytes)
-  void release();
+  size_t n = 0;
+  bool armed = false;            // enqueued and not collected yet (msm_te_enqueue / msm_te_finish)
+  void ensure(size_t bytes);     // the events, the plan words and room for `bytes` of results (grow-only)
+  void disarm() { armed = false; }   // whoever gives up on an enqueued chain (an error between enqueue and finish) says so
+  void release() { *this = MsmChain(); }
 };
 
-// Results of ONE enqueued twisted-Edwards chain kept outside the workspace, so that several chains can be queued behind each
-// other on one lane (stream + workspace): the device-side workspace is reused in stream order, what comes back to the host
-// (window sums, the plan, the timing events of the dominant kernel) lands here.  pool.hip gives every slot one.
-struct MsmPending {
-  uint32_t *bits_host = nullptr, *plan_host = nullptr; size_t cap_bytes = 0;   // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  MsmPlan plan = {0, 0, 0, 0}; int ret = 0, wsum_lg = 4; size_t n = 0; bool armed = false;
-  void ensure(size_t bytes);
-  void release();
+// Device workspace owned by a lane; grows on demand, never shrinks, frees itself.
+struct MsmWorkspace {
+  DevMem keys;       // nwin * n      u16: bucket | sign << 15
+  DevMem sorted;     // nwin * n      term index | sign << 31, grouped by (window, bucket)
+  DevMem hist;       // nwin * ntiles * nb   per-tile histograms -> per-tile prefixes
+  DevMem cnts;       // nwin * nb     entries per bucket
+  DevMem offsets;    // nwin * nb     first entry of the bucket in sorted[]
+  DevMem win_tot;    // nwin          entries per window
+  DevMem lane_base;  // nwin + 1      first k_accumulate lane of every window
+  DevMem heavy;      // nwin * nb     buckets fed by many lanes (summed by k_heavy_sum)
+  DevMem plan_dev;   // {entries per lane, lanes used, heavy buckets}
+  // accumulator arrays (layout of the curve policy: te_ext 128 B, G1 XYZZ 4 * Fq)
+  DevMem buckets;    // nwin * nb
+  DevMem rc;         // nwin * (rows + cols) partial sums of the bucket reduction
+  DevMem part;       // lanes + buckets slots: partial sum of lane t for bucket g at slot t + g
+  DevMem bits;       // nwin * c
+  MsmChain own;      // the record of a chain that no caller's record was handed in for; its results are sized with `bits`
+  bool owns(const MsmChain &rec) const { return &rec == &own; }
+  // per lane, read from outside (avrf_kernel_stats, avrf_pool_stats, ring.hip's trace): k_accumulate time and the plan of the chains collected
+  double accum_ms_total = 0; uint64_t accum_launches = 0; float accum_ms_last = 0;
+  MsmPlan last_plan = {0, 0, 0, 0};
+  void ensure(size_t n, const MsmPlan &p, size_t acc_bytes, size_t batch, size_t lanes_max, size_t part_bytes = 0);   // part_bytes: one slot of `part` (0: acc_bytes)
+  void release() { *this = MsmWorkspace(); }
 };
 
 // MSM of n precomputed device points (Montgomery form) with n plain 256-bit scalars (8 x u32 LE,
@@ -94,16 +111,17 @@ struct MsmPending {
 int msm_te_device(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n,
                   MsmWorkspace &ws, hipStream_t stream, HostExt *out);
 // the same in two halves: msm_te_enqueue launches the whole kernel chain and the copies back on `stream` and returns without
-// waiting; msm_te_finish waits for the stream and folds the window sums on the host.  One chain in flight per workspace.
-// pend != nullptr: the chain's results go to *pend (see MsmPending); msm_te_finish then does NOT wait for the stream -- the
-// caller has seen an event recorded behind the chain complete.
-int msm_te_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, MsmPending *pend = nullptr);
-int msm_te_finish(int suite, MsmWorkspace &ws, hipStream_t stream, HostExt *out, MsmPending *pend = nullptr);
+// waiting; msm_te_finish collects the chain and folds the window sums on the host.  `rec` is the record the chain reports to.
+// ws.own: one chain in flight per workspace, and msm_te_finish waits for the stream.  A caller's record (window-sum form only,
+// msm_te_pending_supported): msm_te_finish does NOT wait -- the caller has seen an event recorded behind the chain complete.
+// msm_te_finish on a record that no enqueue armed returns -1.
+int msm_te_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream);
+int msm_te_finish(int suite, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out);
 // two or more scalar vectors over the SAME n <= 2048 bases (vector v's scalars start at element v * n) through the single-launch
 // form: out[v] = sum_t s_{v,t} P_t.  Synchronises the stream.  Returns -1 when the shape is not the single-launch one.
 int msm_te_small_vectors(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, size_t n_vectors, MsmWorkspace &ws, hipStream_t stream,
                          HostExt *out);
-bool msm_te_pending_supported(int suite);   // external results exist for the window-sum form of the chain only
+bool msm_te_pending_supported(int suite);   // a caller's record is taken by the window-sum form of the chain only
 
 // G1 MSM over a short-Weierstrass curve (curve: 0 BLS12-381, 1 BN254): d_bases = n Montgomery affine
 // points (2 * Fq words each, (0,0) = infinity), d_scalars = n plain 256-bit scalars (< r).

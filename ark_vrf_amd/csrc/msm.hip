@@ -694,101 +694,42 @@ static void poison(void *p, size_t bytes, int which) {
   if (const char *e = getenv("AVRF_MSM_POISON_SKIP")) { if (atoi(e) == which) return; }
   HIP_CHECK(hipMemset(p, 0xA5, bytes)); if (!getenv("AVRF_MSM_POISON_NOSYNC")) HIP_CHECK(hipDeviceSynchronize());
 }
-template <class T> static void grow(T *&p, size_t &cap, size_t need, size_t elem, int which = 0) {
-  if (need <= cap) return;
-  if (p) HIP_CHECK(hipFree(p));
-  p = nullptr; cap = 0;
-  HIP_CHECK(hipMalloc(&p, need * elem + 64));
-  poison(p, need * elem + 64, which);
-  cap = need;
+// one buffer of the workspace: grow-only, exactly `bytes` when it grows; `which` is its number for the poison hook
+static void ws_buf(DevMem &m, size_t bytes, int which) {
+  if (bytes <= m.cap) return;
+  m.ensure(bytes);
+  poison(m.p, bytes, which);
 }
 
+// (buffers listed together grow together: their sizes rise and fall with the same quantity)
 void MsmWorkspace::ensure(size_t n, const MsmPlan &p, size_t acc_bytes, size_t batch, size_t lanes_max, size_t part_bytes) {
   const size_t vwin = (size_t)p.nwin * batch;           // virtual windows
   const size_t nbk = vwin * p.nb, nbits = vwin * p.c;
   const size_t need_n = vwin * n;
   const size_t ntiles = (n + tile_len_for(n, vwin) - 1) / tile_len_for(n, vwin);
-  if (need_n > cap_n) {
-    if (keys) HIP_CHECK(hipFree(keys));
-    if (sorted) HIP_CHECK(hipFree(sorted));
-    keys = nullptr; sorted = nullptr; cap_n = 0;
-    HIP_CHECK(hipMalloc(&keys, need_n * 2 + 16)); HIP_CHECK(hipMalloc(&sorted, need_n * 4 + 16));
-    poison(keys, need_n * 2 + 16, 1); poison(sorted, need_n * 4 + 16, 2);
-    cap_n = need_n;
-  }
-  grow(hist, cap_hist, nbk * ntiles, 4, 3);
-  if (nbk > cap_slots) {
-    if (cnts) HIP_CHECK(hipFree(cnts));
-    if (offsets) HIP_CHECK(hipFree(offsets));
-    if (heavy) HIP_CHECK(hipFree(heavy));
-    cnts = offsets = heavy = nullptr; cap_slots = 0;
-    HIP_CHECK(hipMalloc(&cnts, nbk * 4)); HIP_CHECK(hipMalloc(&offsets, nbk * 4)); HIP_CHECK(hipMalloc(&heavy, nbk * 4));
-    poison(cnts, nbk * 4, 4); poison(offsets, nbk * 4, 5); poison(heavy, nbk * 4, 6);
-    cap_slots = nbk;
-  }
-  if (vwin > cap_vwin) {
-    if (win_tot) HIP_CHECK(hipFree(win_tot));
-    if (lane_base) HIP_CHECK(hipFree(lane_base));
-    win_tot = lane_base = nullptr; cap_vwin = 0;
-    HIP_CHECK(hipMalloc(&win_tot, (vwin + 64) * 4)); HIP_CHECK(hipMalloc(&lane_base, (vwin + 64) * 4));
-    poison(win_tot, (vwin + 64) * 4, 7); poison(lane_base, (vwin + 64) * 4, 8);
-    cap_vwin = vwin;
-  }
-  if (!plan_dev) { HIP_CHECK(hipMalloc(&plan_dev, 64)); HIP_CHECK(hipHostMalloc(&plan_host, 64)); plan_host[0] = plan_host[1] = 0; }
-  if (nbk * acc_bytes > cap_buckets) {
-    if (buckets) HIP_CHECK(hipFree(buckets));
-    if (rc) HIP_CHECK(hipFree(rc));
-    buckets = rc = nullptr; cap_buckets = 0;
-    HIP_CHECK(hipMalloc(&buckets, nbk * acc_bytes));
-    HIP_CHECK(hipMalloc(&rc, nbk * acc_bytes));               // >= nwin * (NR + NC)
-    poison(buckets, nbk * acc_bytes, 9); poison(rc, nbk * acc_bytes, 10);
-    cap_buckets = nbk * acc_bytes;
-  }
-  grow(part, cap_part, (lanes_max + nbk + 64) * (part_bytes ? part_bytes : acc_bytes), 1, 11);
-  if (nbits * acc_bytes > cap_bits) {
-    if (bits) HIP_CHECK(hipFree(bits));
-    if (bits_host) HIP_CHECK(hipHostFree(bits_host));
-    bits = bits_host = nullptr; cap_bits = 0;
-    HIP_CHECK(hipMalloc(&bits, nbits * acc_bytes));
-    poison(bits, nbits * acc_bytes, 12);
-    HIP_CHECK(hipHostMalloc(&bits_host, nbits * acc_bytes));
-    cap_bits = nbits * acc_bytes;
-  }
-}
-void MsmWorkspace::release() {
-  void *dev[] = {keys, sorted, hist, cnts, offsets, heavy, win_tot, lane_base, plan_dev, buckets, rc, part, bits};
-  for (void *q : dev) if (q) (void)hipFree(q);
-  if (bits_host) (void)hipHostFree(bits_host);
-  if (plan_host) (void)hipHostFree(plan_host);
-  if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); ev0 = ev1 = nullptr;
-  keys = nullptr; sorted = hist = cnts = offsets = heavy = win_tot = lane_base = plan_dev = plan_host = nullptr;
-  buckets = rc = part = bits = bits_host = nullptr;
-  cap_n = cap_slots = cap_buckets = cap_bits = cap_part = cap_hist = cap_vwin = 0;
+  ws_buf(keys, need_n * 2 + 16, 1); ws_buf(sorted, need_n * 4 + 16, 2);
+  ws_buf(hist, nbk * ntiles * 4 + 64, 3);
+  ws_buf(cnts, nbk * 4, 4); ws_buf(offsets, nbk * 4, 5); ws_buf(heavy, nbk * 4, 6);
+  ws_buf(win_tot, (vwin + 64) * 4, 7); ws_buf(lane_base, (vwin + 64) * 4, 8);
+  plan_dev.ensure(64);
+  ws_buf(buckets, nbk * acc_bytes, 9); ws_buf(rc, nbk * acc_bytes, 10);               // rc: >= nwin * (NR + NC)
+  ws_buf(part, (lanes_max + nbk + 64) * (part_bytes ? part_bytes : acc_bytes) + 64, 11);
+  ws_buf(bits, nbits * acc_bytes, 12); own.ensure(nbits * acc_bytes);
 }
 
-void MsmPending::ensure(size_t bytes) {
-  if (!plan_host) HIP_CHECK(hipHostMalloc(&plan_host, 64));
-  if (!ev0) { HIP_CHECK(hipEventCreate(&ev0)); HIP_CHECK(hipEventCreate(&ev1)); }
-  if (bytes <= cap_bytes) return;
-  if (bits_host) HIP_CHECK(hipHostFree(bits_host));
-  bits_host = nullptr; cap_bytes = 0;
-  HIP_CHECK(hipHostMalloc(&bits_host, bytes));
-  cap_bytes = bytes;
-}
-void MsmPending::release() {
-  if (bits_host) (void)hipHostFree(bits_host);
-  if (plan_host) (void)hipHostFree(plan_host);
-  if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1);
-  bits_host = plan_host = nullptr; ev0 = ev1 = nullptr; cap_bytes = 0; armed = false;
+void MsmChain::ensure(size_t bytes) {
+  if (!plan_host) { plan_host.ensure(64); plan_host.as()[0] = plan_host.as()[1] = 0; }
+  if (!ev0) { HIP_CHECK(ev0.create()); HIP_CHECK(ev1.create()); }
+  bits_host.ensure(bytes);
 }
 
-// waits for the launch chain msm_device enqueued on `stream` and books its plan / k_accumulate timing
-static void msm_wait(MsmWorkspace &ws, hipStream_t stream) {
-  HIP_CHECK(hipStreamSynchronize(stream));
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventElapsedTime(&ws.accum_ms_last, ws.ev0, ws.ev1));
-  ws.pending_plan.lpb = (int)ws.plan_host[0];
-  ws.accum_ms_total += ws.accum_ms_last; ws.accum_launches++; ws.last_plan = ws.pending_plan;
+// Collects the chain msm_device enqueued on `stream` with `rec` as its record and books its plan / k_accumulate timing on the lane.
+// The workspace's own record: waits for the stream.  A caller's record: no wait, the caller has seen an event behind the chain complete.
+static void msm_collect(MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
+  if (ws.owns(rec)) { HIP_CHECK(hipStreamSynchronize(stream)); HIP_CHECK(hipGetLastError()); }
+  HIP_CHECK(hipEventElapsedTime(&ws.accum_ms_last, rec.ev0, rec.ev1));
+  rec.plan.lpb = (int)rec.plan_host.as()[0];
+  ws.accum_ms_total += ws.accum_ms_last; ws.accum_launches++; ws.last_plan = rec.plan;
 }
 
 // Small MSMs (a BatchVerifier of up to a few hundred items, ONE independent verification run as its own equation, the verifier's
@@ -830,35 +771,42 @@ k_msm_tiny_bits(const uint32_t *__restrict__ bases, const uint32_t *__restrict__
   if (t == 0) CV::store_acc(out + ((size_t)v * gridDim.x + p) * CV::ACC_WORDS, acc);
 }
 
-// Runs the whole device pipeline for one MSM and leaves the nwin*c bit sums T_p in ws.bits_host
-// (accumulator layout of CV); returns the number of bit sums.
-// `batch` scalar vectors of length n over the SAME n bases (d_scalars = batch x n x 8 words): every vector
-// gets its own nwin windows; returns the number of bit sums per vector (vector b's sums start at b * that).
-// Fixed-base mode (table_c != 0): d_bases is a window table T[w * table_stride + i] = 2^(table_c * w) * P_i, so all
-// windows of a vector share ONE bucket set: downstream it is a 1-window MSM over n * nwin (table) bases.
-// Throws HipFailure when a HIP call fails.
+// What msm_device is told beyond bases, scalars and the lane.  The defaults: one scalar vector over plain bases, waited for.
+struct MsmLaunch {
+  size_t batch = 1;                      // scalar vectors of length n over the SAME n bases (d_scalars = batch x n x 8 words): every vector gets its own nwin windows
+  // fixed-base mode (table_c != 0): d_bases is a window table T[w * table_stride + i] = 2^(table_c * w) * P_i, so all windows of a
+  // vector share ONE bucket set: downstream it is a 1-window MSM over n * nwin (table) bases
+  int table_c = 0; size_t table_stride = 0;
+  size_t scalar_stride = 0;              // vector b's scalars start at element b * scalar_stride (0: n)
+  const uint32_t *d_base_idx = nullptr;  // sparse form (msm.h msm_g1_fixed_device)
+  bool defer = false;                    // everything up to the copies back is enqueued, nothing is waited for: the caller collects later (msm_collect)
+  int scalars_mont = 0;                  // the scalars are Montgomery limbs (msm.h msm_g1_fixed_device)
+};
+
+// Runs the whole device pipeline for one MSM and leaves the nwin*c bit sums T_p in rec.bits_host (accumulator layout of CV).
+// `rec` is the record the chain reports to: the workspace's own or a caller's (single-launch and window-sum forms only).
+// Returns the number of bit sums per vector (vector b's sums start at b * that).  Throws HipFailure when a HIP call fails.
 template <class CV>
-static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n_in, int scalar_bits, MsmWorkspace &ws, hipStream_t stream,
-                      size_t batch = 1, int table_c = 0, size_t table_stride = 0, size_t scalar_stride = 0, const uint32_t *d_base_idx = nullptr,
-                      bool defer = false, int scalars_mont = 0, MsmPending *pend = nullptr) {
+static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n_in, int scalar_bits, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream,
+                      const MsmLaunch &o = MsmLaunch()) {
+  const size_t batch = o.batch, scalar_stride = o.scalar_stride ? o.scalar_stride : n_in;
+  const int table_c = o.table_c, scalars_mont = o.scalars_mont;
+  const uint32_t *const d_base_idx = o.d_base_idx;
   MsmPlan p = msm_plan(n_in, scalar_bits);
-  if (!scalar_stride) scalar_stride = n_in;                            // vector b's scalars start at b * scalar_stride
+  auto finish = [&]() { if (!o.defer) msm_collect(ws, rec, stream); };
   // (the G1 callers take eight or more vectors back as finished points -- device Horner below -- so they keep that form)
   if (n_in <= MSM_TINY_TERMS && batch <= (CV::FIXED_TABLE ? (size_t)7 : MSM_TINY_VECTORS) && !table_c && !d_base_idx && !scalars_mont && msm_env().tiny) {
     p.c = 1; p.nwin = scalar_bits; p.nb = 1; p.lpb = 0;
     const size_t acc_b = (size_t)CV::ACC_WORDS * 4, nbits = (size_t)scalar_bits;
     ws.ensure(n_in, p, acc_b, batch, 256);
-    if (!ws.ev0) { HIP_CHECK(hipEventCreate(&ws.ev0)); HIP_CHECK(hipEventCreate(&ws.ev1)); }
-    if (pend) { pend->ensure(batch * nbits * acc_b); pend->plan_host[0] = 0; }
-    hipEvent_t e0 = pend ? pend->ev0 : ws.ev0, e1 = pend ? pend->ev1 : ws.ev1;
-    HIP_CHECK(hipEventRecord(e0, stream));
+    rec.ensure(batch * nbits * acc_b); rec.plan_host.as()[0] = 0; rec.plan = p;
+    HIP_CHECK(hipEventRecord(rec.ev0, stream));
     unsigned threads = 64; while (threads < n_in && threads < 256) threads <<= 1;           // a power of two of waves: the LDS butterfly halves it
     hipLaunchKernelGGL(k_msm_tiny_bits<CV>, dim3((unsigned)nbits, (unsigned)batch), dim3(threads), (threads / 64) * acc_b, stream, d_bases, d_scalars, (uint32_t)n_in,
-                       (uint32_t)scalar_stride, ws.bits);
-    HIP_CHECK(hipEventRecord(e1, stream));
-    HIP_CHECK(hipMemcpyAsync(pend ? pend->bits_host : ws.bits_host, ws.bits, batch * nbits * acc_b, hipMemcpyDeviceToHost, stream));
-    if (pend) pend->plan = p; else ws.pending_plan = p;
-    if (!defer) msm_wait(ws, stream);
+                       (uint32_t)scalar_stride, ws.bits.as());
+    HIP_CHECK(hipEventRecord(rec.ev1, stream));
+    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, batch * nbits * acc_b, hipMemcpyDeviceToHost, stream));
+    finish();
     return (int)nbits;
   }
   const size_t lanes_target = accumulate_lanes<CV>();
@@ -870,7 +818,7 @@ static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t
     dig_nwin = (scalar_bits + 1 + table_c - 1) / table_c;
     p.c = table_c; p.nb = 1 << (table_c - 1); p.nwin = 1;
     n = n_in * (size_t)dig_nwin;                                        // one window of n_in * dig_nwin keys per vector
-    remap_n = (uint32_t)n_in; remap_stride = (uint32_t)table_stride;
+    remap_n = (uint32_t)n_in; remap_stride = (uint32_t)o.table_stride;
   }
   // fixed-base mode: the reduction kernels run over CV::red (G1: general additions on the unsaturated limbs, buckets in raw limbs)
   using RV = typename CV::red;
@@ -884,51 +832,44 @@ static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t
   const uint32_t tile_len = tile_len_for(n, vwin), ntiles = (uint32_t)((n + tile_len - 1) / tile_len);
   const size_t lds_bytes = (size_t)p.nb * 4;
   hipLaunchKernelGGL(k_digits, dim3((unsigned)((n_in + 255) / 256), (unsigned)batch), b256, 0, stream, d_scalars, (uint32_t)n_in, (uint32_t)scalar_stride,
-                     p.c, dig_nwin, ws.keys, scalars_mont);
-  hipLaunchKernelGGL(k_hist, dim3(ntiles, vwin), b256, lds_bytes, stream, ws.keys, (uint32_t)n, tile_len, p.c, ws.hist);
-  hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)((p.nb + 255) / 256), vwin), b256, 0, stream, ws.hist, ntiles, p.c, ws.cnts);
-  hipLaunchKernelGGL(k_scan_offs, dim3(vwin), dim3(1024), 0, stream, (const uint32_t *)ws.cnts, (uint32_t)n, p.c, ws.offsets, ws.win_tot);
-  hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, stream, (const uint32_t *)ws.win_tot, vwin, (uint32_t)lanes_target, (uint32_t)msm_env().per_min,
-                     ws.lane_base, ws.plan_dev);
-  hipLaunchKernelGGL(k_scatter, dim3(8u * ((vwin + 7u) / 8u) * ntiles), b256, lds_bytes, stream, ws.keys, (uint32_t)n, tile_len, p.c, ws.hist, ws.offsets, ws.sorted,
-                     remap_n, remap_stride, d_base_idx, ntiles, vwin);
-  if (!ws.ev0) { HIP_CHECK(hipEventCreate(&ws.ev0)); HIP_CHECK(hipEventCreate(&ws.ev1)); }
-  if (pend) pend->ensure((size_t)vwin * 3 * acc_bytes);
-  hipEvent_t ev0 = pend ? pend->ev0 : ws.ev0, ev1 = pend ? pend->ev1 : ws.ev1;
-  if (CV::ZERO_IS_IDENTITY) HIP_CHECK(hipMemsetAsync(ws.buckets, 0, (size_t)nbk * acc_bytes, stream));   // empty buckets
-  HIP_CHECK(hipEventRecord(ev0, stream));
-  hipLaunchKernelGGL(k_accumulate<CV>, dim3((unsigned)((lanes_max + 255) / 256)), b256, accumulate_shape<CV>().lds, stream, d_bases, (const uint32_t *)ws.sorted,
-                     (const uint32_t *)ws.offsets, (const uint32_t *)ws.win_tot, (const uint32_t *)ws.lane_base, (const uint32_t *)ws.plan_dev, vwin,
-                     (uint32_t)p.nb, (uint32_t)n, ws.part);
-  HIP_CHECK(hipEventRecord(ev1, stream));
+                     p.c, dig_nwin, ws.keys.as<uint16_t>(), scalars_mont);
+  hipLaunchKernelGGL(k_hist, dim3(ntiles, vwin), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)n, tile_len, p.c, ws.hist.as());
+  hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)((p.nb + 255) / 256), vwin), b256, 0, stream, ws.hist.as(), ntiles, p.c, ws.cnts.as());
+  hipLaunchKernelGGL(k_scan_offs, dim3(vwin), dim3(1024), 0, stream, ws.cnts.as(), (uint32_t)n, p.c, ws.offsets.as(), ws.win_tot.as());
+  hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, stream, ws.win_tot.as(), vwin, (uint32_t)lanes_target, (uint32_t)msm_env().per_min,
+                     ws.lane_base.as(), ws.plan_dev.as());
+  hipLaunchKernelGGL(k_scatter, dim3(8u * ((vwin + 7u) / 8u) * ntiles), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)n, tile_len, p.c, ws.hist.as(),
+                     ws.offsets.as(), ws.sorted.as(), remap_n, remap_stride, d_base_idx, ntiles, vwin);
+  rec.ensure((size_t)vwin * 3 * acc_bytes);   // the window triples, which are all a caller's record is sent (the workspace's own is sized with `bits`)
+  if (CV::ZERO_IS_IDENTITY) HIP_CHECK(hipMemsetAsync(ws.buckets.p, 0, (size_t)nbk * acc_bytes, stream));   // empty buckets
+  HIP_CHECK(hipEventRecord(rec.ev0, stream));
+  hipLaunchKernelGGL(k_accumulate<CV>, dim3((unsigned)((lanes_max + 255) / 256)), b256, accumulate_shape<CV>().lds, stream, d_bases, ws.sorted.as(),
+                     ws.offsets.as(), ws.win_tot.as(), ws.lane_base.as(), ws.plan_dev.as(), vwin, (uint32_t)p.nb, (uint32_t)n, ws.part.as());
+  HIP_CHECK(hipEventRecord(rec.ev1, stream));
   auto bucket_sums = [&](auto tag) {
     using BV = typename decltype(tag)::type;
-    hipLaunchKernelGGL(k_bucket_sum<BV>, dim3((nbk + 255) / 256), b256, 0, stream, (const uint32_t *)ws.offsets, (const uint32_t *)ws.cnts,
-                       (const uint32_t *)ws.lane_base, ws.plan_dev, nbk, (uint32_t)p.nb, (uint32_t)n, (const uint32_t *)ws.part, ws.buckets, ws.heavy);
-    hipLaunchKernelGGL(k_heavy_sum<BV>, dim3(nbk < 1024 ? nbk : 1024), b256, 4 * acc_bytes, stream, (const uint32_t *)ws.offsets, (const uint32_t *)ws.cnts,
-                       (const uint32_t *)ws.lane_base, (const uint32_t *)ws.plan_dev, (uint32_t)p.nb, (uint32_t)n, (const uint32_t *)ws.part, ws.buckets,
-                       (const uint32_t *)ws.heavy);
+    hipLaunchKernelGGL(k_bucket_sum<BV>, dim3((nbk + 255) / 256), b256, 0, stream, ws.offsets.as(), ws.cnts.as(), ws.lane_base.as(), ws.plan_dev.as(), nbk,
+                       (uint32_t)p.nb, (uint32_t)n, ws.part.as(), ws.buckets.as(), ws.heavy.as());
+    hipLaunchKernelGGL(k_heavy_sum<BV>, dim3(nbk < 1024 ? nbk : 1024), b256, 4 * acc_bytes, stream, ws.offsets.as(), ws.cnts.as(), ws.lane_base.as(),
+                       ws.plan_dev.as(), (uint32_t)p.nb, (uint32_t)n, ws.part.as(), ws.buckets.as(), ws.heavy.as());
   };
   if (red) bucket_sums(type_tag<RV>{}); else bucket_sums(type_tag<CV>{});
-  HIP_CHECK(hipMemcpyAsync(pend ? pend->plan_host : ws.plan_host, ws.plan_dev, 8, hipMemcpyDeviceToHost, stream));
-  // defer: the caller collects the results later (msm_wait): everything up to the copies back is enqueued, nothing is waited for
-  if (pend) pend->plan = p; else ws.pending_plan = p;
-  auto finish = [&]() { if (!defer) msm_wait(ws, stream); };
+  HIP_CHECK(hipMemcpyAsync(rec.plan_host.p, ws.plan_dev.p, 8, hipMemcpyDeviceToHost, stream));
+  rec.plan = p;
   if constexpr (CV::WINDOW_SUMS) if (batch == 1 && msm_env().window_sums) {
     // weighted bucket sum of every window with the four-lanes-per-point kernels (te_quad.h): three points per window come
     // back; the host folds them into its window Horner (scales 1, 2^4, 16 m), so the device does no doublings at all
     const uint32_t nb = (uint32_t)p.nb;
     const uint32_t wpw = nb >= 256 ? 16u : 1u, m = nb >= 256 ? nb / 256 : (nb >= 16 ? nb / 16 : 1u);
     const uint32_t nwaves = vwin * wpw;
-    hipLaunchKernelGGL(k_wsum_q1<typename CV::suite>, dim3((nwaves + 3) / 4), b256, 0, stream, (const uint32_t *)ws.buckets, nb, m, wpw, nwaves, ws.rc);
-    hipLaunchKernelGGL(k_wsum_q2<typename CV::suite>, dim3(vwin), dim3(64), 0, stream, (const uint32_t *)ws.rc, wpw, ws.bits);
-    HIP_CHECK(hipMemcpyAsync(pend ? pend->bits_host : ws.bits_host, ws.bits, (size_t)vwin * 3 * acc_bytes, hipMemcpyDeviceToHost, stream));
+    hipLaunchKernelGGL(k_wsum_q1<typename CV::suite>, dim3((nwaves + 3) / 4), b256, 0, stream, ws.buckets.as(), nb, m, wpw, nwaves, ws.rc.as());
+    hipLaunchKernelGGL(k_wsum_q2<typename CV::suite>, dim3(vwin), dim3(64), 0, stream, ws.rc.as(), wpw, ws.bits.as());
+    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, (size_t)vwin * 3 * acc_bytes, hipMemcpyDeviceToHost, stream));
+    rec.wsum_lg = 4; while ((1u << rec.wsum_lg) < 16 * m) rec.wsum_lg++;
     finish();
-    int lg = 4; while ((1u << lg) < 16 * m) lg++;
-    if (pend) pend->wsum_lg = lg; else ws.wsum_lg = lg;
     return -(int)vwin;                                       // negative: bits_host holds window triples, not bit sums
   }
-  if (pend) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // external results exist for the window-sum form only
+  if (!ws.owns(rec)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // a caller's record is taken by the window-sum form only
   const int h = (p.c - 1) / 2;
   const uint32_t tasks = (1u << h) + ((uint32_t)p.nb >> h);
   const int nbits = (int)vwin * p.c;
@@ -941,70 +882,54 @@ static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t
     const uint32_t wps_max = batch <= msm_env().wsum_blk_max ? 4 : 1;
     while (wps < wps_max && (uint32_t)p.nb >= 64 * wps * 2) wps *= 2;
     if (wps > 1) {
-      hipLaunchKernelGGL(k_wsum_blk<RV>, dim3((unsigned)batch), dim3(64 * wps), (size_t)wps * 2 * acc_bytes, stream, (const uint32_t *)ws.buckets,
-                         (uint32_t)p.nb, ws.rc);
+      hipLaunchKernelGGL(k_wsum_blk<RV>, dim3((unsigned)batch), dim3(64 * wps), (size_t)wps * 2 * acc_bytes, stream, ws.buckets.as(),
+                         (uint32_t)p.nb, ws.rc.as());
     } else {
       uint32_t lps_log = 6;                                // lanes per bucket set: enough waves to cover the chip, <= nb
       while (lps_log > 2 && (batch << (lps_log - 1)) >= 2048 * 64) lps_log--;
       while ((1u << lps_log) > (uint32_t)p.nb) lps_log--;
-      hipLaunchKernelGGL(k_wsum<RV>, dim3((unsigned)(((batch << lps_log) + 255) / 256)), b256, 0, stream, (const uint32_t *)ws.buckets, (uint32_t)p.nb,
-                         (uint32_t)batch, lps_log, ws.rc);
+      hipLaunchKernelGGL(k_wsum<RV>, dim3((unsigned)(((batch << lps_log) + 255) / 256)), b256, 0, stream, ws.buckets.as(), (uint32_t)p.nb,
+                         (uint32_t)batch, lps_log, ws.rc.as());
     }
-    HIP_CHECK(hipMemcpyAsync(ws.bits_host, ws.rc, batch * (size_t)RV::OUT_WORDS * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * (size_t)RV::OUT_WORDS * 4, hipMemcpyDeviceToHost, stream));
     finish();
     return p.c;
   }
   if (p.nb <= 256 && batch >= 8) {
-    hipLaunchKernelGGL(k_bits_direct<CV>, dim3(((unsigned)nbits + 127) / 128), dim3(128), 0, stream, (const uint32_t *)ws.buckets, p.c, (uint32_t)nbits, ws.bits);
+    hipLaunchKernelGGL(k_bits_direct<CV>, dim3(((unsigned)nbits + 127) / 128), dim3(128), 0, stream, ws.buckets.as(), p.c, (uint32_t)nbits, ws.bits.as());
   } else {
-    hipLaunchKernelGGL(k_rowcol<CV>, dim3(((size_t)vwin * tasks * 64 + 255) / 256), b256, 0, stream, (const uint32_t *)ws.buckets, p.c, h,
-                       vwin * tasks, ws.rc);
-    hipLaunchKernelGGL(k_bits<CV>, dim3(((size_t)nbits * 64 + 255) / 256), b256, 0, stream, (const uint32_t *)ws.buckets, (const uint32_t *)ws.rc,
-                       p.c, h, (uint32_t)nbits, ws.bits);
+    hipLaunchKernelGGL(k_rowcol<CV>, dim3(((size_t)vwin * tasks * 64 + 255) / 256), b256, 0, stream, ws.buckets.as(), p.c, h,
+                       vwin * tasks, ws.rc.as());
+    hipLaunchKernelGGL(k_bits<CV>, dim3(((size_t)nbits * 64 + 255) / 256), b256, 0, stream, ws.buckets.as(), ws.rc.as(),
+                       p.c, h, (uint32_t)nbits, ws.bits.as());
   }
   if (batch >= 8) {                                        // device Horner: only `batch` points come back
-    hipLaunchKernelGGL(k_horner<CV>, dim3(((unsigned)batch + 63) / 64), dim3(64), 0, stream, (const uint32_t *)ws.bits, (uint32_t)(p.nwin * p.c),
-                       (uint32_t)batch, ws.rc);
-    HIP_CHECK(hipMemcpyAsync(ws.bits_host, ws.rc, batch * acc_bytes, hipMemcpyDeviceToHost, stream));
+    hipLaunchKernelGGL(k_horner<CV>, dim3(((unsigned)batch + 63) / 64), dim3(64), 0, stream, ws.bits.as(), (uint32_t)(p.nwin * p.c),
+                       (uint32_t)batch, ws.rc.as());
+    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * acc_bytes, hipMemcpyDeviceToHost, stream));
   } else {
-    HIP_CHECK(hipMemcpyAsync(ws.bits_host, ws.bits, (size_t)nbits * acc_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, (size_t)nbits * acc_bytes, hipMemcpyDeviceToHost, stream));
   }
   finish();
   return p.nwin * p.c;
 }
 
 template <class S>
-static int msm_te_enqueue_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, MsmPending *pend) {
-  if (pend) {
-    pend->n = n; pend->ret = 0; pend->armed = true;
-    if (n) pend->ret = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, stream, 1, 0, 0, 0, nullptr, /*defer=*/true, 0, pend);
-    return 0;
-  }
-  ws.pending_n = n; ws.pending_ret = 0; ws.pending_armed = true;
-  if (n) ws.pending_ret = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, stream, 1, 0, 0, 0, nullptr, /*defer=*/true);
+static int msm_te_enqueue_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
+  rec.n = n; rec.ret = 0; rec.armed = true;
+  MsmLaunch o; o.defer = true;
+  if (n) rec.ret = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, rec, stream, o);
   return 0;
 }
 template <class S>
-static int msm_te_finish_impl(MsmWorkspace &ws, hipStream_t stream, HostExt *out, MsmPending *pend) {
+static int msm_te_finish_impl(MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out) {
   using HT = HostTe<S>;
   *out = HT::identity();
-  int nbits, c, lg; const uint32_t *bh;
-  if (pend) {
-    if (!pend->armed) return -1;
-    pend->armed = false;
-    if (pend->n == 0) return 0;
-    HIP_CHECK(hipEventElapsedTime(&ws.accum_ms_last, pend->ev0, pend->ev1));   // (the caller saw the chain complete)
-    pend->plan.lpb = (int)pend->plan_host[0];
-    ws.accum_ms_total += ws.accum_ms_last; ws.accum_launches++; ws.last_plan = pend->plan;
-    nbits = pend->ret; c = pend->plan.c; lg = pend->wsum_lg; bh = pend->bits_host;
-  } else {
-    if (!ws.pending_armed) return -1;                     // nothing was enqueued (or another call consumed the chain): an error, never the identity
-    ws.pending_armed = false;
-    if (ws.pending_n == 0) return 0;
-    ws.pending_n = 0;
-    msm_wait(ws, stream);
-    nbits = ws.pending_ret; c = ws.last_plan.c; lg = ws.wsum_lg; bh = ws.bits_host;
-  }
+  if (!rec.armed) return -1;                              // nothing was enqueued (or another call consumed the chain): an error, never the identity
+  rec.disarm();
+  if (rec.n == 0) return 0;
+  msm_collect(ws, rec, stream);
+  const int nbits = rec.ret, c = rec.plan.c, lg = rec.wsum_lg; const uint32_t *bh = rec.bits_host.as();
   HostExt acc = HT::identity();
   if (nbits < 0) {                                        // window triples: W_w = P1 + 2^4 P2 + 2^lg P3; sum_w 2^(c w) W_w
     for (int w = -nbits - 1; w >= 0; w--) {
@@ -1023,21 +948,22 @@ static int msm_te_finish_impl(MsmWorkspace &ws, hipStream_t stream, HostExt *out
   return 0;
 }
 
-int msm_te_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, MsmPending *pend) {
+int msm_te_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
   if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
-  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_enqueue_impl<S>(d_pre, d_scalars, n, ws, stream, pend); });
+  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_enqueue_impl<S>(d_pre, d_scalars, n, ws, rec, stream); });
 }
-int msm_te_finish(int suite, MsmWorkspace &ws, hipStream_t stream, HostExt *out, MsmPending *pend) {
+int msm_te_finish(int suite, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out) {
   if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
-  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_finish_impl<S>(ws, stream, out, pend); });
+  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_finish_impl<S>(ws, rec, stream, out); });
 }
 template <class S>
 static int msm_te_small_vectors_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, size_t nv, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
   using HT = HostTe<S>;
   if (!n || n > MSM_TINY_TERMS || !nv || nv > MSM_TINY_VECTORS || !msm_env().tiny) return -1;
-  const int nbits = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, stream, nv, 0, 0, n);
-  ws.pending_armed = false;
-  const uint32_t *bh = ws.bits_host;
+  MsmLaunch o; o.batch = nv; o.scalar_stride = n;
+  const int nbits = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, ws.own, stream, o);
+  ws.own.disarm();
+  const uint32_t *bh = ws.own.bits_host.as();
   parallel_for(nv, [&](size_t v) {                          // the vectors' Horners side by side (sum_p 2^p T_p)
     HostExt acc = HT::identity();
     for (int i = nbits - 1; i >= 0; i--) { acc = HT::dbl(acc); acc = HT::add(acc, HT::from_raw32(bh + ((size_t)v * nbits + i) * 32)); }
@@ -1056,8 +982,8 @@ bool msm_te_pending_supported(int suite) {
 }
 int msm_te_device(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n,
                   MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
-  if (int e = msm_te_enqueue(suite, d_pre, d_scalars, n, ws, stream)) return e;
-  return msm_te_finish(suite, ws, stream, out);
+  if (int e = msm_te_enqueue(suite, d_pre, d_scalars, n, ws, ws.own, stream)) return e;
+  return msm_te_finish(suite, ws, ws.own, stream, out);
 }
 
 // ---------------------------------------------------------------- G1 (KZG) MSM
@@ -1180,19 +1106,18 @@ void build_g1_table(int curve, const uint32_t *d_bases, size_t n, int c, int nwi
 }
 
 template <class C>
-static int msm_g1_impl(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
-                       size_t batch, int table_c = 0, size_t table_stride = 0, size_t scalar_stride = 0, const uint32_t *d_base_idx = nullptr,
-                       int scalars_mont = 0) {
+static int msm_g1_impl(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy, const MsmLaunch &o) {
   using HG = HostG1<C>;
   constexpr size_t OUT = 8 * C::Fq::N;                    // bytes of one affine result
-  int nbits = n ? msm_device<G1Curve<C>>(d_bases, d_scalars, n, C::Fr::BITS, ws, stream, batch, table_c, table_stride, scalar_stride, d_base_idx, false, scalars_mont) : 0;
+  const size_t batch = o.batch; const int table_c = o.table_c;
+  int nbits = n ? msm_device<G1Curve<C>>(d_bases, d_scalars, n, C::Fr::BITS, ws, ws.own, stream, o) : 0;
   std::vector<typename HG::Pt> res(batch);
   // (a few vectors without the device Horner: their bit-sum Horners -- nbits doublings and additions each -- run side by side)
   auto fold = [&](size_t b) {
     typename HG::Pt acc = HG::identity();
-    if (batch >= 8 || table_c) acc = HG::from_raw32(ws.bits_host + b * 4 * C::Fq::N);      // Horner already done on the device
+    if (batch >= 8 || table_c) acc = HG::from_raw32(ws.own.bits_host.as() + b * 4 * C::Fq::N);      // Horner already done on the device
     else if (n) {
-      const uint32_t *bh = ws.bits_host + b * (size_t)nbits * 4 * C::Fq::N;
+      const uint32_t *bh = ws.own.bits_host.as() + b * (size_t)nbits * 4 * C::Fq::N;
       for (int i = nbits - 1; i >= 0; i--) {
         acc = HG::dbl(acc);
         acc = HG::add(acc, HG::from_raw32(bh + (size_t)i * 4 * C::Fq::N));
@@ -1355,8 +1280,9 @@ void launch_g1_bases(int curve, const uint8_t *d_xy, size_t n, uint32_t *d_out, 
 
 int msm_g1_device(int curve, const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
                   size_t batch, size_t scalar_stride) {
-  if (curve == 0) return msm_g1_impl<G1Bls12381>(d_bases, d_scalars, n, ws, stream, out_xy, batch, 0, 0, scalar_stride);
-  if (curve == 1) return msm_g1_impl<G1Bn254>(d_bases, d_scalars, n, ws, stream, out_xy, batch, 0, 0, scalar_stride);
+  MsmLaunch o; o.batch = batch; o.scalar_stride = scalar_stride;
+  if (curve == 0) return msm_g1_impl<G1Bls12381>(d_bases, d_scalars, n, ws, stream, out_xy, o);
+  if (curve == 1) return msm_g1_impl<G1Bn254>(d_bases, d_scalars, n, ws, stream, out_xy, o);
   return -1;
 }
 // ---------------------------------------------------------------- fixed-base MSM over a table of ALL multiples (no buckets, no sort)
@@ -1570,7 +1496,8 @@ static int msm_g1_direct_impl(const G1DirectTable &t, const uint32_t *d_scalars,
   const AccShape shape = accumulate_shape<CV>();
   size_t lpv = shape.lanes / batch; if (lpv > 1024) lpv = 1024; if (lpv < 1) lpv = 1;
   const size_t per = (E + lpv - 1) / lpv, lanes = batch * lpv;
-  // workspace: the entry indices take `sorted`, the partial sums `part`, the results `rc` / `bits_host`
+  // workspace: the entry indices take `sorted`, the partial sums `part`, the results `rc`; the chain reports to the workspace's own record
+  MsmChain &rec = ws.own;
   MsmPlan p; p.c = t.c; p.nwin = 1; p.nb = 1; p.lpb = (int)per;
   ws.ensure(E, p, (size_t)RV::OUT_WORDS * 4 > (size_t)RV::ACC_WORDS * 4 ? (size_t)RV::OUT_WORDS * 4 : (size_t)RV::ACC_WORDS * 4, batch, lanes + 256,
             (size_t)CV::accum::PART_WORDS * 4);
@@ -1579,19 +1506,18 @@ static int msm_g1_direct_impl(const G1DirectTable &t, const uint32_t *d_scalars,
     if (shape.lds > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *)k_accumulate_direct<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
   });
   hipLaunchKernelGGL(k_direct_index, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, stream, d_scalars, (uint32_t)n, (uint32_t)(scalar_stride ? scalar_stride : n),
-                     t, ws.sorted, scalars_mont, d_base_idx);
-  if (!ws.ev0) { HIP_CHECK(hipEventCreate(&ws.ev0)); HIP_CHECK(hipEventCreate(&ws.ev1)); }
-  HIP_CHECK(hipEventRecord(ws.ev0, stream));
-  hipLaunchKernelGGL(k_accumulate_direct<CV>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), shape.lds, stream, (const uint32_t *)t.d, (const uint32_t *)ws.sorted,
-                     (uint32_t)E, (uint32_t)lpv, (uint32_t)per, (uint32_t)batch, ws.part);
-  HIP_CHECK(hipEventRecord(ws.ev1, stream));
-  hipLaunchKernelGGL(k_direct_reduce<RV>, dim3((unsigned)batch), dim3(64), 0, stream, (const uint32_t *)ws.part, (uint32_t)lpv, ws.rc);
-  HIP_CHECK(hipMemcpyAsync(ws.bits_host, ws.rc, batch * (size_t)RV::OUT_WORDS * 4, hipMemcpyDeviceToHost, stream));
-  ws.plan_host[0] = (uint32_t)per;
-  ws.pending_plan = p;
-  msm_wait(ws, stream);
+                     t, ws.sorted.as(), scalars_mont, d_base_idx);
+  HIP_CHECK(hipEventRecord(rec.ev0, stream));
+  hipLaunchKernelGGL(k_accumulate_direct<CV>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), shape.lds, stream, (const uint32_t *)t.d, ws.sorted.as(),
+                     (uint32_t)E, (uint32_t)lpv, (uint32_t)per, (uint32_t)batch, ws.part.as());
+  HIP_CHECK(hipEventRecord(rec.ev1, stream));
+  hipLaunchKernelGGL(k_direct_reduce<RV>, dim3((unsigned)batch), dim3(64), 0, stream, ws.part.as(), (uint32_t)lpv, ws.rc.as());
+  HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * (size_t)RV::OUT_WORDS * 4, hipMemcpyDeviceToHost, stream));
+  rec.plan_host.as()[0] = (uint32_t)per;
+  rec.plan = p;
+  msm_collect(ws, rec, stream);
   std::vector<typename HG::Pt> res(batch);
-  for (size_t b = 0; b < batch; b++) res[b] = HG::from_raw32(ws.bits_host + b * 4 * C::Fq::N);
+  for (size_t b = 0; b < batch; b++) res[b] = HG::from_raw32(rec.bits_host.as() + b * 4 * C::Fq::N);
   HG::to_affine_bytes_batch(res.data(), batch, out_xy);
   return 0;
 }
@@ -1604,8 +1530,9 @@ int msm_g1_direct_device(const G1DirectTable &t, const uint32_t *d_scalars, size
 int msm_g1_fixed_device(int curve, const uint32_t *d_table, int table_c, size_t table_stride, const uint32_t *d_scalars, size_t n,
                         size_t scalar_stride, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy, size_t batch, const uint32_t *d_base_idx,
                         int scalars_mont) {
-  if (curve == 0) return msm_g1_impl<G1Bls12381>(d_table, d_scalars, n, ws, stream, out_xy, batch, table_c, table_stride, scalar_stride, d_base_idx, scalars_mont);
-  if (curve == 1) return msm_g1_impl<G1Bn254>(d_table, d_scalars, n, ws, stream, out_xy, batch, table_c, table_stride, scalar_stride, d_base_idx, scalars_mont);
+  MsmLaunch o; o.batch = batch; o.table_c = table_c; o.table_stride = table_stride; o.scalar_stride = scalar_stride; o.d_base_idx = d_base_idx; o.scalars_mont = scalars_mont;
+  if (curve == 0) return msm_g1_impl<G1Bls12381>(d_table, d_scalars, n, ws, stream, out_xy, o);
+  if (curve == 1) return msm_g1_impl<G1Bn254>(d_table, d_scalars, n, ws, stream, out_xy, o);
   return -1;
 }
 

@@ -43,14 +43,19 @@ struct Slot {
   bool resident_invalid = false;  // the staged bytes did not decode / validate (a wire batch): runs from the resident state answer InvalidData again
   uint64_t ticket = 0;
   int status = 0;
-  hipEvent_t ev = nullptr;        // behind the prepare kernel's copies back, then behind the MSM chain
+  DevEvent ev;                    // behind the prepare kernel's copies back, then behind the MSM chain
   Lane *lane = nullptr;
-  MsmPending pend;                // what the slot's MSM chain sends back (several chains queue on one lane)
+  MsmChain pend;                  // the record of the slot's MSM chain (several chains queue on one lane)
   uint64_t seq = 0;               // order in which the worker enqueued the slot's current phase (oldest is waited for first)
   size_t n = 0;
   const uint8_t *pks = nullptr, *ios = nullptr, *ads = nullptr, *proofs = nullptr;
   const uint32_t *io_counts = nullptr, *ad_lens = nullptr;
   uint8_t digest[64];
+  // the event, the record, then the context: it has no stream or workspace of its own and is detached from the pool's lane before it dies
+  ~Slot() {
+    ev.destroy(); pend.release();
+    if (c) { c->pend = nullptr; c->L = &c->own; c->stream = nullptr; c->run_phase = 0; avrf_ctx_destroy(c); }
+  }
 };
 
 struct Worker {
@@ -172,7 +177,7 @@ struct Run {
     int st = guarded([&] { return batch_launch(S.c, P->kind, S.digest); });
     if (st == AVRF_OK && hipEventRecord(S.ev, S.lane->stream) != hipSuccess) { (void)hipGetLastError(); st = AVRF_ERR_NO_DEVICE; }
     W.cpu_us[3] += thread_cpu_us() - t0;
-    if (st != AVRF_OK) { if (S.c->run_phase == 2) { (void)hipStreamSynchronize(S.lane->stream); S.lane->ws.pending_armed = false; S.pend.armed = false; } done(S, st); return; }
+    if (st != AVRF_OK) { if (S.c->run_phase == 2) { (void)hipStreamSynchronize(S.lane->stream); S.c->chain().disarm(); } done(S, st); return; }
     S.seq = ++seq; S.state = S_MSM;
   }
 
@@ -264,7 +269,7 @@ int avrf_pool_create(int suite, int device, int kind, int n_slots, int n_lanes, 
   for (auto &L : P->lanes) ok = ok && hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) == hipSuccess;
   for (auto &S : P->slots) {
     ok = ok && ctx_create(suite, device, /*lane_owner=*/false, &S.c) == AVRF_OK;
-    ok = ok && hipEventCreateWithFlags(&S.ev, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
+    ok = ok && S.ev.create(hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
     if (ok && ext) S.c->pend = &S.pend;
   }
   for (int w = 0; w < n_threads && ok; w++) {
@@ -292,6 +297,7 @@ int avrf_pool_create(int suite, int device, int kind, int n_slots, int n_lanes, 
   return AVRF_OK;
 }
 
+// The order a pool goes in: stop flag, workers joined, device made current and synchronised, ingest streams, the slots (~Slot), the lanes.
 void avrf_pool_destroy(avrf_pool *P) {
   if (!P) return;
   { std::lock_guard<std::mutex> lk(P->m); P->stop = true; }
@@ -300,8 +306,7 @@ void avrf_pool_destroy(avrf_pool *P) {
   (void)hipSetDevice(P->device);
   (void)hipDeviceSynchronize();
   for (auto &W : P->workers) if (W.ingest) (void)hipStreamDestroy(W.ingest);
-  for (auto &S : P->slots) { if (S.ev) (void)hipEventDestroy(S.ev); S.pend.release(); if (S.c) { S.c->pend = nullptr; S.c->L = &S.c->own; S.c->stream = nullptr; S.c->run_phase = 0; avrf_ctx_destroy(S.c); } }
-  for (auto &L : P->lanes) L.release();
+  P->slots.clear(); P->lanes.clear();
   delete P;
 }
 

@@ -553,13 +553,6 @@ struct DirectEntry {
 static std::mutex g_direct_mu;
 static std::vector<std::weak_ptr<DirectEntry>> g_direct;
 
-struct OwnedWorkspace : MsmWorkspace {               // an MSM workspace released on every path out
-  OwnedWorkspace() = default;
-  OwnedWorkspace(const OwnedWorkspace &) = delete;
-  OwnedWorkspace &operator=(const OwnedWorkspace &) = delete;
-  ~OwnedWorkspace() { release(); }
-};
-
 // What ONE chunk of proofs in flight mutates: a stream, staging, the per-chunk scratch and an MSM workspace.  A setup has two, so
 // that two chunks are in flight and one hides the other's host rounds.  Lane 0 runs on the context's stream and serves every
 // other call on the setup; lane 1 gets a non-blocking stream of its own on the first two-lane prove call and allocates nothing
@@ -570,7 +563,7 @@ struct RingLane {
   // per-chunk scratch: 0 witness evaluations (4 x 4N; later the opening quotients), 1 aggregated constraints (4N; later
   // the aggregated opening polynomial), 2 coefficients (4 x N), 3 parameter block, 4 quotient, 5 linearisation
   DevMem scr[6];
-  OwnedWorkspace ws;
+  MsmWorkspace ws;
   uint32_t *scratch(int which, size_t bytes) { scr[which].ensure(bytes); return scr[which].as(); }
   RingLane() = default;
   RingLane(const RingLane &) = delete;
@@ -941,7 +934,7 @@ template <class S, class G> struct Ring {
     const int c = 4, nwin = (G::Fr::BITS + 1 + c - 1) / c;
     std::vector<uint8_t> xy(n_g1 * e1);
     {
-      OwnedWorkspace ws;
+      MsmWorkspace ws;
       DevMem d_le(e1), d_flag(4), d_base(e1), d_table((size_t)nwin * e1), d_sc(n_g1 * 32); uint32_t flag = 0;
       HIP_CHECK(hipMemcpy(d_le.p, le, e1, hipMemcpyHostToDevice)); HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, stream));   // (the flag reset in stream order with the kernel that sets it)
       HIP_CHECK(hipMemcpy(d_sc.p, pw.data(), n_g1 * 32, hipMemcpyHostToDevice));
