@@ -73,7 +73,7 @@ template <class C> struct AccumG1U {
   static AVRF_DI acc_t identity() { return g1u_identity<C>(); }
   static AVRF_DI acc_t madd(const acc_t &a, const base_t &q, bool neg) {
     return g1u_madd<C>(a, q.x.v, q.y.v, neg, [&]() {
-      base_t t = q; if (neg) t.y = fn_neg<Fq>(t.y);
+      base_t t = q; if (neg) t.y = fp_neg<Fq>(t.y);
       const typename CV::acc_t r = CV::dbl_affine(t);
       return g1u_from_xyzz<C>(r.x.v, r.y.v, r.zz.v, r.zzz.v);
     });
@@ -178,74 +178,74 @@ template <class C> struct G1Curve {
   static constexpr bool ZERO_IS_IDENTITY = true;      // zz = 0; all-zero memory reads as the identity
   static constexpr bool FIXED_TABLE = true;           // KZG SRS: msm_g1_fixed_device
 
-  static AVRF_DI acc_t identity() { acc_t r; r.x = fn_one<Fq>(); r.y = fn_one<Fq>(); r.zz = fn_zero<N>(); r.zzz = fn_zero<N>(); return r; }
-  static AVRF_DI bool is_identity(const acc_t &a) { return fn_is_zero(a.zz); }
+  static AVRF_DI acc_t identity() { acc_t r; r.x = fp_one<Fq>(); r.y = fp_one<Fq>(); r.zz = fp_zero<N>(); r.zzz = fp_zero<N>(); return r; }
+  static AVRF_DI bool is_identity(const acc_t &a) { return fp_is_zero(a.zz); }
   static AVRF_DI acc_t from_affine(const base_t &q) {
-    acc_t r; r.x = q.x; r.y = q.y; r.zz = fn_one<Fq>(); r.zzz = fn_one<Fq>();
-    if (fn_is_zero(q.x) && fn_is_zero(q.y)) { r.zz = fn_zero<N>(); r.zzz = fn_zero<N>(); }
+    acc_t r; r.x = q.x; r.y = q.y; r.zz = fp_one<Fq>(); r.zzz = fp_one<Fq>();
+    if (fp_is_zero(q.x) && fp_is_zero(q.y)) { r.zz = fp_zero<N>(); r.zzz = fp_zero<N>(); }
     return r;
   }
-  static AVRF_DI acc_t from_base(base_t q, bool neg) { if (neg) q.y = fn_neg<Fq>(q.y); return from_affine(q); }
+  static AVRF_DI acc_t from_base(base_t q, bool neg) { if (neg) q.y = fp_neg<Fq>(q.y); return from_affine(q); }
   // 2 * (affine q)  (mdbl-2008-s-1, a = 0)
   static AVRF_DI acc_t dbl_affine(const base_t &q) {
-    el U = fn_dbl<Fq>(q.y), V = fn_sqr<Fq>(U), W = fn_mul<Fq>(U, V), S = fn_mul<Fq>(q.x, V);
-    el X2 = fn_sqr<Fq>(q.x), M = fn_add<Fq>(fn_dbl<Fq>(X2), X2);
+    el U = fp_dbl<Fq>(q.y), V = fp_sqr<Fq>(U), W = fp_mul<Fq>(U, V), S = fp_mul<Fq>(q.x, V);
+    el X2 = fp_sqr<Fq>(q.x), M = fp_add<Fq>(fp_dbl<Fq>(X2), X2);
     acc_t r;
-    r.x = fn_sub<Fq>(fn_sqr<Fq>(M), fn_dbl<Fq>(S));
-    r.y = fn_sub<Fq>(fn_mul<Fq>(M, fn_sub<Fq>(S, r.x)), fn_mul<Fq>(W, q.y));
+    r.x = fp_sub<Fq>(fp_sqr<Fq>(M), fp_dbl<Fq>(S));
+    r.y = fp_sub<Fq>(fp_mul<Fq>(M, fp_sub<Fq>(S, r.x)), fp_mul<Fq>(W, q.y));
     r.zz = V; r.zzz = W;
-    if (fn_is_zero(q.y)) return identity();
+    if (fp_is_zero(q.y)) return identity();
     return r;
   }
   // 2 * a  (dbl-2008-s-1, a = 0)
   static AVRF_DI acc_t dbl(const acc_t &a) {
-    el U = fn_dbl<Fq>(a.y), V = fn_sqr<Fq>(U), W = fn_mul<Fq>(U, V), S = fn_mul<Fq>(a.x, V);
-    el X2 = fn_sqr<Fq>(a.x), M = fn_add<Fq>(fn_dbl<Fq>(X2), X2);
+    el U = fp_dbl<Fq>(a.y), V = fp_sqr<Fq>(U), W = fp_mul<Fq>(U, V), S = fp_mul<Fq>(a.x, V);
+    el X2 = fp_sqr<Fq>(a.x), M = fp_add<Fq>(fp_dbl<Fq>(X2), X2);
     acc_t r;
-    r.x = fn_sub<Fq>(fn_sqr<Fq>(M), fn_dbl<Fq>(S));
-    r.y = fn_sub<Fq>(fn_mul<Fq>(M, fn_sub<Fq>(S, r.x)), fn_mul<Fq>(W, a.y));
-    r.zz = fn_mul<Fq>(V, a.zz); r.zzz = fn_mul<Fq>(W, a.zzz);
+    r.x = fp_sub<Fq>(fp_sqr<Fq>(M), fp_dbl<Fq>(S));
+    r.y = fp_sub<Fq>(fp_mul<Fq>(M, fp_sub<Fq>(S, r.x)), fp_mul<Fq>(W, a.y));
+    r.zz = fp_mul<Fq>(V, a.zz); r.zzz = fp_mul<Fq>(W, a.zzz);
     return r;                                     // a identity (zz = 0) or y = 0 -> zz = 0: identity
   }
   // a + (neg ? -q : q), q affine  (madd-2008-s: 8M + 2S).  The exceptional cases leave early (wave-divergent but rare:
   // the first addition into an empty accumulator, a point at infinity in the table, P = +-Q), so that neither the old
   // accumulator nor q stays live across the main sequence -- that is what lets the 381-bit version fit its registers.
   static AVRF_DI acc_t madd(const acc_t &a, base_t q, bool neg) {
-    if (neg) q.y = fn_neg<Fq>(q.y);
-    if (fn_is_zero(q.x) && fn_is_zero(q.y)) return a;
+    if (neg) q.y = fp_neg<Fq>(q.y);
+    if (fp_is_zero(q.x) && fp_is_zero(q.y)) return a;
     if (is_identity(a)) return from_affine(q);
-    el P = fn_sub<Fq>(fn_mul<Fq>(q.x, a.zz), a.x), R = fn_sub<Fq>(fn_mul<Fq>(q.y, a.zzz), a.y);
-    if (fn_is_zero(P)) return fn_is_zero(R) ? dbl_affine(q) : identity();
+    el P = fp_sub<Fq>(fp_mul<Fq>(q.x, a.zz), a.x), R = fp_sub<Fq>(fp_mul<Fq>(q.y, a.zzz), a.y);
+    if (fp_is_zero(P)) return fp_is_zero(R) ? dbl_affine(q) : identity();
     acc_t r;
-    el PP = fn_sqr<Fq>(P);
-    r.zz = fn_mul<Fq>(a.zz, PP);
-    el Q = fn_mul<Fq>(a.x, PP);
-    el PPP = fn_mul<Fq>(P, PP);
-    r.zzz = fn_mul<Fq>(a.zzz, PPP);
-    el T = fn_mul<Fq>(a.y, PPP);
-    r.x = fn_sub<Fq>(fn_sub<Fq>(fn_sqr<Fq>(R), PPP), fn_dbl<Fq>(Q));
-    r.y = fn_sub<Fq>(fn_mul<Fq>(R, fn_sub<Fq>(Q, r.x)), T);
+    el PP = fp_sqr<Fq>(P);
+    r.zz = fp_mul<Fq>(a.zz, PP);
+    el Q = fp_mul<Fq>(a.x, PP);
+    el PPP = fp_mul<Fq>(P, PP);
+    r.zzz = fp_mul<Fq>(a.zzz, PPP);
+    el T = fp_mul<Fq>(a.y, PPP);
+    r.x = fp_sub<Fq>(fp_sub<Fq>(fp_sqr<Fq>(R), PPP), fp_dbl<Fq>(Q));
+    r.y = fp_sub<Fq>(fp_mul<Fq>(R, fp_sub<Fq>(Q, r.x)), T);
     return r;
   }
   // a + b  (add-2008-s: 12M + 2S); exceptional cases leave early so that a and b die as the sequence consumes them
   static AVRF_DI acc_t add(const acc_t &a, const acc_t &b) {
     if (is_identity(a)) return b;
     if (is_identity(b)) return a;
-    el U1 = fn_mul<Fq>(a.x, b.zz), P = fn_sub<Fq>(fn_mul<Fq>(b.x, a.zz), U1);
-    el S1 = fn_mul<Fq>(a.y, b.zzz), R = fn_sub<Fq>(fn_mul<Fq>(b.y, a.zzz), S1);
-    if (fn_is_zero(P)) return fn_is_zero(R) ? dbl(a) : identity();
+    el U1 = fp_mul<Fq>(a.x, b.zz), P = fp_sub<Fq>(fp_mul<Fq>(b.x, a.zz), U1);
+    el S1 = fp_mul<Fq>(a.y, b.zzz), R = fp_sub<Fq>(fp_mul<Fq>(b.y, a.zzz), S1);
+    if (fp_is_zero(P)) return fp_is_zero(R) ? dbl(a) : identity();
     acc_t r;
-    el PP = fn_sqr<Fq>(P);
-    r.zz = fn_mul<Fq>(fn_mul<Fq>(a.zz, b.zz), PP);
-    el Q = fn_mul<Fq>(U1, PP);
-    el PPP = fn_mul<Fq>(P, PP);
-    r.zzz = fn_mul<Fq>(fn_mul<Fq>(a.zzz, b.zzz), PPP);
-    el T = fn_mul<Fq>(S1, PPP);
-    r.x = fn_sub<Fq>(fn_sub<Fq>(fn_sqr<Fq>(R), PPP), fn_dbl<Fq>(Q));
-    r.y = fn_sub<Fq>(fn_mul<Fq>(R, fn_sub<Fq>(Q, r.x)), T);
+    el PP = fp_sqr<Fq>(P);
+    r.zz = fp_mul<Fq>(fp_mul<Fq>(a.zz, b.zz), PP);
+    el Q = fp_mul<Fq>(U1, PP);
+    el PPP = fp_mul<Fq>(P, PP);
+    r.zzz = fp_mul<Fq>(fp_mul<Fq>(a.zzz, b.zzz), PPP);
+    el T = fp_mul<Fq>(S1, PPP);
+    r.x = fp_sub<Fq>(fp_sub<Fq>(fp_sqr<Fq>(R), PPP), fp_dbl<Fq>(Q));
+    r.y = fp_sub<Fq>(fp_mul<Fq>(R, fp_sub<Fq>(Q, r.x)), T);
     return r;
   }
-  static AVRF_DI base_t load_base(const uint32_t *p) { base_t r; r.x = fn_load<N>(p); r.y = fn_load<N>(p + N); return r; }
+  static AVRF_DI base_t load_base(const uint32_t *p) { base_t r; r.x = fp_load<N>(p); r.y = fp_load<N>(p + N); return r; }
   static AVRF_DI base_t base_from_words(const uint32_t (&w)[BASE_WORDS]) {
     base_t r;
 #pragma unroll
@@ -253,10 +253,10 @@ template <class C> struct G1Curve {
     return r;
   }
   static AVRF_DI acc_t load_acc(const uint32_t *p) {
-    acc_t r; r.x = fn_load<N>(p); r.y = fn_load<N>(p + N); r.zz = fn_load<N>(p + 2 * N); r.zzz = fn_load<N>(p + 3 * N); return r;
+    acc_t r; r.x = fp_load<N>(p); r.y = fp_load<N>(p + N); r.zz = fp_load<N>(p + 2 * N); r.zzz = fp_load<N>(p + 3 * N); return r;
   }
   static AVRF_DI void store_acc(uint32_t *p, const acc_t &a) {
-    fn_store<N>(p, a.x); fn_store<N>(p + N, a.y); fn_store<N>(p + 2 * N, a.zz); fn_store<N>(p + 3 * N, a.zzz);
+    fp_store<N>(p, a.x); fp_store<N>(p + N, a.y); fp_store<N>(p + 2 * N, a.zz); fp_store<N>(p + 3 * N, a.zzz);
   }
   // the reduction kernels of a fixed-base MSM (bucket sums, weighted sums): general additions on the asm multipliers
 #if !defined(AVRF_NO_UNSAT_G1) && !defined(AVRF_NO_UNSAT_G1_RED)
@@ -267,8 +267,8 @@ template <class C> struct G1Curve {
   static constexpr int OUT_WORDS = ACC_WORDS;
   static AVRF_DI void store_out(uint32_t *p, const acc_t &a) { store_acc(p, a); }
   static AVRF_DI acc_t shfl_down(const acc_t &a, int delta) {
-    acc_t r; r.x = fn_shfl_down<N>(a.x, delta); r.y = fn_shfl_down<N>(a.y, delta);
-    r.zz = fn_shfl_down<N>(a.zz, delta); r.zzz = fn_shfl_down<N>(a.zzz, delta); return r;
+    acc_t r; r.x = fp_shfl_down<N>(a.x, delta); r.y = fp_shfl_down<N>(a.y, delta);
+    r.zz = fp_shfl_down<N>(a.zz, delta); r.zzz = fp_shfl_down<N>(a.zzz, delta); return r;
   }
   static AVRF_DI acc_t shfl_from(const acc_t &a, int lane) {
     acc_t r;

@@ -1,134 +1,10 @@
-// fp256.h -- 256-bit prime-field arithmetic for gfx950 VALU (8 x u32 limbs, Montgomery R = 2^256).
-//
-// Device counterpart of what the reference gets from arkworks `Fp<MontBackend<_,4>>`
-// (third-party ark-ff 0.6; reached from src/thin.rs:289-311, src/pedersen.rs:373-410 for the
-// scalar field and from every group operation for the base field).  One field element per
-// lane, limbs in VGPRs; products through v_mad_u64_u32.  The twisted-Edwards suites' moduli have their
-// top bit clear (251..255 bits), which admits the carry-free forms; the two 256-bit fields of secp256r1
-// (F::FULL) keep the 257th bit of a sum or a Montgomery product and fold it into the conditional subtraction.
+// fp256.h -- what the 256-bit prime fields (8 x u32 limbs, Montgomery R = 2^256) have beyond the field layer of fpn.h: square roots,
+// Jacobi symbols, sign and byte conversions, and the out-of-line forms of the per-item protocol kernels (fp_*_nf).
+// `fp` is fpn<8>; every function here takes a field F with F::N == 8.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "consts_gen.h"
-#include "mac96.h"
+#include "fpn.h"
 
 namespace avrf {
-
-#define AVRF_DI __device__ __forceinline__
-
-struct fp { uint32_t v[8]; };
-
-template <class F> AVRF_DI fp fp_const(const uint32_t (&c)[8]) {
-  fp r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = c[i];
-  return r;
-}
-template <class F> AVRF_DI fp fp_one() { return fp_const<F>(F::ONE); }
-AVRF_DI fp fp_zero() { fp r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = 0;
-  return r; }
-
-AVRF_DI bool fp_is_zero(const fp &a) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) o |= a.v[i];
-  return o == 0;
-}
-AVRF_DI bool fp_eq(const fp &a, const fp &b) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) o |= a.v[i] ^ b.v[i];
-  return o == 0;
-}
-
-// r = a + b, returns carry
-// (carry chains through __builtin_addc / __builtin_subc: one v_addc_co_u32 / v_subb_co_u32 per limb.  The uint64_t / int64_t
-// accumulator idiom compiled to ~90 instructions per field addition -- 64-bit adds, arithmetic shifts and the moves that build
-// their register pairs -- against ~30 in this form; a mixed addition has eleven of them.)
-AVRF_DI uint32_t add8(fp &r, const fp &a, const fp &b) {
-  unsigned c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = __builtin_addc(a.v[i], b.v[i], c, &c);
-  return c;
-}
-// r = a - b, returns borrow (0/1)
-AVRF_DI uint32_t sub8(fp &r, const fp &a, const fp &b) {
-  unsigned br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = __builtin_subc(a.v[i], b.v[i], br, &br);
-  return br;
-}
-template <class F> AVRF_DI uint32_t sub_p(fp &r, const fp &a) {
-  unsigned br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = __builtin_subc(a.v[i], (unsigned)F::P[i], br, &br);
-  return br;
-}
-// a >= p ?  (plain integer compare)
-template <class F> AVRF_DI bool ge_p(const fp &a) { fp t; return sub_p<F>(t, a) == 0; }
-
-template <class F> AVRF_DI fp fp_add(const fp &a, const fp &b) {
-  fp t, u; uint32_t c = add8(t, a, b);  // < 2p; a carry out only when the top bit of p is set (F::FULL)
-  uint32_t br = sub_p<F>(u, t);
-  if constexpr (F::FULL) br = br && !c; else (void)c;
-#pragma unroll
-  for (int i = 0; i < 8; i++) t.v[i] = br ? t.v[i] : u.v[i];
-  return t;
-}
-template <class F> AVRF_DI fp fp_sub(const fp &a, const fp &b) {
-  fp t; const uint32_t m = 0u - sub8(t, a, b);           // borrow: add p back
-  unsigned c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) t.v[i] = __builtin_addc(t.v[i], (unsigned)(F::P[i] & m), c, &c);
-  return t;
-}
-template <class F> AVRF_DI fp fp_neg(const fp &a) {
-  fp t; unsigned br = 0; const bool z = fp_is_zero(a);
-#pragma unroll
-  for (int i = 0; i < 8; i++) { const unsigned d = __builtin_subc((unsigned)F::P[i], a.v[i], br, &br); t.v[i] = z ? 0u : d; }
-  return t;
-}
-template <class F> AVRF_DI fp fp_dbl(const fp &a) { return fp_add<F>(a, a); }
-
-// Montgomery product a*b/R mod p (top bit of p clear), product scanning (mac96.h)
-template <class F> AVRF_DI fp fp_mul(const fp &a, const fp &b) {
-  fp r, u;
-  uint32_t c = mont_mul_ps<8, F>(r.v, a.v, b.v);
-  uint32_t br = sub_p<F>(u, r);
-  if constexpr (F::FULL) br = br && !c; else (void)c;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = br ? r.v[i] : u.v[i];
-  return r;
-}
-template <class F> AVRF_DI fp fp_sqr(const fp &a) {
-  fp r, u;
-  uint32_t c = mont_sqr_ps<8, F>(r.v, a.v);
-  uint32_t br = sub_p<F>(u, r);
-  if constexpr (F::FULL) br = br && !c; else (void)c;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = br ? r.v[i] : u.v[i];
-  return r;
-}
-
-template <class F> AVRF_DI fp fp_to_mont(const fp &a) { return fp_mul<F>(a, fp_const<F>(F::R2)); }
-template <class F> AVRF_DI fp fp_from_mont(const fp &a) {
-  fp one = fp_zero(); one.v[0] = 1; return fp_mul<F>(a, one);
-}
-
-// a^e for a constant exponent (plain 256-bit integer), square-and-multiply MSB first.
-template <class F> AVRF_DI fp fp_pow_const(const fp &a, const uint32_t (&e)[8]) {
-  fp r = fp_one<F>();
-  bool started = false;
-  for (int i = 255; i >= 0; i--) {
-    if (started) r = fp_sqr<F>(r);
-    if ((e[i >> 5] >> (i & 31)) & 1) { r = started ? fp_mul<F>(r, a) : a; started = true; }
-  }
-  return r;
-}
-template <class F> AVRF_DI fp fp_inv(const fp &a) { return fp_pow_const<F>(a, F::PM2); }
-
 
 // Square root by Tonelli-Shanks (p - 1 = 2^s * t, ROOT = g^t for a non-residue g).  Returns
 // false when `a` is a non-residue.  Which of the two roots is returned is unspecified; callers
@@ -159,10 +35,10 @@ template <class F> AVRF_DI bool fp_sqrt(const fp &a, fp &out) {
 template <class F> AVRF_DI bool fp_is_negative_mont(const fp &a_mont) {
   fp a = fp_from_mont<F>(a_mont), t;
   // a > HALF  <=>  HALF - a borrows
-  return sub8(t, fp_const<F>(F::HALF), a) != 0;
+  return fp_subb(t, fp_const<F>(F::HALF), a) != 0;
 }
 template <class F> AVRF_DI bool fp_is_negative_plain(const fp &a) {
-  fp t; return sub8(t, fp_const<F>(F::HALF), a) != 0;
+  fp t; return fp_subb(t, fp_const<F>(F::HALF), a) != 0;
 }
 
 // little-endian bytes <-> limbs (global or local memory)
@@ -208,66 +84,21 @@ template <class F> AVRF_DI fp fp_from_wide_mont(const fp &lo, const fp &hi) {
 }
 
 
-// ---- out-of-line variants for the per-item protocol kernels (code size / compile time);
-// the MSM hot loops keep the force-inlined forms above.
-#define AVRF_DN __device__ __noinline__ static
-template <class F> AVRF_DN fp fp_mul_nf(fp a, fp b) { return fp_mul<F>(a, b); }
+// ---- out-of-line variants for the per-item protocol kernels (code size / compile time): everything through the shared multiplier
+// fp_mul_nf of fpn.h; the MSM hot loops keep the force-inlined forms.
 template <class F> AVRF_DI fp fp_sqr_nf(const fp &a) { return fp_mul_nf<F>(a, a); }
 template <class F> AVRF_DI fp fp_to_mont_nf(const fp &a) { return fp_mul_nf<F>(a, fp_const<F>(F::R2)); }
 template <class F> AVRF_DI fp fp_from_mont_nf(const fp &a) { fp one = fp_zero(); one.v[0] = 1; return fp_mul_nf<F>(a, one); }
 template <class F> AVRF_DI bool fp_is_negative_mont_nf(const fp &a_mont) {
-  fp a = fp_from_mont_nf<F>(a_mont), t; return sub8(t, fp_const<F>(F::HALF), a) != 0;
+  fp a = fp_from_mont_nf<F>(a_mont), t; return fp_subb(t, fp_const<F>(F::HALF), a) != 0;
 }
 template <class F> AVRF_DI fp fp_from_wide_mont_nf(const fp &lo, const fp &hi) {
   fp r2 = fp_const<F>(F::R2);
   return fp_add<F>(fp_mul_nf<F>(lo, r2), fp_mul_nf<F>(fp_mul_nf<F>(hi, r2), r2));
 }
-// a^-1 (0 -> 0) for the lane-per-item kernels: the binary GCD with ONE fused step per iteration, written without branches so that the
-// 64 different values of a wave walk the same instruction stream (only the trip count differs, ~1.4 x 255 +- a few):
-//   u even:          u <- u / 2,        x1 <- x1 / 2
-//   u odd, u >= v:   u <- (u - v) / 2,  x1 <- (x1 - x2) / 2
-//   u odd, u <  v:   (u, v) <- ((v - u) / 2, u),  (x1, x2) <- ((x2 - x1) / 2, x1)
-// with x1 a = u, x2 a = v (mod p), v odd throughout; u = 0 leaves v = 1, x2 = a^-1.  ~120 carry / select instructions per step,
-// ~45 k per inversion against ~110 k (two thirds multiply-adds) for the fixed power a^(p-2) it replaces: 0.23 -> ~0.1 ms of a
-// prover kernel's single wave per SIMD.  (The few-items kernels use fp_inv_few below: same data in all lanes, plain loops.)
-template <class F> AVRF_DN fp fp_inv_nf(fp a) {
-  const fp P = fp_const<F>(F::P);
-  fp u = a, v = P, x1 = fp_zero(), x2 = fp_zero();
-  x1.v[0] = 1;
-#pragma unroll 1
-  while (!fp_is_zero(u)) {
-    const bool odd = (u.v[0] & 1u) != 0;
-    fp d1, d2;
-    const bool lt = sub8(d1, u, v) != 0;                   // d1 = u - v, d2 = v - u
-    sub8(d2, v, u);
-    const bool sw = odd && lt;
-    fp xa, xb;                                            // minuend / subtrahend of the x update
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const uint32_t un = odd ? (lt ? d2.v[i] : d1.v[i]) : u.v[i];
-      v.v[i] = sw ? u.v[i] : v.v[i];
-      u.v[i] = un;
-      xa.v[i] = sw ? x2.v[i] : x1.v[i];
-      xb.v[i] = odd ? (sw ? x1.v[i] : x2.v[i]) : 0u;
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) u.v[i] = (u.v[i] >> 1) | (u.v[i + 1] << 31);
-    u.v[7] >>= 1;
-#pragma unroll
-    for (int i = 0; i < 8; i++) x2.v[i] = sw ? x1.v[i] : x2.v[i];
-    fp t = fp_sub<F>(xa, xb);                             // in [0, p)
-    uint32_t c = 0;
-    { const uint32_t m = 0u - (t.v[0] & 1u); fp pm;        // t / 2 mod p: (t + p) / 2 when t is odd
-#pragma unroll
-      for (int i = 0; i < 8; i++) pm.v[i] = F::P[i] & m;
-      c = add8(t, t, pm); }
-#pragma unroll
-    for (int i = 0; i < 7; i++) x1.v[i] = (t.v[i] >> 1) | (t.v[i + 1] << 31);
-    x1.v[7] = (t.v[7] >> 1) | (c << 31);
-  }
-  const fp r2 = fp_const<F>(F::R2);                        // x2 = (a' R)^-1 for a = a' R; times R^3 / R gives a'^-1 R
-  return fp_mul_nf<F>(x2, fp_mul_nf<F>(r2, r2));
-}
+// a^-1 (0 -> 0) for the lane-per-item kernels: the branch-free GCD of fpn.h, rescaled through the out-of-line multiplier.
+// (The few-items kernels use fp_inv_few below: same data in all lanes, plain loops.)
+template <class F> AVRF_DI fp fp_inv_nf(const fp &a) { return fp_inv_gcd<F, true>(a); }
 // The Jacobi symbols (a / p), (b / p) = the quadratic characters of a and b (p prime): +1, -1, or 0 for a = 0.  Exact binary algorithm on
 // (a, n), n odd, in MACRO steps -- one step removes ALL trailing zeros of a (v_ffbl_b32 + a funnel shift per limb), then subtracts:
 //   z = ctz(a) (at most 30 per step):  a <- a / 2^z            sign *= (2 / n)^z,  (2 / n) = -1 iff n = 3, 5 mod 8
@@ -339,15 +170,7 @@ template <class F> AVRF_DN void fp_jacobi2_nf(fp a, fp b, int *ja, int *jb) {
   *ja = jac_result(s1); *jb = jac_result(s2);
 }
 // the fixed power a^(p-2), kept as the cross-check of the two Euclidean forms (tools/ubench.hip)
-template <class F> AVRF_DN fp fp_inv_fermat_nf(fp a) {
-  fp r = fp_one<F>();
-  bool started = false;
-  for (int i = 255; i >= 0; i--) {
-    if (started) r = fp_mul_nf<F>(r, r);
-    if ((F::PM2[i >> 5] >> (i & 31)) & 1) { r = started ? fp_mul_nf<F>(r, a) : a; started = true; }
-  }
-  return r;
-}
+template <class F> AVRF_DN fp fp_inv_fermat_nf(fp a) { return fp_pow_const<F, true>(a, F::PM2); }
 // a^-1 of a Montgomery-form a (0 -> 0, as a^(p-2) gives) by the binary extended Euclidean algorithm on the plain integers:
 // ~1.4 * 255 halvings and ~0.7 * 255 subtractions of 8-limb values (~20 k carry instructions) instead of the 255 squarings and
 // ~130 products of the fixed power (~110 k instructions, two thirds of them multiply-adds).  For the LATENCY kernels only
@@ -361,7 +184,7 @@ template <class F> AVRF_DN fp fp_inv_few(fp a) {
   x1.v[0] = 1;
   auto is_one = [](const fp &x) { uint32_t o = x.v[0] ^ 1u; for (int i = 1; i < 8; i++) o |= x.v[i]; return o == 0; };
   auto shr1 = [](fp &x, uint32_t top) { for (int i = 0; i < 7; i++) x.v[i] = (x.v[i] >> 1) | (x.v[i + 1] << 31); x.v[7] = (x.v[7] >> 1) | (top << 31); };
-  auto halve_mod = [&](fp &x) { uint32_t c = 0; if (x.v[0] & 1u) c = add8(x, x, P); shr1(x, c); };
+  auto halve_mod = [&](fp &x) { uint32_t c = 0; if (x.v[0] & 1u) c = fp_addc(x, x, P); shr1(x, c); };
   // (u = 0 cannot happen for a canonical non-zero a -- gcd(a, p) = 1 -- but a loop on the device must end whatever it is fed)
 #pragma unroll 1
   while (!is_one(u) && !is_one(v) && !fp_is_zero(u)) {
@@ -370,8 +193,8 @@ template <class F> AVRF_DN fp fp_inv_few(fp a) {
 #pragma unroll 1
     while (!(v.v[0] & 1u)) { shr1(v, 0); halve_mod(x2); }
     fp t;
-    if (sub8(t, u, v) == 0) { u = t; x1 = fp_sub<F>(x1, x2); }
-    else { sub8(v, v, u); x2 = fp_sub<F>(x2, x1); }
+    if (fp_subb(t, u, v) == 0) { u = t; x1 = fp_sub<F>(x1, x2); }
+    else { fp_subb(v, v, u); x2 = fp_sub<F>(x2, x1); }
   }
   const fp r = is_one(u) ? x1 : x2;                       // (a' R)^-1 for a = a' R; times R^3 / R gives a'^-1 R
   const fp r2 = fp_const<F>(F::R2);

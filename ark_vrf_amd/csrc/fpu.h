@@ -1,7 +1,7 @@
 // fpu.h -- unsaturated-limb ("carry-free") prime-field arithmetic for the bucket-accumulation kernels of the MSMs
 // (reference call sites: the MSM of src/thin.rs:319, src/pedersen.rs:420, src/ring.rs:220).
 //
-// fp256.h / fpn.h keep a field element in N saturated 32-bit limbs: every limb product of a Montgomery multiplication is a
+// fpn.h keeps a field element in N saturated 32-bit limbs: every limb product of a Montgomery multiplication is a
 // v_mad_u64_u32 that can carry out of its 64-bit accumulator, so each one drags a v_addc_co_u32 behind it (the pair issues at
 // 17.9 T/s against 31.7 T/s for the multiply-add alone, profiles/r4_ubench.txt).  Here an element is L SIGNED limbs of W bits
 // (9 x 29 for the 251..255-bit fields, 14 x 28 for the 381-bit one): a column of the schoolbook product is at most L products
@@ -18,7 +18,6 @@
 // that constant.
 #pragma once
 #include "fp256.h"
-#include "fpn.h"
 
 namespace avrf {
 
@@ -27,7 +26,7 @@ template <int L> struct ulimbs { uint32_t v[L]; };
 
 // layout of field F in unsaturated limbs + its constants (evaluated at compile time from consts_gen.h's 32-bit limbs)
 template <class F> struct UL {
-  static constexpr int N = (int)(sizeof(F::P) / sizeof(uint32_t));
+  static constexpr int N = F::N;
   static constexpr int W = N == 8 ? 29 : 28;
   static constexpr int L = N == 8 ? 9 : 14;
   static constexpr int SH = W * L - 32 * N;                       // 5 (8 limbs), 8 (12 limbs)

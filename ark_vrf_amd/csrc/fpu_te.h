@@ -48,7 +48,7 @@ template <class S> AVRF_DI te_acc_u<S> teu_madd(const te_acc_u<S> &p, const te_p
   const uint32_t e = neg ? 0xffffffffu : 0u;
   const int32_t flip = (int32_t)(p.neg ^ e);
   const fu<L> X1 = fu_cneg<L>(p.x, flip), T1 = fu_cneg<L>(p.t, flip);
-  fp xy; add8(xy, q.x, q.y);                                                 // x + y < 2p < 2^256 (top bit of p clear)
+  fp xy; fp_addc(xy, q.x, q.y);                                                 // x + y < 2p < 2^256 (top bit of p clear)
   const fu<L> A = fu_mul<Fq>(X1, fu_slice<Fq, SH>(q.x.v));
   const fu<L> B = fu_mul<Fq>(p.y, fu_slice<Fq, SH>(q.y.v));
   const fu<L> C = fu_mul<Fq>(T1, fu_slice<Fq, SH>(q.k.v));
@@ -141,7 +141,7 @@ template <class S> AVRF_DI teu4<S> teu4_dbl(const teu4<S> &p) {
 template <class S> AVRF_DI teu4<S> teu4_add_sat(const teu4<S> &p, const te_ext &e) {
   using Fq = typename S::Fq;
   constexpr int L = UL<Fq>::L, SH = UL<Fq>::SH;
-  fp xy; add8(xy, e.x, e.y);
+  fp xy; fp_addc(xy, e.x, e.y);
   const fu<L> A = fu_mul<Fq>(p.x, fu_slice<Fq, SH>(e.x.v)), B = fu_mul<Fq>(p.y, fu_slice<Fq, SH>(e.y.v));
   const fu<L> C = fu_mul<Fq>(fu_mul<Fq>(p.t, fu_slice<Fq, SH>(e.t.v)), fu_slice<Fq, SH>(S::D));
   const fu<L> D = fu_mul<Fq>(p.z, fu_slice<Fq, SH>(e.z.v));
@@ -156,7 +156,7 @@ template <class S> AVRF_DI teu4<S> teu4_add_sat(const teu4<S> &p, const te_ext &
 template <class S> AVRF_DI teu4<S> teu4_madd_pre(const teu4<S> &p, const te_pre &q) {
   using Fq = typename S::Fq;
   constexpr int L = UL<Fq>::L, SH = UL<Fq>::SH;
-  fp xy; add8(xy, q.x, q.y);
+  fp xy; fp_addc(xy, q.x, q.y);
   const fu<L> A = fu_mul<Fq>(p.x, fu_slice<Fq, SH>(q.x.v)), B = fu_mul<Fq>(p.y, fu_slice<Fq, SH>(q.y.v));
   const fu<L> C = fu_mul<Fq>(p.t, fu_slice<Fq, SH>(q.k.v));
   fu<L> E = fu_mul<Fq>(fu_add<L>(p.x, p.y), fu_slice<Fq, SH>(xy.v));

@@ -15,7 +15,7 @@
 namespace avrf {
 
 template <class C> struct HostPairing {
-  using Fp = HostFieldN<typename C::Fq>;
+  using Fp = HostField<typename C::Fq>;
   using El = typename Fp::El;
   struct F2 { El a, b; };                    // a + b u
   struct F6 { F2 c0, c1, c2; };              // c0 + c1 v + c2 v^2

@@ -1,4 +1,4 @@
-// mac96.h -- the multiply-accumulate step of the product-scanning Montgomery multiplications (fp256.h, fpn.h).
+// mac96.h -- the multiply-accumulate step of the product-scanning Montgomery multiplications (fpn.h).
 // A column of the schoolbook product is summed in ONE 96-bit accumulator (lo64 | ex): each limb product is a single
 // v_mad_u64_u32 accumulating in place, and its carry-out (VOP3B sdst) is folded into `ex` by one v_addc_co_u32 --
 // 2 VALU ops per limb product.  (The operand-scanning CIOS form costs a mad plus a 64-bit add and zero-extension

@@ -80,9 +80,9 @@ __global__ void __launch_bounds__(256) k_scalars_from_mont(uint32_t *__restrict_
   using Fr = typename S::Fr;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  fp k = load_fp(sc + 8 * (size_t)i);
+  fp k = fp_load(sc + 8 * (size_t)i);
   if (ge_p<Fr>(k)) atomicOr(flag, 4u);
-  store_fp(sc + 8 * (size_t)i, fp_from_mont<Fr>(k));
+  fp_store(sc + 8 * (size_t)i, fp_from_mont<Fr>(k));
 }
 void launch_scalars_from_mont(int suite, uint32_t *d_scalars, size_t n, uint32_t *d_flag, hipStream_t stream) {
   if (!n) return;
@@ -995,9 +995,9 @@ __global__ void __launch_bounds__(256) k_g1_bases(const uint8_t *__restrict__ xy
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t *src = reinterpret_cast<const uint32_t *>(xy + (size_t)i * N * 8);
-  fpn<N> x = fn_load<N>(src), y = fn_load<N>(src + N);
-  if (fn_ge_p<Fq>(x) || fn_ge_p<Fq>(y)) atomicOr(flag, 1u);
-  fn_store<N>(out + (size_t)i * 2 * N, fn_to_mont<Fq>(x)); fn_store<N>(out + (size_t)i * 2 * N + N, fn_to_mont<Fq>(y));
+  fpn<N> x = fp_load<N>(src), y = fp_load<N>(src + N);
+  if (ge_p<Fq>(x) || ge_p<Fq>(y)) atomicOr(flag, 1u);
+  fp_store<N>(out + (size_t)i * 2 * N, fp_to_mont<Fq>(x)); fp_store<N>(out + (size_t)i * 2 * N + N, fp_to_mont<Fq>(y));
 }
 
 // CanonicalDeserialize of compressed G1 points (ark-serialize; the zcash big-endian form for BLS12-381, little-endian with the
@@ -1027,28 +1027,28 @@ __global__ void __launch_bounds__(64) k_g1_decompress(const uint8_t *__restrict_
   for (int k = 0; k < N; k++) x.v[k] = (uint32_t)le[4 * k] | ((uint32_t)le[4 * k + 1] << 8) | ((uint32_t)le[4 * k + 2] << 16) | ((uint32_t)le[4 * k + 3] << 24);
   uint32_t *o = reinterpret_cast<uint32_t *>(out_xy + (size_t)i * 2 * FQB);
   if (inf) {                                                          // canonical encoding only: no sort flag, every other bit zero
-    const bool good = !big && fn_is_zero(x);
-    fn_store<N>(o, fn_zero<N>()); fn_store<N>(o + N, fn_zero<N>());
+    const bool good = !big && fp_is_zero(x);
+    fp_store<N>(o, fp_zero<N>()); fp_store<N>(o + N, fp_zero<N>());
     ok[i] = good ? 2 : 0; return;
   }
-  if (fn_ge_p<Fq>(x)) { ok[i] = 0; return; }
-  const fpn<N> xm = fn_to_mont<Fq>(x);
-  const fpn<N> rhs = fn_add<Fq>(fn_mul<Fq>(fn_sqr<Fq>(xm), xm), fn_const<Fq>(C::B));
+  if (ge_p<Fq>(x)) { ok[i] = 0; return; }
+  const fpn<N> xm = fp_to_mont<Fq>(x);
+  const fpn<N> rhs = fp_add<Fq>(fp_mul<Fq>(fp_sqr<Fq>(xm), xm), fp_const<Fq>(C::B));
   uint32_t e[N];                                                      // (p + 1) / 4 = ((p - 1) / 2 + 1) / 2
   { uint64_t c = 1; for (int k = 0; k < N; k++) { c += Fq::HALF[k]; e[k] = (uint32_t)c; c >>= 32; } }
   for (int k = 0; k < N; k++) e[k] = (e[k] >> 1) | (k + 1 < N ? e[k + 1] << 31 : 0u);
-  fpn<N> y = fn_one<Fq>();
+  fpn<N> y = fp_one<Fq>();
 #pragma unroll 1
   for (int k = 32 * N - 1; k >= 0; k--) {
-    y = fn_sqr<Fq>(y);
-    if ((e[k >> 5] >> (k & 31)) & 1) y = fn_mul<Fq>(y, rhs);
+    y = fp_sqr<Fq>(y);
+    if ((e[k >> 5] >> (k & 31)) & 1) y = fp_mul<Fq>(y, rhs);
   }
-  if (!fn_eq(fn_sqr<Fq>(y), rhs)) { ok[i] = 0; return; }             // not on the curve
-  fpn<N> yp = fn_from_mont<Fq>(y);
+  if (!fp_eq(fp_sqr<Fq>(y), rhs)) { ok[i] = 0; return; }             // not on the curve
+  fpn<N> yp = fp_from_mont<Fq>(y);
   bool is_big = false;                                                // yp > (p - 1) / 2 ?
   for (int k = N - 1; k >= 0; k--) if (yp.v[k] != Fq::HALF[k]) { is_big = yp.v[k] > Fq::HALF[k]; break; }
-  if (is_big != big) yp = fn_from_mont<Fq>(fn_neg<Fq>(y));
-  fn_store<N>(o, x); fn_store<N>(o + N, yp);
+  if (is_big != big) yp = fp_from_mont<Fq>(fp_neg<Fq>(y));
+  fp_store<N>(o, x); fp_store<N>(o + N, yp);
   ok[i] = 1;
 }
 
@@ -1065,26 +1065,26 @@ k_g1_table(const uint32_t *__restrict__ bases, uint32_t n, int c, int nwin, uint
   if (i >= n) return;
   typename CV::base_t b = CV::load_base(bases + (size_t)i * 2 * N);
   typename CV::acc_t acc = CV::from_affine(b);
-  fpn<N> run = fn_one<Fq>();
+  fpn<N> run = fp_one<Fq>();
 #pragma unroll 1
   for (int w = 0; w < nwin; w++) {
     const size_t e = (size_t)w * n + i;
-    fn_store<N>(table + e * 2 * N, acc.x); fn_store<N>(table + e * 2 * N + N, acc.y);
-    fn_store<N>(tmp + e * 3 * N, acc.zz); fn_store<N>(tmp + e * 3 * N + N, acc.zzz); fn_store<N>(tmp + e * 3 * N + 2 * N, run);
-    if (!CV::is_identity(acc)) run = fn_mul<Fq>(run, fn_mul<Fq>(acc.zz, acc.zzz));
+    fp_store<N>(table + e * 2 * N, acc.x); fp_store<N>(table + e * 2 * N + N, acc.y);
+    fp_store<N>(tmp + e * 3 * N, acc.zz); fp_store<N>(tmp + e * 3 * N + N, acc.zzz); fp_store<N>(tmp + e * 3 * N + 2 * N, run);
+    if (!CV::is_identity(acc)) run = fp_mul<Fq>(run, fp_mul<Fq>(acc.zz, acc.zzz));
     if (w + 1 < nwin) for (int k = 0; k < c; k++) acc = CV::dbl(acc);
   }
-  fpn<N> inv = fn_inv<Fq>(run);
+  fpn<N> inv = fp_inv_gcd<Fq>(run);
 #pragma unroll 1
   for (int w = nwin - 1; w >= 0; w--) {
     const size_t e = (size_t)w * n + i;
     uint32_t *o = table + e * 2 * N;
-    const fpn<N> zz = fn_load<N>(tmp + e * 3 * N), zzz = fn_load<N>(tmp + e * 3 * N + N);
-    if (fn_is_zero(zz)) { fn_store<N>(o, fn_zero<N>()); fn_store<N>(o + N, fn_zero<N>()); continue; }
-    const fpn<N> dinv = fn_mul<Fq>(inv, fn_load<N>(tmp + e * 3 * N + 2 * N));     // 1 / (ZZ ZZZ) of this row
-    inv = fn_mul<Fq>(inv, fn_mul<Fq>(zz, zzz));
-    fn_store<N>(o, fn_mul<Fq>(fn_load<N>(o), fn_mul<Fq>(dinv, zzz)));             // X / ZZ
-    fn_store<N>(o + N, fn_mul<Fq>(fn_load<N>(o + N), fn_mul<Fq>(dinv, zz)));      // Y / ZZZ
+    const fpn<N> zz = fp_load<N>(tmp + e * 3 * N), zzz = fp_load<N>(tmp + e * 3 * N + N);
+    if (fp_is_zero(zz)) { fp_store<N>(o, fp_zero<N>()); fp_store<N>(o + N, fp_zero<N>()); continue; }
+    const fpn<N> dinv = fp_mul<Fq>(inv, fp_load<N>(tmp + e * 3 * N + 2 * N));     // 1 / (ZZ ZZZ) of this row
+    inv = fp_mul<Fq>(inv, fp_mul<Fq>(zz, zzz));
+    fp_store<N>(o, fp_mul<Fq>(fp_load<N>(o), fp_mul<Fq>(dinv, zzz)));             // X / ZZ
+    fp_store<N>(o + N, fp_mul<Fq>(fp_load<N>(o + N), fp_mul<Fq>(dinv, zz)));      // Y / ZZZ
   }
 }
 
@@ -1145,7 +1145,7 @@ k_g1_subgroup_bls(const uint32_t *__restrict__ bases, uint32_t n, uint32_t *__re
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const CV::base_t P = CV::load_base(bases + (size_t)i * 2 * N);
-  if (fn_is_zero(P.x) && fn_is_zero(P.y)) return;
+  if (fp_is_zero(P.x) && fp_is_zero(P.y)) return;
   const uint64_t z = 0xd201000000010000ull;
   CV::acc_t a = CV::from_affine(P);
 #pragma unroll 1
@@ -1155,9 +1155,9 @@ k_g1_subgroup_bls(const uint32_t *__restrict__ bases, uint32_t n, uint32_t *__re
   for (int b = 62; b >= 0; b--) { a = CV::dbl(a); if ((z >> b) & 1) a = CV::add(a, q1); }      // [z^2] P
   fpn<N> beta; for (int k = 0; k < N; k++) beta.v[k] = BLS12_381_BETA_MONT[k];
   // [z^2] P == (beta x, -y)  in XYZZ:  X = beta x ZZ,  Y = -y ZZZ,  ZZ != 0
-  bool ok = !fn_is_zero(a.zz);
-  ok = ok && fn_eq(a.x, fn_mul<Fq>(fn_mul<Fq>(beta, P.x), a.zz));
-  ok = ok && fn_eq(a.y, fn_neg<Fq>(fn_mul<Fq>(P.y, a.zzz)));
+  bool ok = !fp_is_zero(a.zz);
+  ok = ok && fp_eq(a.x, fp_mul<Fq>(fp_mul<Fq>(beta, P.x), a.zz));
+  ok = ok && fp_eq(a.y, fp_neg<Fq>(fp_mul<Fq>(P.y, a.zzz)));
   if (!ok) { atomicOr(flag, 2u); if (rec_status) rec_status[i / ppr] = 2; }
 }
 void launch_g1_subgroup_check(int curve, const uint32_t *d_bases, size_t n, uint32_t *d_flag, hipStream_t stream, int32_t *d_rec_status, uint32_t ppr) {
@@ -1194,8 +1194,8 @@ k_g1_lincomb(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ sc
       { fpn<N> beta;
 #pragma unroll
         for (int i = 0; i < N; i++) beta.v[i] = BLS12_381_BETA_MONT[i];
-        Q.x = fn_mul<Fq>(beta, P.x); Q.y = fn_neg<Fq>(P.y);
-        if (fn_is_zero(P.x) && fn_is_zero(P.y)) Q = P; }               // infinity stays infinity
+        Q.x = fp_mul<Fq>(beta, P.x); Q.y = fp_neg<Fq>(P.y);
+        if (fp_is_zero(P.x) && fp_is_zero(P.y)) Q = P; }               // infinity stays infinity
       typename CV::acc_t tab[16];                                      // tab[4 j + i] = i P + j Q (per-lane scratch)
       tab[0] = CV::identity(); tab[4] = CV::from_affine(Q);
       tab[8] = CV::madd(tab[4], Q, false); tab[12] = CV::madd(tab[8], Q, false);
@@ -1233,11 +1233,11 @@ k_g1_lincomb(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ sc
   }
   if (live && (k == 0 || k == split)) {
     uint32_t *o = out + ((size_t)item * 2 + (k == 0 ? 0 : 1)) * 2 * N;
-    if (CV::is_identity(acc)) { fn_store<N>(o, fn_zero<N>()); fn_store<N>(o + N, fn_zero<N>()); }
+    if (CV::is_identity(acc)) { fp_store<N>(o, fp_zero<N>()); fp_store<N>(o + N, fp_zero<N>()); }
     else {
-      const fpn<N> inv = fn_inv<Fq>(fn_mul<Fq>(acc.zz, acc.zzz));
-      fn_store<N>(o, fn_mul<Fq>(acc.x, fn_mul<Fq>(inv, acc.zzz)));       // X / ZZ
-      fn_store<N>(o + N, fn_mul<Fq>(acc.y, fn_mul<Fq>(inv, acc.zz)));    // Y / ZZZ
+      const fpn<N> inv = fp_inv_gcd<Fq>(fp_mul<Fq>(acc.zz, acc.zzz));
+      fp_store<N>(o, fp_mul<Fq>(acc.x, fp_mul<Fq>(inv, acc.zzz)));       // X / ZZ
+      fp_store<N>(o + N, fp_mul<Fq>(acc.y, fp_mul<Fq>(inv, acc.zz)));    // Y / ZZZ
     }
   }
 }
@@ -1335,27 +1335,27 @@ k_g1_multiples(const uint32_t *__restrict__ rowbase, uint32_t n, uint32_t rows, 
   const typename CV::base_t B = CV::load_base(rowbase + ((size_t)w * n + i) * 2 * N);
   typename CV::acc_t acc = CV::from_affine(B);
   if (m0) acc = CV::madd(CV::from_affine(CV::load_base(table + (t.off[w] + (uint64_t)(m0 - 1) * n + i) * 2 * N)), B, false);
-  fpn<N> run = fn_one<Fq>();
+  fpn<N> run = fp_one<Fq>();
 #pragma unroll 1
   for (uint32_t m = m0; m < kend; m++) {
     uint32_t *o = table + (t.off[w] + (uint64_t)m * n + i) * 2 * N;
     uint32_t *q = tmp + ((size_t)(m - m0) * lanes + lane) * 3 * N;
-    fn_store<N>(o, acc.x); fn_store<N>(o + N, acc.y);
-    fn_store<N>(q, acc.zz); fn_store<N>(q + N, acc.zzz); fn_store<N>(q + 2 * N, run);
-    if (!CV::is_identity(acc)) run = fn_mul<Fq>(run, fn_mul<Fq>(acc.zz, acc.zzz));
+    fp_store<N>(o, acc.x); fp_store<N>(o + N, acc.y);
+    fp_store<N>(q, acc.zz); fp_store<N>(q + N, acc.zzz); fp_store<N>(q + 2 * N, run);
+    if (!CV::is_identity(acc)) run = fp_mul<Fq>(run, fp_mul<Fq>(acc.zz, acc.zzz));
     if (m + 1 < kend) acc = m == 0 ? CV::dbl(acc) : CV::madd(acc, B, false);
   }
-  fpn<N> inv = fn_inv<Fq>(run);
+  fpn<N> inv = fp_inv_gcd<Fq>(run);
 #pragma unroll 1
   for (uint32_t m = kend; m-- > m0;) {
     uint32_t *o = table + (t.off[w] + (uint64_t)m * n + i) * 2 * N;
     const uint32_t *q = tmp + ((size_t)(m - m0) * lanes + lane) * 3 * N;
-    const fpn<N> zz = fn_load<N>(q), zzz = fn_load<N>(q + N);
-    if (fn_is_zero(zz)) { fn_store<N>(o, fn_zero<N>()); fn_store<N>(o + N, fn_zero<N>()); continue; }
-    const fpn<N> dinv = fn_mul<Fq>(inv, fn_load<N>(q + 2 * N));              // 1 / (ZZ ZZZ) of this multiple
-    inv = fn_mul<Fq>(inv, fn_mul<Fq>(zz, zzz));
-    fn_store<N>(o, fn_mul<Fq>(fn_load<N>(o), fn_mul<Fq>(dinv, zzz)));        // X / ZZ
-    fn_store<N>(o + N, fn_mul<Fq>(fn_load<N>(o + N), fn_mul<Fq>(dinv, zz)));  // Y / ZZZ
+    const fpn<N> zz = fp_load<N>(q), zzz = fp_load<N>(q + N);
+    if (fp_is_zero(zz)) { fp_store<N>(o, fp_zero<N>()); fp_store<N>(o + N, fp_zero<N>()); continue; }
+    const fpn<N> dinv = fp_mul<Fq>(inv, fp_load<N>(q + 2 * N));              // 1 / (ZZ ZZZ) of this multiple
+    inv = fp_mul<Fq>(inv, fp_mul<Fq>(zz, zzz));
+    fp_store<N>(o, fp_mul<Fq>(fp_load<N>(o), fp_mul<Fq>(dinv, zzz)));        // X / ZZ
+    fp_store<N>(o + N, fp_mul<Fq>(fp_load<N>(o + N), fp_mul<Fq>(dinv, zz)));  // Y / ZZZ
   }
 }
 template <class C> static void build_direct_impl(const uint32_t *d_bases, G1DirectTable *t, hipStream_t stream) {

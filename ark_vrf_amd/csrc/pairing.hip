@@ -57,7 +57,7 @@ template <class F> AVRF_DI void wide_fold(uint32_t (&acc)[2 * F::N]) {
   fe<F> h, u;
 #pragma unroll
   for (int i = 0; i < N; i++) h.v[i] = acc[N + i];
-  const uint32_t br = fn_sub_p<F>(u, h);
+  const uint32_t br = sub_p<F>(u, h);
 #pragma unroll
   for (int i = 0; i < N; i++) acc[N + i] = br ? h.v[i] : u.v[i];
 }
@@ -83,7 +83,7 @@ template <class F> AVRF_DI fe<F> redc(const uint32_t (&t)[2 * F::N]) {
     r.v[k - N] = (uint32_t)lo;
     lo = (lo >> 32) | ((uint64_t)ex << 32); ex = 0;
   }
-  const uint32_t br = fn_sub_p<F>(u, r);
+  const uint32_t br = sub_p<F>(u, r);
 #pragma unroll
   for (int i = 0; i < N; i++) r.v[i] = br ? r.v[i] : u.v[i];
   return r;
@@ -102,7 +102,7 @@ template <int N> AVRF_DI fpn<N> grp_shfl(const fpn<N> &a, int src_k) {   // valu
 template <class C> struct Cst {
   using F = typename C::Fq; static constexpr int N = F::N;
   const uint32_t *p;
-  AVRF_DI fe<F> at(int idx) const { return fn_load<N>(p + (size_t)idx * N); }
+  AVRF_DI fe<F> at(int idx) const { return fp_load<N>(p + (size_t)idx * N); }
 };
 
 // the reduction of the two raw sums (coefficients k and k + 12) shared by the three multiplication forms
@@ -115,8 +115,8 @@ template <class C> AVRF_DI fpn<C::Fq::N> f12_finish(uint32_t (&lo_acc)[2 * C::Fq
   const fe<F> Hp = grp_shfl<N>(H, lowk ? k + 6 : k - 6);
   Cst<C> K{cst};
   const fe<F> c1 = K.at(lowk ? PC_KAPPA : PC_4XI2_MINUS_KAPPA), c2 = K.at(lowk ? PC_2XI_KAPPA : PC_2XI);
-  const fe<F> t1 = fn_mul<F>(H, c1), t2 = fn_mul<F>(Hp, c2);
-  return lowk ? fn_sub<F>(fn_sub<F>(L, t1), t2) : fn_add<F>(fn_add<F>(L, t1), t2);
+  const fe<F> t1 = fp_mul<F>(H, c1), t2 = fp_mul<F>(Hp, c2);
+  return lowk ? fp_sub<F>(fp_sub<F>(L, t1), t2) : fp_add<F>(fp_add<F>(L, t1), t2);
 }
 // product of two Fp12 elements; k = this lane's coefficient index (lanes 12..15 produce garbage that nobody reads)
 template <class C> __device__ __noinline__ static fpn<C::Fq::N> f12_mul(fpn<C::Fq::N> a, fpn<C::Fq::N> b, int k, const uint32_t *cst) {
@@ -205,11 +205,11 @@ template <class C> __device__ __noinline__ static fpn<C::Fq::N> f12_mul_line(fpn
   return f12_finish<C>(lo_acc, hi_acc, k, cst);
 }
 
-template <class C> AVRF_DI fpn<C::Fq::N> f12_one(int k) { return k == 0 ? fn_one<typename C::Fq>() : fn_zero<C::Fq::N>(); }
-template <class C> AVRF_DI fpn<C::Fq::N> f12_conj(const fpn<C::Fq::N> &a, int k) { return (k & 1) ? fn_neg<typename C::Fq>(a) : a; }   // a^(p^6)
+template <class C> AVRF_DI fpn<C::Fq::N> f12_one(int k) { return k == 0 ? fp_one<typename C::Fq>() : fp_zero<C::Fq::N>(); }
+template <class C> AVRF_DI fpn<C::Fq::N> f12_conj(const fpn<C::Fq::N> &a, int k) { return (k & 1) ? fp_neg<typename C::Fq>(a) : a; }   // a^(p^6)
 // a^(p^2), a^(p^4): the Fp2 coefficient of w^(k mod 6) is scaled by gamma^(k mod 6), gamma = xi^((p^2-1)/6) in Fp
 template <class C> AVRF_DI fpn<C::Fq::N> f12_frob2(const fpn<C::Fq::N> &a, int k, const uint32_t *cst) {
-  Cst<C> K{cst}; return fn_mul<typename C::Fq>(a, K.at(PC_FROB2 + (k < 12 ? k % 6 : 0)));
+  Cst<C> K{cst}; return fp_mul<typename C::Fq>(a, K.at(PC_FROB2 + (k < 12 ? k % 6 : 0)));
 }
 // a^p: A_k -> conj(A_k) * gamma1_k with A_k = (d_k + xi0 d_(k+6)) + d_(k+6) u
 template <class C> __device__ __noinline__ static fpn<C::Fq::N> f12_frob1(fpn<C::Fq::N> a, int k, const uint32_t *cst) {
@@ -218,12 +218,12 @@ template <class C> __device__ __noinline__ static fpn<C::Fq::N> f12_frob1(fpn<C:
   const bool lowk = k < 6; const int kk = k < 12 ? k % 6 : 0;
   const fe<F> other = grp_shfl<N>(a, lowk ? k + 6 : (k < 12 ? k - 6 : 0));
   const fe<F> d_lo = lowk ? a : other, d_hi = lowk ? other : a;
-  const fe<F> x0 = fn_add<F>(d_lo, fn_mul<F>(d_hi, K.at(PC_XI0))), x1 = fn_neg<F>(d_hi);   // conj(A) = x0 + x1 u
+  const fe<F> x0 = fp_add<F>(d_lo, fp_mul<F>(d_hi, K.at(PC_XI0))), x1 = fp_neg<F>(d_hi);   // conj(A) = x0 + x1 u
   const fe<F> g0 = K.at(PC_FROB1 + 2 * kk), g1 = K.at(PC_FROB1 + 2 * kk + 1);
-  const fe<F> y1 = fn_add<F>(fn_mul<F>(x0, g1), fn_mul<F>(x1, g0));                        // imaginary part of the product
+  const fe<F> y1 = fp_add<F>(fp_mul<F>(x0, g1), fp_mul<F>(x1, g0));                        // imaginary part of the product
   if (!lowk) return y1;                                                                   // d'_(k+6) = y1
-  const fe<F> y0 = fn_sub<F>(fn_mul<F>(x0, g0), fn_mul<F>(x1, g1));
-  return fn_sub<F>(y0, fn_mul<F>(y1, K.at(PC_XI0)));                                       // d'_k = y0 - xi0 y1
+  const fe<F> y0 = fp_sub<F>(fp_mul<F>(x0, g0), fp_mul<F>(x1, g1));
+  return fp_sub<F>(y0, fp_mul<F>(y1, K.at(PC_XI0)));                                       // d'_k = y0 - xi0 y1
 }
 // 1 / a: n = a conj(a) in Fp6, N = n n^(p^2) n^(p^4) in Fp2, one Fp inversion of its norm
 template <class C> __device__ __noinline__ static fpn<C::Fq::N> f12_inv(fpn<C::Fq::N> a, int k, const uint32_t *cst) {
@@ -235,11 +235,11 @@ template <class C> __device__ __noinline__ static fpn<C::Fq::N> f12_inv(fpn<C::F
   const fe<F> t = f12_mul<C>(n2, n4, k, cst);
   const fe<F> Nn = f12_mul<C>(n, t, k, cst);                     // only coefficients 0 and 6 are non-zero
   const fe<F> d0 = grp_shfl<N>(Nn, 0), d6 = grp_shfl<N>(Nn, 6);
-  const fe<F> xa = fn_add<F>(d0, fn_mul<F>(d6, K.at(PC_XI0)));   // N = xa + d6 u
-  const fe<F> ni = fn_inv<F>(fn_add<F>(fn_sqr<F>(xa), fn_sqr<F>(d6)));
-  const fe<F> ia = fn_mul<F>(xa, ni), ib = fn_neg<F>(fn_mul<F>(d6, ni));                    // 1/N = ia + ib u
-  fe<F> Ninv = fn_zero<N>();
-  if (k == 0) Ninv = fn_sub<F>(ia, fn_mul<F>(ib, K.at(PC_XI0)));
+  const fe<F> xa = fp_add<F>(d0, fp_mul<F>(d6, K.at(PC_XI0)));   // N = xa + d6 u
+  const fe<F> ni = fp_inv_gcd<F>(fp_add<F>(fp_sqr<F>(xa), fp_sqr<F>(d6)));
+  const fe<F> ia = fp_mul<F>(xa, ni), ib = fp_neg<F>(fp_mul<F>(d6, ni));                    // 1/N = ia + ib u
+  fe<F> Ninv = fp_zero<N>();
+  if (k == 0) Ninv = fp_sub<F>(ia, fp_mul<F>(ib, K.at(PC_XI0)));
   if (k == 6) Ninv = ib;
   const fe<F> ninv = f12_mul<C>(t, Ninv, k, cst);
   return f12_mul<C>(ac, ninv, k, cst);
@@ -278,11 +278,11 @@ k_pairing_check(const uint32_t *__restrict__ pts, const uint32_t *__restrict__ t
 #pragma unroll 1
       for (uint32_t q = 0; q < np; q++) {
         const uint32_t *pp = pts + ((size_t)item * np + q) * 2 * N;
-        const fe<F> xp = fn_load<N>(pp), yp = fn_load<N>(pp + N);
-        if (fn_is_zero(xp) && fn_is_zero(yp)) continue;          // point at infinity (uniform inside the group)
+        const fe<F> xp = fp_load<N>(pp), yp = fp_load<N>(pp + N);
+        if (fp_is_zero(xp) && fp_is_zero(yp)) continue;          // point at infinity (uniform inside the group)
         const uint32_t *tp = tab + (((size_t)q * steps + s) * 36 + kc) * N;
-        fe<F> l = fn_add<F>(fn_load<N>(tp), fn_add<F>(fn_mul<F>(fn_load<N>(tp + 12 * N), xp), fn_mul<F>(fn_load<N>(tp + 24 * N), yp)));
-        if (k >= 12) l = fn_zero<N>();
+        fe<F> l = fp_add<F>(fp_load<N>(tp), fp_add<F>(fp_mul<F>(fp_load<N>(tp + 12 * N), xp), fp_mul<F>(fp_load<N>(tp + 24 * N), yp)));
+        if (k >= 12) l = fp_zero<N>();
         f = f12_mul_line<C>(f, l, k, cst);
       }
     }
@@ -306,7 +306,7 @@ k_pairing_check(const uint32_t *__restrict__ pts, const uint32_t *__restrict__ t
       if ((C::HARD_EXP[bit >> 6] >> (bit & 63)) & 1) out = f12_mul<C>(out, t, k, cst);
     }
   }
-  const bool mine = k >= 12 || (k == 0 ? fn_eq(out, fn_one<F>()) : fn_is_zero(out));
+  const bool mine = k >= 12 || (k == 0 ? fp_eq(out, fp_one<F>()) : fp_is_zero(out));
   const uint64_t m = __ballot(mine);
   if (live && k == 0) ok[item] = (((m >> (16 * grp)) & 0xffffu) == 0xffffu) ? 1 : 0;
 }
@@ -315,17 +315,17 @@ k_pairing_check(const uint32_t *__restrict__ pts, const uint32_t *__restrict__ t
 
 // Fp2 = Fp[u] / (u^2 + 1) in one lane
 template <class F> struct f2d { fe<F> a, b; };
-template <class F> AVRF_DI f2d<F> f2_add(const f2d<F> &x, const f2d<F> &y) { return {fn_add<F>(x.a, y.a), fn_add<F>(x.b, y.b)}; }
-template <class F> AVRF_DI f2d<F> f2_sub(const f2d<F> &x, const f2d<F> &y) { return {fn_sub<F>(x.a, y.a), fn_sub<F>(x.b, y.b)}; }
+template <class F> AVRF_DI f2d<F> f2_add(const f2d<F> &x, const f2d<F> &y) { return {fp_add<F>(x.a, y.a), fp_add<F>(x.b, y.b)}; }
+template <class F> AVRF_DI f2d<F> f2_sub(const f2d<F> &x, const f2d<F> &y) { return {fp_sub<F>(x.a, y.a), fp_sub<F>(x.b, y.b)}; }
 template <class F> __device__ __noinline__ static f2d<F> f2_mul(f2d<F> x, f2d<F> y) {
-  const fe<F> t0 = fn_mul<F>(x.a, y.a), t1 = fn_mul<F>(x.b, y.b), t2 = fn_mul<F>(fn_add<F>(x.a, x.b), fn_add<F>(y.a, y.b));
-  return {fn_sub<F>(t0, t1), fn_sub<F>(fn_sub<F>(t2, t0), t1)};
+  const fe<F> t0 = fp_mul<F>(x.a, y.a), t1 = fp_mul<F>(x.b, y.b), t2 = fp_mul<F>(fp_add<F>(x.a, x.b), fp_add<F>(y.a, y.b));
+  return {fp_sub<F>(t0, t1), fp_sub<F>(fp_sub<F>(t2, t0), t1)};
 }
 template <class F> __device__ __noinline__ static f2d<F> f2_inv(f2d<F> x) {
-  const fe<F> n = fn_inv<F>(fn_add<F>(fn_sqr<F>(x.a), fn_sqr<F>(x.b)));
-  return {fn_mul<F>(x.a, n), fn_neg<F>(fn_mul<F>(x.b, n))};
+  const fe<F> n = fp_inv_gcd<F>(fp_add<F>(fp_sqr<F>(x.a), fp_sqr<F>(x.b)));
+  return {fp_mul<F>(x.a, n), fp_neg<F>(fp_mul<F>(x.b, n))};
 }
-template <class F> AVRF_DI bool f2_is_zero(const f2d<F> &x) { return fn_is_zero(x.a) && fn_is_zero(x.b); }
+template <class F> AVRF_DI bool f2_is_zero(const f2d<F> &x) { return fp_is_zero(x.a) && fp_is_zero(x.b); }
 
 // One lane per G2 point Q (affine on the sextic twist, Montgomery x.a | x.b | y.a | y.b): walks the ate loop with affine
 // doubling / addition over Fp2 and writes, per step, the line's three coefficient vectors in the direct basis:
@@ -340,24 +340,24 @@ k_g2_lines(const uint32_t *__restrict__ q_in, uint32_t nq, uint32_t steps, const
   const uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x;
   if (qi >= nq) return;
   Cst<C> K{cst};
-  const fe<F> xi0 = K.at(PC_XI0), zero = fn_zero<N>();
+  const fe<F> xi0 = K.at(PC_XI0), zero = fp_zero<N>();
   const uint32_t *src = q_in + (size_t)qi * 4 * N;
-  const f2d<F> qx = {fn_load<N>(src), fn_load<N>(src + N)}, qy = {fn_load<N>(src + 2 * N), fn_load<N>(src + 3 * N)};
+  const f2d<F> qx = {fp_load<N>(src), fp_load<N>(src + N)}, qy = {fp_load<N>(src + 2 * N), fp_load<N>(src + 3 * N)};
   f2d<F> tx = qx, ty = qy;
   uint32_t s = 0;
   auto emit = [&](const f2d<F> &lam, const f2d<F> &c) {
     uint32_t *o = tab + ((size_t)qi * steps + s) * 36 * N;
-    for (int i = 0; i < 36; i++) fn_store<N>(o + (size_t)i * N, zero);
-    const fe<F> c_lo = fn_sub<F>(c.a, fn_mul<F>(c.b, xi0)), m_lo = fn_neg<F>(fn_sub<F>(lam.a, fn_mul<F>(lam.b, xi0))), m_hi = fn_neg<F>(lam.b);
-    const fe<F> one = fn_one<F>();
+    for (int i = 0; i < 36; i++) fp_store<N>(o + (size_t)i * N, zero);
+    const fe<F> c_lo = fp_sub<F>(c.a, fp_mul<F>(c.b, xi0)), m_lo = fp_neg<F>(fp_sub<F>(lam.a, fp_mul<F>(lam.b, xi0))), m_hi = fp_neg<F>(lam.b);
+    const fe<F> one = fp_one<F>();
     if (C::MTWIST) {
-      fn_store<N>(o + 0 * N, c_lo); fn_store<N>(o + 6 * N, c.b);                          // T0: c at w^0
-      fn_store<N>(o + (12 + 2) * N, m_lo); fn_store<N>(o + (12 + 8) * N, m_hi);           // TX: -lam at w^2
-      fn_store<N>(o + (24 + 3) * N, one);                                                 // TY: 1 at w^3
+      fp_store<N>(o + 0 * N, c_lo); fp_store<N>(o + 6 * N, c.b);                          // T0: c at w^0
+      fp_store<N>(o + (12 + 2) * N, m_lo); fp_store<N>(o + (12 + 8) * N, m_hi);           // TX: -lam at w^2
+      fp_store<N>(o + (24 + 3) * N, one);                                                 // TY: 1 at w^3
     } else {
-      fn_store<N>(o + (24 + 0) * N, one);                                                 // TY: 1 at w^0
-      fn_store<N>(o + (12 + 1) * N, m_lo); fn_store<N>(o + (12 + 7) * N, m_hi);           // TX: -lam at w^1
-      fn_store<N>(o + 3 * N, c_lo); fn_store<N>(o + 9 * N, c.b);                          // T0: c at w^3
+      fp_store<N>(o + (24 + 0) * N, one);                                                 // TY: 1 at w^0
+      fp_store<N>(o + (12 + 1) * N, m_lo); fp_store<N>(o + (12 + 7) * N, m_hi);           // TX: -lam at w^1
+      fp_store<N>(o + 3 * N, c_lo); fp_store<N>(o + 9 * N, c.b);                          // T0: c at w^3
     }
     s++;
   };

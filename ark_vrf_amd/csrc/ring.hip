@@ -54,8 +54,8 @@ __global__ void k_ntt_bitrev(uint32_t *__restrict__ data, uint32_t n, int logn, 
   uint32_t j = __brev(i) >> (32 - logn);
   if (i < j) {
     uint32_t *p = data + ((size_t)b * n + i) * 8, *q = data + ((size_t)b * n + j) * 8;
-    fp x = load_fp(p), y = load_fp(q);
-    store_fp(p, y); store_fp(q, x);
+    fp x = fp_load(p), y = fp_load(q);
+    fp_store(p, y); fp_store(q, x);
   }
 }
 template <class F>
@@ -63,7 +63,7 @@ __global__ void k_ntt_scale(uint32_t *__restrict__ data, uint32_t total, fp k) {
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
   uint32_t *p = data + (size_t)t * 8;
-  store_fp(p, fp_mul<F>(load_fp(p), k));
+  fp_store(p, fp_mul<F>(fp_load(p), k));
 }
 
 // Up to 8 consecutive butterfly stages [s0, s1) on a tile held in LDS: 2^(s1-s0) rows with row stride 2^s0 elements
@@ -84,9 +84,9 @@ k_ntt_fused(const uint32_t *__restrict__ src, uint32_t src_n, uint32_t *__restri
   for (uint32_t e = threadIdx.x; e < tile; e += blockDim.x) {
     const uint32_t i = base + ((e >> cols_log) << s0) + (e & (cols - 1));
     fp v;
-    if (brev_load) { const uint32_t j = __brev(i) >> (32 - logn); v = j < src_n ? load_fp(src + ((size_t)b * src_n + j) * 8) : fp_zero(); }
-    else v = load_fp(src + ((size_t)b * n + i) * 8);
-    store_fp(sh + e * 8, v);
+    if (brev_load) { const uint32_t j = __brev(i) >> (32 - logn); v = j < src_n ? fp_load(src + ((size_t)b * src_n + j) * 8) : fp_zero(); }
+    else v = fp_load(src + ((size_t)b * n + i) * 8);
+    fp_store(sh + e * 8, v);
   }
   __syncthreads();
   // (the twiddles are read from global memory inside the butterflies: preloading the tile - cols <= 255 twiddles of a pass into a
@@ -98,18 +98,18 @@ k_ntt_fused(const uint32_t *__restrict__ src, uint32_t src_n, uint32_t *__restri
       const uint32_t grp = jr >> hl, pos = jr & ((1u << hl) - 1);
       const uint32_t r0 = (grp << (hl + 1)) + pos, r1 = r0 + (1u << hl);
       const uint32_t pg = (pos << s0) + (lo << cols_log) + c;          // position inside the stage's global group
-      const fp w = load_fp(tw + ((size_t)pg << (logn - 1 - s)) * 8);
+      const fp w = fp_load(tw + ((size_t)pg << (logn - 1 - s)) * 8);
       uint32_t *p = sh + ((r0 << cols_log) + c) * 8, *q = sh + ((r1 << cols_log) + c) * 8;
-      const fp u = load_fp(p), v = fp_mul<F>(load_fp(q), w);
-      store_fp(p, fp_add<F>(u, v)); store_fp(q, fp_sub<F>(u, v));
+      const fp u = fp_load(p), v = fp_mul<F>(fp_load(q), w);
+      fp_store(p, fp_add<F>(u, v)); fp_store(q, fp_sub<F>(u, v));
     }
     __syncthreads();
   }
   for (uint32_t e = threadIdx.x; e < tile; e += blockDim.x) {
     const uint32_t i = base + ((e >> cols_log) << s0) + (e & (cols - 1));
-    fp v = load_fp(sh + e * 8);
+    fp v = fp_load(sh + e * 8);
     if (do_scale) v = fp_mul<F>(v, scale);
-    store_fp(dst + ((size_t)b * n + i) * 8, v);
+    fp_store(dst + ((size_t)b * n + i) * 8, v);
   }
 }
 
@@ -155,13 +155,13 @@ k_ring_constraints(const uint32_t *__restrict__ e4, const uint32_t *__restrict__
   e4 += (size_t)proof * 4 * M * 8; out += (size_t)proof * M * 8;
   const RingConsts &c = consts[proof];
   const uint32_t is = (i + 4) & (M - 1);                              // column(wX) on the 4N domain
-  auto at = [&](const uint32_t *base, uint32_t col, uint32_t idx) { return load_fp(base + ((size_t)col * M + idx) * 8); };
+  auto at = [&](const uint32_t *base, uint32_t col, uint32_t idx) { return fp_load(base + ((size_t)col * M + idx) * 8); };
   const fp one = fp_one<F>();
   const fp b = at(e4, 0, i), ip = at(e4, 1, i), x1 = at(e4, 2, i), y1 = at(e4, 3, i);
   const fp ips = at(e4, 1, is), x3 = at(e4, 2, is), y3 = at(e4, 3, is);
   const fp x2 = at(fixed4, 0, i), y2 = at(fixed4, 1, i), sel = at(fixed4, 2, i);
   const fp lf = at(l4, 0, i), ll = at(l4, 1, i);
-  fp xi = load_fp(tw4 + (size_t)(i & (M / 2 - 1)) * 8);
+  fp xi = fp_load(tw4 + (size_t)(i & (M / 2 - 1)) * 8);
   if (i >= M / 2) xi = fp_neg<F>(xi);
   const fp nl = fp_sub<F>(xi, c.w_last), omb = fp_sub<F>(one, b);
   const fp x1y1 = fp_mul<F>(x1, y1), x2y2 = fp_mul<F>(x2, y2);
@@ -177,7 +177,7 @@ k_ring_constraints(const uint32_t *__restrict__ e4, const uint32_t *__restrict__
   fp s = fp_mul<F>(c.alpha[0], c0);
   s = fp_add<F>(s, fp_mul<F>(c.alpha[1], c1)); s = fp_add<F>(s, fp_mul<F>(c.alpha[2], c2)); s = fp_add<F>(s, fp_mul<F>(c.alpha[3], c3));
   s = fp_add<F>(s, fp_mul<F>(c.alpha[4], c4)); s = fp_add<F>(s, fp_mul<F>(c.alpha[5], c5)); s = fp_add<F>(s, fp_mul<F>(c.alpha[6], c6));
-  store_fp(out + (size_t)i * 8, s);
+  fp_store(out + (size_t)i * 8, s);
 }
 
 
@@ -196,20 +196,20 @@ template <class F> AVRF_DI fp fp_pow_u32(fp a, uint32_t e) {
 template <class F> AVRF_DI fp block_sum256(fp v, uint32_t *sh) {
   const uint32_t t = threadIdx.x;
   __syncthreads();
-  store_fp(sh + t * 8, v);
+  fp_store(sh + t * 8, v);
   __syncthreads();
   for (uint32_t s = 128; s > 0; s >>= 1) {
-    if (t < s) store_fp(sh + t * 8, fp_add<F>(load_fp(sh + t * 8), load_fp(sh + (t + s) * 8)));
+    if (t < s) fp_store(sh + t * 8, fp_add<F>(fp_load(sh + t * 8), fp_load(sh + (t + s) * 8)));
     __syncthreads();
   }
-  return load_fp(sh);
+  return fp_load(sh);
 }
 // value at x of the length-len polynomial c: lane t takes coefficients [t*L, (t+1)*L)
 template <class F> AVRF_DI fp block_eval256(const uint32_t *c, uint32_t len, const fp &x, uint32_t *sh) {
   const uint32_t t = threadIdx.x, L = (len + 255) / 256;
   uint32_t lo = t * L, hi = lo + L; if (hi > len) hi = len;
   fp h = fp_zero();
-  for (uint32_t i = hi; i > lo; i--) h = fp_add<F>(fp_mul<F>(h, x), load_fp(c + (size_t)(i - 1) * 8));
+  for (uint32_t i = hi; i > lo; i--) h = fp_add<F>(fp_mul<F>(h, x), fp_load(c + (size_t)(i - 1) * 8));
   if (lo < hi) h = fp_mul<F>(h, fp_pow_u32<F>(x, lo));
   return block_sum256<F>(h, sh);
 }
@@ -224,12 +224,12 @@ k_ring_quotient(const uint32_t *__restrict__ agg, uint32_t N, uint32_t qlen, Fp3
   const uint32_t *a = agg + (size_t)blockIdx.y * M * 8;
   fp acc = fp_zero();
   for (uint32_t k = i + N; k <= M + 2; k += N) {
-    if (k < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[0], load_fp(a + (size_t)k * 8)));
-    if (k >= 1 && k - 1 < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[1], load_fp(a + (size_t)(k - 1) * 8)));
-    if (k >= 2 && k - 2 < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[2], load_fp(a + (size_t)(k - 2) * 8)));
-    if (k >= 3 && k - 3 < M) acc = fp_add<F>(acc, load_fp(a + (size_t)(k - 3) * 8));
+    if (k < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[0], fp_load(a + (size_t)k * 8)));
+    if (k >= 1 && k - 1 < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[1], fp_load(a + (size_t)(k - 1) * 8)));
+    if (k >= 2 && k - 2 < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[2], fp_load(a + (size_t)(k - 2) * 8)));
+    if (k >= 3 && k - 3 < M) acc = fp_add<F>(acc, fp_load(a + (size_t)(k - 3) * 8));
   }
-  store_fp(q + ((size_t)blockIdx.y * qlen + i) * 8, acc);
+  fp_store(q + ((size_t)blockIdx.y * qlen + i) * 8, acc);
 }
 
 // ev[proof][c] = poly_c(zeta_proof), c: px | py | sel (fixed, shared) | bits | ip | ax | ay (coef: proof x 4 x N)
@@ -240,8 +240,8 @@ k_ring_evals(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ fix
   __shared__ uint32_t sh[256 * 8];
   const uint32_t c = blockIdx.x, p = blockIdx.y;
   const uint32_t *poly = c < 3 ? fixed + (size_t)c * N * 8 : coef + ((size_t)p * 4 + (c - 3)) * N * 8;
-  fp v = block_eval256<F>(poly, N, load_fp(zeta + (size_t)p * 8), sh);
-  if (threadIdx.x == 0) store_fp(ev + ((size_t)p * 7 + c) * 8, v);
+  fp v = block_eval256<F>(poly, N, fp_load(zeta + (size_t)p * 8), sh);
+  if (threadIdx.x == 0) fp_store(ev + ((size_t)p * 7 + c) * 8, v);
 }
 
 // linearisation polynomial lin = f0 ip + f1 ax + f2 ay (f from the evaluations, A.7 step 6) and lin(zeta w)
@@ -254,8 +254,8 @@ k_ring_lin(const uint32_t *__restrict__ coef, const RingConsts *__restrict__ con
   const uint32_t p = blockIdx.x, t = threadIdx.x;
   const RingConsts &c = consts[p];
   const uint32_t *e = ev + (size_t)p * 7 * 8;
-  const fp z = load_fp(zeta + (size_t)p * 8), one = fp_one<F>();
-  const fp x2 = load_fp(e), y2 = load_fp(e + 8), b = load_fp(e + 24), x1 = load_fp(e + 40), y1 = load_fp(e + 48);
+  const fp z = fp_load(zeta + (size_t)p * 8), one = fp_one<F>();
+  const fp x2 = fp_load(e), y2 = fp_load(e + 8), b = fp_load(e + 24), x1 = fp_load(e + 40), y1 = fp_load(e + 48);
   const fp nlz = fp_sub<F>(z, c.w_last), omb = fp_sub<F>(one, b);
   const fp k1 = fp_add<F>(fp_mul<F>(b, fp_add<F>(fp_mul<F>(y1, y2), mul_a<S>(fp_mul<F>(x1, x2)))), omb);
   const fp k2 = fp_add<F>(fp_mul<F>(b, fp_sub<F>(fp_mul<F>(x1, y2), fp_mul<F>(x2, y1))), omb);
@@ -263,11 +263,11 @@ k_ring_lin(const uint32_t *__restrict__ coef, const RingConsts *__restrict__ con
   const uint32_t *ip = coef + ((size_t)p * 4 + 1) * N * 8, *ax = ip + (size_t)N * 8, *ay = ax + (size_t)N * 8;
   uint32_t *out = lin + (size_t)p * N * 8;
   for (uint32_t i = t; i < N; i += 256)
-    store_fp(out + (size_t)i * 8, fp_add<F>(fp_add<F>(fp_mul<F>(f0, load_fp(ip + (size_t)i * 8)), fp_mul<F>(f1, load_fp(ax + (size_t)i * 8))),
-                                            fp_mul<F>(f2, load_fp(ay + (size_t)i * 8))));
+    fp_store(out + (size_t)i * 8, fp_add<F>(fp_add<F>(fp_mul<F>(f0, fp_load(ip + (size_t)i * 8)), fp_mul<F>(f1, fp_load(ax + (size_t)i * 8))),
+                                            fp_mul<F>(f2, fp_load(ay + (size_t)i * 8))));
   __syncthreads();
   fp v = block_eval256<F>(out, N, fp_mul<F>(z, w), sh);
-  if (t == 0) store_fp(lin_zw + (size_t)p * 8, v);
+  if (t == 0) fp_store(lin_zw + (size_t)p * 8, v);
 }
 
 // aggregated opening polynomial at zeta: sum_c nu_c poly_c + nu_7 q   (length qlen; the 7 columns have length N)
@@ -278,12 +278,12 @@ k_ring_aggz(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ fixe
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
   if (i >= qlen) return;
   const uint32_t *nup = nu + (size_t)p * 8 * 8;
-  fp acc = fp_mul<F>(load_fp(nup + 7 * 8), load_fp(q + ((size_t)p * qlen + i) * 8));
+  fp acc = fp_mul<F>(fp_load(nup + 7 * 8), fp_load(q + ((size_t)p * qlen + i) * 8));
   if (i < N) {
-    for (int c = 0; c < 3; c++) acc = fp_add<F>(acc, fp_mul<F>(load_fp(nup + c * 8), load_fp(fixed + ((size_t)c * N + i) * 8)));
-    for (int c = 0; c < 4; c++) acc = fp_add<F>(acc, fp_mul<F>(load_fp(nup + (3 + c) * 8), load_fp(coef + (((size_t)p * 4 + c) * N + i) * 8)));
+    for (int c = 0; c < 3; c++) acc = fp_add<F>(acc, fp_mul<F>(fp_load(nup + c * 8), fp_load(fixed + ((size_t)c * N + i) * 8)));
+    for (int c = 0; c < 4; c++) acc = fp_add<F>(acc, fp_mul<F>(fp_load(nup + (3 + c) * 8), fp_load(coef + (((size_t)p * 4 + c) * N + i) * 8)));
   }
-  store_fp(out + ((size_t)p * qlen + i) * 8, acc);
+  fp_store(out + ((size_t)p * qlen + i) * 8, acc);
 }
 
 // out = (c(X) - c(z)) / (X - z), z = zs[proof] * zmul: out[i-1] = A_i = c[i] + z A_{i+1}.  Lane t owns indices
@@ -296,25 +296,25 @@ k_ring_divlin(const uint32_t *__restrict__ in, uint32_t in_stride, uint32_t len,
   const uint32_t p = blockIdx.x, t = threadIdx.x, L = (len + 255) / 256;
   const uint32_t *c = in + (size_t)p * in_stride * 8;
   uint32_t *o = out + (size_t)p * out_stride * 8;
-  const fp z = fp_mul<F>(load_fp(zs + (size_t)p * 8), zmul);
+  const fp z = fp_mul<F>(fp_load(zs + (size_t)p * 8), zmul);
   uint32_t lo = t * L, hi = lo + L; if (hi > len) hi = len; if (lo > len) lo = len;
   fp h = fp_zero();
-  for (uint32_t i = hi; i > lo; i--) h = fp_add<F>(fp_mul<F>(h, z), load_fp(c + (size_t)(i - 1) * 8));
+  for (uint32_t i = hi; i > lo; i--) h = fp_add<F>(fp_mul<F>(h, z), fp_load(c + (size_t)(i - 1) * 8));
   // carry[t] = sum_{t' > t} h_{t'} z^(L (t' - t - 1)):  start from h_{t+1}, then Hillis-Steele with z^(L d)
-  store_fp(sh + t * 8, h);
+  fp_store(sh + t * 8, h);
   __syncthreads();
-  fp A = t + 1 < 256 ? load_fp(sh + (t + 1) * 8) : fp_zero();
+  fp A = t + 1 < 256 ? fp_load(sh + (t + 1) * 8) : fp_zero();
   fp mul = fp_pow_u32<F>(z, L);
   for (uint32_t d = 1; d < 256; d <<= 1) {
     __syncthreads();
-    store_fp(sh + t * 8, A);
+    fp_store(sh + t * 8, A);
     __syncthreads();
-    if (t + d < 256) A = fp_add<F>(A, fp_mul<F>(mul, load_fp(sh + (t + d) * 8)));
+    if (t + d < 256) A = fp_add<F>(A, fp_mul<F>(mul, fp_load(sh + (t + d) * 8)));
     mul = fp_sqr<F>(mul);
   }
   for (uint32_t i = hi; i > lo; i--) {
-    A = fp_add<F>(load_fp(c + (size_t)(i - 1) * 8), fp_mul<F>(A, z));
-    if (i >= 2) store_fp(o + (size_t)(i - 2) * 8, A);
+    A = fp_add<F>(fp_load(c + (size_t)(i - 1) * 8), fp_mul<F>(A, z));
+    if (i >= 2) fp_store(o + (size_t)(i - 2) * 8, A);
   }
 }
 
@@ -338,14 +338,14 @@ k_ring_witness_cols(const uint32_t *__restrict__ pos, const uint32_t *__restrict
   uint32_t *c = cols + (size_t)p * 4 * N * 8;
   if (i >= cap) {                                          // the 3 zero-knowledge rows: random when hiding, else zero
     for (int col = 0; col < 4; col++)
-      store_fp(c + ((size_t)col * N + i) * 8, zk ? load_fp(zk + (((size_t)p * 4 + col) * 3 + (i - cap)) * 8) : zero);
+      fp_store(c + ((size_t)col * N + i) * 8, zk ? fp_load(zk + (((size_t)p * 4 + col) * 3 + (i - cap)) * 8) : zero);
     return;
   }
-  store_fp(c + (size_t)i * 8, bit ? one : zero);
-  store_fp(c + ((size_t)N + i) * 8, i > ki ? one : zero);
+  fp_store(c + (size_t)i * 8, bit ? one : zero);
+  fp_store(c + ((size_t)N + i) * 8, i > ki ? one : zero);
   const uint32_t *v = vals + ((size_t)p * 257 + lo) * 16;
-  store_fp(c + ((size_t)2 * N + i) * 8, load_fp(v));
-  store_fp(c + ((size_t)3 * N + i) * 8, load_fp(v + 8));
+  fp_store(c + ((size_t)2 * N + i) * 8, fp_load(v));
+  fp_store(c + ((size_t)3 * N + i) * 8, fp_load(v + 8));
 }
 // RingProver round 0 on the device (A.7 step 1; w3f-ring-proof `PiopProver::build`): the witness in sparse form.  One lane per
 // proof.  Rows with bit 1: the signer's key, then the set bits of the blinding (row keyset + i).  The accumulator column only
@@ -390,7 +390,7 @@ k_ring_witness_acc(const te_pre *__restrict__ points, const uint32_t *__restrict
 #pragma unroll 1
   for (uint32_t j = 0; j <= m; j++) {
     const fp z = qperm<3, 3, 3, 3>(acc);
-    if (live) store_fp(sp + (size_t)j * 32 + 8 * (jc == 2 ? 3 : jc == 3 ? 2 : jc), jc == 2 ? run : acc);   // x, y, [z at block 2 from lane 3], run at block 3 from lane 2
+    if (live) fp_store(sp + (size_t)j * 32 + 8 * (jc == 2 ? 3 : jc == 3 ? 2 : jc), jc == 2 ? run : acc);   // x, y, [z at block 2 from lane 3], run at block 3 from lane 2
     run = fp_mul<F>(run, z);
     if (j < m) {
       const te_pre q = points[next_row];
@@ -408,7 +408,7 @@ k_ring_witness_acc(const te_pre *__restrict__ points, const uint32_t *__restrict
   for (uint32_t i = m + 1; i-- > 0;) {
     const uint32_t *e = sp + (size_t)i * 32;
     // round 1: lane 3: zi = inv * pre_i; lane 2: inv * z_i (the next inv); lanes 0, 1: from_mont of the previous row's difference
-    const fp z = load_fp(e + 16), pre = load_fp(e + 24), xy = load_fp(e + 8 * (jc & 1));
+    const fp z = fp_load(e + 16), pre = fp_load(e + 24), xy = fp_load(e + 8 * (jc & 1));
     fp one_plain = fp_zero(); one_plain.v[0] = 1;
     const fp a1 = jc >= 2 ? inv : fp_zero(), b1 = jc == 3 ? pre : z;
     const fp r1 = fp_mul<F>(a1, b1);
@@ -416,10 +416,10 @@ k_ring_witness_acc(const te_pre *__restrict__ points, const uint32_t *__restrict
     inv = qperm<2, 2, 2, 2>(r1);
     // round 2: lanes 0, 1: x_i zi, y_i zi
     const fp aff = fp_mul<F>(xy, zi);
-    if (live && jc < 2) store_fp(v + (size_t)i * 16 + 8 * jc, aff);
+    if (live && jc < 2) fp_store(v + (size_t)i * 16 + 8 * jc, aff);
     if (i < m) {                                                               // scalar of row i: from_mont(v_i - v_{i+1}), base N + pos_i + 1
       const fp d = fp_from_mont<F>(fp_sub<F>(aff, prev));
-      if (live && jc < 2) store_fp(qv + (size_t)((2 + jc) * MP + i) * 8, d);
+      if (live && jc < 2) fp_store(qv + (size_t)((2 + jc) * MP + i) * 8, d);
     }
     if (i == m) res = aff;
     prev = aff;
@@ -431,30 +431,30 @@ k_ring_witness_acc(const te_pre *__restrict__ points, const uint32_t *__restrict
   te_ext r; r.x = resx; r.y = resy; r.t = fp_mul<F>(resx, resy); r.z = fp_one<F>();
   const te_aff inst = te_to_aff<S>(te_madd<S>(r, te_make_pre<S>(fp_neg<F>(seedx), seedy)));
   uint32_t *o = out + (size_t)p * 32;
-  store_fp(o, resx); store_fp(o + 8, resy); store_fp(o + 16, inst.x); store_fp(o + 24, inst.y);
+  fp_store(o, resx); fp_store(o + 8, resy); fp_store(o + 16, inst.x); fp_store(o + 24, inst.y);
   // sparse vectors: bits | ip | ax | ay   (the host zeroed both arrays: unused entries are scalar 0 at base 0)
   fp one_plain = fp_zero(); one_plain.v[0] = 1;
   const fp minus1 = fp_from_mont<F>(fp_neg<F>(fp_one<F>()));
-  for (uint32_t j = 0; j < m; j++) { b[j] = ppos[j]; store_fp(qv + (size_t)j * 8, one_plain); }
-  b[MP] = N + cap; store_fp(qv + (size_t)MP * 8, one_plain);
-  b[MP + 1] = N + ki + 1; store_fp(qv + (size_t)(MP + 1) * 8, minus1);
+  for (uint32_t j = 0; j < m; j++) { b[j] = ppos[j]; fp_store(qv + (size_t)j * 8, one_plain); }
+  b[MP] = N + cap; fp_store(qv + (size_t)MP * 8, one_plain);
+  b[MP + 1] = N + ki + 1; fp_store(qv + (size_t)(MP + 1) * 8, minus1);
   for (uint32_t j = 0; j < m; j++) b[2 * MP + j] = b[3 * MP + j] = N + ppos[j] + 1;
   b[2 * MP + m] = b[3 * MP + m] = N + cap;
-  store_fp(qv + (size_t)(2 * MP + m) * 8, fp_from_mont<F>(resx)); store_fp(qv + (size_t)(3 * MP + m) * 8, fp_from_mont<F>(resy));
+  fp_store(qv + (size_t)(2 * MP + m) * 8, fp_from_mont<F>(resx)); fp_store(qv + (size_t)(3 * MP + m) * 8, fp_from_mont<F>(resy));
   if (zk) for (uint32_t col = 0; col < 4; col++) for (uint32_t j = 0; j < 3; j++) {     // + zk_j * L_{cap+j}(tau) G
     b[col * MP + m + 1 + j] = cap + j;
-    store_fp(qv + (size_t)(col * MP + m + 1 + j) * 8, fp_from_mont<F>(load_fp(zk + (((size_t)p * 4 + col) * 3 + j) * 8)));
+    fp_store(qv + (size_t)(col * MP + m + 1 + j) * 8, fp_from_mont<F>(fp_load(zk + (((size_t)p * 4 + col) * 3 + j) * 8)));
   }
 }
 template <class S>
 __global__ void k_ring_points_pre(const uint32_t *__restrict__ xy_mont, uint32_t n, te_pre *__restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = te_make_pre<S>(load_fp(xy_mont + (size_t)i * 16), load_fp(xy_mont + (size_t)i * 16 + 8));
+  if (i < n) out[i] = te_make_pre<S>(fp_load(xy_mont + (size_t)i * 16), fp_load(xy_mont + (size_t)i * 16 + 8));
 }
 template <class F>
 __global__ void k_set_diag(uint32_t *__restrict__ mat, uint32_t n, uint32_t rows, uint32_t col0) {   // row i of the tile = unit vector e_(col0 + i)
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < rows) store_fp(mat + ((size_t)i * n + col0 + i) * 8, fp_one<F>());
+  if (i < rows) fp_store(mat + ((size_t)i * n + col0 + i) * 8, fp_one<F>());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -477,7 +477,7 @@ template <class S, class G> struct RingTypes {
   using Fr = HostField<typename S::Fq>;              // Fr(pairing curve) = Fq(TE curve)
   using Te = HostTe<S>;
   using HG = HostG1<G>;
-  using FqN = HostFieldN<typename G::Fq>;
+  using FqN = HostField<typename G::Fq>;
   static constexpr int FQB = G::Fq::N * 4;            // bytes of a G1 coordinate
 };
 
@@ -517,7 +517,7 @@ static size_t ring_domain_size(size_t ring_size, size_t scalar_bits) {
 // ark-serialize G1 encodings: BLS12-381 zcash big-endian; BN254 arkworks little-endian
 template <class G> static void g1_encode(const G1Aff &p, bool compressed, std::vector<uint8_t> &out) {
   constexpr int B = G::Fq::N * 4;
-  using FqN = HostFieldN<typename G::Fq>;
+  using FqN = HostField<typename G::Fq>;
   typename FqN::El y, half = FqN::from32(G::Fq::HALF), t;
   memcpy(y.l, p.xy + B, B);
   bool big = !p.inf && FqN::subb(t, half, y) != 0;    // y > (p-1)/2
@@ -684,7 +684,7 @@ template <class S, class G> struct Ring {
     int lg = 0; while (((size_t)1 << lg) < N) lg++;
     H256 w4 = root; for (int i = 0; i < G::TWO_ADICITY - (lg + 2); i++) w4 = Fr::sqr(w4);
     su->w4 = w4; su->w = Fr::sqr(Fr::sqr(w4));
-    su->ninv = Fr::inv(fr_small<F>(N)); su->n4inv = Fr::inv(fr_small<F>(4 * N));
+    su->ninv = Fr::inv_fermat(fr_small<F>(N)); su->n4inv = Fr::inv_fermat(fr_small<F>(4 * N));
     return su;
   }
 
@@ -762,8 +762,8 @@ template <class S, class G> struct Ring {
         HIP_CHECK(hipStreamSynchronize(ln.stream));
       }
     }
-    su->d_tw_n = make_twiddles(su->w, N); su->d_tw_n_inv = make_twiddles(Fr::inv(su->w), N);
-    su->d_tw_4n = make_twiddles(su->w4, 4 * N); su->d_tw_4n_inv = make_twiddles(Fr::inv(su->w4), 4 * N);
+    su->d_tw_n = make_twiddles(su->w, N); su->d_tw_n_inv = make_twiddles(Fr::inv_fermat(su->w), N);
+    su->d_tw_4n = make_twiddles(su->w4, 4 * N); su->d_tw_4n_inv = make_twiddles(Fr::inv_fermat(su->w4), 4 * N);
     {  // Lagrange basis polynomials of rows 0 and cap-1, evaluated on the 4N domain (shared by every proof)
       const H256 zero = {{0, 0, 0, 0}};
       std::vector<H256> lfl(2 * N, zero); lfl[0] = Fr::one(); lfl[N + su->cap - 1] = Fr::one();
@@ -776,7 +776,7 @@ template <class S, class G> struct Ring {
     // 2^i * H  (A.5)
     HostExt h; h.x = Fr::from32(S::B_X); h.y = Fr::from32(S::B_Y); h.t = Fr::mul(h.x, h.y); h.z = Fr::one();
     for (size_t i = 0; i < L; i++) {
-      H256 zi = Fr::inv(h.z); su->h_pows.push_back({Fr::mul(h.x, zi), Fr::mul(h.y, zi)});
+      H256 zi = Fr::inv_fermat(h.z); su->h_pows.push_back({Fr::mul(h.x, zi), Fr::mul(h.y, zi)});
       h = Te::dbl(h);
     }
     *out = owner.release();
@@ -1599,7 +1599,7 @@ template <class S, class G> struct Ring {
       const bool z_zero = Fr::is_zero(rs.z);
       const H256 v0 = Fr::sub(zeta, one), v1 = nl, v2 = z_zero ? one : rs.z, v3 = zn1;
       const H256 p01 = Fr::mul(v0, v1), p012 = Fr::mul(p01, v2);
-      H256 tinv = Fr::inv(Fr::mul(p012, v3));
+      H256 tinv = Fr::inv_fermat(Fr::mul(p012, v3));
       const H256 i3 = Fr::mul(tinv, p012); tinv = Fr::mul(tinv, v3);
       const H256 i2 = Fr::mul(tinv, p01); tinv = Fr::mul(tinv, v2);
       const H256 i1 = Fr::mul(tinv, v0), i0 = Fr::mul(tinv, v1);

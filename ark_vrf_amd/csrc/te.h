@@ -214,27 +214,17 @@ AVRF_DI te_pre load_pre(const te_pre *p) {
   r.k.v[0] = a4.x; r.k.v[1] = a4.y; r.k.v[2] = a4.z; r.k.v[3] = a4.w; r.k.v[4] = a5.x; r.k.v[5] = a5.y; r.k.v[6] = a5.z; r.k.v[7] = a5.w;
   return r;
 }
-AVRF_DI void store_fp(uint32_t *d, const fp &a) {
-  uint4 *d4 = reinterpret_cast<uint4 *>(d);
-  d4[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]); d4[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-AVRF_DI fp load_fp(const uint32_t *s) {
-  const uint4 *s4 = reinterpret_cast<const uint4 *>(s);
-  uint4 a = s4[0], b = s4[1]; fp r;
-  r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-  return r;
-}
 AVRF_DI void store_pre(te_pre *p, const te_pre &v) {
   uint32_t *d = reinterpret_cast<uint32_t *>(p);
-  store_fp(d, v.x); store_fp(d + 8, v.y); store_fp(d + 16, v.k);
+  fp_store(d, v.x); fp_store(d + 8, v.y); fp_store(d + 16, v.k);
 }
 AVRF_DI void store_ext(te_ext *p, const te_ext &v) {
   uint32_t *d = reinterpret_cast<uint32_t *>(p);
-  store_fp(d, v.x); store_fp(d + 8, v.y); store_fp(d + 16, v.t); store_fp(d + 24, v.z);
+  fp_store(d, v.x); fp_store(d + 8, v.y); fp_store(d + 16, v.t); fp_store(d + 24, v.z);
 }
 AVRF_DI te_ext load_ext(const te_ext *p) {
   const uint32_t *s = reinterpret_cast<const uint32_t *>(p);
-  te_ext r; r.x = load_fp(s); r.y = load_fp(s + 8); r.t = load_fp(s + 16); r.z = load_fp(s + 24); return r;
+  te_ext r; r.x = fp_load(s); r.y = fp_load(s + 8); r.t = fp_load(s + 16); r.z = fp_load(s + 24); return r;
 }
 
 }  // namespace avrf

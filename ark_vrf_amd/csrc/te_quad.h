@@ -181,10 +181,10 @@ template <class S> struct QuadSat {
   static AVRF_DI el sel(bool c, const el &a, const el &b) { return fp_sel(c, a, b); }
   static AVRF_DI el shfl_down(const el &a, int d) { return fp_shfl_down(a, d); }
   static AVRF_DI el shfl_xor(const el &a, int m) { return fp_shfl_xor(a, m); }
-  static AVRF_DI el load(const uint32_t *p) { return load_fp(p); }                 // 8 canonical words
-  static AVRF_DI void store(uint32_t *p, const el &v) { store_fp(p, v); }
+  static AVRF_DI el load(const uint32_t *p) { return fp_load(p); }                 // 8 canonical words
+  static AVRF_DI void store(uint32_t *p, const el &v) { fp_store(p, v); }
   static AVRF_DI el load_part(const uint32_t *part, size_t k, int j) {             // coordinate j of partial sum k (the k_accumulate policy's format)
-    if constexpr (TeCurve<S>::accum::PART_WORDS == 32) return load_fp(part + k * 32 + j * 8);
+    if constexpr (TeCurve<S>::accum::PART_WORDS == 32) return fp_load(part + k * 32 + j * 8);
     else return teu_load_part_coord<S>(part + k * TEU_PART_WORDS, j);
   }
 };
@@ -203,8 +203,8 @@ template <class S> struct QuadUns {
 #pragma unroll
     for (int i = 0; i < L; i++) r.v[i] = __shfl_xor(a.v[i], m);
     return r; }
-  static AVRF_DI el load(const uint32_t *p) { const fp v = load_fp(p); return fu_slice<Fq, 0>(v.v); }
-  static AVRF_DI void store(uint32_t *p, const el &v) { fp r; fu_to_packed<Fq>(r.v, v); store_fp(p, r); }
+  static AVRF_DI el load(const uint32_t *p) { const fp v = fp_load(p); return fu_slice<Fq, 0>(v.v); }
+  static AVRF_DI void store(uint32_t *p, const el &v) { fp r; fu_to_packed<Fq>(r.v, v); fp_store(p, r); }
   static AVRF_DI el load_part(const uint32_t *part, size_t k, int j) { return teu_load_part_coord_raw<S>(part + k * TEU_PART_WORDS, j); }
 };
 #if !defined(AVRF_NO_UNSAT) && !defined(AVRF_NO_UNSAT_QUAD)

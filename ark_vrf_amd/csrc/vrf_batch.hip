@@ -88,7 +88,7 @@ AVRF_DI fp fp_from_u128(const uint32_t *w) {
 }
 template <class S> AVRF_DI void emit_term(uint32_t *scalars, te_pre *pre, uint32_t t, const fp &scalar_plain, const uint8_t *xy) {
   using Fq = typename S::Fq;
-  store_fp(scalars + 8 * (size_t)t, scalar_plain);
+  fp_store(scalars + 8 * (size_t)t, scalar_plain);
   fp x = fp_to_mont<Fq>(fp_load_le(xy)), y = fp_to_mont<Fq>(fp_load_le(xy + 32));
   store_pre(pre + t, te_make_pre<S>(x, y));
 }
@@ -133,7 +133,7 @@ k_thin_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ 
     if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
     __syncthreads();
   }
-  if (threadIdx.x == 0) store_fp(gpart + 8 * (size_t)blockIdx.x, red[0]);
+  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, red[0]);
 }
 
 // g = -(sum of partials); last term (G, g)   (thin.rs:303,316-317)
@@ -144,7 +144,7 @@ k_g_final(const uint32_t *__restrict__ gpart, uint32_t nparts, uint32_t *__restr
   using Fr = typename S::Fr; using Fq = typename S::Fq;
   __shared__ fp red[256];
   fp acc = fp_zero();
-  for (uint32_t i = threadIdx.x; i < nparts; i += 256) acc = fp_add<Fr>(acc, load_fp(gpart + 8 * (size_t)i));
+  for (uint32_t i = threadIdx.x; i < nparts; i += 256) acc = fp_add<Fr>(acc, fp_load(gpart + 8 * (size_t)i));
   red[threadIdx.x] = acc;
   __syncthreads();
   for (int s2 = 128; s2 >= 1; s2 >>= 1) {
@@ -152,7 +152,7 @@ k_g_final(const uint32_t *__restrict__ gpart, uint32_t nparts, uint32_t *__restr
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    store_fp(scalars + 8 * (size_t)t_last, fp_from_mont<Fr>(fp_neg<Fr>(red[0])));
+    fp_store(scalars + 8 * (size_t)t_last, fp_from_mont<Fr>(fp_neg<Fr>(red[0])));
     te_pre g;
     if (which_base == 0) { g.x = fp_const<Fq>(S::G_X); g.y = fp_const<Fq>(S::G_Y); g.k = fp_const<Fq>(S::G_K); }
     else { g.x = fp_const<Fq>(S::B_X); g.y = fp_const<Fq>(S::B_Y); g.k = fp_const<Fq>(S::B_K); }
@@ -253,7 +253,7 @@ k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c
     if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
     __syncthreads();
   }
-  if (threadIdx.x == 0) store_fp(gpart + 8 * (size_t)blockIdx.x, red[0]);
+  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, red[0]);
   __syncthreads();
   red[threadIdx.x] = usb;
   __syncthreads();
@@ -261,7 +261,7 @@ k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c
     if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
     __syncthreads();
   }
-  if (threadIdx.x == 0) store_fp(bpart + 8 * (size_t)blockIdx.x, red[0]);
+  if (threadIdx.x == 0) fp_store(bpart + 8 * (size_t)blockIdx.x, red[0]);
 }
 
 template <class S> void BatchOps<S>::ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, hipStream_t st) {

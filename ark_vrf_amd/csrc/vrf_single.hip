@@ -202,12 +202,12 @@ k_thin_prove_begin(BatchDev b, uint32_t *__restrict__ scalars, te_pre *__restric
   tr_base<S>(t, TINY ? DS_TINY : DS_THIN, true, pkx, pky, ios, m, b.ads + ad0, adl, &pf);
   f |= pf & FLAG_RANGE;
   const fp k = nonce<S>(sk, t);                                                 // thin.rs:115 (Montgomery)
-  store_fp(scalars, fp_from_mont<Fr>(k));
+  fp_store(scalars, fp_from_mont<Fr>(k));
   store_pre(pre, g_pre<S>());
   if (m) {
     auto dseed = delin_seed(t);
     for (uint32_t i = 0; i < m; i++) {
-      store_fp(scalars + 8 * (size_t)(1 + i), fp_mul<Fr>(k, xof128(dseed, i)));  // Montgomery k times plain z_i: plain k z_i mod r
+      fp_store(scalars + 8 * (size_t)(1 + i), fp_mul<Fr>(k, xof128(dseed, i)));  // Montgomery k times plain z_i: plain k z_i mod r
       store_pre(pre + 1 + i, pre_from_xy<S>(ios + 128 * (size_t)i));
     }
   }
@@ -519,15 +519,15 @@ k_ped_prove_begin(BatchDev b, uint32_t *__restrict__ scalars, te_pre *__restrict
   f |= pf & FLAG_RANGE;
   if (m > 1) {                                                                  // weights of the merged input: 1, z_0, z_1, ..
     auto dseed = delin_seed(t);
-    for (uint32_t i = 1; i < m; i++) store_fp(wts + 8 * (size_t)i, xof128(dseed, i - 1));
+    for (uint32_t i = 1; i < m; i++) fp_store(wts + 8 * (size_t)i, xof128(dseed, i - 1));
   }
   suite_tr<S> tb = t; tr_byte(tb, DS_PEDERSEN_BLINDING);
   const fp bl = nonce<S>(sk, tb);                                               // pedersen.rs:51-54,145
   // Yb = pk + bl B (:148-149): (pk, 1), (B, bl) -- or (G, sk), (B, bl) when the caller gave no public key
   fp one = fp_zero(); one.v[0] = 1;
-  if (b.pks_xy) { store_pre(pre, pre_from_xy<S>(b.pks_xy + 64 * (size_t)j)); store_fp(scalars, one); }
-  else { store_pre(pre, g_pre<S>()); store_fp(scalars, sk); }
-  store_pre(pre + 1, b_pre<S>()); store_fp(scalars + 8, fp_from_mont<Fr>(bl));
+  if (b.pks_xy) { store_pre(pre, pre_from_xy<S>(b.pks_xy + 64 * (size_t)j)); fp_store(scalars, one); }
+  else { store_pre(pre, g_pre<S>()); fp_store(scalars, sk); }
+  store_pre(pre + 1, b_pre<S>()); fp_store(scalars + 8, fp_from_mont<Fr>(bl));
   st->t = t; st->bl = bl; st->f = f;
 }
 template <class S>
@@ -549,12 +549,12 @@ k_ped_prove_mid(BatchDev b, uint32_t *__restrict__ scalars, te_pre *__restrict__
   // vector 0: R = k G + kb B; vector 1: Ok = k I_m = sum_i (k w_i) I_i
   const fp zero = fp_zero();
   store_pre(pre, g_pre<S>()); store_pre(pre + 1, b_pre<S>());
-  store_fp(scalars, fp_from_mont<Fr>(k)); store_fp(scalars + 8, fp_from_mont<Fr>(kb));
-  store_fp(scalars + 8 * (size_t)nt, zero); store_fp(scalars + 8 * (size_t)(nt + 1), zero);
+  fp_store(scalars, fp_from_mont<Fr>(k)); fp_store(scalars + 8, fp_from_mont<Fr>(kb));
+  fp_store(scalars + 8 * (size_t)nt, zero); fp_store(scalars + 8 * (size_t)(nt + 1), zero);
   for (uint32_t i = 0; i < m; i++) {
     store_pre(pre + 2 + i, pre_from_xy<S>(ios + 128 * (size_t)i));
-    store_fp(scalars + 8 * (size_t)(2 + i), zero);
-    store_fp(scalars + 8 * (size_t)(nt + 2 + i), i == 0 ? fp_from_mont<Fr>(k) : fp_mul<Fr>(k, load_fp(wts + 8 * (size_t)i)));   // Montgomery k times plain w_i: plain
+    fp_store(scalars + 8 * (size_t)(2 + i), zero);
+    fp_store(scalars + 8 * (size_t)(nt + 2 + i), i == 0 ? fp_from_mont<Fr>(k) : fp_mul<Fr>(k, fp_load(wts + 8 * (size_t)i)));   // Montgomery k times plain w_i: plain
   }
   st->t = t; st->k = k; st->kb = kb;
 }

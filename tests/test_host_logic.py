@@ -82,6 +82,35 @@ def test_host_pairing_on_reference_srs(tmp_path, golden_dir, curve, srs):
     assert out.stdout.strip() == "consistent=1 negative=0 consistent_high=1 g2_codec=1 g2_law=1 cyclo_sqr=1 f12_inv=1 line_tables=1"
 
 
+HOST_FIELDS = ["FqBandersnatch", "FrBandersnatch", "FqBabyJubJub", "FrBabyJubJub", "FrJubJub", "FqEd25519", "FrEd25519",
+               "FqSecp256r1", "FrSecp256r1", "FqBls12381", "FqBn254"]     # the order of tests/cpp/host_field_check.cpp
+
+
+def test_host_field_matches_python_integers(tmp_path):
+    """host_te.h HostField on every field struct of consts_gen.h (secp256r1's two full-width fields and both pairing base fields
+    included): add, sub, neg, dbl, mul, sqr, to_mont, from_mont, inv (Euclid), inv_fermat, geq_p and the byte round trip against
+    Python integers, on 0, 1, p-1, p-2, (p-1)/2, 2^k +- 1, values whose top limb equals p's and 2000 random pairs; mul also with first
+    operands in [p, 2^(64 L)) where the modulus leaves its top bit clear.  Compiled with g++, no GPU."""
+    import os
+    import subprocess
+    from conftest import ROOT
+    import field_vectors as fv
+    fields = fv.consts_fields()
+    assert [f[0] for f in fields] == HOST_FIELDS
+    rng = random.Random(2024)
+    cs = [(nl, p) + fv.cases(p, nl, rng, 2000) for _, nl, p in fields]
+    exe, fin, fout = str(tmp_path / "hf"), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "host_field_check.cpp"), "-o", exe])
+    open(fin, "wb").write(fv.pack([(nl, pairs, wide) for nl, _, pairs, wide in cs]))
+    out = subprocess.run([exe, fin, fout], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "host field ok", out.stdout + out.stderr
+    want = [(nl, fv.expected(p, nl, pairs, wide)) for nl, p, pairs, wide in cs]
+    got = fv.unpack(open(fout, "rb").read(), want)
+    for name, (nl, p, pairs, wide), (_, w), g in zip(HOST_FIELDS, cs, want, got):
+        bad = [i for i in range(len(w)) if w[i] != g[i]]
+        assert not bad, (name, len(bad), [fv.describe(nl, pairs, wide, i) + (hex(g[i]), hex(w[i])) for i in bad[:4]])
+
+
 def test_multibuffer_weight_hash_matches_scalar():
     """host_sha512_mb.h: eight weight transcripts in the lanes of an AVX-512 register must give the digests of the scalar
     chain (avrf_batch_weight_seed), for equal and unequal batch sizes, empty batches, both record sizes and every lane count."""

@@ -47,12 +47,12 @@ __global__ void __launch_bounds__(256, 2) k_chain(const uint32_t *tab, const uin
 __global__ void __launch_bounds__(256) k_inv_check(const uint32_t *tab, uint32_t n, uint32_t *bad, int which, uint32_t *sink) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  fpn<N> a = fn_load<N>(tab + (size_t)i * 2 * N);
-  if (fn_is_zero(a)) return;
+  fpn<N> a = fp_load<N>(tab + (size_t)i * 2 * N);
+  if (fp_is_zero(a)) return;
   fpn<N> r;
-  if (which == 0) r = fn_inv<Fq>(a);
-  else if (which == 1) r = fn_inv_gcd<Fq>(a);
-  else { r = fn_inv_gcd<Fq>(a); if (!fn_eq(fn_mul<Fq>(r, a), fn_one<Fq>())) atomicAdd(bad, 1u); }
+  if (which == 0) r = fp_inv_gcd<Fq>(a);
+  else if (which == 1) r = ba_inv_gcd<Fq>(a);
+  else { r = ba_inv_gcd<Fq>(a); if (!fp_eq(fp_mul<Fq>(r, a), fp_one<Fq>())) atomicAdd(bad, 1u); }
   sink[i] = r.v[0];
 }
 
@@ -63,10 +63,10 @@ __global__ void __launch_bounds__(64) k_check(const uint32_t *tab, const uint32_
   bool ia, ib;
   CV::base_t A = ba_load_entry<C>(tab, idx[2 * p], ia), B = ba_load_entry<C>(tab, idx[2 * p + 1], ib);
   CV::acc_t r = CV::madd(CV::from_affine(A), B, false);
-  fpn<N> x = fn_zero<N>(), y = fn_zero<N>();
-  if (!CV::is_identity(r)) { x = fn_mul<Fq>(r.x, fn_inv<Fq>(r.zz)); y = fn_mul<Fq>(r.y, fn_inv<Fq>(r.zzz)); }
-  fpn<N> gx = fn_load<N>(dst + (size_t)p * 2 * N), gy = fn_load<N>(dst + (size_t)p * 2 * N + N);
-  if (!fn_eq(x, gx) || !fn_eq(y, gy)) { if (!(!ia && !ib && fn_eq(A.x, B.x))) atomicAdd(bad, 1u); }
+  fpn<N> x = fp_zero<N>(), y = fp_zero<N>();
+  if (!CV::is_identity(r)) { x = fp_mul<Fq>(r.x, fp_inv_gcd<Fq>(r.zz)); y = fp_mul<Fq>(r.y, fp_inv_gcd<Fq>(r.zzz)); }
+  fpn<N> gx = fp_load<N>(dst + (size_t)p * 2 * N), gy = fp_load<N>(dst + (size_t)p * 2 * N + N);
+  if (!fp_eq(x, gx) || !fp_eq(y, gy)) { if (!(!ia && !ib && fp_eq(A.x, B.x))) atomicAdd(bad, 1u); }
 }
 
 int main(int argc, char **argv) {

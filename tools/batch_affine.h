@@ -23,7 +23,7 @@ namespace avrf {
 // a^-1 for a in Montgomery form (result in Montgomery form); 0 -> 0.  Binary extended Euclid, 2 BITS + 2 fixed iterations,
 // branch-free: x1 a = u R^-2 ..., kept as  x1 * abar = u * R^2,  x2 * abar = v * R^2  (mod p) with abar = a R, so that v = 1
 // leaves x2 = R^2 / abar = a^-1 R.
-template <class F> AVRF_DI fe<F> fn_inv_gcd(const fe<F> &a) {
+template <class F> AVRF_DI fe<F> ba_inv_gcd(const fe<F> &a) {
   constexpr int N = F::N;
   uint32_t u[N], v[N], x1[N], x2[N];
 #pragma unroll
@@ -79,10 +79,10 @@ template <class F> AVRF_DI fe<F> fn_inv_gcd(const fe<F> &a) {
 template <class C> AVRF_DI typename G1Curve<C>::base_t ba_load_entry(const uint32_t *pts, uint32_t e, bool &inf) {
   using CV = G1Curve<C>; using Fq = typename C::Fq; constexpr int N = Fq::N;
   typename CV::base_t q;
-  if (e == 0xffffffffu) { q.x = fn_zero<N>(); q.y = fn_zero<N>(); inf = true; return q; }
+  if (e == 0xffffffffu) { q.x = fp_zero<N>(); q.y = fp_zero<N>(); inf = true; return q; }
   q = CV::load_base(pts + (size_t)(e & 0x7fffffffu) * 2 * N);
-  inf = fn_is_zero(q.x) && fn_is_zero(q.y);
-  if ((e & 0x80000000u) && !inf) q.y = fn_neg<Fq>(q.y);
+  inf = fp_is_zero(q.x) && fp_is_zero(q.y);
+  if ((e & 0x80000000u) && !inf) q.y = fp_neg<Fq>(q.y);
   return q;
 }
 
@@ -95,7 +95,7 @@ k_ba_round(const uint32_t *__restrict__ pts, const uint32_t *__restrict__ idx, u
   const size_t base = (size_t)wave * 64 * K;
   if (base >= npairs) return;
   uint32_t *sc = scratch + (base + lane) * N;                                // prefix j of this lane: sc + j * 64 * N
-  el acc = fn_one<Fq>();
+  el acc = fp_one<Fq>();
   uint32_t live = 0;                                                         // pairs of this lane
 #pragma unroll 1
   for (uint32_t j = 0; j < K; j++) {
@@ -105,13 +105,13 @@ k_ba_round(const uint32_t *__restrict__ pts, const uint32_t *__restrict__ idx, u
     bool ia, ib;
     const typename CV::base_t A = ba_load_entry<C>(pts, INDEXED ? idx[2 * p] : (uint32_t)(2 * p), ia);
     const typename CV::base_t B = ba_load_entry<C>(pts, INDEXED ? idx[2 * p + 1] : (uint32_t)(2 * p + 1), ib);
-    el d = fn_sub<Fq>(B.x, A.x);
-    if (ia || ib) d = fn_one<Fq>();
-    else if (fn_is_zero(d)) { atomicOr(flag, 1u); d = fn_one<Fq>(); }
-    fn_store<N>(sc + (size_t)j * 64 * N, acc);
-    acc = fn_mul<Fq>(acc, d);
+    el d = fp_sub<Fq>(B.x, A.x);
+    if (ia || ib) d = fp_one<Fq>();
+    else if (fp_is_zero(d)) { atomicOr(flag, 1u); d = fp_one<Fq>(); }
+    fp_store<N>(sc + (size_t)j * 64 * N, acc);
+    acc = fp_mul<Fq>(acc, d);
   }
-  el run = fn_inv_gcd<Fq>(acc);
+  el run = ba_inv_gcd<Fq>(acc);
 #pragma unroll 1
   for (uint32_t j = live; j-- > 0;) {
     const size_t p = base + (size_t)j * 64 + lane;
@@ -119,15 +119,15 @@ k_ba_round(const uint32_t *__restrict__ pts, const uint32_t *__restrict__ idx, u
     const typename CV::base_t A = ba_load_entry<C>(pts, INDEXED ? idx[2 * p] : (uint32_t)(2 * p), ia);
     const typename CV::base_t B = ba_load_entry<C>(pts, INDEXED ? idx[2 * p + 1] : (uint32_t)(2 * p + 1), ib);
     uint32_t *o = dst + p * 2 * N;
-    if (ia || ib) { fn_store<N>(o, ia ? B.x : A.x); fn_store<N>(o + N, ia ? B.y : A.y); continue; }
-    const el d = fn_sub<Fq>(B.x, A.x);
-    if (fn_is_zero(d)) { fn_store<N>(o, A.x); fn_store<N>(o + N, A.y); continue; }          // flagged in pass A
-    const el inv = fn_mul<Fq>(run, fn_load<N>(sc + (size_t)j * 64 * N));
-    run = fn_mul<Fq>(run, d);
-    const el lam = fn_mul<Fq>(fn_sub<Fq>(B.y, A.y), inv);
-    const el x3 = fn_sub<Fq>(fn_sub<Fq>(fn_sqr<Fq>(lam), A.x), B.x);
-    fn_store<N>(o, x3);
-    fn_store<N>(o + N, fn_sub<Fq>(fn_mul<Fq>(lam, fn_sub<Fq>(A.x, x3)), A.y));
+    if (ia || ib) { fp_store<N>(o, ia ? B.x : A.x); fp_store<N>(o + N, ia ? B.y : A.y); continue; }
+    const el d = fp_sub<Fq>(B.x, A.x);
+    if (fp_is_zero(d)) { fp_store<N>(o, A.x); fp_store<N>(o + N, A.y); continue; }          // flagged in pass A
+    const el inv = fp_mul<Fq>(run, fp_load<N>(sc + (size_t)j * 64 * N));
+    run = fp_mul<Fq>(run, d);
+    const el lam = fp_mul<Fq>(fp_sub<Fq>(B.y, A.y), inv);
+    const el x3 = fp_sub<Fq>(fp_sub<Fq>(fp_sqr<Fq>(lam), A.x), B.x);
+    fp_store<N>(o, x3);
+    fp_store<N>(o + N, fp_sub<Fq>(fp_mul<Fq>(lam, fp_sub<Fq>(A.x, x3)), A.y));
   }
 }
 

@@ -21,6 +21,7 @@ def field(name, p):
     ninv = (-pow(p, -1, 1 << 32)) % (1 << 32)
     s = []
     s.append(f"struct {name} {{")
+    s.append("  static constexpr int N = 8;")
     s.append(f"  static constexpr uint32_t P[8] = {{{limbs(p)}}};")
     s.append(f"  static constexpr uint32_t ONE[8] = {{{limbs(R % p)}}};   /* R mod p */")
     s.append(f"  static constexpr uint32_t R2[8] = {{{limbs(R * R % p)}}};    /* R^2 mod p */")

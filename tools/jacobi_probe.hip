@@ -18,8 +18,8 @@ template <class F> AVRF_DN int jacobi_single_bit(fp a) {
   while (!fp_is_zero(a)) {
     const bool odd = (a.v[0] & 1u) != 0;
     fp d1, d2;
-    const bool lt = sub8(d1, a, n) != 0;
-    sub8(d2, n, a);
+    const bool lt = fp_subb(d1, a, n) != 0;
+    fp_subb(d2, n, a);
     const bool sw = odd && lt;
     t ^= sw ? ((a.v[0] & n.v[0]) >> 1) & 1u : 0u;
 #pragma unroll

@@ -1,7 +1,7 @@
 // tools/ubench_fpu.hip -- the unsaturated-limb field / point arithmetic (ark_vrf_amd/csrc/fpu*.h) against the saturated
 // forms it replaces inside k_accumulate: agreement on the device (chains of mixed additions compared as projective points)
 // and throughput per chip at 1 .. 8 waves per SIMD.  The gate of round 5: fu_mul >= 150 G/s (fp_mul: 126), teu_madd >= 17 G/s
-// (te_madd: 14.4), fu_mul<FqBls12381> >= 70 G/s (fn_mul: 58.8).
+// (te_madd: 14.4), fu_mul<FqBls12381> >= 70 G/s (fp_mul: 58.8).
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -mllvm -enable-ipra=0 -Iark_vrf_amd/csrc -o /tmp/ubench_fpu tools/ubench_fpu.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -127,13 +127,13 @@ template <class C> __global__ void k_g1_table(uint32_t *bases, int nbases, const
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nbases) return;
   typename CV::base_t q;
-  q.x = fn_to_mont<Fq>(fn_load<N>(g)); q.y = fn_to_mont<Fq>(fn_load<N>(g + N));
+  q.x = fp_to_mont<Fq>(fp_load<N>(g)); q.y = fp_to_mont<Fq>(fp_load<N>(g + N));
   const int k = i == 4 ? 3 : i;
   typename CV::acc_t p = CV::identity();
   for (int bit = 15; bit >= 0; bit--) { p = CV::dbl(p); if ((k >> bit) & 1) p = CV::madd(p, q, false); }
-  fe<Fq> x = fn_zero<N>(), y = fn_zero<N>();
-  if (k) { const fe<Fq> izz = fn_inv<Fq>(p.zz), izzz = fn_inv<Fq>(p.zzz); x = fn_mul<Fq>(p.x, izz); y = fn_mul<Fq>(p.y, izzz); }
-  fn_store<N>(bases + (size_t)i * 2 * N, x); fn_store<N>(bases + (size_t)i * 2 * N + N, y);
+  fe<Fq> x = fp_zero<N>(), y = fp_zero<N>();
+  if (k) { const fe<Fq> izz = fp_inv_gcd<Fq>(p.zz), izzz = fp_inv_gcd<Fq>(p.zzz); x = fp_mul<Fq>(p.x, izz); y = fp_mul<Fq>(p.y, izzz); }
+  fp_store<N>(bases + (size_t)i * 2 * N, x); fp_store<N>(bases + (size_t)i * 2 * N + N, y);
 }
 template <class C> __global__ void k_same_g1(const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *bad) {
   using CV = G1Curve<C>; using Fq = typename C::Fq;
@@ -143,9 +143,9 @@ template <class C> __global__ void k_same_g1(const uint32_t *a, const uint32_t *
   bool ok;
   if (CV::is_identity(p) || CV::is_identity(q)) ok = CV::is_identity(p) && CV::is_identity(q);
   else {
-    ok = fn_eq(fn_mul<Fq>(p.x, q.zz), fn_mul<Fq>(q.x, p.zz)) && fn_eq(fn_mul<Fq>(p.y, q.zzz), fn_mul<Fq>(q.y, p.zzz));
-    ok = ok && fn_eq(fn_mul<Fq>(fn_sqr<Fq>(q.zz), q.zz), fn_sqr<Fq>(q.zzz));
-    ok = ok && !fn_ge_p<Fq>(q.x) && !fn_ge_p<Fq>(q.y) && !fn_ge_p<Fq>(q.zz) && !fn_ge_p<Fq>(q.zzz);
+    ok = fp_eq(fp_mul<Fq>(p.x, q.zz), fp_mul<Fq>(q.x, p.zz)) && fp_eq(fp_mul<Fq>(p.y, q.zzz), fp_mul<Fq>(q.y, p.zzz));
+    ok = ok && fp_eq(fp_mul<Fq>(fp_sqr<Fq>(q.zz), q.zz), fp_sqr<Fq>(q.zzz));
+    ok = ok && !ge_p<Fq>(q.x) && !ge_p<Fq>(q.y) && !ge_p<Fq>(q.zz) && !ge_p<Fq>(q.zzz);
   }
   if (!ok) atomicAdd(bad, 1u);
 }
@@ -216,9 +216,9 @@ int main(int argc, char **argv) {
     RATE("fu_mul<FqBandersnatch> 9x29", (k_fumul<FqBandersnatch>), 2, "Gmul/s");
     RATE("fu_sqr<FqBandersnatch> 9x29", (k_fusqr<FqBandersnatch>), 2, "Gsqr/s");
     RATE("fu_mul<FqBabyJubJub> 9x29", (k_fumul<FqBabyJubJub>), 2, "Gmul/s");
-    RATE("fn_mul<FqBn254> (saturated)", (k_fmul_sat<FqBn254>), 2, "Gmul/s");
+    RATE("fp_mul<FqBn254> (saturated)", (k_fmul_sat<FqBn254>), 2, "Gmul/s");
     RATE("fu_mul<FqBn254> 9x29", (k_fumul<FqBn254>), 2, "Gmul/s");
-    RATE("fn_mul<FqBls12381> (saturated)", (k_fmul_sat<FqBls12381>), 2, "Gmul/s");
+    RATE("fp_mul<FqBls12381> (saturated)", (k_fmul_sat<FqBls12381>), 2, "Gmul/s");
     RATE("fu_mul<FqBls12381> 14x28", (k_fumul<FqBls12381>), 2, "Gmul/s");
     RATE("fu_sqr<FqBls12381> 14x28", (k_fusqr<FqBls12381>), 2, "Gsqr/s");
 #undef RATE
