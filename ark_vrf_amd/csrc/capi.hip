@@ -77,9 +77,9 @@ static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status) {
   if (c->validate <= 0 || !c->n) return;
   uint32_t *fl = c->d_flags.as<uint32_t>();
   const uint32_t n = (uint32_t)c->n;
-  if (kind != 2 && c->d_pks.p) AVRF_SINGLE(c->suite, validate_xy(c->d_pks.as<uint8_t>(), 64, 1, n, c->validate, fl, d_rec_status, c->stream));
-  if (kind == 1) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), 96, 1, n, c->validate, fl, d_rec_status, c->stream));
-  else if (kind == 2) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), 256, 3, n, c->validate, fl, d_rec_status, c->stream));
+  const KindFacts &k = kind_facts(kind);
+  if (k.pk && c->d_pks.p) AVRF_SINGLE(c->suite, validate_xy(c->d_pks.as<uint8_t>(), 64, 1, n, c->validate, fl, d_rec_status, c->stream));
+  if (k.points) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, d_rec_status, c->stream));
   if (c->tot_io) {
     if (!d_rec_status) AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>(), 128, 2, (uint32_t)c->tot_io, c->validate, fl, nullptr, c->stream));
     else {   // per-item status: the I/O pairs of item j are records io_off[j] .. io_off[j+1]; uniform M = 1 is the common case
@@ -172,54 +172,42 @@ static bool scalar_in_range(int suite, const uint8_t *s) {
   return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return !HostField<typename S::Fr>::geq_p(v); });
 }
 
-int avrf_msm_te(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t out_xy[64]) {
+// n affine bases into d_misc, the scalars into the lane's array, the input flag cleared (avrf_msm_te, _mont, avrf_scalar_mul's few-points route)
+static int upload_bases_and_scalars(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *scalars, size_t scalar_bytes) {
+  HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->L->d_scalars.ensure(scalar_bytes)); HIP_TRY(c->L->d_pre.ensure(n * sizeof(te_pre_raw)));
+  HIP_TRY(hipMemcpyAsync(c->d_misc.p, bases_xy, n * 64, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, scalars, scalar_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+  return AVRF_OK;
+}
+
+// avrf_msm_te, and (`mont`) the same MSM on arkworks' IN-MEMORY values (SURVEY.md 8b "zero-copy option"): bases = n x Affine { x, y }
+// with each coordinate an Fp<MontBackend, 4> (four little-endian u64 limbs, Montgomery form R = 2^256), scalars = n x ScalarField in
+// the same form -- what `msm_unchecked(&[Affine], &[ScalarField])` is handed (src/thin.rs:319) -- and the result as Montgomery x || y.
+// The canonical <-> Montgomery conversions of avrf_msm_te disappear on the host side; the device converts the scalars (one
+// multiplication each, range-checked there) and takes the bases as they are.
+static int msm_te_call(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t out_xy[64], bool mont) {
   if (!c || !out_xy || (n && (!bases_xy || !scalars))) return AVRF_ERR_BAD_ARG;
   if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  for (size_t i = 0; i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
+  for (size_t i = 0; !mont && i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
   HostExt r;
   if (n) {
-    HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->L->d_scalars.ensure(n * 32)); HIP_TRY(c->L->d_pre.ensure(n * sizeof(te_pre_raw)));
-    HIP_TRY(hipMemcpyAsync(c->d_misc.p, bases_xy, n * 64, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-    launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
+    if (int e = upload_bases_and_scalars(c, n, bases_xy, scalars, n * 32)) return e;
+    launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream, mont);
+    if (mont) launch_scalars_from_mont(c->suite, c->L->d_scalars.as<uint32_t>(), n, c->d_flags.as<uint32_t>(), c->stream);
     HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
   c->staged_kind = 0;
   if (int e = lane_msm(c, n, &r)) return e;
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
-  return finish_point(c, r, out_xy);
-}
-
-// The same MSM on arkworks' IN-MEMORY values (SURVEY.md 8b "zero-copy option"): bases = n x Affine { x, y } with each coordinate
-// an Fp<MontBackend, 4> (four little-endian u64 limbs, Montgomery form R = 2^256), scalars = n x ScalarField in the same form
-// -- what `msm_unchecked(&[Affine], &[ScalarField])` is handed (src/thin.rs:319) -- and the result as Montgomery x || y.  The
-// canonical <-> Montgomery conversions of avrf_msm_te disappear on the host side; the device converts the scalars (one
-// multiplication each) and takes the bases as they are.
-int avrf_msm_te_mont(avrf_ctx *c, size_t n, const uint8_t *bases_mont_xy, const uint8_t *scalars_mont, uint8_t out_mont_xy[64]) {
-  if (!c || !out_mont_xy || (n && (!bases_mont_xy || !scalars_mont))) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  HostExt r;
-  if (n) {
-    HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->L->d_scalars.ensure(n * 32)); HIP_TRY(c->L->d_pre.ensure(n * sizeof(te_pre_raw)));
-    HIP_TRY(hipMemcpyAsync(c->d_misc.p, bases_mont_xy, n * 64, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, scalars_mont, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-    launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream, 1);
-    launch_scalars_from_mont(c->suite, c->L->d_scalars.as<uint32_t>(), n, c->d_flags.as<uint32_t>(), c->stream);
-    HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  c->staged_kind = 0;
-  if (int e = lane_msm(c, n, &r)) return e;
-  if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
-  uint8_t canon[64];
-  finish_point(c, r, canon);
-  with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; using Fq = HostField<typename S::Fq>;
-    Fq::store_le(out_mont_xy, Fq::to_mont(Fq::load_le(canon))); Fq::store_le(out_mont_xy + 32, Fq::to_mont(Fq::load_le(canon + 32))); });
+  finish_point(c, r, out_xy);
+  if (mont) with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; using Fq = HostField<typename S::Fq>;
+    Fq::store_le(out_xy, Fq::to_mont(Fq::load_le(out_xy))); Fq::store_le(out_xy + 32, Fq::to_mont(Fq::load_le(out_xy + 32))); });
   return AVRF_OK;
 }
+int avrf_msm_te(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t out_xy[64]) { return msm_te_call(c, n, bases_xy, scalars, out_xy, false); }
+int avrf_msm_te_mont(avrf_ctx *c, size_t n, const uint8_t *bases_mont_xy, const uint8_t *scalars_mont, uint8_t out_mont_xy[64]) { return msm_te_call(c, n, bases_mont_xy, scalars_mont, out_mont_xy, true); }
 
 // G1 MSM of the suite's pairing curve (KZG commit / open): bases as canonical little-endian x || y
 // (48+48 bytes BLS12-381, 32+32 bytes BN254; all-zero = infinity), scalars LE32 < r.
@@ -250,64 +238,53 @@ int avrf_g1_msm(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *s
 
 // ---------------------------------------------------------------- staging
 
-// kind: 1 thin (pks + 96-byte proofs), 2 pedersen (256-byte proofs); proofs/pks/sks may be NULL for provers
+// kind: a ProofKind (proof_kind.h: Thin pks + 96-byte proofs, Pedersen 256-byte proofs, Tiny 48); proofs/pks/sks may be NULL for provers
 // wait = false (pool.hip): the copies are left in flight on c->stream -- from buffers of avrf_host_alloc they are DMA transfers
 // that cost no host time; the caller's buffers must stay untouched until the batch's verdict is out
 }  // extern "C"
 namespace avrf {
-static bool suite_host_weights(int suite) { return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; }); }
-int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
-              const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait) {
-  if (!c || c->run_phase) return AVRF_ERR_BAD_ARG;              // (a run in flight owns the staged buffers)
-  if (n && (!io_counts || !ad_lens)) return AVRF_ERR_BAD_ARG;
-  if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->stage_gen++; c->wire_pending = false;
-  if (n == 0) { c->staged_kind = kind; return AVRF_OK; }
-  HIP_TRY(c->h_io.ensure((n + 1) * 8));
-  uint32_t *io_off = c->h_io.as<uint32_t>(), *ad_off = io_off + (n + 1);
-  uint64_t a = 0, b = 0;
-  for (size_t j = 0; j < n; j++) { io_off[j] = (uint32_t)a; ad_off[j] = (uint32_t)b; a += io_counts[j]; b += ad_lens[j]; }
-  if (a > 0x1fffffffULL || b > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
-  if ((a && !ios_xy) || (b && !ads)) return AVRF_ERR_BAD_ARG;
-  io_off[n] = (uint32_t)a; ad_off[n] = (uint32_t)b;
-  c->tot_io = (size_t)a;
-  HIP_TRY(c->d_io_off.ensure((n + 1) * 4)); HIP_TRY(c->d_ad_off.ensure((n + 1) * 4));
-  HIP_TRY(c->d_ios.ensure(a * 128 + 16)); HIP_TRY(c->d_ads.ensure(b + 16));
-  HIP_TRY(hipMemcpyAsync(c->d_io_off.p, io_off, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_ad_off.p, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (a) HIP_TRY(hipMemcpyAsync(c->d_ios.p, ios_xy, a * 128, hipMemcpyHostToDevice, c->stream));
-  if (b) HIP_TRY(hipMemcpyAsync(c->d_ads.p, ads, b, hipMemcpyHostToDevice, c->stream));
-  const size_t psz = kind == 1 ? 96 : kind == 3 ? 48 : 256;
-  if (pks_xy) { HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(hipMemcpyAsync(c->d_pks.p, pks_xy, n * 64, hipMemcpyHostToDevice, c->stream)); }
-  if (sks) { HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(hipMemcpyAsync(c->d_sks.p, sks, n * 32, hipMemcpyHostToDevice, c->stream)); }
-  if (proofs) {
-    HIP_TRY(c->d_proofs.ensure(n * psz)); HIP_TRY(hipMemcpyAsync(c->d_proofs.p, proofs, n * psz, hipMemcpyHostToDevice, c->stream));
-    if (kind == 3) { HIP_TRY(hipStreamSynchronize(c->stream)); c->staged_kind = kind; return AVRF_OK; }   // Tiny: no batch verifier
-    if (suite_host_weights(c->suite)) {       // a sponge transcript absorbs the responses on the host; counter-mode ones hash the device's records
-      const size_t rsz = kind == 1 ? 32 : 64, roff = kind == 1 ? 64 : 192;
-      c->h_resp.resize(n * rsz);
-      for (size_t j = 0; j < n; j++) memcpy(&c->h_resp[rsz * j], proofs + psz * j + roff, rsz);
-    }
-    c->n_terms = kind == 1 ? 2 * n + 2 * c->tot_io + 1 : 5 * n + 2;
-    HIP_TRY(c->d_c.ensure(n * 16)); HIP_TRY(c->h_c.ensure(n * 16));
-    HIP_TRY(c->d_z.ensure(kind == 1 ? c->tot_io * 16 + 16 : n * 128));
-    if (c->lane_owner) { HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((n + 127) / 128) * 64 + 64)); }
-  }
-  if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
-  c->staged_kind = kind;
+// HOST_WEIGHTS is exactly "the transcript is not the counter-mode SHA-512 one" (batch_seed squeezes a sponge's or SHA-256's stream)
+template <class... S> constexpr bool host_weights_defined = ((S::HOST_WEIGHTS == (S::XOF_SHAKE || S::TR_SHA256)) && ...);
+static_assert(host_weights_defined<SuiteBandersnatch, SuiteBabyJubJub, SuiteJubJub, SuiteEd25519, SuiteBandersnatchSW, SuiteBandersnatchShake, SuiteTesting, SuiteSecp256r1>);
+bool suite_host_weights(int suite) { return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; }); }
+
+// The weight transcript (src/thin.rs:274-279, src/pedersen.rs:361-367): new(SUITE_ID); absorb [0x50]; per item absorb LE32(c) || LE32(s)
+// [|| LE32(sb)] -- the message  prefix || per item c(16) || 0(16) || resp(rsz)  into any hasher with update() (host_sha512_mb.h's lanes build the same bytes)
+static size_t batch_prefix(int suite, uint8_t prefix[64]) {
+  size_t pl = 0;
+  with_suite(suite, [&](auto tag_) { using S = typename decltype(tag_)::type; memcpy(prefix, S::SUITE_ID, S::SUITE_ID_LEN); pl = S::SUITE_ID_LEN; });
+  prefix[pl++] = DS_BATCH_VERIFY;
+  return pl;
+}
+template <class H> static void absorb_weight_message(H &h, const uint8_t *prefix, size_t prefix_len, size_t n, const uint8_t *c16, const uint8_t *resp, size_t rsz) {
+  h.update(prefix, prefix_len);
+  uint8_t rec[96]; memset(rec, 0, sizeof rec);
+  for (size_t k = 0; k < n; k++) { memcpy(rec, c16 + 16 * k, 16); memcpy(rec + 32, resp + rsz * k, rsz); h.update(rec, 32 + rsz); }
+}
+static void weight_digest_scalar(WeightJob &j) {
+  HostSha512 h;
+  if (j.msg) h.update(j.msg, j.msg_len); else absorb_weight_message(h, j.prefix, j.prefix_len, j.n, j.c16, j.resp, j.rsz);
+  h.final(j.digest);
+}
+// several transcripts together: one through the scalar code, more through the widest multi-buffer form the host CPU has
+void sha512_many(WeightJob *const *jobs, int k) {
+  if (k == 1 || !sha512_mb_available()) { for (int i = 0; i < k; i++) weight_digest_scalar(*jobs[i]); }
+  else if (sha512_mb16_available()) sha512_weights_x16(jobs, k);
+  else for (int i = 0; i < k; i += 8) sha512_weights_x8(jobs + i, k - i < 8 ? k - i : 8);
+}
+
+// d_scalars / d_pre / d_gpart of the context's lane for the staged batch's n_terms
+static int ensure_terms(avrf_ctx *c) {
+  HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((c->n + 127) / 128) * 64 + 64));
   return AVRF_OK;
 }
-// The wire flavour of the batch verifiers' staging (SURVEY.md 8b; src/thin.rs:78-94, src/pedersen.rs:106-134 deserialise, then
-// `push`): the caller's `serialize_compressed` bytes go to the device as they are, every point is decompressed (validate: + not the
-// identity, + prime-order subgroup, src/lib.rs:410-433) STRAIGHT INTO the context's staged x || y buffers, the proofs' scalars are
-// copied beside their points -- no decompressed byte crosses PCIe or a host core.  A point that fails makes the batch InvalidData
-// here, before any equation (as the reference's deserialisation would).  kind 1 thin (pk, R || s), 2 pedersen (Yb, R, Ok || s || sb).
-// wait = false (pool.hip): nothing is waited for -- the flag is read by batch_collect once the stream's work has completed
-int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
-                   const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait) {
-  if (!c || c->run_phase || (kind != 1 && kind != 2)) return AVRF_ERR_BAD_ARG;
-  if (n && (!io_counts || !ad_lens || !proofs || (kind == 1 && !pks))) return AVRF_ERR_BAD_ARG;
+
+// The opening both stagers share: argument checks (`args_ok`: the flavour's own), state reset, prefix sums of io_counts / ad_lens into h_io
+// with their limits, offsets and `ads` copied -- and between them the I/O pairs when they come as x || y.  n == 0 stages the empty batch.
+static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8_t *ios, bool ios_xy, const uint32_t *io_counts,
+                      const uint8_t *ads, const uint32_t *ad_lens) {
+  if (!c || c->run_phase || !args_ok) return AVRF_ERR_BAD_ARG;   // (a run in flight owns the staged buffers)
+  if (n && (!io_counts || !ad_lens)) return AVRF_ERR_BAD_ARG;
   if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
   c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->stage_gen++; c->wire_pending = false;
@@ -320,37 +297,75 @@ int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const ui
   if ((a && !ios) || (b && !ads)) return AVRF_ERR_BAD_ARG;
   io_off[n] = (uint32_t)a; ad_off[n] = (uint32_t)b;
   c->tot_io = (size_t)a;
-  const size_t L = (size_t)point_len_of(c->suite), ppts = kind == 1 ? 1 : 3, tail = kind == 1 ? 32 : 64, plen = ppts * L + tail, psz = kind == 1 ? 96 : 256;
-  const size_t w_pks = kind == 1 ? n * L : 0, w_ios = 2 * (size_t)a * L, w_pr = n * plen;
   HIP_TRY(c->d_io_off.ensure((n + 1) * 4)); HIP_TRY(c->d_ad_off.ensure((n + 1) * 4));
-  HIP_TRY(c->d_ios.ensure(a * 128 + 16)); HIP_TRY(c->d_ads.ensure(b + 16)); HIP_TRY(c->d_proofs.ensure(n * psz));
-  if (kind == 1) HIP_TRY(c->d_pks.ensure(n * 64));
-  HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
-  uint8_t *dw = c->d_misc.as<uint8_t>();
+  HIP_TRY(c->d_ios.ensure(a * 128 + 16)); HIP_TRY(c->d_ads.ensure(b + 16));
   HIP_TRY(hipMemcpyAsync(c->d_io_off.p, io_off, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_ad_off.p, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (ios_xy && a) HIP_TRY(hipMemcpyAsync(c->d_ios.p, ios, a * 128, hipMemcpyHostToDevice, c->stream));
   if (b) HIP_TRY(hipMemcpyAsync(c->d_ads.p, ads, b, hipMemcpyHostToDevice, c->stream));
+  return AVRF_OK;
+}
+// The close both stagers share for a batch VERIFIER: the host copy of the responses (item 0's at `resp`, `stride` apart) for a sponge
+// transcript, which absorbs them on the host (counter-mode ones hash the device's records); the term count; the buffers the run writes.
+static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t stride) {
+  const size_t n = c->n, rsz = kind_facts(kind).resp;
+  if (suite_host_weights(c->suite)) {
+    c->h_resp.resize(n * rsz);
+    for (size_t j = 0; j < n; j++) memcpy(&c->h_resp[rsz * j], resp + stride * j, rsz);
+  }
+  c->n_terms = n_terms(kind, n, c->tot_io);
+  HIP_TRY(c->d_c.ensure(n * 16)); HIP_TRY(c->h_c.ensure(n * 16));
+  HIP_TRY(c->d_z.ensure(z_bytes(kind, n, c->tot_io)));
+  return c->lane_owner ? ensure_terms(c) : (int)AVRF_OK;
+}
+
+int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
+              const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait) {
+  if (int e = stage_open(c, kind, n, true, ios_xy, true, io_counts, ads, ad_lens)) return e;
+  if (n == 0) return AVRF_OK;
+  const size_t psz = kind_facts(kind).xy_proof();
+  if (pks_xy) { HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(hipMemcpyAsync(c->d_pks.p, pks_xy, n * 64, hipMemcpyHostToDevice, c->stream)); }
+  if (sks) { HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(hipMemcpyAsync(c->d_sks.p, sks, n * 32, hipMemcpyHostToDevice, c->stream)); }
+  if (proofs) {
+    HIP_TRY(c->d_proofs.ensure(n * psz)); HIP_TRY(hipMemcpyAsync(c->d_proofs.p, proofs, n * psz, hipMemcpyHostToDevice, c->stream));
+    if (kind == Tiny) { HIP_TRY(hipStreamSynchronize(c->stream)); c->staged_kind = kind; return AVRF_OK; }   // Tiny: no batch verifier
+    if (int e = stage_verifier(c, kind, proofs + kind_facts(kind).resp_at_xy(), psz)) return e;
+  }
+  if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
+  c->staged_kind = kind;
+  return AVRF_OK;
+}
+// The wire flavour of the batch verifiers' staging (SURVEY.md 8b; src/thin.rs:78-94, src/pedersen.rs:106-134 deserialise, then
+// `push`): the caller's `serialize_compressed` bytes go to the device as they are, every point is decompressed (validate: + not the
+// identity, + prime-order subgroup, src/lib.rs:410-433) STRAIGHT INTO the context's staged x || y buffers, the proofs' scalars are
+// copied beside their points -- no decompressed byte crosses PCIe or a host core.  A point that fails makes the batch InvalidData
+// here, before any equation (as the reference's deserialisation would).  kind Thin (pk, R || s), Pedersen (Yb, R, Ok || s || sb).
+// wait = false (pool.hip): nothing is waited for -- the flag is read by batch_collect once the stream's work has completed
+int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                   const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait) {
+  const bool args_ok = (kind == Thin || kind == Pedersen) && (!n || (proofs && (kind != Thin || pks)));
+  if (int e = stage_open(c, kind, n, args_ok, ios, false, io_counts, ads, ad_lens)) return e;
+  if (n == 0) return AVRF_OK;
+  const KindFacts &k = kind_facts(kind);
+  const size_t L = (size_t)point_len_of(c->suite), a = c->tot_io, ppts = k.points, plen = k.wire_proof(L), psz = k.xy_proof();
+  const size_t w_pks = k.pk ? n * L : 0, w_ios = 2 * a * L, w_pr = n * plen;
+  HIP_TRY(c->d_proofs.ensure(n * psz));
+  if (k.pk) HIP_TRY(c->d_pks.ensure(n * 64));
+  HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
+  uint8_t *dw = c->d_misc.as<uint8_t>();
   if (w_pks) HIP_TRY(hipMemcpyAsync(dw, pks, w_pks, hipMemcpyHostToDevice, c->stream));
   if (w_ios) HIP_TRY(hipMemcpyAsync(dw + w_pks, ios, w_ios, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dw + w_pks + w_ios, proofs, w_pr, hipMemcpyHostToDevice, c->stream));
   uint32_t *d_flag = c->d_status.as<uint32_t>(), *h_flag = c->h_flags.as<uint32_t>() + 2;
   HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
-  if (kind == 1) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, validate, d_flag, c->stream));
+  if (k.pk) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, validate, d_flag, c->stream));
   AVRF_SINGLE(c->suite, decompress_strided(dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>(), 64, validate, d_flag, c->stream));
   const uint8_t *dpr = dw + w_pks + w_ios;
   for (size_t p = 0; p < ppts; p++)
     AVRF_SINGLE(c->suite, decompress_strided(dpr + L * p, (uint32_t)plen, (uint32_t)n, c->d_proofs.as<uint8_t>() + 64 * p, (uint32_t)psz, validate, d_flag, c->stream));
-  HIP_TRY(hipMemcpy2DAsync(c->d_proofs.as<uint8_t>() + 64 * ppts, psz, dpr + L * ppts, plen, tail, n, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpy2DAsync(c->d_proofs.as<uint8_t>() + 64 * ppts, psz, dpr + L * ppts, plen, k.tail, n, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  if (suite_host_weights(c->suite)) {
-    const size_t rsz = kind == 1 ? 32 : 64, roff = ppts * L;
-    c->h_resp.resize(n * rsz);
-    for (size_t j = 0; j < n; j++) memcpy(&c->h_resp[rsz * j], proofs + plen * j + roff, rsz);
-  }
-  c->n_terms = kind == 1 ? 2 * n + 2 * c->tot_io + 1 : 5 * n + 2;
-  HIP_TRY(c->d_c.ensure(n * 16)); HIP_TRY(c->h_c.ensure(n * 16));
-  HIP_TRY(c->d_z.ensure(kind == 1 ? c->tot_io * 16 + 16 : n * 128));
-  if (c->lane_owner) { HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((n + 127) / 128) * 64 + 64)); }
+  if (int e = stage_verifier(c, kind, proofs + k.resp_at_wire(L), plen)) return e;
   if (!wait) { c->wire_pending = true; c->staged_kind = kind; return AVRF_OK; }
   HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
   if (*h_flag) return AVRF_INVALID_DATA;
@@ -362,34 +377,26 @@ extern "C" {
 int avrf_thin_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                                const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
   if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  return avrf::ctx_stage_wire(c, 1, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, true);
+  return avrf::ctx_stage_wire(c, Thin, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, true);
 }
 int avrf_pedersen_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                                    const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
   if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  return avrf::ctx_stage_wire(c, 2, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, true);
+  return avrf::ctx_stage_wire(c, Pedersen, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, true);
 }
 
 int avrf_thin_batch_stage(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && (!pks_xy || !proofs)) return AVRF_ERR_BAD_ARG;
-  return ctx_stage(c, 1, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, true);
+  return ctx_stage(c, Thin, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, true);
 }
 int avrf_pedersen_batch_stage(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts,
                               const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && !proofs) return AVRF_ERR_BAD_ARG;
-  return ctx_stage(c, 2, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs, true);
+  return ctx_stage(c, Pedersen, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs, true);
 }
 
 // ---- the weight transcripts of the contexts in flight, hashed together (host_sha512_mb.h)
-static void weight_digest_scalar(WeightJob &j) {
-  HostSha512 h;
-  if (j.msg) { h.update(j.msg, j.msg_len); h.final(j.digest); return; }
-  h.update(j.prefix, j.prefix_len);
-  uint8_t rec[96]; memset(rec, 0, sizeof rec);
-  for (size_t k = 0; k < j.n; k++) { memcpy(rec, j.c16 + 16 * k, 16); memcpy(rec + 32, j.resp + j.rsz * k, j.rsz); h.update(rec, 32 + j.rsz); }
-  h.final(j.digest);
-}
 namespace {
 // OPT-IN (AVRF_HASH_THREADS = number of workers; default 0 = every context hashes its own transcript on its own thread).
 // Contexts hand their transcript to a small pool; a worker takes up to eight pending ones and advances them in the eight lanes
@@ -433,8 +440,9 @@ class WeightHashService {
         if (stop_) return;
         while (cnt < 8 && !q_.empty()) { take[cnt++] = q_.front(); q_.pop_front(); }
       }
-      if (cnt == 1) weight_digest_scalar(*take[0]->job);
-      else if (cnt > 1) { WeightJob *jobs[8]; for (int i = 0; i < cnt; i++) jobs[i] = take[i]->job; sha512_weights_x8(jobs, cnt); }
+      WeightJob *jobs[8];
+      for (int i = 0; i < cnt; i++) jobs[i] = take[i]->job;
+      sha512_many(jobs, cnt);
       { std::lock_guard<std::mutex> lk(m_); for (int i = 0; i < cnt; i++) take[i]->done = true; }
       cv_done_.notify_all();
     }
@@ -450,14 +458,22 @@ class WeightHashService {
 // pieces themselves (batch_collect / batch_seed / batch_launch) and hash several contexts' transcripts together.
 }  // extern "C"
 namespace avrf {
-static int host_stream_kind(int suite) { return with_suite(suite, [&](auto tag_) { using S = typename decltype(tag_)::type; return S::XOF_SHAKE ? 1 : S::TR_SHA256 ? 2 : 0; }); }
-static size_t batch_prefix(int suite, uint8_t prefix[64]) {
-  size_t pl = 0;
-  with_suite(suite, [&](auto tag_) { using S = typename decltype(tag_)::type; memcpy(prefix, S::SUITE_ID, S::SUITE_ID_LEN); pl = S::SUITE_ID_LEN; });
-  prefix[pl++] = DS_BATCH_VERIFY;
-  return pl;
+static Seed64 seed_of(const uint8_t digest[64]) {
+  Seed64 seed;
+  for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, digest + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
+  return seed;
 }
-bool batch_host_weights(const avrf_ctx *c) { return host_stream_kind(c->suite) != 0; }
+// the kind's prepare kernel (challenges into d_c, the terms kernel's other inputs into d_z, the checks into d_flags) and terms kernel
+static void launch_prepare(avrf_ctx *c, int kind, const BatchDev &b) {
+  if (kind == Thin) AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
+  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
+}
+static void launch_terms(avrf_ctx *c, int kind, const BatchDev &b, const Seed64 &seed, uint64_t first, uint32_t *d_scalars) {
+  if (kind == Thin) AVRF_BATCH(c->suite, thin_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), d_scalars,
+                                                    c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
+  else AVRF_BATCH(c->suite, ped_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), d_scalars,
+                                      c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
+}
 
 int batch_begin(avrf_ctx *c, int kind) {
   if (!c || c->staged_kind != kind || c->run_phase != 0) return AVRF_ERR_BAD_ARG;
@@ -469,17 +485,16 @@ int batch_begin(avrf_ctx *c, int kind) {
   BatchDev b = batch_of(c);
   HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
   validate_staged(c, kind, nullptr);
-  const int host_stream = host_stream_kind(c->suite);
+  const bool host_weights = suite_host_weights(c->suite);
   // the weight transcript's message, prefix || records: the prepare kernel writes the records, one copy brings them back
-  const size_t recsz = kind == 1 ? 64 : 96;
+  const size_t recsz = kind_facts(kind).record();
   uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
-  if (!host_stream) {
+  if (!host_weights) {
     HIP_TRY(c->d_rec.ensure(n * recsz)); HIP_TRY(c->h_msg.ensure(pl + n * recsz));
     b.records = c->d_rec.as<uint8_t>();
   }
-  if (kind == 1) AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
-  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
-  if (!host_stream) {
+  launch_prepare(c, kind, b);
+  if (!host_weights) {
     memcpy(c->h_msg.p, prefix, pl);
     HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl, c->d_rec.p, n * recsz, hipMemcpyDeviceToHost, c->stream));
     c->h_msg_len = pl + n * recsz;
@@ -501,34 +516,27 @@ int batch_collect(avrf_ctx *c, int kind) {
   return AVRF_OK;
 }
 
-// weight transcript (src/thin.rs:274-279, src/pedersen.rs:361-367):
-//   new(SUITE_ID); absorb [0x50]; per item absorb LE32(c) || LE32(s) [|| LE32(sb)]
-// counter-mode transcripts: SHA-512 of prefix || records -> digest.  Sponge / SHA-256 transcripts (Shake128Transcript: the
-// weights are the sponge's OUTPUT STREAM, 16 bytes per item, 32 for Pedersen -- sequential, so the host squeezes it and the
-// terms kernel reads it from HBM instead of deriving block j / 4 from a seed; HashTranscript<Sha256> of the test suite takes
-// the same route): the stream goes to c->h_weights and the digest is not used.
+// The weight transcript of the staged batch on the calling thread.  Counter-mode transcripts: SHA-512 of prefix || records ->
+// digest.  Sponge / SHA-256 transcripts (Shake128Transcript: the weights are the sponge's OUTPUT STREAM, 16 bytes per item, 32 for
+// Pedersen -- sequential, so the host squeezes it and the terms kernel reads it from HBM instead of deriving block j / 4 from a
+// seed; HashTranscript<Sha256> of the test suite takes the same route): the stream goes to c->h_weights and the digest is not used.
 int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]) {
   const size_t n = c->n;
   memset(digest, 0, 64);
   if (!n) return AVRF_OK;
-  const int host_stream = host_stream_kind(c->suite);
-  if (host_stream) {
-    const uint8_t tag = DS_BATCH_VERIFY;
-    const uint8_t *cs = c->h_c.as<uint8_t>();
-    const size_t rsz = kind == 1 ? 32 : 64, wsz = kind == 1 ? 16 : 32;
-    uint8_t rec[96]; memset(rec, 0, sizeof rec);
-    c->h_weights.resize(n * wsz);
-    auto run = [&](auto &h) {
-      with_suite(c->suite, [&](auto tag_) { using S = typename decltype(tag_)::type; h.update(S::SUITE_ID, S::SUITE_ID_LEN); });
-      h.update(&tag, 1);
-      for (size_t j = 0; j < n; j++) { memcpy(rec, cs + 16 * j, 16); memcpy(rec + 32, &c->h_resp[rsz * j], rsz); h.update(rec, 32 + rsz); }
-      h.squeeze_copy(c->h_weights.data(), n * wsz);
-    };
-    if (host_stream == 1) { HostShake128 h; run(h); } else { HostSha256 h; run(h); }
+  if (suite_host_weights(c->suite)) {
+    const KindFacts &k = kind_facts(kind);
+    uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+    c->h_weights.resize(n * k.weight);
+    with_suite(c->suite, [&](auto tag_) {
+      using S = typename decltype(tag_)::type;
+      std::conditional_t<S::XOF_SHAKE, HostShake128, HostSha256> h;
+      absorb_weight_message(h, prefix, pl, n, c->h_c.as<uint8_t>(), c->h_resp.data(), k.resp);
+      h.squeeze_copy(c->h_weights.data(), n * k.weight);
+    });
     return AVRF_OK;
   }
-  WeightJob job; job.prefix = nullptr; job.prefix_len = 0; job.c16 = nullptr; job.resp = nullptr; job.n = n; job.rsz = 0;
-  job.msg = c->h_msg.as<uint8_t>(); job.msg_len = c->h_msg_len;
+  WeightJob job = WeightJob::whole(c->h_msg.as<uint8_t>(), c->h_msg_len);
   WeightHashService &svc = WeightHashService::get();
   if (svc.enabled()) svc.run(job); else weight_digest_scalar(job);
   memcpy(digest, job.digest, 64);
@@ -542,27 +550,19 @@ int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]) {
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = c->n;
   BatchDev b = batch_of(c);
-  if (c->unit_weights) {                                               // (kind 1 only) w_j = 1: the sum IS the item's own equation
+  if (c->unit_weights) {                                               // (Thin only) w_j = 1: the sum IS the item's own equation
     c->h_weights.assign(n * 16, 0);
     for (size_t j = 0; j < n; j++) c->h_weights[16 * j] = 1;
-    HIP_TRY(c->d_weights.ensure(n * 16));
-    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), n * 16, hipMemcpyHostToDevice, c->stream));
-    b.weights = c->d_weights.as<uint8_t>();
-  } else if (!host_stream_kind(c->suite)) b.records = c->d_rec.as<uint8_t>();
-  else {
-    const size_t wsz = kind == 1 ? 16 : 32;
-    HIP_TRY(c->d_weights.ensure(n * wsz));
-    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), n * wsz, hipMemcpyHostToDevice, c->stream));
-    b.weights = c->d_weights.as<uint8_t>();
   }
-  Seed64 seed;
-  for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, digest + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
-  HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((n + 127) / 128) * 64 + 64));
+  if (c->unit_weights || suite_host_weights(c->suite)) {               // the weights as a stream in HBM; else the terms kernel derives them from the seed
+    const size_t wbytes = n * kind_facts(kind).weight;
+    HIP_TRY(c->d_weights.ensure(wbytes));
+    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), wbytes, hipMemcpyHostToDevice, c->stream));
+    b.weights = c->d_weights.as<uint8_t>();
+  } else b.records = c->d_rec.as<uint8_t>();
+  if (int e = ensure_terms(c)) return e;
   const double t2 = now_us();
-  if (kind == 1) AVRF_BATCH(c->suite, thin_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
-                                                 c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
-  else AVRF_BATCH(c->suite, ped_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
-                                      c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
+  launch_terms(c, kind, b, seed_of(digest), 0, c->L->d_scalars.as<uint32_t>());
   const double t3 = now_us();
   if (int e = guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->chain(), c->stream) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
   c->timing[3] = t3 - t2;
@@ -611,8 +611,8 @@ static int batch_run(avrf_ctx *c, int kind) {
   return batch_end(c, kind);
 }
 
-int avrf_thin_batch_run(avrf_ctx *c) { return batch_run(c, 1); }
-int avrf_pedersen_batch_run(avrf_ctx *c) { return batch_run(c, 2); }
+int avrf_thin_batch_run(avrf_ctx *c) { return batch_run(c, Thin); }
+int avrf_pedersen_batch_run(avrf_ctx *c) { return batch_run(c, Pedersen); }
 // (defensive: a run can only be open on a staged batch -- every entry point that would un-stage it is refused while
 // run_phase != 0 -- but should the two ever disagree the run is closed rather than leaving the context refusing every call)
 static int run_call(avrf_ctx *c, int (*phase)(avrf_ctx *, int)) {
@@ -645,13 +645,10 @@ int avrf_batch_weight_seed(int suite, int pedersen, size_t n, const uint8_t *c16
   if (suite < 0 || suite >= AVRF_N_SUITES || !seed_out || (n && (!c16 || !resp))) return AVRF_ERR_BAD_ARG;
   // a sponge transcript has no seed to hand to the shards (its weight stream is sequential): the split-one-batch mode is for the
   // counter-mode (HashTranscript) suites; whole batches shard over GPUs for every suite
-  if (with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; })) return AVRF_ERR_BAD_ARG;
+  if (suite_host_weights(suite)) return AVRF_ERR_BAD_ARG;
+  uint8_t prefix[64]; const size_t pl = batch_prefix(suite, prefix);
   HostSha512 h;
-  with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; h.update(S::SUITE_ID, S::SUITE_ID_LEN); });
-  const uint8_t tag = DS_BATCH_VERIFY; h.update(&tag, 1);
-  const size_t rsz = pedersen ? 64 : 32;
-  uint8_t rec[96]; memset(rec, 0, sizeof rec);
-  for (size_t j = 0; j < n; j++) { memcpy(rec, c16 + 16 * j, 16); memcpy(rec + 32, resp + rsz * j, rsz); h.update(rec, 32 + rsz); }
+  absorb_weight_message(h, prefix, pl, n, c16, resp, kind_facts(pedersen ? Pedersen : Thin).resp);
   h.final(seed_out);
   return AVRF_OK;
 }
@@ -660,63 +657,51 @@ int avrf_batch_weight_seed(int suite, int pedersen, size_t n, const uint8_t *c16
 // CPU has no AVX-512 (the library then hashes every transcript on its context's thread)
 int avrf_batch_weight_seeds_x8(int suite, int pedersen, int count, const size_t *n, const uint8_t *const *c16, const uint8_t *const *resp, uint8_t *seeds_out) {
   if (suite < 0 || suite >= AVRF_N_SUITES || count < 1 || count > 8 || !n || !c16 || !resp || !seeds_out) return AVRF_ERR_BAD_ARG;
-  if (with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; })) return AVRF_ERR_BAD_ARG;
+  if (suite_host_weights(suite)) return AVRF_ERR_BAD_ARG;
   if (!sha512_mb_available()) return AVRF_ERR_NO_DEVICE;
-  uint8_t prefix[64]; size_t pl = 0;
-  with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; memcpy(prefix, S::SUITE_ID, S::SUITE_ID_LEN); pl = S::SUITE_ID_LEN; });
-  prefix[pl++] = DS_BATCH_VERIFY;
+  uint8_t prefix[64]; const size_t pl = batch_prefix(suite, prefix);
   WeightJob jobs[8]; WeightJob *pj[8];
   for (int i = 0; i < count; i++) {
     if (n[i] && (!c16[i] || !resp[i])) return AVRF_ERR_BAD_ARG;
-    jobs[i].prefix = prefix; jobs[i].prefix_len = pl; jobs[i].c16 = c16[i]; jobs[i].resp = resp[i]; jobs[i].n = n[i]; jobs[i].rsz = pedersen ? 64 : 32; pj[i] = &jobs[i];
+    jobs[i].prefix = prefix; jobs[i].prefix_len = pl; jobs[i].c16 = c16[i]; jobs[i].resp = resp[i]; jobs[i].n = n[i]; jobs[i].rsz = kind_facts(pedersen ? Pedersen : Thin).resp; pj[i] = &jobs[i];
   }
   sha512_weights_x8(pj, count);
   for (int i = 0; i < count; i++) memcpy(seeds_out + 64 * i, jobs[i].digest, 64);
   return AVRF_OK;
 }
 
-// SHA-512 of up to eight contiguous messages through the same multi-buffer code -- the form avrf_*_batch_run hands to the
-// hash service (prefix || records, one buffer per batch); exported so that a test can hold it against an independent SHA-512
-int avrf_sha512_x8(int count, const uint8_t *const *msgs, const size_t *lens, uint8_t *digests_out) {
-  if (count < 1 || count > 8 || !msgs || !lens || !digests_out) return AVRF_ERR_BAD_ARG;
-  if (!sha512_mb_available()) return AVRF_ERR_NO_DEVICE;
-  static const uint8_t empty = 0;
-  WeightJob jobs[8]; WeightJob *pj[8];
-  for (int i = 0; i < count; i++) {
-    if (lens[i] && !msgs[i]) return AVRF_ERR_BAD_ARG;
-    jobs[i].msg = lens[i] ? msgs[i] : &empty; jobs[i].msg_len = lens[i]; pj[i] = &jobs[i];
-  }
-  sha512_weights_x8(pj, count);
-  for (int i = 0; i < count; i++) memcpy(digests_out + 64 * i, jobs[i].digest, 64);
-  return AVRF_OK;
-}
-
-// the same for up to sixteen messages through the form the pool uses (host_sha512_mb.h sha512_weights_x16: more than eight lanes
-// run as two groups of eight in one interleaved round loop)
-int avrf_sha512_x16(int count, const uint8_t *const *msgs, const size_t *lens, uint8_t *digests_out) {
-  if (count < 1 || count > 16 || !msgs || !lens || !digests_out) return AVRF_ERR_BAD_ARG;
-  if (!sha512_mb16_available()) return AVRF_ERR_NO_DEVICE;
+// SHA-512 of contiguous messages through ONE named form of the multi-buffer code, whatever sha512_many would pick: exported for tests
+static int sha512_messages(int count, int lanes, bool available, void (*many)(WeightJob *const *, int), const uint8_t *const *msgs, const size_t *lens, uint8_t *digests_out) {
+  if (count < 1 || count > lanes || !msgs || !lens || !digests_out) return AVRF_ERR_BAD_ARG;
+  if (!available) return AVRF_ERR_NO_DEVICE;
   static const uint8_t empty = 0;
   WeightJob jobs[16]; WeightJob *pj[16];
   for (int i = 0; i < count; i++) {
     if (lens[i] && !msgs[i]) return AVRF_ERR_BAD_ARG;
-    jobs[i].msg = lens[i] ? msgs[i] : &empty; jobs[i].msg_len = lens[i]; pj[i] = &jobs[i];
+    jobs[i] = WeightJob::whole(lens[i] ? msgs[i] : &empty, lens[i]); pj[i] = &jobs[i];
   }
-  sha512_weights_x16(pj, count);
+  many(pj, count);
   for (int i = 0; i < count; i++) memcpy(digests_out + 64 * i, jobs[i].digest, 64);
   return AVRF_OK;
 }
+// the form avrf_*_batch_run hands to the hash service (prefix || records, one buffer per batch), eight lanes
+int avrf_sha512_x8(int count, const uint8_t *const *msgs, const size_t *lens, uint8_t *digests_out) {
+  return sha512_messages(count, 8, sha512_mb_available(), sha512_weights_x8, msgs, lens, digests_out);
+}
+// the form the pool uses (host_sha512_mb.h sha512_weights_x16: more than eight lanes run as two groups of eight in one interleaved round loop)
+int avrf_sha512_x16(int count, const uint8_t *const *msgs, const size_t *lens, uint8_t *digests_out) {
+  return sha512_messages(count, 16, sha512_mb16_available(), sha512_weights_x16, msgs, lens, digests_out);
+}
 
-// prepare (src/thin.rs:209-226) on the staged shard: per-item challenges, 16 bytes each
-int avrf_thin_batch_challenges(avrf_ctx *c, uint8_t *c_out) {
-  if (!c || c->staged_kind != 1 || (c->n && !c_out)) return AVRF_ERR_BAD_ARG;
+// prepare (src/thin.rs:209-226, src/pedersen.rs:276-293) on the staged shard: per-item challenges, 16 bytes each
+static int batch_challenges(avrf_ctx *c, int kind, uint8_t *c_out) {
+  if (!c || c->staged_kind != kind || (c->n && !c_out)) return AVRF_ERR_BAD_ARG;
   if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   if (c->n == 0) return AVRF_OK;
   HIP_TRY(hipSetDevice(c->device));
-  BatchDev b = batch_of(c);
   HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  validate_staged(c, 1, nullptr);
-  AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
+  validate_staged(c, kind, nullptr);
+  launch_prepare(c, kind, batch_of(c));
   HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -724,63 +709,26 @@ int avrf_thin_batch_challenges(avrf_ctx *c, uint8_t *c_out) {
   c->chal_gen = c->stage_gen;                                         // the challenges in d_c / d_z belong to THIS staging
   return AVRF_OK;
 }
-
-// MSM of the staged shard's terms under the GLOBAL weight stream `seed`; the shard's first item has
-// global index first_index.  Includes the shard's share (G, -sum w s z0) of the shared-generator term,
-// so the partial points of all shards add up to the batch MSM of src/thin.rs:319.
-int avrf_thin_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t first_index, uint8_t out_xy[64]) {
-  if (!c || c->staged_kind != 1 || !seed64 || !out_xy) return AVRF_ERR_BAD_ARG;
+// MSM of the staged shard's terms under the GLOBAL weight stream `seed`; the shard's first item has global index first_index.
+// Includes the shard's shares of the shared-generator terms (Thin: (G, -sum w s z0); Pedersen: the G and BLINDING_BASE terms), so
+// the partial points of all shards add up to the batch MSM of src/thin.rs:319 / src/pedersen.rs:420.
+static int batch_partial(avrf_ctx *c, int kind, const uint8_t seed64[64], uint64_t first_index, uint8_t out_xy[64]) {
+  if (!c || c->staged_kind != kind || !seed64 || !out_xy) return AVRF_ERR_BAD_ARG;
   if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   // a sponge / SHA-256 transcript has no seed to hand to the shards (avrf_batch_weight_seed refuses those suites too)
-  if (with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; })) return AVRF_ERR_BAD_ARG;
-  if (c->n && c->chal_gen != c->stage_gen) return AVRF_ERR_BAD_ARG;     // avrf_thin_batch_challenges has not run on this staging (or it failed)
+  if (suite_host_weights(c->suite)) return AVRF_ERR_BAD_ARG;
+  if (c->n && c->chal_gen != c->stage_gen) return AVRF_ERR_BAD_ARG;     // *_batch_challenges has not run on this staging (or it failed)
   HIP_TRY(hipSetDevice(c->device));
   HostExt r;
   if (c->n == 0) { r = with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; return HostTe<S>::identity(); }); return finish_point(c, r, out_xy); }
-  Seed64 seed;
-  for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, seed64 + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
-  BatchDev b = batch_of(c);
-  AVRF_BATCH(c->suite, thin_terms(b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(),
-                                  c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
+  launch_terms(c, kind, batch_of(c), seed_of(seed64), first_index, c->L->d_scalars.as<uint32_t>());
   if (int e = lane_msm(c, c->n_terms, &r)) return e;
   return finish_point(c, r, out_xy);
 }
-
-// The same two steps for pedersen::BatchVerifier (src/pedersen.rs:341-426): challenges of the staged shard, then the MSM
-// of its 5 n_shard + 2 terms under the global weight stream (the shard's shares of the G and BLINDING_BASE terms included).
-int avrf_pedersen_batch_challenges(avrf_ctx *c, uint8_t *c_out) {
-  if (!c || c->staged_kind != 2 || (c->n && !c_out)) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  if (c->n == 0) return AVRF_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  BatchDev b = batch_of(c);
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
-  validate_staged(c, 2, nullptr);
-  AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
-  HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (*c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
-  c->chal_gen = c->stage_gen;                                         // the challenges in d_c / d_z belong to THIS staging
-  return AVRF_OK;
-}
-int avrf_pedersen_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t first_index, uint8_t out_xy[64]) {
-  if (!c || c->staged_kind != 2 || !seed64 || !out_xy) return AVRF_ERR_BAD_ARG;
-  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  // a sponge / SHA-256 transcript has no seed to hand to the shards (avrf_batch_weight_seed refuses those suites too)
-  if (with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; })) return AVRF_ERR_BAD_ARG;
-  if (c->n && c->chal_gen != c->stage_gen) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  HostExt r;
-  if (c->n == 0) { r = with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; return HostTe<S>::identity(); }); return finish_point(c, r, out_xy); }
-  Seed64 seed;
-  for (int i = 0; i < 8; i++) { uint64_t v; memcpy(&v, seed64 + 8 * i, 8); seed.w[i] = __builtin_bswap64(v); }
-  BatchDev b = batch_of(c);
-  AVRF_BATCH(c->suite, ped_terms(b, seed, first_index, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>(),
-                                 c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
-  if (int e = lane_msm(c, c->n_terms, &r)) return e;
-  return finish_point(c, r, out_xy);
-}
+int avrf_thin_batch_challenges(avrf_ctx *c, uint8_t *c_out) { return batch_challenges(c, Thin, c_out); }
+int avrf_thin_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t first_index, uint8_t out_xy[64]) { return batch_partial(c, Thin, seed64, first_index, out_xy); }
+int avrf_pedersen_batch_challenges(avrf_ctx *c, uint8_t *c_out) { return batch_challenges(c, Pedersen, c_out); }
+int avrf_pedersen_batch_partial(avrf_ctx *c, const uint8_t seed64[64], uint64_t first_index, uint8_t out_xy[64]) { return batch_partial(c, Pedersen, seed64, first_index, out_xy); }
 
 // sum of k affine points on the host (combining per-GPU partial MSM results)
 int avrf_points_sum(int suite, size_t k, const uint8_t *points_xy, uint8_t out_xy[64]) {
@@ -862,7 +810,7 @@ static bool one_as_msm() { static const bool on = getenv("AVRF_NO_ONE_AS_MSM") =
 // for one proof; same bytes (any evaluation of R gives the same group element).  The nonce never leaves device memory.
 static Route prove_one_as_msm(avrf_ctx *c, bool have_pk, bool tiny, uint8_t *proofs_out) {
   if (c->tot_io >= 1000) return {};
-  const size_t nt = 1 + c->tot_io, plen = tiny ? 48 : 96, sb = AVRF_SINGLE(c->suite, prove_state_bytes());
+  const size_t nt = 1 + c->tot_io, plen = kind_facts(tiny ? Tiny : Thin).xy_proof(), sb = AVRF_SINGLE(c->suite, prove_state_bytes());
   HIP_TRY(c->h_c.ensure(64));
   if (!have_pk) { if (int fs = ensure_fixed(c)) return fs; }
   HIP_TRY(c->L->d_scalars.ensure(nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw))); HIP_TRY(c->d_misc.ensure(sb + 64)); HIP_TRY(c->d_out.ensure(plen));
@@ -888,7 +836,7 @@ static Route prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out
   if (!have_pk) { if (int fs = ensure_fixed(c)) return fs; }
   const size_t m = c->tot_io, nt = 2 + m, sb = AVRF_SINGLE(c->suite, ped_state_bytes()), wb = (m * 32 + 63) / 64 * 64 + 64;
   HIP_TRY(c->L->d_scalars.ensure(2 * nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw)));
-  HIP_TRY(c->d_misc.ensure(sb + wb + 192 + 32)); HIP_TRY(c->d_out.ensure(256)); HIP_TRY(c->h_c.ensure(192));
+  HIP_TRY(c->d_misc.ensure(sb + wb + 192 + 32)); HIP_TRY(c->d_out.ensure(kind_facts(Pedersen).xy_proof())); HIP_TRY(c->h_c.ensure(192));
   BatchDev b = batch_of(c);
   if (!have_pk) b.pks_xy = nullptr;
   uint8_t *d_state = c->d_misc.as<uint8_t>(), *d_pts = d_state + sb + wb, *d_blind = d_pts + 192;
@@ -905,7 +853,7 @@ static Route prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out
   finish_point(c, r[0], pts + 64); finish_point(c, r[1], pts + 128);
   HIP_TRY(hipMemcpyAsync(d_pts + 64, pts + 64, 128, hipMemcpyHostToDevice, c->stream));
   AVRF_SINGLE(c->suite, ped_prove_end(b, d_state, d_pts, c->d_out.as<uint8_t>(), blindings_out ? d_blind : nullptr, c->d_flags.as<uint32_t>(), c->stream));
-  HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, 256, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(proofs_out, c->d_out.p, kind_facts(Pedersen).xy_proof(), hipMemcpyDeviceToHost, c->stream));
   if (blindings_out) HIP_TRY(hipMemcpyAsync(blindings_out, d_blind, 32, hipMemcpyDeviceToHost, c->stream));
   return read_flags(c);
 }
@@ -919,9 +867,9 @@ static Route verify_one_as_msm(avrf_ctx *c, int32_t *status_out) {
   if (!c->n_terms || c->n_terms > 2048) return {};
   uint8_t zero[64] = {0};
   c->unit_weights = true;
-  int st = batch_begin(c, 1);
-  if (st == AVRF_OK) st = batch_launch(c, 1, zero);
-  if (st == AVRF_OK) st = batch_end(c, 1);
+  int st = batch_begin(c, Thin);
+  if (st == AVRF_OK) st = batch_launch(c, Thin, zero);
+  if (st == AVRF_OK) st = batch_end(c, Thin);
   c->unit_weights = false;
   if (st != AVRF_OK && st != AVRF_VERIFICATION_FAILURE) { c->run_phase = 0; return st; }
   status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : st;
@@ -933,7 +881,7 @@ static Route verify_one_as_msm(avrf_ctx *c, int32_t *status_out) {
 // Horners side by side (see verify_one_as_msm): both sums must be the identity, exactly the reference's two checks.  0.52 -> ~0.33 ms.
 static Route verify_ped_one_as_msm(avrf_ctx *c, int32_t *status_out) {
   if (!c->n_terms || c->n_terms > 2048) return {};
-  int st = batch_begin(c, 2);                                          // validation + prepare kernel (challenge, merged pair) + flags copy
+  int st = batch_begin(c, Pedersen);                                        // validation + prepare kernel (challenge, merged pair) + flags copy
   c->run_phase = 0;
   if (st != AVRF_OK) return st;
   const size_t nt = c->n_terms;
@@ -942,11 +890,10 @@ static Route verify_ped_one_as_msm(avrf_ctx *c, int32_t *status_out) {
   HIP_TRY(c->d_weights.ensure(64));
   HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), 64, hipMemcpyHostToDevice, c->stream));
   BatchDev b = batch_of(c);
-  Seed64 seed; for (int i = 0; i < 8; i++) seed.w[i] = 0;
+  const uint8_t zero[64] = {0};
   for (int v = 0; v < 2; v++) {
     b.weights = c->d_weights.as<uint8_t>() + 32 * v;
-    AVRF_BATCH(c->suite, ped_terms(b, seed, 0, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_scalars.as<uint32_t>() + (size_t)v * nt * 8,
-                                   c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)nt, c->stream));
+    launch_terms(c, Pedersen, b, seed_of(zero), 0, c->L->d_scalars.as<uint32_t>() + (size_t)v * nt * 8);
   }
   HostExt r[2];
   if (int e = lane_msm_vectors(c, nt, 2, r)) return e;
@@ -956,9 +903,8 @@ static Route verify_ped_one_as_msm(avrf_ctx *c, int32_t *status_out) {
 
 // What a per-item entry point hands the route driver besides its inputs
 struct ItemCall {
-  int kind;                  // 1 thin, 2 pedersen, 3 tiny (ctx_stage)
+  int kind;                  // ProofKind (ctx_stage); the proofs are kind_facts(kind).xy_proof() bytes each
   bool prover;
-  size_t psz;                // proof bytes: 96 / 256 / 48
   uint8_t *proofs_out;       // provers: n proofs
   uint8_t *blindings_out;    // the Pedersen prover: n blindings, or NULL
   int32_t *status_out;       // verifiers: n statuses
@@ -972,22 +918,23 @@ template <class One, class Wave, class Lane>
 static int item_call(avrf_ctx *c, const ItemCall &k, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
                      const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, One one, Wave wave, Lane lane) {
   // Tiny waits for its staging copies; Thin and Pedersen leave them in flight (the call waits for the stream before it returns)
-  int st = ctx_stage(c, k.kind, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, k.kind == 3);
+  int st = ctx_stage(c, k.kind, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, k.kind == Tiny);
   if (st || !n) return st;
+  const size_t psz = kind_facts(k.kind).xy_proof();
   if (k.prover) {
     c->staged_kind = 0;       // (a Thin / Pedersen verifier leaves its batch staged: avrf_batch_last_terms and avrf_*_batch_run see it)
-    HIP_TRY(c->d_out.ensure(n * k.psz));
-    if (k.kind == 2) HIP_TRY(c->d_misc.ensure(n * 32));                // the blindings
+    HIP_TRY(c->d_out.ensure(n * psz));
+    if (k.kind == Pedersen) HIP_TRY(c->d_misc.ensure(n * 32));                // the blindings
   } else HIP_TRY(c->d_status.ensure(n * 4));
   // the provers read the input flags back; the Tiny verifier has always cleared them too, the Thin / Pedersen verifiers never have
-  if (k.prover || k.kind == 3) HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+  if (k.prover || k.kind == Tiny) HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
   auto finish = [&](bool wave_statuses) -> int {
     if (!k.prover) {
       validate_staged(c, k.kind, c->d_status.as<int32_t>());           // Validate::Yes failures overwrite the item's status with InvalidData
       HIP_TRY(hipMemcpyAsync(k.status_out, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
       return sync_stream(c);
     }
-    HIP_TRY(hipMemcpyAsync(k.proofs_out, c->d_out.p, n * k.psz, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(k.proofs_out, c->d_out.p, n * psz, hipMemcpyDeviceToHost, c->stream));
     if (k.blindings_out) HIP_TRY(hipMemcpyAsync(k.blindings_out, c->d_misc.p, n * 32, hipMemcpyDeviceToHost, c->stream));
     if (wave_statuses) HIP_TRY(hipMemcpyAsync(c->h_c.p, c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     return read_flags(c);
@@ -995,7 +942,7 @@ static int item_call(avrf_ctx *c, const ItemCall &k, size_t n, const uint8_t *sk
   auto routes = [&]() -> int {
     if (n == 1 && one_as_msm()) { if (Route r = one()) return *r; }
     if ((!k.prover || pks_xy) && wave_shape(c, n, io_counts)) {      // (the wave provers take the public keys as given)
-      if (k.prover && k.kind == 2) { if (int fs = ensure_fixed(c)) return fs; }   // (the Pedersen one reads the fixed-base tables)
+      if (k.prover && k.kind == Pedersen) { if (int fs = ensure_fixed(c)) return fs; }   // (the Pedersen one reads the fixed-base tables)
       if (k.prover) { HIP_TRY(c->d_status.ensure(n * 4)); HIP_TRY(c->h_c.ensure(n * 4)); }
       if (wave(batch_of(c))) {
         const int ws = finish(true);
@@ -1013,7 +960,7 @@ static int item_call(avrf_ctx *c, const ItemCall &k, size_t n, const uint8_t *sk
   const double t0 = now_us();
   st = routes();
   c->timing[0] = now_us() - t0;               // avrf_last_timing: the routes' wall time, for every kind and on every return
-  if (k.kind == 3 && st == AVRF_OK) c->staged_kind = 0;                 // Tiny has no batch verifier: nothing stays staged
+  if (k.kind == Tiny && st == AVRF_OK) c->staged_kind = 0;                 // Tiny has no batch verifier: nothing stays staged
   return st;
 }
 
@@ -1033,7 +980,7 @@ extern "C" {
 static int thin_or_tiny_prove(avrf_ctx *c, bool tiny, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
                               const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, uint8_t *proofs_out) {
   if (n && (!sks || !proofs_out)) return AVRF_ERR_BAD_ARG;
-  return item_call(c, {tiny ? 3 : 1, true, size_t(tiny ? 48 : 96), proofs_out, nullptr, nullptr}, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr,
+  return item_call(c, {tiny ? Tiny : Thin, true, proofs_out, nullptr, nullptr}, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr,
       [&] { return prove_one_as_msm(c, pks_xy != nullptr, tiny, proofs_out); },
       [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, thin_prove_wave(b, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream, tiny)); },
       [&](const BatchDev &b) { AVRF_SINGLE(c->suite, thin_prove(b, c->d_out.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream, tiny)); });
@@ -1047,7 +994,7 @@ int avrf_thin_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t *pk
 int avrf_thin_verify(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                      const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int32_t *status_out) {
   if (n && (!pks_xy || !proofs || !status_out)) return AVRF_ERR_BAD_ARG;
-  return item_call(c, {1, false, 96, nullptr, nullptr, status_out}, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs,
+  return item_call(c, {Thin, false, nullptr, nullptr, status_out}, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs,
       [&] { return verify_one_as_msm(c, status_out); },
       [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, thin_verify_wave(b, c->d_status.as<int32_t>(), c->stream)); },
       [&](const BatchDev &b) { AVRF_SINGLE(c->suite, thin_verify(b, c->d_status.as<int32_t>(), c->stream)); });
@@ -1061,7 +1008,7 @@ int avrf_tiny_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t *pk
 int avrf_tiny_verify(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                      const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int32_t *status_out) {
   if (n && (!pks_xy || !proofs || !status_out)) return AVRF_ERR_BAD_ARG;
-  return item_call(c, {3, false, 48, nullptr, nullptr, status_out}, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs,
+  return item_call(c, {Tiny, false, nullptr, nullptr, status_out}, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs,
       [] { return Route(); },                                          // (no one-item route)
       [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, tiny_verify_wave(b, c->d_status.as<int32_t>(), c->stream)); },
       [&](const BatchDev &b) { AVRF_SINGLE(c->suite, tiny_verify(b, c->d_status.as<int32_t>(), c->stream)); });
@@ -1070,7 +1017,7 @@ int avrf_tiny_verify(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t
 int avrf_pedersen_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                         const uint8_t *ads, const uint32_t *ad_lens, uint8_t *proofs_out, uint8_t *blindings_out) {
   if (n && (!sks || !proofs_out)) return AVRF_ERR_BAD_ARG;
-  return item_call(c, {2, true, 256, proofs_out, blindings_out, nullptr}, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr,
+  return item_call(c, {Pedersen, true, proofs_out, blindings_out, nullptr}, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, nullptr,
       [&] { return prove_ped_one_as_msm(c, pks_xy != nullptr, proofs_out, blindings_out); },
       [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, ped_prove_wave(b, c->d_out.as<uint8_t>(), c->d_misc.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->d_status.as<int32_t>(), c->stream)); },
       [&](const BatchDev &b) { AVRF_SINGLE(c->suite, ped_prove(b, c->d_out.as<uint8_t>(), c->d_misc.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream)); });
@@ -1079,7 +1026,7 @@ int avrf_pedersen_prove(avrf_ctx *c, size_t n, const uint8_t *sks, const uint8_t
 int avrf_pedersen_verify(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts,
                          const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int32_t *status_out) {
   if (n && (!proofs || !status_out)) return AVRF_ERR_BAD_ARG;
-  return item_call(c, {2, false, 256, nullptr, nullptr, status_out}, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs,
+  return item_call(c, {Pedersen, false, nullptr, nullptr, status_out}, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs,
       [&] { return verify_ped_one_as_msm(c, status_out); },
       [&](const BatchDev &b) { return AVRF_SINGLE(c->suite, ped_verify_wave(b, c->d_status.as<int32_t>(), c->stream)); },
       [&](const BatchDev &b) { AVRF_SINGLE(c->suite, ped_verify(b, c->d_status.as<int32_t>(), c->stream)); });
@@ -1093,12 +1040,9 @@ static int smul_common(avrf_ctx *c, size_t n, const uint8_t *scalars, const uint
     // The bit sums are the literal product for ANY curve point, like the lane kernel's window form (no endomorphism split).
     if (points_xy && n <= 32 && one_as_msm()) {
       for (size_t i = 0; i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
-      HIP_TRY(c->d_misc.ensure(n * 64)); HIP_TRY(c->L->d_scalars.ensure(n * n * 32)); HIP_TRY(c->L->d_pre.ensure(n * sizeof(te_pre_raw)));
       std::vector<uint8_t> diag(n * n * 32, 0);
       for (size_t i = 0; i < n; i++) memcpy(&diag[(i * n + i) * 32], scalars + 32 * i, 32);
-      HIP_TRY(hipMemcpyAsync(c->d_misc.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, diag.data(), diag.size(), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+      if (int e = upload_bases_and_scalars(c, n, points_xy, diag.data(), diag.size())) return e;
       launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
       HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
       HostExt r[32];

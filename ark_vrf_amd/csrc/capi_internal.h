@@ -5,6 +5,7 @@
 #include "../../include/avrf.h"
 #include "host_te.h"
 #include "msm.h"
+#include "proof_kind.h"
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <new>
@@ -61,7 +62,7 @@ struct avrf_ctx {
   int validate = 0;               // avrf_ctx_set_validation: 0 unchecked (typed-point callers), 1 on-curve, 2 + subgroup
   bool wire_pending = false;              // staged from wire bytes without waiting: batch_collect reads the decode flag (h_flags[2])
   uint64_t stage_gen = 0, chal_gen = 0;   // challenges of *_batch_challenges belong to staging generation chal_gen
-  int staged_kind = 0;            // 0 none, 1 thin, 2 pedersen
+  int staged_kind = 0;            // 0 none, else the ProofKind staged (proof_kind.h)
   size_t n = 0, tot_io = 0, n_terms = 0;
   avrf::DevBuf d_pks, d_ios, d_io_off, d_ads, d_ad_off, d_proofs, d_sks;
   std::vector<uint8_t> h_resp;    // host copy of the response scalars (s [, sb]) for the weight transcript (sponge transcripts only)
@@ -83,7 +84,9 @@ struct avrf_ctx {
 };
 
 namespace avrf {
-// the phases of a staged batch's run, shared by the three-call ABI (capi.hip) and the pool's workers (pool.hip)
+struct WeightJob;
+// Staging, then the phases of a staged batch's run, shared by the three-call ABI (capi.hip) and the pool's workers (pool.hip).  `kind` is
+// a ProofKind (sizes: proof_kind.h).  The stagers share opening and close and differ in the payload: x || y arrays, or wire bytes decompressed on the device.
 int ctx_create(int suite, int device, bool lane_owner, avrf_ctx **out);
 int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
               const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait);
@@ -91,8 +94,9 @@ int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const ui
                    const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait);   // serialize_compressed bytes in, decompressed on the device
 int batch_begin(avrf_ctx *c, int kind);                               // validation + prepare kernel + copies back enqueued on c->stream
 int batch_collect(avrf_ctx *c, int kind);                             // (c->stream's work has completed) AVRF_INVALID_DATA for a refused item
-bool batch_host_weights(const avrf_ctx *c);                           // sponge / SHA-256 transcript: batch_seed squeezes the weight stream itself
+bool suite_host_weights(int suite);                                   // sponge / SHA-256 transcript: batch_seed squeezes the weight stream itself (no seed)
 int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]);            // the weight transcript on the calling thread
+void sha512_many(WeightJob *const *jobs, int k);                      // k <= 16 transcripts hashed together: scalar, eight or sixteen lanes, as the host CPU allows
 int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]);    // terms kernel + MSM chain enqueued on c->stream / c->L
 int batch_end(avrf_ctx *c, int kind);                                 // waits for the chain, folds, verdict
 double now_us();

@@ -9,11 +9,13 @@
 //   pedersen proof  Yb(32) || R(32) || Ok(32) || s || sb    src/pedersen.rs:69-75      (160 bytes)
 //   ring-VRF proof  pedersen proof || ring proof            src/ring.rs:160-166        (752 / 640 bytes)
 #include "../../include/avrf.h"
+#include "proof_kind.h"
 #include <string.h>
 #include <thread>
 #include <vector>
 
 extern "C" int avrf_ctx_suite_(avrf_ctx *c);
+using namespace avrf;
 
 namespace {
 
@@ -36,7 +38,7 @@ int decompress_all(avrf_ctx *ctx, const Gather &g, int validate, std::vector<uin
 }
 size_t sum_counts(const uint32_t *c, size_t n) { size_t t = 0; for (size_t i = 0; i < n; i++) t += c[i]; return t; }
 
-// shared by the thin / tiny / pedersen wire verifiers: kind 1 thin (64-byte proofs, 1 point), 3 tiny (48, 0 points), 2 pedersen (160, 3)
+// shared by the thin / tiny / pedersen wire verifiers: kind is a ProofKind, its layouts those of proof_kind.h
 // pp0_xy / pp0_st (optional): xy and decode status of every item's FIRST proof point (the Pedersen key commitment Yb, which
 // ring::Verifier also needs as the ring proof's instance) -- so that a caller does not decompress it a second time
 // (Until the single-launch MSM -- msm.hip k_msm_tiny_bits -- a "batch" of <= 64 items went through the per-item
@@ -55,27 +57,28 @@ struct WirePrep {
 int wire_prepare(avrf_ctx *ctx, int kind, bool batch, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                  const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool have_status_out, WirePrep &w,
                  std::vector<uint8_t> *pp0_xy = nullptr, std::vector<int32_t> *pp0_st = nullptr) {
-  w.small = batch && n <= SMALL_BATCH && kind != 3;
+  const KindFacts &k = kind_facts(kind);
+  w.small = batch && n <= SMALL_BATCH && kind != Tiny;
   if (w.small) { w.small_status.assign(n ? n : 1, 0); batch = false; have_status_out = true; }
-  if (!ctx || (n && (!io_counts || !ad_lens || !proofs)) || (n && kind != 2 && !pks) || (!batch && n && !have_status_out)) return AVRF_ERR_BAD_ARG;
+  if (!ctx || (n && (!io_counts || !ad_lens || !proofs)) || (n && k.pk && !pks) || (!batch && n && !have_status_out)) return AVRF_ERR_BAD_ARG;
   w.kind = kind; w.batch = batch; w.n = n; w.io_counts = io_counts; w.ad_lens = ad_lens; w.ads = ads;
   if (!n) return AVRF_OK;
   const size_t tot = sum_counts(io_counts, n);
   if (tot && !ios) return AVRF_ERR_BAD_ARG;
   w.tot = tot;
   const size_t L = avrf_point_len(avrf_ctx_suite_(ctx));
-  const size_t ppts = kind == 1 ? 1 : kind == 3 ? 0 : 3, plen = ppts * L + (kind == 1 ? 32 : kind == 3 ? 48 : 64), xlen = kind == 1 ? 96 : kind == 3 ? 48 : 256;
+  const size_t ppts = k.points, plen = k.wire_proof(L), xlen = k.xy_proof();
   w.ppts = ppts;
   Gather g(L);
-  if (kind != 2) g.add(pks, n, L);
+  if (k.pk) g.add(pks, n, L);
   g.add(ios, 2 * tot, L);
   for (size_t p = 0; p < ppts; p++) g.add(proofs + L * p, n, plen);
   int rc = decompress_all(ctx, g, validate, w.xy, (batch && !pp0_st) ? nullptr : &w.pst);
   if (rc != AVRF_OK) return rc;
-  w.x_pks = w.xy.data(); w.x_ios = w.xy.data() + (kind != 2 ? n * 64 : 0);
+  w.x_pks = w.xy.data(); w.x_ios = w.xy.data() + (k.pk ? n * 64 : 0);
   const uint8_t *x_pp = w.x_ios + 2 * tot * 64;
   if (pp0_xy && ppts) pp0_xy->assign(x_pp, x_pp + n * 64);
-  if (pp0_st && ppts) pp0_st->assign(w.pst.begin() + ((kind != 2 ? n : 0) + 2 * tot), w.pst.begin() + ((kind != 2 ? n : 0) + 2 * tot + n));
+  if (pp0_st && ppts) pp0_st->assign(w.pst.begin() + ((k.pk ? n : 0) + 2 * tot), w.pst.begin() + ((k.pk ? n : 0) + 2 * tot + n));
   if (batch && pp0_st) for (size_t i = 0; i < w.pst.size(); i++) if (w.pst[i]) return AVRF_INVALID_DATA;
   w.px.resize(n * xlen);
   for (size_t j = 0; j < n; j++) {
@@ -89,18 +92,18 @@ int wire_finish(avrf_ctx *ctx, WirePrep &w, int32_t *status_out) {
   if (!n) return AVRF_OK;
   if (w.small) status_out = w.small_status.data();
   if (w.batch) {
-    if (kind == 1) return avrf_thin_batch_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data());
+    if (kind == Thin) return avrf_thin_batch_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data());
     return avrf_pedersen_batch_verify(ctx, n, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data());
   }
   int rc;
-  if (kind == 1) rc = avrf_thin_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data(), status_out);
-  else if (kind == 3) rc = avrf_tiny_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data(), status_out);
+  if (kind == Thin) rc = avrf_thin_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data(), status_out);
+  else if (kind == Tiny) rc = avrf_tiny_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data(), status_out);
   else rc = avrf_pedersen_verify(ctx, n, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data(), status_out);
   if (rc != AVRF_OK) return rc;
   // a point that does not decode (or fails validation) makes ITS item InvalidData
   const std::vector<int32_t> &pst = w.pst;
   size_t at = 0, io_at = 0;
-  if (kind != 2) { for (size_t j = 0; j < n; j++) if (pst[j]) status_out[j] = AVRF_INVALID_DATA; at = n; }
+  if (kind != Pedersen) { for (size_t j = 0; j < n; j++) if (pst[j]) status_out[j] = AVRF_INVALID_DATA; at = n; }
   for (size_t j = 0; j < n; j++) { for (size_t k = 0; k < 2 * (size_t)w.io_counts[j]; k++) if (pst[at + io_at + k]) status_out[j] = AVRF_INVALID_DATA; io_at += 2 * w.io_counts[j]; }
   at += 2 * tot;
   for (size_t p = 0; p < ppts; p++) for (size_t j = 0; j < n; j++) if (pst[at + p * n + j]) status_out[j] = AVRF_INVALID_DATA;
@@ -114,12 +117,12 @@ int wire_finish(avrf_ctx *ctx, WirePrep &w, int32_t *status_out) {
 int verify_wire(avrf_ctx *ctx, int kind, bool batch, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                 const uint32_t *ad_lens, const uint8_t *proofs, int validate, int32_t *status_out,
                 std::vector<uint8_t> *pp0_xy = nullptr, std::vector<int32_t> *pp0_st = nullptr) {
-  if (batch && !pp0_xy && !pp0_st && (kind == 1 || kind == 2)) {
+  if (batch && !pp0_xy && !pp0_st && (kind == Thin || kind == Pedersen)) {
     // BatchVerifier from wire bytes: decompression on the device straight into the staged buffers (capi.hip ctx_stage_wire), then the run
-    int rc = kind == 1 ? avrf_thin_batch_stage_wire(ctx, n, pks, ios, io_counts, ads, ad_lens, proofs, validate)
+    int rc = kind == Thin ? avrf_thin_batch_stage_wire(ctx, n, pks, ios, io_counts, ads, ad_lens, proofs, validate)
                        : avrf_pedersen_batch_stage_wire(ctx, n, ios, io_counts, ads, ad_lens, proofs, validate);
     if (rc != AVRF_OK) return rc;
-    return kind == 1 ? avrf_thin_batch_run(ctx) : avrf_pedersen_batch_run(ctx);
+    return kind == Thin ? avrf_thin_batch_run(ctx) : avrf_pedersen_batch_run(ctx);
   }
   WirePrep w;
   int rc = wire_prepare(ctx, kind, batch, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, status_out != nullptr, w, pp0_xy, pp0_st);
@@ -133,23 +136,23 @@ extern "C" {
 
 int avrf_thin_batch_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                                 const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
-  return verify_wire(ctx, 1, true, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, nullptr);
+  return verify_wire(ctx, Thin, true, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, nullptr);
 }
 int avrf_thin_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                           const uint32_t *ad_lens, const uint8_t *proofs, int validate, int32_t *status_out) {
-  return verify_wire(ctx, 1, false, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, status_out);
+  return verify_wire(ctx, Thin, false, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, status_out);
 }
 int avrf_tiny_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                           const uint32_t *ad_lens, const uint8_t *proofs, int validate, int32_t *status_out) {
-  return verify_wire(ctx, 3, false, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, status_out);
+  return verify_wire(ctx, Tiny, false, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, status_out);
 }
 int avrf_pedersen_batch_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                                     const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
-  return verify_wire(ctx, 2, true, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, nullptr);
+  return verify_wire(ctx, Pedersen, true, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, nullptr);
 }
 int avrf_pedersen_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                               const uint32_t *ad_lens, const uint8_t *proofs, int validate, int32_t *status_out) {
-  return verify_wire(ctx, 2, false, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, status_out);
+  return verify_wire(ctx, Pedersen, false, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, status_out);
 }
 
 // ring::Prover::prove (src/ring.rs:211-226) for n provers of one ring: Pedersen proof + ring proof for its blinding, serialised
@@ -162,7 +165,7 @@ int avrf_ring_vrf_prove(avrf_ctx *ctx, avrf_ring_key *key, size_t ring_proof_len
   avrf_ring_setup *setup = avrf_ring_key_setup(key);
   if (!setup || avrf_ring_setup_suite(setup) != avrf_ctx_suite_(ctx) || ring_proof_len != avrf_ring_proof_len(setup)) return AVRF_ERR_BAD_ARG;
   if (!n) return AVRF_OK;
-  const size_t L = avrf_point_len(avrf_ctx_suite_(ctx)), pedlen = 3 * L + 64;
+  const size_t L = avrf_point_len(avrf_ctx_suite_(ctx)), pedlen = kind_facts(Pedersen).wire_proof(L);
   std::vector<uint8_t> ped(n * 256), blind(n * 32), rp(n * ring_proof_len), comp(n * 3 * L), pts(n * 3 * 64);
   int rc = avrf_pedersen_prove(ctx, n, sks, nullptr, ios_xy, io_counts, ads, ad_lens, ped.data(), blind.data());
   if (rc != AVRF_OK) return rc;
@@ -187,7 +190,7 @@ int avrf_ring_vrf_verify(avrf_ctx *ctx, avrf_ring_setup *setup, size_t n, const 
   if (!ctx || !setup || (n && (!ring_commitments || !n_rings || !io_counts || !ad_lens || !proofs)) || (each && n && !status_out)) return AVRF_ERR_BAD_ARG;
   if (avrf_ring_setup_suite(setup) != avrf_ctx_suite_(ctx)) return AVRF_ERR_BAD_ARG;
   if (!n) return AVRF_OK;
-  const size_t L = avrf_point_len(avrf_ctx_suite_(ctx)), pedlen = 3 * L + 64;
+  const size_t L = avrf_point_len(avrf_ctx_suite_(ctx)), pedlen = kind_facts(Pedersen).wire_proof(L);
   const size_t rlen = avrf_ring_proof_len(setup), plen = pedlen + rlen, tot = sum_counts(io_counts, n);
   if (tot && !ios) return AVRF_ERR_BAD_ARG;
   std::vector<uint8_t> ped(n * pedlen), rp(n * rlen);
@@ -199,7 +202,7 @@ int avrf_ring_vrf_verify(avrf_ctx *ctx, avrf_ring_setup *setup, size_t n, const 
   std::vector<uint8_t> yb; std::vector<int32_t> yst;
   std::vector<int32_t> s1(n), s2(n);
   WirePrep w;
-  int rc = wire_prepare(ctx, 2, !each, n, nullptr, ios, io_counts, ads, ad_lens, ped.data(), validate, each != 0, w, &yb, &yst);
+  int rc = wire_prepare(ctx, Pedersen, !each, n, nullptr, ios, io_counts, ads, ad_lens, ped.data(), validate, each != 0, w, &yb, &yst);
   if (rc != AVRF_OK) return rc;
   int rc_ped = AVRF_OK;
   std::thread ped_half; bool threaded = true;

@@ -23,11 +23,12 @@
 namespace avrf {
 
 struct WeightJob {
-  const uint8_t *prefix; size_t prefix_len;
-  const uint8_t *c16; const uint8_t *resp; size_t n, rsz;
+  const uint8_t *prefix = nullptr; size_t prefix_len = 0;
+  const uint8_t *c16 = nullptr, *resp = nullptr; size_t n = 0, rsz = 0;
   // or the whole message in one piece (prefix and records contiguous, as the prepare kernels deliver it): msg != nullptr
   const uint8_t *msg = nullptr; size_t msg_len = 0;
   uint8_t digest[64];
+  static WeightJob whole(const uint8_t *msg, size_t len) { WeightJob j; j.msg = msg; j.msg_len = len; return j; }
 };
 
 inline bool sha512_mb_available() { return __builtin_cpu_supports("avx512f"); }

@@ -13,11 +13,11 @@
 //     chains, folds finished ones (host_te.h) -- all from completion events, sleeping in the driver only when idle;
 //   * inputs are read where the caller put them: from buffers of avrf_host_alloc the staging copies are DMA transfers that
 //     overlap the other batches' kernels and cost no host time (include/avrf.h "Ownership").
-// Verdicts are those of avrf_thin_batch_run / avrf_pedersen_batch_run: the workers call the same phases (capi_internal.h), each
+// Verdicts are those of avrf_thin_batch_run / avrf_pedersen_batch_run: the workers call the same stagers and phases (capi_internal.h:
+// ctx_stage / ctx_stage_wire, batch_begin / _collect / _seed / _launch / _end; grouped hashing through sha512_many), each
 // under `guarded` -- a failed HIP call or allocation inside a worker becomes the batch's status, never an exception off the thread.
 #include "capi_internal.h"
 #include "suite_dispatch.h"
-#include "host_sha512.h"
 #include "host_sha512_mb.h"
 #include "host_numa.h"
 #include <pthread.h>
@@ -99,8 +99,6 @@ struct avrf_pool {
 
 namespace {
 
-void scalar_digest(const uint8_t *msg, size_t len, uint8_t out[64]) { HostSha512 h; h.update(msg, len); h.final(out); }
-
 struct Run {
   avrf_pool *P; Worker &W; uint64_t seq = 0;
   Run(avrf_pool *p, Worker &w) : P(p), W(w) {}
@@ -147,17 +145,15 @@ struct Run {
     WeightJob jobs[16]; WeightJob *pj[16]; Slot *ss[16]; int k = 0;
     for (size_t i = 0; i < count; i++) {
       Slot &S = P->slots[ready[i]];
-      if (batch_host_weights(S.c) || S.c->n == 0) {                    // sponge transcripts squeeze their own stream; empty batches have no transcript
+      if (suite_host_weights(P->suite) || S.c->n == 0) {               // sponge transcripts squeeze their own stream; empty batches have no transcript
         int st = guarded([&] { return batch_seed(S.c, P->kind, S.digest); });
         if (st != AVRF_OK) { done(S, st); continue; }
         S.state = S_HASHED;
         continue;
       }
-      jobs[k].prefix = nullptr; jobs[k].prefix_len = 0; jobs[k].c16 = nullptr; jobs[k].resp = nullptr; jobs[k].n = 0; jobs[k].rsz = 0;
-      jobs[k].msg = S.c->h_msg.as<uint8_t>(); jobs[k].msg_len = S.c->h_msg_len; pj[k] = &jobs[k]; ss[k] = &S; k++;
+      jobs[k] = WeightJob::whole(S.c->h_msg.as<uint8_t>(), S.c->h_msg_len); pj[k] = &jobs[k]; ss[k] = &S; k++;
     }
-    if (k == 1 || (k > 1 && !sha512_mb_available())) { for (int i = 0; i < k; i++) scalar_digest(jobs[i].msg, jobs[i].msg_len, jobs[i].digest); }
-    else if (k > 1) { if (sha512_mb16_available()) sha512_weights_x16(pj, k); else { sha512_weights_x8(pj, k < 8 ? k : 8); if (k > 8) sha512_weights_x8(pj + 8, k - 8); } }
+    if (k) sha512_many(pj, k);
     for (int i = 0; i < k; i++) { memcpy(ss[i]->digest, jobs[i].digest, 64); ss[i]->state = S_HASHED; }
     ready.erase(ready.begin(), ready.begin() + count);
     if (k) { W.hash_groups++; W.hash_msgs += k; }
@@ -248,7 +244,7 @@ struct Run {
 extern "C" {
 
 int avrf_pool_create(int suite, int device, int kind, int n_slots, int n_lanes, int lane_depth, int n_threads, int hash_group, avrf_pool **out) {
-  if (!out || suite < 0 || suite >= AVRF_N_SUITES || (kind != 1 && kind != 2) || n_slots < 1 || n_slots > 4096 || n_lanes < 1 || n_lanes > 64 ||
+  if (!out || suite < 0 || suite >= AVRF_N_SUITES || (kind != Thin && kind != Pedersen) || n_slots < 1 || n_slots > 4096 || n_lanes < 1 || n_lanes > 64 ||
       lane_depth < 0 || lane_depth > 64 || n_threads < 1 || n_threads > 64 || hash_group < 0 || hash_group > 16) return AVRF_ERR_BAD_ARG;
   *out = nullptr;
   if (n_threads > n_slots) n_threads = n_slots;
@@ -332,7 +328,7 @@ int avrf_pool_submit_wire(avrf_pool *P, size_t n, const uint8_t *pks, const uint
 }
 static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
                        const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate) {
-  if (!P || !ticket || (n && (!proofs || !io_counts || !ad_lens)) || (n && P->kind == 1 && !pks_xy)) return AVRF_ERR_BAD_ARG;
+  if (!P || !ticket || (n && (!proofs || !io_counts || !ad_lens)) || (n && kind_facts(P->kind).pk && !pks_xy)) return AVRF_ERR_BAD_ARG;
   std::unique_lock<std::mutex> lk(P->m);
   if (P->cycling) return AVRF_ERR_BAD_ARG;
   for (;;) {

@@ -165,6 +165,28 @@ def test_partial_requires_fresh_challenges():
     st, _ = eng.challenges(bad)
     assert st == 2
     assert nat.lib().avrf_thin_batch_partial(eng.ctx._h, nat._u8(seed), C.c_uint64(0), out) == nat.ERR_BAD_ARG
+    # the same rule for pedersen::BatchVerifier's pair of calls
+    from ark_vrf_amd.dist import shard_pedersen_batch
+    bp = orc.gen_batch(0, 1, 64)
+    shp = shard_pedersen_batch(bp, 0, 64)
+    st, c = eng.ped_challenges(shp)
+    assert st == 0
+    seed = eng.ped_weight_seed(0, c, b"".join(bp["proofs"][256 * j + 192: 256 * j + 256] for j in range(64)))
+    eng.ped_partial(seed, 0)                                                   # fine
+    npb = nat.Batch(64, bp["ios_xy"], bp["io_counts"], bp["ads"], bp["ad_lens"], proofs=bp["proofs"])
+    assert eng.ctx.pedersen_batch_stage(npb) == 0                              # a second staging: challenges are stale
+    assert nat.lib().avrf_pedersen_batch_partial(eng.ctx._h, nat._u8(seed), C.c_uint64(0), out) == nat.ERR_BAD_ARG
+    assert eng.ped_challenges(shp)[0] == 0
+    eng.ped_partial(seed, 0)                                                   # legal again behind its own challenges
+    # sponge transcript (suite 5): no seed to hand to the shards -- the seed and both partial calls refuse, challenges or not
+    e5 = GpuEngine(nat.Context(5))
+    b5, p5 = orc.gen_batch(5, 0, 16), orc.gen_batch(5, 1, 16)
+    st, c5 = e5.challenges(shard_thin_batch(b5, 0, 16))
+    assert st == 0
+    assert nat.lib().avrf_batch_weight_seed(5, 0, C.c_size_t(16), nat._u8(c5), nat._u8(bytes(32 * 16)), out) == nat.ERR_BAD_ARG
+    assert nat.lib().avrf_thin_batch_partial(e5.ctx._h, nat._u8(seed), C.c_uint64(0), out) == nat.ERR_BAD_ARG
+    assert e5.ped_challenges(shard_pedersen_batch(p5, 0, 16))[0] == 0
+    assert nat.lib().avrf_pedersen_batch_partial(e5.ctx._h, nat._u8(seed), C.c_uint64(0), out) == nat.ERR_BAD_ARG
 
 
 _RCCL_SCRIPT = r"""

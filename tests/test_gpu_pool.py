@@ -240,3 +240,44 @@ def test_pool_wire_ingest(nat, kind):
         assert [pool.wait(t) for t in tk] == [0, 1, 0]
     finally:
         pool.close()
+
+
+@pytest.mark.parametrize("kind", [0, 1])
+def test_pool_wire_ingest_host_weights(nat, golden_dir, kind):
+    """avrf_pool_submit_wire on a suite whose weight transcript absorbs the responses on the host (5, Shake128Transcript): the wire
+    staging takes them from behind the proof's compressed points.  The 7 reference vectors three times, the middle batch with a
+    flipped response: verdicts 0 / 1 / 0, those of the one-call wire verifier, and the same again from the slots' resident state."""
+    import ctypes as C
+    import json
+    import os
+    suite = 5
+    load = lambda k: json.load(open(os.path.join(golden_dir, f"bandersnatch_shake128_ell2_{k}.json")))
+    th, pe = load("thin"), load("pedersen")
+    pks = b"".join(bytes.fromhex(v["pk"]) for v in th)
+    ios = b"".join(bytes.fromhex(v["h"] + v["gamma"]) for v in th)
+    ads = [bytes.fromhex(v["ad"]) for v in th]
+    if kind == 0:
+        proofs = [bytes.fromhex(v["proof_r"] + v["proof_s"]) for v in th]
+    else:
+        proofs = [bytes.fromhex(v["proof_pk_com"] + v["proof_r"] + v["proof_ok"] + v["proof_s"] + v["proof_sb"]) for v in pe]
+    at = len(proofs[3]) - 20                                            # inside the last response scalar (s / sb) of item 3
+    tam = proofs[:3] + [proofs[3][:at] + bytes([proofs[3][at] ^ 1]) + proofs[3][at + 1:]] + proofs[4:]
+    wire = lambda pr: nat.Batch(7, ios, [1] * 7, b"".join(ads), [len(a) for a in ads], pks_xy=(pks if kind == 0 else None), proofs=b"".join(pr))
+    batches = [wire(proofs), wire(tam), wire(proofs)]
+    c = nat.Context(suite)
+    one_call = []
+    for b in batches:
+        if kind == 0:
+            one_call.append(nat.lib().avrf_thin_batch_verify_wire(c._h, C.c_size_t(7), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, 1))
+        else:
+            one_call.append(nat.lib().avrf_pedersen_batch_verify_wire(c._h, C.c_size_t(7), b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, 1))
+    c.close()
+    assert one_call == [0, 1, 0]
+    pool = nat.Pool(suite, kind=kind + 1, slots=3, lanes=2, threads=2, hash_group=8)
+    try:
+        tk = [pool.submit_wire(b, validate=1) for b in batches]
+        assert [pool.wait(t) for t in tk] == one_call
+        tk = [pool.resubmit(t, from_host=False) for t in tk]
+        assert [pool.wait(t) for t in tk] == one_call
+    finally:
+        pool.close()

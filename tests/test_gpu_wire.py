@@ -76,6 +76,76 @@ def test_thin_tiny_pedersen_vectors_wire(ctxs, golden_dir, suite, validate):
     assert st[:6] == [0] * 6 and st[6] == (2 if validate else 1)
 
 
+HOST_WEIGHT_NAMES = {5: "bandersnatch_shake128_ell2", 6: "testing_sha-256_tai"}
+
+
+@pytest.fixture(scope="module")
+def host_weight_vectors(golden_dir):
+    """The 7 reference vectors of the two suites whose weight stream the host squeezes (Shake128Transcript, HashTranscript<Sha256>):
+    wire items, and the same items as typed points."""
+    from helpers import proof_xy, xy
+    out = {}
+    for suite, name in HOST_WEIGHT_NAMES.items():
+        load = lambda k: json.load(open(os.path.join(golden_dir, f"{name}_{k}.json")))
+        th, pe = load("thin"), load("pedersen")
+        pks = [bytes.fromhex(v["pk"]) for v in th]
+        ios = [[(bytes.fromhex(v["h"]), bytes.fromhex(v["gamma"]))] for v in th]
+        ads = [bytes.fromhex(v["ad"]) for v in th]
+        tp = [bytes.fromhex(v["proof_r"] + v["proof_s"]) for v in th]
+        pp = [bytes.fromhex(v["proof_pk_com"] + v["proof_r"] + v["proof_ok"] + v["proof_s"] + v["proof_sb"]) for v in pe]
+        assert all(len(p) == 64 for p in tp) and all(len(p) == 160 for p in pp)
+        bad_y = next(k.to_bytes(32, "little") for k in range(2, 300) if orc.point_decompress(suite, k.to_bytes(32, "little"))[0] != 0)
+        out[suite] = dict(pks=pks, ios=ios, ads=ads, tp=tp, pp=pp, bad_y=bad_y, pks_xy=[xy(suite, p) for p in pks],
+                          ios_xy=[[(xy(suite, i), xy(suite, o))] for it in ios for i, o in it],
+                          tp_xy=[proof_xy(suite, p, 0) for p in tp], pp_xy=[proof_xy(suite, p, 1) for p in pp])
+    return out
+
+
+@pytest.mark.parametrize("suite", [5, 6])
+@pytest.mark.parametrize("validate", [0, 1])
+def test_batch_verify_wire_host_weight_suites(host_weight_vectors, suite, validate):
+    """avrf_{thin,pedersen}_batch_verify_wire on the suites whose weight transcript absorbs the responses on the host: the staging takes
+    them from the WIRE proof (behind its 1 / 3 compressed points), not from offset 64 / 192 of the x || y proof.  Valid vectors 0; one
+    flipped byte in s (Thin), in s and in sb (Pedersen) VerificationFailure; an undecodable y in a proof point InvalidData; and every
+    verdict is the one avrf_*_batch_verify gives on the same items as typed points (the point that does not decode: as the off-curve
+    (0, y) under the context's on-curve check, which is what the typed-point entry has for Validate)."""
+    from ark_vrf_amd import _native as nat
+    v = host_weight_vectors[suite]
+    c = nat.Context(suite)
+    one = [1] * 7
+    flip = lambda p, at: p[:at] + bytes([p[at] ^ 1]) + p[at + 1:]
+
+    def thin(tp, tp_xy, level=0):
+        got = _call("avrf_thin_batch_verify_wire", c, 7, v["pks"], v["ios"], one, v["ads"], tp, validate, False)[0]
+        c.set_validation(level)
+        typed = c.thin_batch_verify(v["pks_xy"], v["ios_xy"], v["ads"], tp_xy)
+        c.set_validation(0)
+        assert got == typed
+        return got
+
+    def ped(pp, pp_xy, level=0):
+        got = _call("avrf_pedersen_batch_verify_wire", c, 7, None, v["ios"], one, v["ads"], pp, validate, False)[0]
+        c.set_validation(level)
+        typed = c.pedersen_batch_verify(v["ios_xy"], v["ads"], pp_xy)
+        c.set_validation(0)
+        assert got == typed
+        return got
+    try:
+        assert thin(v["tp"], v["tp_xy"]) == 0
+        assert ped(v["pp"], v["pp_xy"]) == 0
+        k = 4                                                                   # wire: R(32) || s; x || y: R(64) || s
+        assert thin(v["tp"][:k] + [flip(v["tp"][k], 32 + 9)] + v["tp"][k + 1:], v["tp_xy"][:k] + [flip(v["tp_xy"][k], 64 + 9)] + v["tp_xy"][k + 1:]) == 1
+        for at in (5, 32 + 7):                                                  # wire: 3 points(96) || s || sb; x || y: 3 points(192) || s || sb
+            assert ped(v["pp"][:k] + [flip(v["pp"][k], 96 + at)] + v["pp"][k + 1:], v["pp_xy"][:k] + [flip(v["pp_xy"][k], 192 + at)] + v["pp_xy"][k + 1:]) == 1
+        off_curve = bytes(32) + v["bad_y"]
+        assert thin([v["bad_y"] + v["tp"][0][32:]] + v["tp"][1:], [off_curve + v["tp_xy"][0][64:]] + v["tp_xy"][1:], level=1) == 2
+        for p in range(3):
+            assert ped(v["pp"][:6] + [v["pp"][6][:32 * p] + v["bad_y"] + v["pp"][6][32 * p + 32:]],
+                       v["pp_xy"][:6] + [v["pp_xy"][6][:64 * p] + off_curve + v["pp_xy"][6][64 * p + 64:]], level=1) == 2
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("suite", [0, 1])
 def test_torsion_points(ctxs, golden_dir, suite):
     """Points with a torsion component, P' = P + (0, -1) = (-x, -y): on the curve, outside the prime-order subgroup
