@@ -127,7 +127,8 @@ template <class F> AVRF_DI fuF<F> fu_carry(const fuF<F> &a) {
 }
 
 // the same pass for sums of NON-NEGATIVE limbs that need all 32 bits (B + 5 A < 6 * 2^29): unsigned arithmetic and logical shifts
-// for limbs 0 .. L-2 (a signed int32 would overflow -- undefined behaviour, however the hardware wraps); the top limb stays signed
+// for limbs 0 .. L-2 (a signed int32 would overflow -- undefined behaviour, however the hardware wraps); the top limb stays signed.
+// The carry is at most 5 here: limbs in [0, 2^W + 4], both ends reached (tools/fpu_model.py bounds the next product's operand by 2^W + 4)
 template <class F> AVRF_DI fuF<F> fu_carry_u(const uint32_t (&a)[UL<F>::L - 1], int32_t top) {
   using U = UL<F>;
   fuF<F> r;
@@ -137,7 +138,7 @@ template <class F> AVRF_DI fuF<F> fu_carry_u(const uint32_t (&a)[UL<F>::L - 1], 
   r.v[U::L - 1] = top + (int32_t)(a[U::L - 2] >> U::W);
   return r;
 }
-// 5 a for a with limbs 0 .. L-2 in [0, 2^W + 4) (a product's output, or carried), carried to limbs in [0, 2^W + 4)
+// 5 a for a with limbs 0 .. L-2 in [0, 2^W + 4) (a product's output, or carried), carried to limbs in [0, 2^W + 4] (2^W + 4 included)
 template <class F> AVRF_DI fuF<F> fu_times5(const fuF<F> &a) {
   constexpr int L = UL<F>::L;
   uint32_t t[L - 1];

@@ -99,7 +99,7 @@ template <class S> AVRF_DI te_ext teu4_to_ext(const teu4<S> &p) {
   using Fq = typename S::Fq;
   te_ext r; fu_to_packed<Fq>(r.x.v, p.x); fu_to_packed<Fq>(r.y.v, p.y); fu_to_packed<Fq>(r.t.v, p.t); fu_to_packed<Fq>(r.z.v, p.z); return r;
 }
-// B - a A for the closing products: carried to limbs in [0, 2^W + 4) where the sum can exceed 2^30
+// B - a A for the closing products: carried to limbs in [0, 2^W + 4] where the sum can exceed 2^30
 template <class S, int L> AVRF_DI fu<L> teu_h(const fu<L> &A, const fu<L> &B) {
   using Fq = typename S::Fq;
   if (S::A_KIND == 1) {

@@ -1,8 +1,9 @@
 """tools/fpu_model.py: the exact-integer model of the unsaturated-limb arithmetic the bucket-accumulation kernels run on
 (csrc/fpu.h, fpu_te.h, fpu_g1.h) -- no column of a multiplication leaves the signed 64-bit accumulator, the inductive value
 bounds hold in the worst case, mixed additions agree with the affine group laws, the exceptional cases of the XYZZ law are
-detected exactly.  The kernels are generated from the same layout constants (UL<F>, G1U<C>); the device-side agreement with the
-saturated form is tests/test_gpu_unsat_accumulate.py and tools/ubench_fpu.hip."""
+detected exactly.  The kernels are generated from the same layout constants (UL<F>, G1U<C>); the device-side agreement is
+tests/test_gpu_fpu.py (tools/fpu_probe.hip: every function of the layer on operands at the ends of these bounds, against Python
+integers) and, through the C ABI against the saturated form, tests/test_gpu_unsat_accumulate.py."""
 import os
 import subprocess
 import sys
