@@ -87,6 +87,44 @@ class Batch:
                    j(pks_xy), j(proofs), j(sks))
 
 
+class SharedBatch:
+    """A Thin batch over a table of shared points in the C-ABI layout (include/avrf.h avrf_thin_batch_stage_shared): shared_xy
+    n_shared x 64, pk_index one row per item, input_index one row per I/O pair (item-major), outputs_xy one point per pair."""
+
+    def __init__(self, n, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs):
+        self.n = n
+        self.n_shared = len(shared_xy if isinstance(shared_xy, C.Array) else bytes(shared_xy)) // 64
+        self.shared_xy, self.outputs_xy, self.ads, self.proofs = _u8(shared_xy), _u8(outputs_xy), _u8(ads), _u8(proofs)
+        self.pk_index, self.input_index, self.io_counts, self.ad_lens = _u32(pk_index), _u32(input_index), _u32(io_counts), _u32(ad_lens)
+
+    def args(self):
+        return (C.c_size_t(self.n), C.c_size_t(self.n_shared), self.shared_xy, self.pk_index, self.input_index, self.outputs_xy,
+                self.io_counts, self.ads, self.ad_lens, self.proofs)
+
+
+def dedup_points(pks_xy, ios_xy):
+    """An expanded batch's points -> (shared_xy, pk_index, input_index, outputs_xy): the byte-wise distinct rows among the public
+    keys (n x 64) and the inputs (the first 64 of every 128 bytes of ios_xy), the row of every key and of every input, and the
+    outputs on their own.  shared_xy[pk_index[j]] is item j's key again, shared_xy[input_index[k]] pair k's input."""
+    import numpy as np
+    pks = np.frombuffer(bytes(pks_xy), dtype=np.uint8).reshape(-1, 64)
+    ios = np.frombuffer(bytes(ios_xy), dtype=np.uint8).reshape(-1, 128)
+    pts = np.concatenate([pks, ios[:, :64]], axis=0)
+    if not len(pts):
+        return b"", [], [], b""
+    rows, inverse = np.unique(pts, axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    return (rows.tobytes(), [int(i) for i in inverse[: len(pks)]], [int(i) for i in inverse[len(pks):]],
+            np.ascontiguousarray(ios[:, 64:]).tobytes())
+
+
+def thin_shared_n_terms(n, tot_io, n_shared):
+    """Terms of the MSM a shared-table Thin batch builds (host arithmetic; no device needed)."""
+    f = lib().avrf_thin_shared_n_terms
+    f.restype = C.c_size_t
+    return f(C.c_size_t(n), C.c_size_t(tot_io), C.c_size_t(n_shared))
+
+
 class Context:
     """One engine instance = suite + HIP stream + device workspace (avrf_ctx)."""
 
@@ -147,6 +185,10 @@ class Context:
 
     def thin_batch_stage(self, b):
         return lib().avrf_thin_batch_stage(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
+
+    def thin_batch_stage_shared(self, b):
+        """b: SharedBatch.  Staged for thin_batch_run / batch_run_begin .. / last_terms like a plain batch."""
+        return lib().avrf_thin_batch_stage_shared(self._h, *b.args())
 
     def thin_batch_run(self):
         return lib().avrf_thin_batch_run(self._h)
@@ -337,6 +379,18 @@ class PinnedBatch:
             pass
 
 
+class PinnedSharedBatch(PinnedBatch):
+    """A SharedBatch whose buffers live in page-locked host memory."""
+
+    def __init__(self, n, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs):
+        self.n, self.n_shared = n, len(bytes(shared_xy)) // 64
+        self._ptrs = []
+        self.shared_xy, self.outputs_xy, self.ads, self.proofs = (self._pin(bytes(v)) for v in (shared_xy, outputs_xy, ads, proofs))
+        self.pk_index, self.input_index, self.io_counts, self.ad_lens = (self._pin(bytes(_u32(v))) for v in (pk_index, input_index, io_counts, ad_lens))
+
+    args = SharedBatch.args
+
+
 class Pool:
     """avrf_pool: many BatchVerifier::verify jobs in flight on one device (include/avrf.h).  kind 1 thin, 2 pedersen."""
 
@@ -369,6 +423,15 @@ class Pool:
         st = lib().avrf_pool_submit(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, C.byref(t))
         if st != OK:
             raise AvrfError(f"avrf_pool_submit -> {st}")
+        self._keep[t.value] = b
+        return t.value
+
+    def submit_shared(self, b):
+        """b: SharedBatch (a kind 1 pool).  Returns the ticket."""
+        t = C.c_uint64(0)
+        st = lib().avrf_pool_submit_shared(self._h, *b.args(), C.byref(t))
+        if st != OK:
+            raise AvrfError(f"avrf_pool_submit_shared -> {st}")
         self._keep[t.value] = b
         return t.value
 

@@ -15,9 +15,11 @@
 #include <thread>
 #include "proto_dev.h"
 #include "vrf_batch.h"
+#include "thin_shared.h"
 #include "suite_dispatch.h"
 #include <chrono>
 #include <optional>
+#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -78,6 +80,14 @@ static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status) {
   uint32_t *fl = c->d_flags.as<uint32_t>();
   const uint32_t n = (uint32_t)c->n;
   const KindFacts &k = kind_facts(kind);
+  if (c->n_shared) {                                                   // a shared table: every row once, not once per reference; the outputs where they were gathered
+    // (batch verifiers only: the per-item calls, which want d_rec_status, restage through ctx_stage and so never see a shared staging)
+    assert(!d_rec_status);
+    AVRF_SINGLE(c->suite, validate_xy(c->d_table.as<uint8_t>(), 64, 1, (uint32_t)c->n_shared, c->validate, fl, nullptr, c->stream));
+    AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>() + 64, 128, 1, (uint32_t)c->tot_io, c->validate, fl, nullptr, c->stream));
+    AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, nullptr, c->stream));
+    return;
+  }
   if (k.pk && c->d_pks.p) AVRF_SINGLE(c->suite, validate_xy(c->d_pks.as<uint8_t>(), 64, 1, n, c->validate, fl, d_rec_status, c->stream));
   if (k.points) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, d_rec_status, c->stream));
   if (c->tot_io) {
@@ -276,6 +286,7 @@ void sha512_many(WeightJob *const *jobs, int k) {
 // d_scalars / d_pre / d_gpart of the context's lane for the staged batch's n_terms
 static int ensure_terms(avrf_ctx *c) {
   HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((c->n + 127) / 128) * 64 + 64));
+  if (c->n_shared) HIP_TRY(c->L->d_shared.ensure(shared_scratch_words(c->n + c->tot_io) * 4));
   return AVRF_OK;
 }
 
@@ -287,7 +298,7 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
   if (n && (!io_counts || !ad_lens)) return AVRF_ERR_BAD_ARG;
   if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->stage_gen++; c->wire_pending = false;
+  c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->n_shared = 0; c->stage_gen++; c->wire_pending = false;
   if (n == 0) { c->staged_kind = kind; return AVRF_OK; }
   HIP_TRY(c->h_io.ensure((n + 1) * 8));
   uint32_t *io_off = c->h_io.as<uint32_t>(), *ad_off = io_off + (n + 1);
@@ -313,7 +324,7 @@ static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t str
     c->h_resp.resize(n * rsz);
     for (size_t j = 0; j < n; j++) memcpy(&c->h_resp[rsz * j], resp + stride * j, rsz);
   }
-  c->n_terms = n_terms(kind, n, c->tot_io);
+  c->n_terms = c->n_shared ? thin_shared_n_terms(n, c->tot_io, c->n_shared) : n_terms(kind, n, c->tot_io);
   HIP_TRY(c->d_c.ensure(n * 16)); HIP_TRY(c->h_c.ensure(n * 16));
   HIP_TRY(c->d_z.ensure(z_bytes(kind, n, c->tot_io)));
   return c->lane_owner ? ensure_terms(c) : (int)AVRF_OK;
@@ -333,6 +344,45 @@ int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t
   }
   if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
   c->staged_kind = kind;
+  return AVRF_OK;
+}
+// Thin over a table of shared points (include/avrf.h; thin_shared.h): the table, the indices, the outputs and the proofs go up; the
+// device gathers the rows into the plain staged layout, converts each row once and sorts the references by row -- the host only checks
+// the indices.  What the staging leaves is reused by every run of it (resident reruns, the pool's resubmission without host sources).
+bool shared_indices_ok(size_t n, size_t n_shared, const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts) {
+  if (!n) return true;
+  if (!n_shared || n_shared > 0x0fffffffULL || n > 0x0fffffffULL || !pk_index || !io_counts) return false;
+  uint64_t a = 0; uint32_t over = 0;
+  for (size_t j = 0; j < n; j++) { over |= pk_index[j] >= n_shared; a += io_counts[j]; }
+  if (over || a > 0x1fffffffULL || (a && (!input_index || !outputs_xy))) return false;
+  for (size_t k = 0; k < a; k++) over |= input_index[k] >= n_shared;
+  return !over;
+}
+int ctx_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
+                     const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait) {
+  const bool args_ok = !n || (shared_xy && proofs && shared_indices_ok(n, n_shared, pk_index, input_index, outputs_xy, io_counts));   // (refused before anything is staged)
+  if (int e = stage_open(c, Thin, n, args_ok, outputs_xy, false, io_counts, ads, ad_lens)) return e;
+  if (n == 0) return AVRF_OK;
+  const size_t a = c->tot_io, nc = n + a;
+  HIP_TRY(c->d_table.ensure(n_shared * 64)); HIP_TRY(c->d_table_idx.ensure(nc * 4)); HIP_TRY(c->d_table_outs.ensure(a * 64 + 16));
+  HIP_TRY(c->d_table_rows.ensure(n_shared * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(n_shared, nc) * 4));
+  HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(c->d_proofs.ensure(n * 96));
+  HIP_TRY(hipMemcpyAsync(c->d_table.p, shared_xy, n_shared * 64, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_table_idx.p, pk_index, n * 4, hipMemcpyHostToDevice, c->stream));
+  if (a) {
+    HIP_TRY(hipMemcpyAsync(c->d_table_idx.as<uint32_t>() + n, input_index, a * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_table_outs.p, outputs_xy, a * 64, hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_proofs.p, proofs, n * 96, hipMemcpyHostToDevice, c->stream));
+  uint32_t *plan = c->d_table_plan.as<uint32_t>(), *flag = shared_plan_flag(plan, n_shared, nc);
+  HIP_TRY(hipMemsetAsync(flag, 0, 4, c->stream));
+  HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)n_shared, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)n, (uint32_t)a,
+                      c->d_pks.as<uint8_t>(), c->d_ios.as<uint8_t>(), plan, c->stream));
+  HIP_TRY(AVRF_SHARED(c->suite, rows_pre(c->d_table.as<uint8_t>(), (uint32_t)n_shared, c->d_table_rows.as<te_pre_raw>(), flag, c->stream)));
+  c->n_shared = n_shared;
+  if (int e = stage_verifier(c, Thin, proofs + kind_facts(Thin).resp_at_xy(), 96)) { c->n_shared = 0; return e; }
+  if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
+  c->staged_kind = Thin;
   return AVRF_OK;
 }
 // The wire flavour of the batch verifiers' staging (src/thin.rs:78-94, src/pedersen.rs:106-134 deserialise, then
@@ -384,6 +434,12 @@ int avrf_pedersen_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *ios, co
   if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   return avrf::ctx_stage_wire(c, Pedersen, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, true);
 }
+
+int avrf_thin_batch_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
+                                 const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
+  return ctx_stage_shared(c, n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs, true);
+}
+size_t avrf_thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared) { return thin_shared_n_terms(n, tot_io, n_shared); }
 
 int avrf_thin_batch_stage(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
@@ -464,12 +520,21 @@ static Seed64 seed_of(const uint8_t digest[64]) {
   return seed;
 }
 // the kind's prepare kernel (challenges into d_c, the terms kernel's other inputs into d_z, the checks into d_flags) and terms kernel
+// The run's check flags start clear -- or, over a shared table, from what staging found in it (a non-canonical coordinate in any row)
+static hipError_t reset_flags(avrf_ctx *c) {
+  if (!c->n_shared) return hipMemsetAsync(c->d_flags.p, 0, 4, c->stream);
+  return hipMemcpyAsync(c->d_flags.p, shared_plan_flag(c->d_table_plan.as<uint32_t>(), c->n_shared, c->n + c->tot_io), 4, hipMemcpyDeviceToDevice, c->stream);
+}
 static void launch_prepare(avrf_ctx *c, int kind, const BatchDev &b) {
   if (kind == Thin) AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
   else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
 }
 static void launch_terms(avrf_ctx *c, int kind, const BatchDev &b, const Seed64 &seed, uint64_t first, uint32_t *d_scalars) {
-  if (kind == Thin) AVRF_BATCH(c->suite, thin_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), d_scalars,
+  if (kind == Thin && c->n_shared)
+    AVRF_SHARED(c->suite, thin_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(),
+                                     shared_plan_view(c->d_table_plan.as<uint32_t>(), c->d_table_rows.as<te_pre_raw>(), c->n_shared, c->n + c->tot_io),
+                                     (uint32_t)c->tot_io, c->L->d_shared.as<uint32_t>(), d_scalars, c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), c->stream));
+  else if (kind == Thin) AVRF_BATCH(c->suite, thin_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), d_scalars,
                                                     c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
   else AVRF_BATCH(c->suite, ped_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), d_scalars,
                                       c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
@@ -483,7 +548,7 @@ int batch_begin(avrf_ctx *c, int kind) {
   c->run_t0 = now_us();
   const size_t n = c->n;
   BatchDev b = batch_of(c);
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+  HIP_TRY(reset_flags(c));
   validate_staged(c, kind, nullptr);
   const bool host_weights = suite_host_weights(c->suite);
   // the weight transcript's message, prefix || records: the prepare kernel writes the records, one copy brings them back
@@ -699,7 +764,7 @@ static int batch_challenges(avrf_ctx *c, int kind, uint8_t *c_out) {
   if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   if (c->n == 0) return AVRF_OK;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+  HIP_TRY(reset_flags(c));
   validate_staged(c, kind, nullptr);
   launch_prepare(c, kind, batch_of(c));
   HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));

@@ -47,6 +47,7 @@ struct Lane : LaneStream {
   int queued = 0;                 // chains enqueued and not yet collected (pool.hip)
   MsmWorkspace ws;
   DevBuf d_scalars, d_pre, d_gpart;
+  DevBuf d_shared;                // a shared-table Thin batch: the row scalars' contributions and partial sums of the chain being built (thin_shared.h)
 };
 
 }  // namespace avrf
@@ -65,6 +66,10 @@ struct avrf_ctx {
   int staged_kind = 0;            // 0 none, else the ProofKind staged (proof_kind.h)
   size_t n = 0, tot_io = 0, n_terms = 0;
   avrf::DevBuf d_pks, d_ios, d_io_off, d_ads, d_ad_off, d_proofs, d_sks;
+  // a Thin batch staged over a table of shared points (avrf_thin_batch_stage_shared; thin_shared.h): n_shared rows, 0 for a plain staging.
+  // d_pks / d_ios hold the gathered rows, so that the prepare kernel runs as on a plain batch; the terms come from the table and the plan.
+  size_t n_shared = 0;
+  avrf::DevBuf d_table, d_table_idx, d_table_outs, d_table_rows, d_table_plan;
   std::vector<uint8_t> h_resp;    // host copy of the response scalars (s [, sb]) for the weight transcript (sponge transcripts only)
   avrf::DevBuf d_rec; avrf::PinBuf h_msg;     // counter-mode transcripts: the records written by the prepare kernel, and prefix || records on the host
   size_t h_msg_len = 0;
@@ -90,6 +95,11 @@ struct WeightJob;
 int ctx_create(int suite, int device, bool lane_owner, avrf_ctx **out);
 int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
               const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait);
+// Thin over a table of shared points (include/avrf.h); shared_indices_ok is the host's index check (every index < n_shared; outputs present), which
+// ctx_stage_shared makes itself and the pool makes on the submitting thread as well
+bool shared_indices_ok(size_t n, size_t n_shared, const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts);
+int ctx_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
+                     const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait);
 int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                    const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait);   // serialize_compressed bytes in, decompressed on the device
 int batch_begin(avrf_ctx *c, int kind);                               // validation + prepare kernel + copies back enqueued on c->stream

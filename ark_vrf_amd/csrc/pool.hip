@@ -50,6 +50,8 @@ struct Slot {
   size_t n = 0;
   const uint8_t *pks = nullptr, *ios = nullptr, *ads = nullptr, *proofs = nullptr;
   const uint32_t *io_counts = nullptr, *ad_lens = nullptr;
+  // the host sources are a table of shared points (avrf_pool_submit_shared): pks = the table, ios = the outputs, and the indices into the table
+  bool shared = false; size_t n_shared = 0; const uint32_t *pk_index = nullptr, *input_index = nullptr;
   uint8_t digest[64];
   // the event, the record, then the context: it has no stream or workspace of its own and is detached from the pool's lane before it dies
   ~Slot() {
@@ -129,7 +131,8 @@ struct Run {
     if (!S.from_host && S.resident_invalid) { W.cpu_us[0] += thread_cpu_us() - t0; done(S, AVRF_INVALID_DATA); return; }
     if (S.from_host) {
       S.resident_invalid = false;
-      if (S.wire) st = guarded([&] { return ctx_stage_wire(c, P->kind, S.n, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, S.validate, /*wait=*/false); });
+      if (S.shared) st = guarded([&] { return ctx_stage_shared(c, S.n, S.n_shared, S.pks, S.pk_index, S.input_index, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
+      else if (S.wire) st = guarded([&] { return ctx_stage_wire(c, P->kind, S.n, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, S.validate, /*wait=*/false); });
       else st = guarded([&] { return ctx_stage(c, P->kind, S.n, nullptr, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
       S.has_batch = st == AVRF_OK;
     }
@@ -313,8 +316,9 @@ int avrf_pool_set_validation(avrf_pool *P, int level) {
   return AVRF_OK;
 }
 
+struct SharedSource { size_t n_shared; const uint32_t *pk_index, *input_index; };   // pool_submit: pks_xy is the table, ios_xy the outputs
 static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
-                       const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate);
+                       const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate, const SharedSource *shared = nullptr);
 int avrf_pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
                      const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket) {
   return pool_submit(P, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, ticket, false, 0);
@@ -326,8 +330,17 @@ int avrf_pool_submit_wire(avrf_pool *P, size_t n, const uint8_t *pks, const uint
                           const uint32_t *ad_lens, const uint8_t *proofs, int validate, uint64_t *ticket) {
   return pool_submit(P, n, pks, ios, io_counts, ads, ad_lens, proofs, ticket, true, validate);
 }
+// the same job over a table of shared points (include/avrf.h avrf_thin_batch_stage_shared); the indices are checked here, on the calling
+// thread, before a ticket exists
+int avrf_pool_submit_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
+                            const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                            uint64_t *ticket) {
+  if (!P || P->kind != Thin || !shared_indices_ok(n, n_shared, pk_index, input_index, outputs_xy, io_counts)) return AVRF_ERR_BAD_ARG;
+  const SharedSource src{n_shared, pk_index, input_index};
+  return pool_submit(P, n, shared_xy, outputs_xy, io_counts, ads, ad_lens, proofs, ticket, false, 0, &src);
+}
 static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
-                       const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate) {
+                       const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate, const SharedSource *shared) {
   if (!P || !ticket || (n && (!proofs || !io_counts || !ad_lens)) || (n && kind_facts(P->kind).pk && !pks_xy)) return AVRF_ERR_BAD_ARG;
   std::unique_lock<std::mutex> lk(P->m);
   if (P->cycling) return AVRF_ERR_BAD_ARG;
@@ -342,6 +355,7 @@ static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint
     if (best >= 0) {
       Slot &S = P->slots[best];
       S.n = n; S.pks = pks_xy; S.ios = ios_xy; S.io_counts = io_counts; S.ads = ads; S.ad_lens = ad_lens; S.proofs = proofs;
+      S.shared = shared != nullptr; S.n_shared = shared ? shared->n_shared : 0; S.pk_index = shared ? shared->pk_index : nullptr; S.input_index = shared ? shared->input_index : nullptr;
       S.from_host = true; S.wire = wire; S.validate = validate; S.resident_invalid = false; S.ticket = P->next_ticket++; S.status = 0;
       S.state = S_SUBMITTED;
       *ticket = S.ticket;

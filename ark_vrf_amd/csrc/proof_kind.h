@@ -27,6 +27,8 @@ constexpr KindFacts KIND_FACTS[4] = {{false, 0, 0, 0, 0}, {true, 1, 32, 32, 16},
 constexpr const KindFacts &kind_facts(int kind) { return KIND_FACTS[kind]; }
 // terms of the batch verifier's MSM (src/thin.rs:282-317: 2 per item, 2 per I/O pair, G; src/pedersen.rs:369-418: 5 per item, G, B)
 constexpr size_t n_terms(int kind, size_t n, size_t tot_io) { return kind == Thin ? 2 * n + 2 * tot_io + 1 : 5 * n + 2; }
+// Thin over a table of n_shared points (include/avrf.h avrf_thin_batch_stage_shared): R per item, O per I/O pair, one term per row, G
+constexpr size_t thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared) { return n + tot_io + n_shared + 1; }
 // what the prepare kernel leaves the terms kernel besides the challenges: Thin z_{j,i} (16 bytes per I/O pair), Pedersen the merged pair
 constexpr size_t z_bytes(int kind, size_t n, size_t tot_io) { return kind == Thin ? tot_io * 16 + 16 : n * 128; }
 

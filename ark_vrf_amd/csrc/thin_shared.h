@@ -1,0 +1,64 @@
+// thin_shared.h -- thin::BatchVerifier over a table of shared points (avrf_thin_batch_stage_shared, include/avrf.h).
+//
+// The reference merges ONE shared base into a single MSM term: the generator, g -= w s z0 (src/thin.rs:303,316-317).  A batch
+// whose public keys and inputs come from a table of T points gets the same treatment for every row: the scalars of all the
+// terms that share a base are added in Fr, which leaves sum scalar * base -- the group element the verdict tests -- unchanged
+// and the MSM at n + tot_io + T + 1 terms instead of 2 n + 2 tot_io + 1.
+//
+//   staging (once per staged batch, shared_plan + rows_pre):
+//     gather    the table rows into the plain staged layout (d_pks, d_ios with the outputs beside their inputs), so that
+//               k_thin_prepare and its per-item checks run as they are; histogram of the references per row
+//     scan      row_off[T + 1]: where each row's contributions start in row order
+//     place     pos[C]: the slot of contribution t (item j's key: t = j; I/O pair k's input: t = n + k) in row order,
+//               slot_row[C]: the row a slot belongs to.  C = n + tot_io.  The order inside a row is whatever the atomics
+//               gave: Fr addition is exact, so it cannot change a result.
+//     rows_pre  every row once to te_pre (Montgomery x, y, k = d x y); canonical-range check of every row
+//   run (thin_terms): k_thin_terms_shared emits the R and O terms and stores the key / input scalars (Montgomery form) to
+//     contrib[pos[.]]; k_shared_lanes sums equal contiguous shares of SHARED_SHARE slots per lane -- rows inside a share are
+//     finished there, a row that crosses a share boundary leaves partials; k_shared_merge adds the partials of each such row
+//     (min(lanes, T) units, four per block, 256 threads on each cut row) and the generator term.  Three launches whatever the distribution of the references.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "msm.h"
+#include "suite_dispatch.h"
+
+namespace avrf {
+
+struct BatchDev;
+struct Seed64;
+
+enum { SHARED_SHARE = 8 };                                            // slots one lane of k_shared_lanes sums
+constexpr size_t shared_lanes(size_t n_contrib) { return (n_contrib + SHARED_SHARE - 1) / SHARED_SHARE; }
+// per-run scratch of a lane: contrib (8 words per slot), then per lane of k_shared_lanes head and tail partials (16 words) and the tail's row (1)
+constexpr size_t shared_scratch_words(size_t n_contrib) { return 8 * n_contrib + 17 * shared_lanes(n_contrib) + 16; }
+// the plan of a staging: cursor[T + 1] | row_off[T + 1] | pos[C] | slot_row[C] | range flag of the table
+constexpr size_t shared_plan_words(size_t n_shared, size_t n_contrib) { return 2 * (n_shared + 1) + 2 * n_contrib + 4; }
+
+struct SharedPlan {
+  const uint32_t *row_off, *pos, *slot_row;
+  const te_pre_raw *rows;          // n_shared precomputed bases
+  uint32_t n_shared, n_contrib;
+};
+
+// Gather + counting sort of a staging (suite-independent).  idx: pk_index (n) then input_index (tot_io); plan: shared_plan_words.
+// An index >= n_shared is the host's to refuse; the kernels clamp it so that no read leaves the table.
+// (a refused memset or launch comes back as its error, so that a failed plan is never reported as a good staging)
+hipError_t shared_plan(const uint8_t *d_table, uint32_t n_shared, const uint32_t *d_idx, const uint8_t *d_outputs, uint32_t n, uint32_t tot_io,
+                       uint8_t *d_pks, uint8_t *d_ios, uint32_t *d_plan, hipStream_t st);
+inline SharedPlan shared_plan_view(const uint32_t *d_plan, const te_pre_raw *d_rows, size_t n_shared, size_t n_contrib) {
+  const uint32_t *row_off = d_plan + (n_shared + 1);
+  return SharedPlan{row_off, row_off + (n_shared + 1), row_off + (n_shared + 1) + n_contrib, d_rows, (uint32_t)n_shared, (uint32_t)n_contrib};
+}
+inline uint32_t *shared_plan_flag(uint32_t *d_plan, size_t n_shared, size_t n_contrib) { return d_plan + 2 * (n_shared + 1) + 2 * n_contrib; }
+
+// Per-suite launch table (thin_shared.hip, built once per suite like vrf_batch.hip).
+template <class S> struct SharedOps {
+  static hipError_t rows_pre(const uint8_t *d_table, uint32_t n_shared, te_pre_raw *d_rows, uint32_t *d_flag, hipStream_t st);
+  // terms in the layout of include/avrf.h: (R_j, w_j) at j + io_off[j], (O_ji, w c z_i) behind it, row r at n + tot_io + r, (G, g) last
+  static void thin_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint32_t *d_z, const SharedPlan &p,
+                         uint32_t tot_io, uint32_t *d_scratch, uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, hipStream_t st);
+};
+#define AVRF_SHARED(suite, CALL) with_suite((suite), [&](auto tag_) { return SharedOps<typename decltype(tag_)::type>::CALL; })
+
+}  // namespace avrf

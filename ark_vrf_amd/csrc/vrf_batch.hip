@@ -9,6 +9,7 @@
 // 8 x u32 Montgomery form (fp256.h).
 #include "vrf_batch.h"
 #include "proto_dev.h"
+#include "batch_terms_dev.h"
 #include "suite_dispatch.h"
 
 // Built once per suite (-DAVRF_TU_SUITE=<id>: the kernels of that suite and the explicit instantiation of BatchOps<S>, which
@@ -82,16 +83,7 @@ k_thin_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint32_t *__restrict__ 
   if (f) atomicOr(flags, f);
 }
 
-AVRF_DI fp fp_from_u128(const uint32_t *w) {
-  fp a = fp_zero(); uint4 v = *reinterpret_cast<const uint4 *>(w);
-  a.v[0] = v.x; a.v[1] = v.y; a.v[2] = v.z; a.v[3] = v.w; return a;
-}
-template <class S> AVRF_DI void emit_term(uint32_t *scalars, te_pre *pre, uint32_t t, const fp &scalar_plain, const uint8_t *xy) {
-  using Fq = typename S::Fq;
-  fp_store(scalars + 8 * (size_t)t, scalar_plain);
-  fp x = fp_to_mont<Fq>(fp_load_le(xy)), y = fp_to_mont<Fq>(fp_load_le(xy + 32));
-  store_pre(pre + t, te_make_pre<S>(x, y));
-}
+// (fp_from_u128, emit_term: batch_terms_dev.h -- shared with k_thin_terms_shared of thin_shared.hip, which restates this kernel's per-item arithmetic)
 
 template <class S>
 __global__ void __launch_bounds__(128)

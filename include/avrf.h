@@ -148,6 +148,40 @@ int avrf_batch_run_begin(avrf_ctx *ctx);
 int avrf_batch_run_hash(avrf_ctx *ctx);
 int avrf_batch_run_end(avrf_ctx *ctx);
 
+/* ---- thin::BatchVerifier over a table of shared points.
+ * Block and seal verification by a known validator set: a few hundred to a few thousand distinct keys, a handful of distinct
+ * inputs.  The reference merges one shared base, the generator, into a single MSM term (src/thin.rs:303,316-317); here every
+ * base that several items share is merged the same way -- the scalars of a row's references are added in the scalar field on
+ * the device, which leaves sum scalar * base, and so the verdict, unchanged.  The MSM has n + tot_io + n_shared + 1 terms
+ * instead of 2 n + 2 tot_io + 1, and an item sends 2 indices instead of 128 bytes of key and input.
+ *
+ * shared_xy: n_shared x 64 (x || y).  pk_index[j] is the row that is item j's public key; input_index[k] the row that is the
+ * input of I/O pair k (k runs over sum(io_counts), item-major, as ios_xy does); outputs_xy: sum(io_counts) x 64; everything
+ * else as avrf_thin_batch_stage.  A row may be referenced any number of times, by keys and inputs alike, or not at all.
+ *
+ * A batch staged this way runs through every run entry point unchanged (avrf_thin_batch_run, avrf_batch_run_begin / _hash /
+ * _end, avrf_thin_batch_challenges / _partial, avrf_batch_last_terms; the pool's wait / resubmit / cycle), and its verdict is
+ * the one avrf_thin_batch_verify gives for the EXPANDED batch, every index replaced by its row: AVRF_INVALID_DATA for an
+ * identity key or I/O point (src/thin.rs:266-271), AVRF_OK for the empty batch.
+ *   checks    the identity check applies to REFERENCED rows only, the canonical-range check to every row; under
+ *             avrf_ctx_set_validation / avrf_pool_set_validation 1 or 2 the table is validated once per row (not once per
+ *             reference), the outputs and R as in a plain batch.
+ *   indices   an index >= n_shared (or n_shared == 0 with n > 0) is AVRF_ERR_BAD_ARG: nothing is staged, the context and
+ *             what it had staged stay usable.  avrf_pool_submit_shared checks the indices on the calling thread, before it
+ *             returns a ticket.  No kernel reads outside the table whatever the indices say.
+ *   terms     (avrf_batch_last_terms; this layout is ABI) for item j with io0 = io_counts[0] + .. + io_counts[j - 1]:
+ *             (R_j, w_j) at j + io0; (O_ji, w c z_i) at j + io0 + 1 + i; row r at n + tot_io + r with the scalar
+ *             sum of w c z0 over the items whose key is r  -  sum of w s z_i over the pairs whose input is r   (mod r_order),
+ *             0 for a row nothing refers to; (G, g) last.  avrf_thin_shared_n_terms = n + tot_io + n_shared + 1 (host
+ *             arithmetic only, no device needed).
+ * Measured (tools/shared_bench.py): 1 024 keys + 3 inputs, 65 536 items: 1.34 x the plain call resident and
+ * 1.30 x from page-locked host buffers.  USE THE PLAIN CALL WHEN NOTHING IS SHARED: with every point its own row the term count
+ * is the plain one and staging the table from the host costs a quarter of the throughput (0.74 x; resident runs 1.00 x). */
+int avrf_thin_batch_stage_shared(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared_xy,
+                                 const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs_xy,
+                                 const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs);
+size_t avrf_thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared);
+
 /* ---- Ownership of host buffers; page-locked memory (SURVEY.md 8b "Ownership").
  * Every entry point copies what it needs out of the caller's buffers before it returns, EXCEPT avrf_pool_submit (below), whose
  * copies are left in flight.  From ordinary (pageable) memory a copy to the device goes through the runtime's bounce buffers
@@ -204,6 +238,15 @@ int avrf_pool_submit(avrf_pool *pool, size_t n, const uint8_t *pks_xy, const uin
  * fails makes the verdict AVRF_INVALID_DATA.  Resubmission and the cycle mode work on such slots as on any other. */
 int avrf_pool_submit_wire(avrf_pool *pool, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts,
                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate, uint64_t *ticket);
+/* avrf_pool_submit_shared (kind 1 pools): the same job over a table of shared points, arguments and contract as
+ * avrf_thin_batch_stage_shared above.  All eight host buffers must stay untouched until the verdict is out: shared_xy, pk_index,
+ * input_index, outputs_xy, ads and proofs are copied asynchronously, io_counts and ad_lens are read when the batch is staged --
+ * and all eight again by every avrf_pool_resubmit with from_host = 1.  The indices, and a missing outputs_xy or input_index where
+ * there are I/O pairs, are refused here, before a ticket exists.  Resubmission and the cycle mode work on such slots as on any
+ * other: without host sources they reuse the gathered rows and the plan. */
+int avrf_pool_submit_shared(avrf_pool *pool, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index,
+                            const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts,
+                            const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket);
 int avrf_pool_wait(avrf_pool *pool, uint64_t ticket, int *status);
 int avrf_pool_resubmit(avrf_pool *pool, uint64_t ticket, int from_host, uint64_t *new_ticket);
 int avrf_pool_cycle(avrf_pool *pool, int from_host, uint64_t steps_block, double min_seconds, uint64_t max_steps, int expect_status,
