@@ -13,7 +13,8 @@
 //               slot_row[C]: the row a slot belongs to.  C = n + tot_io.  The order inside a row is whatever the atomics
 //               gave: Fr addition is exact, so it cannot change a result.
 //     rows_pre  every row once to te_pre (Montgomery x, y, k = d x y); canonical-range check of every row
-//   run (thin_terms): k_thin_terms_shared emits the R and O terms and stores the key / input scalars (Montgomery form) to
+//   run (thin_terms): k_thin_terms_shared calls thin_item (batch_terms_dev.h), the one statement of an item's arithmetic that
+//     k_thin_terms calls too; its sink emits the R and O terms and stores the key / input scalars (Montgomery form) to
 //     contrib[pos[.]]; k_shared_lanes sums equal contiguous shares of SHARED_SHARE slots per lane -- rows inside a share are
 //     finished there, a row that crosses a share boundary leaves partials; k_shared_merge adds the partials of each such row
 //     (min(lanes, T) units, four per block, 256 threads on each cut row) and the generator term.  Three launches whatever the distribution of the references.
@@ -41,7 +42,7 @@ struct SharedPlan {
   uint32_t n_shared, n_contrib;
 };
 
-// Gather + counting sort of a staging (suite-independent).  idx: pk_index (n) then input_index (tot_io); plan: shared_plan_words.
+// Gather + counting sort of a staging (suite-independent: shared_stage.hip).  idx: pk_index (n) then input_index (tot_io); plan: shared_plan_words.
 // An index >= n_shared is the host's to refuse; the kernels clamp it so that no read leaves the table.
 // (a refused memset or launch comes back as its error, so that a failed plan is never reported as a good staging)
 hipError_t shared_plan(const uint8_t *d_table, uint32_t n_shared, const uint32_t *d_idx, const uint8_t *d_outputs, uint32_t n, uint32_t tot_io,

@@ -1,118 +1,21 @@
 // thin_shared.hip -- the device side of thin::BatchVerifier over a table of shared points (thin_shared.h).
 //
-//   k_shared_gather / _scan / _place : staging -- the plain staged layout from the table, and the counting sort of the
-//                                      n + tot_io references by row (32-bit integer atomics on counters only)
 //   k_shared_pre                     : every table row once to te_pre, through the suite's own te_make_pre
-//   k_thin_terms_shared              : k_thin_terms (vrf_batch.hip; src/thin.rs:287-313) without the key and input terms:
-//                                      their scalars go to contrib[pos[.]] in Montgomery form
+//   k_thin_terms_shared              : thin_item (batch_terms_dev.h; src/thin.rs:287-313), as k_thin_terms of vrf_batch.hip: the R and
+//                                      output terms; the key and input scalars go to contrib[pos[.]] in Montgomery form
 //   k_shared_lanes / k_shared_merge  : the segmented sum of contrib in Fr -> the T row terms; the generator term (src/thin.rs:303,316-317)
 // One lane per item / reference / share; scalar-field sums in 8 x u32 Montgomery form (fp256.h).
+// (the staging -- k_shared_gather / _scan / _place, shared_plan -- knows no suite: shared_stage.hip)
 #include "thin_shared.h"
 #include "proto_dev.h"
 #include "batch_terms_dev.h"
 
 // Built once per suite (-DAVRF_TU_SUITE=<id>, csrc/Makefile): the suite's kernels and the explicit instantiation of SharedOps<S>,
-// which capi.hip reaches through AVRF_SHARED.  The suite-independent staging kernels live in suite 0's unit.
+// which capi.hip reaches through AVRF_SHARED.
 #ifndef AVRF_TU_SUITE
 #error "thin_shared.hip is built once per suite: -DAVRF_TU_SUITE=<id> (csrc/Makefile)"
 #endif
 namespace avrf {
-
-#if AVRF_TU_SUITE == 0
-// ---------------------------------------------------------------- staging: gather and plan
-
-// ctr[r] += 1 for every active lane, returning the value each lane's own increment saw.  References crowd on few rows (a handful of
-// inputs, one key), and same-address atomics serialise: the lanes of a wave that name the row of the wave's first pending lane are
-// counted with ONE atomic, four times over; what is still pending after that (rows that differ lane by lane) goes one by one.
-AVRF_DI uint32_t wave_count(uint32_t *ctr, uint32_t r, bool active) {
-  const uint32_t lane = threadIdx.x & 63;
-  uint32_t slot = 0;
-  bool todo = active;
-  for (int round = 0; round < 4; round++) {
-    const unsigned long long pending = __ballot(todo);
-    if (!pending) break;                                                // (wave-uniform)
-    const int leader = __ffsll(pending) - 1;
-    const uint32_t key = __shfl(r, leader);
-    const bool mine = todo && r == key;
-    const unsigned long long m = __ballot(mine);
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(ctr + key, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (mine) { slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1)); todo = false; }
-  }
-  if (todo) slot = atomicAdd(ctr + r, 1u);
-  return slot;
-}
-
-// reference t: item t's key (t < n) or the input of I/O pair t - n.  Copies the row (and the pair's output) into the plain staged
-// layout and counts the reference of its row.
-__global__ void __launch_bounds__(256)
-k_shared_gather(const uint8_t *__restrict__ table, uint32_t n_shared, const uint32_t *__restrict__ idx, const uint8_t *__restrict__ outs,
-                uint32_t n, uint32_t tot_io, uint8_t *__restrict__ pks, uint8_t *__restrict__ ios, uint32_t *__restrict__ cnt) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = t < n + tot_io;
-  uint32_t r = active ? idx[t] : 0;
-  if (r >= n_shared) r = n_shared - 1;                                  // (refused on the host; never a read outside the table)
-  wave_count(cnt, r, active);
-  if (!active) return;
-  const uint4 *src = reinterpret_cast<const uint4 *>(table + 64 * (size_t)r);
-  uint4 *dst = reinterpret_cast<uint4 *>(t < n ? pks + 64 * (size_t)t : ios + 128 * (size_t)(t - n));
-#pragma unroll
-  for (int i = 0; i < 4; i++) dst[i] = src[i];
-  if (t >= n) {
-    const uint4 *o = reinterpret_cast<const uint4 *>(outs + 64 * (size_t)(t - n));
-#pragma unroll
-    for (int i = 0; i < 4; i++) dst[4 + i] = o[i];
-  }
-}
-
-// exclusive prefix sums of the counts (one block; every thread a contiguous chunk): row_off[0 .. T], and the counts replaced by
-// the same offsets as the placement's cursors
-__global__ void __launch_bounds__(1024)
-k_shared_scan(uint32_t *__restrict__ cursor, uint32_t *__restrict__ row_off, uint32_t n_shared) {
-  __shared__ uint32_t sums[1024];
-  const uint32_t tid = threadIdx.x, chunk = (n_shared + 1023) / 1024;
-  const uint32_t lo = tid * chunk < n_shared ? tid * chunk : n_shared, hi = lo + chunk < n_shared ? lo + chunk : n_shared;
-  uint32_t s = 0;
-  for (uint32_t i = lo; i < hi; i++) s += cursor[i];
-  sums[tid] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {
-    const uint32_t v = tid >= d ? sums[tid - d] : 0;
-    __syncthreads();
-    sums[tid] += v;
-    __syncthreads();
-  }
-  uint32_t base = sums[tid] - s;
-  for (uint32_t i = lo; i < hi; i++) { const uint32_t c = cursor[i]; row_off[i] = base; cursor[i] = base; base += c; }
-  if (tid == 1023) row_off[n_shared] = sums[1023];
-}
-
-__global__ void __launch_bounds__(256)
-k_shared_place(const uint32_t *__restrict__ idx, uint32_t n_shared, uint32_t n_contrib, uint32_t *__restrict__ cursor,
-               uint32_t *__restrict__ pos, uint32_t *__restrict__ slot_row) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = t < n_contrib;
-  uint32_t r = active ? idx[t] : 0;
-  if (r >= n_shared) r = n_shared - 1;
-  const uint32_t s = wave_count(cursor, r, active);                     // < row_off[r + 1] <= n_contrib: the same references were counted
-  if (active) { pos[t] = s; slot_row[s] = r; }
-}
-
-hipError_t shared_plan(const uint8_t *d_table, uint32_t n_shared, const uint32_t *d_idx, const uint8_t *d_outputs, uint32_t n, uint32_t tot_io,
-                       uint8_t *d_pks, uint8_t *d_ios, uint32_t *d_plan, hipStream_t st) {
-  const uint32_t nc = n + tot_io;
-  if (!nc || !n_shared) return hipSuccess;
-  uint32_t *cursor = d_plan, *row_off = d_plan + (n_shared + 1), *pos = row_off + (n_shared + 1), *slot_row = pos + nc;
-  if (hipError_t e = hipMemsetAsync(cursor, 0, (size_t)(n_shared + 1) * 4, st)) return e;
-  hipLaunchKernelGGL(k_shared_gather, dim3((nc + 255) / 256), dim3(256), 0, st, d_table, n_shared, d_idx, d_outputs, n, tot_io, d_pks, d_ios, cursor);
-  hipLaunchKernelGGL(k_shared_scan, dim3(1), dim3(1024), 0, st, cursor, row_off, n_shared);
-  hipLaunchKernelGGL(k_shared_place, dim3((nc + 255) / 256), dim3(256), 0, st, d_idx, n_shared, nc, cursor, pos, slot_row);
-  return hipGetLastError();                                             // (a launch that was refused)
-}
-#endif  // AVRF_TU_SUITE == 0
-
-// ---------------------------------------------------------------- per suite
 
 // row r -> Montgomery x, y, k = d x y (what emit_term of vrf_batch.hip computes per reference); a coordinate >= q is flagged
 template <class S>
@@ -128,8 +31,16 @@ k_shared_pre(const uint8_t *__restrict__ table, uint32_t n_shared, te_pre *__res
 }
 
 
-// The per-item arithmetic of k_thin_terms: weights from the seed or from b.weights, j0, the block sum of w s into gpart.  Item j
-// emits (R_j, w_j) at j + io0 and (O_i, w c z_i) at j + io0 + 1 + i; w c (its key's row) and -w s z_i (its inputs' rows) go to contrib.
+// k_thin_terms_shared's sink of thin_item's terms: item j emits (R_j, w_j) at j + io0 and (O_i, w c z_i) at j + io0 + 1 + i; w c (its
+// key's row) and -w s z_i (its inputs' rows) go to contrib, in Montgomery form.
+template <class S> struct SharedTerms {
+  uint32_t *__restrict__ scalars; te_pre *__restrict__ pre; const uint32_t *__restrict__ pos; uint32_t *__restrict__ contrib; uint32_t n;
+  AVRF_DI void r(uint32_t j, uint32_t io0, const fp &w_plain, const uint8_t *xy) const { emit_term<S>(scalars, pre, j + io0, w_plain, xy); }
+  AVRF_DI void key(uint32_t j, uint32_t, const fp &wc) const { fp_store(contrib + 8 * (size_t)pos[j], wc); }
+  AVRF_DI void output(uint32_t j, uint32_t io0, uint32_t i, const fp &sc_plain, const uint8_t *xy) const { emit_term<S>(scalars, pre, j + io0 + 1 + i, sc_plain, xy); }
+  AVRF_DI void input(uint32_t, uint32_t io0, uint32_t i, const fp &sc_mont, const uint8_t *) const { fp_store(contrib + 8 * (size_t)pos[n + io0 + i], sc_mont); }
+};
+
 template <class S>
 __global__ void __launch_bounds__(128)
 k_thin_terms_shared(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c_in, const uint32_t *__restrict__ z_in,
@@ -139,37 +50,9 @@ k_thin_terms_shared(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__rest
   __shared__ fp red[128];
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   fp ws = fp_zero();
-  if (j < b.n) {
-    uint32_t io0 = b.io_off[j], m = b.io_off[j + 1] - io0;
-    uint64_t gj = j0 + j;
-    uint32_t ww[4];
-    if (b.weights) { const uint4 v = *reinterpret_cast<const uint4 *>(b.weights + 16 * (size_t)j); ww[0] = v.x; ww[1] = v.y; ww[2] = v.z; ww[3] = v.w; }
-    else { uint64_t blk[8]; sha512_xof_block(seed.w, gj >> 2, blk); digest_le128(blk, (int)(gj & 3), ww); }
-    fp w_plain = fp_zero(); w_plain.v[0] = ww[0]; w_plain.v[1] = ww[1]; w_plain.v[2] = ww[2]; w_plain.v[3] = ww[3];
-    fp w = fp_to_mont<Fr>(w_plain);
-    fp c = fp_to_mont<Fr>(fp_from_u128(c_in + 4 * (size_t)j));
-    const uint8_t *pr = b.proofs + 96 * (size_t)j;
-    fp s = fp_to_mont<Fr>(fp_load_le(pr + 64));
-    fp wc = fp_mul<Fr>(w, c);                               // thin.rs:291-292
-    ws = fp_mul<Fr>(w, s);
-    uint32_t t = j + io0;
-    emit_term<S>(scalars, pre, t, w_plain, pr);                                           // (R_j, w_j)        :295-296
-    fp_store(contrib + 8 * (size_t)pos[j], wc);                                           // (pk_j, w c z0)    :299-300, z0 = 1
-    for (uint32_t i = 0; i < m; i++) {                                                    // :306-312
-      fp z = fp_to_mont<Fr>(fp_from_u128(z_in + 4 * (size_t)(io0 + i)));
-      const uint8_t *p = b.ios_xy + 128 * (size_t)(io0 + i);
-      emit_term<S>(scalars, pre, t + 1 + i, fp_from_mont<Fr>(fp_mul<Fr>(wc, z)), p + 64);              // (O_i, w c z_i)
-      fp_store(contrib + 8 * (size_t)pos[b.n + io0 + i], fp_neg<Fr>(fp_mul<Fr>(ws, z)));               // (I_i, -w s z_i)
-    }
-  }
-  // block sum of w_j s_j z0 (Montgomery form), thin.rs:303
-  red[threadIdx.x] = ws;
-  __syncthreads();
-  for (int s2 = 64; s2 >= 1; s2 >>= 1) {
-    if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, red[0]);
+  if (j < b.n) ws = thin_item<S>(b, seed, j0, c_in, z_in, j, SharedTerms<S>{scalars, pre, pos, contrib, b.n});
+  const fp sum = block_sum<Fr, 128>(ws, red);                                  // of w_j s_j z0 (Montgomery form), thin.rs:303
+  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, sum);
 }
 
 enum : uint32_t { SHARED_NO_ROW = 0xffffffffu };
@@ -212,32 +95,15 @@ k_shared_lanes(SharedPlan p, const uint32_t *__restrict__ contrib, uint32_t *__r
 // all its 256 threads add one cut row's partials (four independent running sums per thread, then a tree in LDS), so that ONE row of
 // all 131 072 references -- 16 384 partials -- costs each thread 64 additions.  A unit is a ROW when there are no more rows than
 // lanes (the shared case: a cut row is known from row_off alone), else a LANE (tail_row says whether it left a tail): min(lanes, T)
-// units.  The last block sums the partials of w s into the generator term, as k_g_final does.
+// units.  The last block is the generator term (base_term, as k_g_final).
 template <class S>
 __global__ void __launch_bounds__(256)
 k_shared_merge(SharedPlan p, const uint32_t *__restrict__ part, const uint32_t *__restrict__ tail_row, uint32_t n_units, int by_row,
                const uint32_t *__restrict__ gpart, uint32_t nparts, uint32_t *__restrict__ scalars, te_pre *__restrict__ pre, uint32_t t0) {
-  using Fr = typename S::Fr; using Fq = typename S::Fq;
+  using Fr = typename S::Fr;
   __shared__ fp red[256];
   const uint32_t tid = threadIdx.x;
-  if (blockIdx.x == gridDim.x - 1) {                                    // g = -(sum of partials); last term (G, g)
-    fp acc = fp_zero();
-    for (uint32_t i = tid; i < nparts; i += 256) acc = fp_add<Fr>(acc, fp_load(gpart + 8 * (size_t)i));
-    red[tid] = acc;
-    __syncthreads();
-#pragma unroll 1                                                        // (unrolled, the tree's eight masked additions spill SGPRs)
-    for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-      if ((int)tid < s2) red[tid] = fp_add<Fr>(red[tid], red[tid + s2]);
-      __syncthreads();
-    }
-    if (tid == 0) {
-      const uint32_t t_last = t0 + p.n_shared;
-      fp_store(scalars + 8 * (size_t)t_last, fp_from_mont<Fr>(fp_neg<Fr>(red[0])));
-      te_pre g; g.x = fp_const<Fq>(S::G_X); g.y = fp_const<Fq>(S::G_Y); g.k = fp_const<Fq>(S::G_K);
-      store_pre(pre + t_last, g);
-    }
-    return;
-  }
+  if (blockIdx.x == gridDim.x - 1) { base_term<S, true>(gpart, nparts, scalars, pre, t0 + p.n_shared, 0, red); return; }   // (G, g), rolled as below
   for (uint32_t i = 0; i < 4; i++) {                                    // (everything that decides control flow below is block-uniform)
     const uint32_t u = blockIdx.x * 4 + i;
     if (u >= n_units) break;
@@ -261,14 +127,8 @@ k_shared_merge(SharedPlan p, const uint32_t *__restrict__ part, const uint32_t *
       acc = fp_add<Fr>(fp_add<Fr>(fp_add<Fr>(fp_add<Fr>(acc, b0), b1), b2), b3);
     }
     for (; k <= last; k += 256) acc = fp_add<Fr>(acc, fp_load(part + 16 * (size_t)k));
-    red[tid] = acc;
-    __syncthreads();
-#pragma unroll 1                                                        // (unrolled, the tree's eight masked additions spill SGPRs)
-    for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-      if ((int)tid < s2) red[tid] = fp_add<Fr>(red[tid], red[tid + s2]);
-      __syncthreads();
-    }
-    if (tid == 0) fp_store(scalars + 8 * (size_t)(t0 + r), fp_from_mont<Fr>(red[0]));
+    const fp sum = block_sum<Fr, 256, true>(acc, red);                  // (rolled: unrolled, the tree's eight masked additions spill SGPRs)
+    if (tid == 0) fp_store(scalars + 8 * (size_t)(t0 + r), fp_from_mont<Fr>(sum));
     __syncthreads();                                                    // red is reused by the next unit
   }
 }

@@ -3,8 +3,8 @@
 //   k_thin_prepare : thin::BatchVerifier::prepare, src/thin.rs:209-226
 //                    (vrf_transcript_scalars_with_schnorr src/utils/common.rs:251-258,
 //                     vrf_transcript_base :159-173, DelinearizeScalars :335-369, challenge :270-280)
-//   k_thin_terms   : the per-item part of thin::BatchVerifier::verify, src/thin.rs:287-313
-//   k_g_final      : the shared-generator term, src/thin.rs:303,316-317
+//   k_thin_terms   : the per-item part of thin::BatchVerifier::verify, src/thin.rs:287-313 (thin_item, batch_terms_dev.h)
+//   k_g_final      : the shared-generator term, src/thin.rs:303,316-317 (base_term, batch_terms_dev.h)
 // One lane per batch item; SHA-512 state in VGPRs (sha512_dev.h); scalar-field products in
 // 8 x u32 Montgomery form (fp256.h).
 #include "vrf_batch.h"
@@ -83,7 +83,15 @@ k_thin_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint32_t *__restrict__ 
   if (f) atomicOr(flags, f);
 }
 
-// (fp_from_u128, emit_term: batch_terms_dev.h -- shared with k_thin_terms_shared of thin_shared.hip, which restates this kernel's per-item arithmetic)
+// k_thin_terms' sink of thin_item's terms: item j's four kinds at 2 j + 2 io0 (+1, +2 + 2 i, +3 + 2 i), every scalar in plain form
+template <class S> struct PlainTerms {
+  uint32_t *__restrict__ scalars; te_pre *__restrict__ pre; const uint8_t *__restrict__ pks_xy;
+  using Fr = typename S::Fr;
+  AVRF_DI void r(uint32_t j, uint32_t io0, const fp &w_plain, const uint8_t *xy) const { emit_term<S>(scalars, pre, 2 * j + 2 * io0, w_plain, xy); }
+  AVRF_DI void key(uint32_t j, uint32_t io0, const fp &wc) const { emit_term<S>(scalars, pre, 2 * j + 2 * io0 + 1, fp_from_mont<Fr>(wc), pks_xy + 64 * (size_t)j); }
+  AVRF_DI void output(uint32_t j, uint32_t io0, uint32_t i, const fp &sc_plain, const uint8_t *xy) const { emit_term<S>(scalars, pre, 2 * j + 2 * io0 + 2 + 2 * i, sc_plain, xy); }
+  AVRF_DI void input(uint32_t j, uint32_t io0, uint32_t i, const fp &sc_mont, const uint8_t *xy) const { emit_term<S>(scalars, pre, 2 * j + 2 * io0 + 3 + 2 * i, fp_from_mont<Fr>(sc_mont), xy); }
+};
 
 template <class S>
 __global__ void __launch_bounds__(128)
@@ -93,63 +101,18 @@ k_thin_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ 
   __shared__ fp red[128];
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   fp ws = fp_zero();
-  if (j < b.n) {
-    uint32_t io0 = b.io_off[j], m = b.io_off[j + 1] - io0;
-    // w_j = challenge_scalar(&mut t): 16 bytes of the weight stream (thin.rs:289, common.rs:72-76)
-    // (j0 = global index of this shard's first item when one batch is split over several GPUs)
-    uint64_t gj = j0 + j;
-    uint32_t ww[4];
-    if (b.weights) { const uint4 v = *reinterpret_cast<const uint4 *>(b.weights + 16 * (size_t)j); ww[0] = v.x; ww[1] = v.y; ww[2] = v.z; ww[3] = v.w; }
-    else { uint64_t blk[8]; sha512_xof_block(seed.w, gj >> 2, blk); digest_le128(blk, (int)(gj & 3), ww); }
-    fp w_plain = fp_zero(); w_plain.v[0] = ww[0]; w_plain.v[1] = ww[1]; w_plain.v[2] = ww[2]; w_plain.v[3] = ww[3];
-    fp w = fp_to_mont<Fr>(w_plain);
-    fp c = fp_to_mont<Fr>(fp_from_u128(c_in + 4 * (size_t)j));
-    const uint8_t *pr = b.proofs + 96 * (size_t)j;
-    fp s = fp_to_mont<Fr>(fp_load_le(pr + 64));
-    fp wc = fp_mul<Fr>(w, c);                               // thin.rs:291-292
-    ws = fp_mul<Fr>(w, s);
-    uint32_t t = 2 * j + 2 * io0;
-    emit_term<S>(scalars, pre, t, w_plain, pr);                                           // (R_j, w_j)        :295-296
-    emit_term<S>(scalars, pre, t + 1, fp_from_mont<Fr>(wc), b.pks_xy + 64 * (size_t)j);   // (pk_j, w c z0)    :299-300, z0 = 1
-    for (uint32_t i = 0; i < m; i++) {                                                    // :306-312
-      fp z = fp_to_mont<Fr>(fp_from_u128(z_in + 4 * (size_t)(io0 + i)));
-      const uint8_t *p = b.ios_xy + 128 * (size_t)(io0 + i);
-      emit_term<S>(scalars, pre, t + 2 + 2 * i, fp_from_mont<Fr>(fp_mul<Fr>(wc, z)), p + 64);             // (O_i, w c z_i)
-      emit_term<S>(scalars, pre, t + 3 + 2 * i, fp_from_mont<Fr>(fp_neg<Fr>(fp_mul<Fr>(ws, z))), p);      // (I_i, -w s z_i)
-    }
-  }
-  // block sum of w_j s_j z0 (Montgomery form), thin.rs:303
-  red[threadIdx.x] = ws;
-  __syncthreads();
-  for (int s2 = 64; s2 >= 1; s2 >>= 1) {
-    if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, red[0]);
+  if (j < b.n) ws = thin_item<S>(b, seed, j0, c_in, z_in, j, PlainTerms<S>{scalars, pre, b.pks_xy});
+  const fp sum = block_sum<Fr, 128>(ws, red);                                  // of w_j s_j z0 (Montgomery form), thin.rs:303
+  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, sum);
 }
 
-// g = -(sum of partials); last term (G, g)   (thin.rs:303,316-317)
+// last term (G, g) -- for Pedersen the last two, on G and BLINDING_BASE
 template <class S>
 __global__ void __launch_bounds__(256)
 k_g_final(const uint32_t *__restrict__ gpart, uint32_t nparts, uint32_t *__restrict__ scalars, te_pre *__restrict__ pre,
           uint32_t t_last, int which_base) {
-  using Fr = typename S::Fr; using Fq = typename S::Fq;
   __shared__ fp red[256];
-  fp acc = fp_zero();
-  for (uint32_t i = threadIdx.x; i < nparts; i += 256) acc = fp_add<Fr>(acc, fp_load(gpart + 8 * (size_t)i));
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-    if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    fp_store(scalars + 8 * (size_t)t_last, fp_from_mont<Fr>(fp_neg<Fr>(red[0])));
-    te_pre g;
-    if (which_base == 0) { g.x = fp_const<Fq>(S::G_X); g.y = fp_const<Fq>(S::G_Y); g.k = fp_const<Fq>(S::G_K); }
-    else { g.x = fp_const<Fq>(S::B_X); g.y = fp_const<Fq>(S::B_Y); g.k = fp_const<Fq>(S::B_K); }
-    store_pre(pre + t_last, g);
-  }
+  base_term<S>(gpart, nparts, scalars, pre, t_last, which_base, red);
 }
 
 
@@ -239,21 +202,11 @@ k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c
     emit_term<S>(scalars, pre, k + 4, u_plain, pr + 64);                                             // (R, u)        :401-402
     us = fp_mul<Fr>(uu, s); usb = fp_mul<Fr>(uu, sb);                                                // :405-406
   }
-  red[threadIdx.x] = us;
+  const fp gsum = block_sum<Fr, 128>(us, red);
+  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, gsum);
   __syncthreads();
-  for (int s2 = 64; s2 >= 1; s2 >>= 1) {
-    if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, red[0]);
-  __syncthreads();
-  red[threadIdx.x] = usb;
-  __syncthreads();
-  for (int s2 = 64; s2 >= 1; s2 >>= 1) {
-    if ((int)threadIdx.x < s2) red[threadIdx.x] = fp_add<Fr>(red[threadIdx.x], red[threadIdx.x + s2]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) fp_store(bpart + 8 * (size_t)blockIdx.x, red[0]);
+  const fp bsum = block_sum<Fr, 128>(usb, red);
+  if (threadIdx.x == 0) fp_store(bpart + 8 * (size_t)blockIdx.x, bsum);
 }
 
 template <class S> void BatchOps<S>::ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, hipStream_t st) {
