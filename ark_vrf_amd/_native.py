@@ -118,6 +118,31 @@ def dedup_points(pks_xy, ios_xy):
             np.ascontiguousarray(ios[:, 64:]).tobytes())
 
 
+class SharedWireBatch(SharedBatch):
+    """A SharedBatch from wire bytes (include/avrf.h avrf_thin_batch_stage_shared_wire): `shared` n_shared x L and `outputs` one
+    L-byte compressed point per pair, proofs n x (L + 32) laid out R || s; L = Context.point_len of the suite."""
+
+    def __init__(self, n, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, L=32):
+        SharedBatch.__init__(self, n, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs)
+        self.n_shared = len(shared if isinstance(shared, C.Array) else bytes(shared)) // L
+
+
+def dedup_points_wire(pks, ios, L=32):
+    """dedup_points on compressed points: pks n x L, ios pairs of L-byte points (input || output) -> (shared, pk_index,
+    input_index, outputs), the rows being the byte-wise distinct compressed keys and inputs.  The encoding is canonical, so equal
+    bytes <=> equal point."""
+    import numpy as np
+    pk = np.frombuffer(bytes(pks), dtype=np.uint8).reshape(-1, L)
+    io = np.frombuffer(bytes(ios), dtype=np.uint8).reshape(-1, 2 * L)
+    pts = np.concatenate([pk, io[:, :L]], axis=0)
+    if not len(pts):
+        return b"", [], [], b""
+    rows, inverse = np.unique(pts, axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    return (rows.tobytes(), [int(i) for i in inverse[: len(pk)]], [int(i) for i in inverse[len(pk):]],
+            np.ascontiguousarray(io[:, L:]).tobytes())
+
+
 def thin_shared_n_terms(n, tot_io, n_shared):
     """Terms of the MSM a shared-table Thin batch builds (host arithmetic; no device needed)."""
     f = lib().avrf_thin_shared_n_terms
@@ -189,6 +214,13 @@ class Context:
     def thin_batch_stage_shared(self, b):
         """b: SharedBatch.  Staged for thin_batch_run / batch_run_begin .. / last_terms like a plain batch."""
         return lib().avrf_thin_batch_stage_shared(self._h, *b.args())
+
+    def thin_batch_stage_shared_wire(self, b, validate=1):
+        """b: SharedWireBatch.  INVALID_DATA when a row, an output or an R does not decode (validate: or fails Validate::Yes)."""
+        return lib().avrf_thin_batch_stage_shared_wire(self._h, *b.args(), int(validate))
+
+    def thin_batch_verify_shared_wire(self, b, validate=1):
+        return lib().avrf_thin_batch_verify_shared_wire(self._h, *b.args(), int(validate))
 
     def thin_batch_run(self):
         return lib().avrf_thin_batch_run(self._h)
@@ -391,6 +423,14 @@ class PinnedSharedBatch(PinnedBatch):
     args = SharedBatch.args
 
 
+class PinnedSharedWireBatch(PinnedSharedBatch):
+    """A SharedWireBatch whose buffers live in page-locked host memory."""
+
+    def __init__(self, n, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, L=32):
+        PinnedSharedBatch.__init__(self, n, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs)
+        self.n_shared = len(bytes(shared)) // L
+
+
 class Pool:
     """avrf_pool: many BatchVerifier::verify jobs in flight on one device (include/avrf.h).  kind 1 thin, 2 pedersen."""
 
@@ -432,6 +472,15 @@ class Pool:
         st = lib().avrf_pool_submit_shared(self._h, *b.args(), C.byref(t))
         if st != OK:
             raise AvrfError(f"avrf_pool_submit_shared -> {st}")
+        self._keep[t.value] = b
+        return t.value
+
+    def submit_shared_wire(self, b, validate=1):
+        """b: SharedWireBatch / PinnedSharedWireBatch (a kind 1 pool).  Returns the ticket."""
+        t = C.c_uint64(0)
+        st = lib().avrf_pool_submit_shared_wire(self._h, *b.args(), int(validate), C.byref(t))
+        if st != OK:
+            raise AvrfError(f"avrf_pool_submit_shared_wire -> {st}")
         self._keep[t.value] = b
         return t.value
 

@@ -422,6 +422,48 @@ int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const ui
   c->staged_kind = kind;
   return AVRF_OK;
 }
+// The two together: a shared-table Thin batch whose table, outputs and proofs come as wire bytes.  The bytes go to d_misc (rows | outputs |
+// proofs, three copies) and ONE kernel does all the decoding (vrf_single.hip k_decode_shared_wire): every row, referenced or not, once to
+// d_table (x || y) and d_table_rows (te_pre, what rows_pre leaves after ctx_stage_shared), every output to d_table_outs, every R || s to
+// d_proofs.  shared_plan then runs on d_table as it does after ctx_stage_shared, and the batch is a shared-table batch to every run entry
+// point.  What decodes is canonical, so the plan's range flag stays clear; a point that fails raises the decode flag of ctx_stage_wire
+// (d_status -> h_flags[2]): AVRF_INVALID_DATA here, or from batch_collect when nothing was waited for (wire_pending).
+int ctx_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                          const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                          int validate, bool wait) {
+  const bool args_ok = !n || (shared && proofs && shared_indices_ok(n, n_shared, pk_index, input_index, outputs, io_counts));   // (refused before anything is staged)
+  if (int e = stage_open(c, Thin, n, args_ok, outputs, false, io_counts, ads, ad_lens)) return e;
+  if (n == 0) return AVRF_OK;
+  const KindFacts &k = kind_facts(Thin);
+  const size_t L = (size_t)point_len_of(c->suite), a = c->tot_io, nc = n + a, plen = k.wire_proof(L);
+  const size_t w_rows = n_shared * L, w_outs = a * L, w_pr = n * plen;
+  HIP_TRY(c->d_table.ensure(n_shared * 64)); HIP_TRY(c->d_table_idx.ensure(nc * 4)); HIP_TRY(c->d_table_outs.ensure(a * 64 + 16));
+  HIP_TRY(c->d_table_rows.ensure(n_shared * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(n_shared, nc) * 4));
+  HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(c->d_proofs.ensure(n * k.xy_proof()));
+  HIP_TRY(c->d_misc.ensure(w_rows + w_outs + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
+  uint8_t *dw = c->d_misc.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(dw, shared, w_rows, hipMemcpyHostToDevice, c->stream));
+  if (w_outs) HIP_TRY(hipMemcpyAsync(dw + w_rows, outputs, w_outs, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dw + w_rows + w_outs, proofs, w_pr, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_table_idx.p, pk_index, n * 4, hipMemcpyHostToDevice, c->stream));
+  if (a) HIP_TRY(hipMemcpyAsync(c->d_table_idx.as<uint32_t>() + n, input_index, a * 4, hipMemcpyHostToDevice, c->stream));
+  uint32_t *d_flag = c->d_status.as<uint32_t>(), *h_flag = c->h_flags.as<uint32_t>() + 2;
+  uint32_t *plan = c->d_table_plan.as<uint32_t>();
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
+  HIP_TRY(hipMemsetAsync(shared_plan_flag(plan, n_shared, nc), 0, 4, c->stream));
+  HIP_TRY(AVRF_SINGLE(c->suite, decode_shared_wire(dw, (uint32_t)n_shared, (uint32_t)a, (uint32_t)n, c->d_table.as<uint8_t>(), c->d_table_rows.as<te_pre_raw>(),
+                                                   c->d_table_outs.as<uint8_t>(), c->d_proofs.as<uint8_t>(), validate, d_flag, c->stream)));
+  HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)n_shared, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)n, (uint32_t)a,
+                      c->d_pks.as<uint8_t>(), c->d_ios.as<uint8_t>(), plan, c->stream));
+  c->n_shared = n_shared;
+  if (int e = stage_verifier(c, Thin, proofs + k.resp_at_wire(L), plen)) { c->n_shared = 0; return e; }
+  if (!wait) { c->wire_pending = true; c->staged_kind = Thin; return AVRF_OK; }
+  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
+  if (*h_flag) { c->n_shared = 0; return AVRF_INVALID_DATA; }
+  c->staged_kind = Thin;
+  return AVRF_OK;
+}
 }  // namespace avrf
 extern "C" {
 int avrf_thin_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
@@ -440,6 +482,18 @@ int avrf_thin_batch_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const u
   return ctx_stage_shared(c, n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs, true);
 }
 size_t avrf_thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared) { return thin_shared_n_terms(n, tot_io, n_shared); }
+int avrf_thin_batch_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                                      const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                                      int validate) {
+  if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
+  return ctx_stage_shared_wire(c, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, validate, true);
+}
+int avrf_thin_batch_verify_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                                       const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                                       int validate) {
+  if (int e = avrf_thin_batch_stage_shared_wire(c, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, validate)) return e;
+  return avrf_thin_batch_run(c);
+}
 
 int avrf_thin_batch_stage(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {

@@ -102,6 +102,10 @@ int ctx_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shar
                      const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait);
 int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                    const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait);   // serialize_compressed bytes in, decompressed on the device
+// both: the table, the outputs and R || s as wire bytes, all decoded by one kernel launch; then a shared-table batch like ctx_stage_shared's
+int ctx_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                          const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                          int validate, bool wait);
 int batch_begin(avrf_ctx *c, int kind);                               // validation + prepare kernel + copies back enqueued on c->stream
 int batch_collect(avrf_ctx *c, int kind);                             // (c->stream's work has completed) AVRF_INVALID_DATA for a refused item
 bool suite_host_weights(int suite);                                   // sponge / SHA-256 transcript: batch_seed squeezes the weight stream itself (no seed)

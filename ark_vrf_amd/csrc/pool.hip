@@ -51,6 +51,7 @@ struct Slot {
   const uint8_t *pks = nullptr, *ios = nullptr, *ads = nullptr, *proofs = nullptr;
   const uint32_t *io_counts = nullptr, *ad_lens = nullptr;
   // the host sources are a table of shared points (avrf_pool_submit_shared): pks = the table, ios = the outputs, and the indices into the table
+  // (with `wire` as well -- avrf_pool_submit_shared_wire -- table, outputs and proofs are wire bytes: ctx_stage_shared_wire)
   bool shared = false; size_t n_shared = 0; const uint32_t *pk_index = nullptr, *input_index = nullptr;
   uint8_t digest[64];
   // the event, the record, then the context: it has no stream or workspace of its own and is detached from the pool's lane before it dies
@@ -131,7 +132,8 @@ struct Run {
     if (!S.from_host && S.resident_invalid) { W.cpu_us[0] += thread_cpu_us() - t0; done(S, AVRF_INVALID_DATA); return; }
     if (S.from_host) {
       S.resident_invalid = false;
-      if (S.shared) st = guarded([&] { return ctx_stage_shared(c, S.n, S.n_shared, S.pks, S.pk_index, S.input_index, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
+      if (S.shared && S.wire) st = guarded([&] { return ctx_stage_shared_wire(c, S.n, S.n_shared, S.pks, S.pk_index, S.input_index, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, S.validate, /*wait=*/false); });
+      else if (S.shared) st = guarded([&] { return ctx_stage_shared(c, S.n, S.n_shared, S.pks, S.pk_index, S.input_index, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
       else if (S.wire) st = guarded([&] { return ctx_stage_wire(c, P->kind, S.n, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, S.validate, /*wait=*/false); });
       else st = guarded([&] { return ctx_stage(c, P->kind, S.n, nullptr, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
       S.has_batch = st == AVRF_OK;
@@ -338,6 +340,14 @@ int avrf_pool_submit_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8
   if (!P || P->kind != Thin || !shared_indices_ok(n, n_shared, pk_index, input_index, outputs_xy, io_counts)) return AVRF_ERR_BAD_ARG;
   const SharedSource src{n_shared, pk_index, input_index};
   return pool_submit(P, n, shared_xy, outputs_xy, io_counts, ads, ad_lens, proofs, ticket, false, 0, &src);
+}
+// both: the table, the outputs and the proofs as wire bytes (include/avrf.h avrf_thin_batch_stage_shared_wire); indices checked here as above
+int avrf_pool_submit_shared_wire(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                                 const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                                 int validate, uint64_t *ticket) {
+  if (!P || P->kind != Thin || !shared_indices_ok(n, n_shared, pk_index, input_index, outputs, io_counts)) return AVRF_ERR_BAD_ARG;
+  const SharedSource src{n_shared, pk_index, input_index};
+  return pool_submit(P, n, shared, outputs, io_counts, ads, ad_lens, proofs, ticket, true, validate, &src);
 }
 static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
                        const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate, const SharedSource *shared) {

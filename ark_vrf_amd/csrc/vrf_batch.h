@@ -66,6 +66,10 @@ template <class S> struct SingleOps {
                           int32_t *d_rec_status, hipStream_t st, const uint32_t *d_item_off = nullptr, uint32_t n_items = 0);
   static void compress(const uint8_t *d_in, uint32_t n, uint8_t *d_out, hipStream_t st);
   static void decompress_strided(const uint8_t *d_in, uint32_t in_stride, uint32_t n, uint8_t *d_out, uint32_t out_stride, int validate, uint32_t *d_flags, hipStream_t st);
+  // a shared-table Thin batch from wire bytes (k_decode_shared_wire): d_wire = n_rows rows | n_outs outputs | n proofs R || s; one launch decodes
+  // every point into d_table (x || y) + d_rows (te_pre), d_outs, d_proofs (x || y || s, 96 apart); FLAG_CURVE in *d_flags for a failing point
+  static hipError_t decode_shared_wire(const uint8_t *d_wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *d_table, te_pre_raw *d_rows,
+                                       uint8_t *d_outs, uint8_t *d_proofs, int validate, uint32_t *d_flags, hipStream_t st);
   static void output_hash(const uint8_t *d_in, uint32_t n, uint32_t len, uint8_t *d_out, hipStream_t st);   // Output::hash, src/lib.rs:605-609
   static void secret_from_seed(const uint8_t *d_seeds, uint32_t n, uint8_t *d_sk, uint32_t *d_flags, hipStream_t st);   // Secret::from_seed, src/lib.rs:346-369
 };

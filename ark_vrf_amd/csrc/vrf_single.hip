@@ -954,21 +954,21 @@ template <class S> AVRF_DI int32_t decode_point_at(const uint8_t *__restrict__ s
   }
   return st;
 }
+// Validate::Yes's subgroup test of a decoded point (decode_point_at left `check` set): two Jacobi symbols where the suite has the
+// 2-descent (glv.h), r * P == 0 elsewhere
+template <class S> AVRF_DI bool point_in_subgroup(const fp &xm, const fp &ym) {
+  using Fr = typename S::Fr;
+  if constexpr (S::HAS_2DESCENT) return te_in_subgroup_2descent<S>(ym);
+  else return te_is_identity<S>(te_smul<S>(te_make_pre<S>(xm, ym), fp_const<Fr>(Fr::P), Fr::BITS));
+}
 template <class S>
 __global__ void __launch_bounds__(128)
 k_decompress(const uint8_t *__restrict__ in, uint32_t n, uint8_t *__restrict__ out_xy, int validate, int32_t *__restrict__ status) {
-  using Fr = typename S::Fr;
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   fp xm, ym, x, y; bool check;
   int32_t st = decode_point<S>(in, j, validate, xm, ym, x, y, check);
-  if (check) {
-    if constexpr (S::HAS_2DESCENT) { if (!te_in_subgroup_2descent<S>(ym)) st = 2; }      // two Jacobi symbols (glv.h)
-    else {
-      te_ext rp = te_smul<S>(te_make_pre<S>(xm, ym), fp_const<Fr>(Fr::P), Fr::BITS);   // r * P == 0
-      if (!te_is_identity<S>(rp)) st = 2;
-    }
-  }
+  if (check && !point_in_subgroup<S>(xm, ym)) st = 2;
   fp_store_le(out_xy + 64 * (size_t)j, x); fp_store_le(out_xy + 64 * (size_t)j + 32, y);
   status[j] = st;
 }
@@ -980,19 +980,47 @@ template <class S>
 __global__ void __launch_bounds__(128)
 k_decompress_strided(const uint8_t *__restrict__ in, uint32_t in_stride, uint32_t n, uint8_t *__restrict__ out_xy, uint32_t out_stride, int validate,
                      uint32_t *__restrict__ flags) {
-  using Fr = typename S::Fr;
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   fp xm, ym, x, y; bool check;
   int32_t st = decode_point_at<S>(in + (size_t)in_stride * j, validate, xm, ym, x, y, check);
-  if (check) {
-    if constexpr (S::HAS_2DESCENT) { if (!te_in_subgroup_2descent<S>(ym)) st = 2; }
-    else {
-      te_ext rp = te_smul<S>(te_make_pre<S>(xm, ym), fp_const<Fr>(Fr::P), Fr::BITS);
-      if (!te_is_identity<S>(rp)) st = 2;
-    }
-  }
+  if (check && !point_in_subgroup<S>(xm, ym)) st = 2;
   fp_store_le(out_xy + (size_t)out_stride * j, x); fp_store_le(out_xy + (size_t)out_stride * j + 32, y);
+  if (st) atomicOr(flags, (uint32_t)FLAG_CURVE);
+}
+// ALL the decoding of a shared-table Thin batch staged from wire bytes (capi.hip ctx_stage_shared_wire), one launch: `wire` holds the
+// n_rows table rows and the n_outs outputs as POINT_LEN-byte points back to back, then the n proofs R || s.  Thread g takes one point:
+// row g, output g - n_rows, or the R of proof j = g - n_rows - n_outs.  The segment only picks addresses; the decoding and the
+// subgroup test are one instruction stream for every lane, and what differs afterwards is which stores a lane makes:
+//   row     x || y to table (k_shared_gather and the transcript read it) and te_pre, from the Montgomery coordinates at hand, to rows
+//           (x, y, k = d x y as te_make_pre has them, stored one by one: no 96-byte temporary in the kernel's frame)
+//   output  x || y to outs
+//   R       x || y to proofs + 96 j, and s copied behind it
+// A failing point raises FLAG_CURVE as in k_decompress_strided and its destination is STILL written, as the decoder leaves it: the
+// prepare kernel may be enqueued before the host has read the flag and must find initialised memory.
+template <class S>
+__global__ void __launch_bounds__(128)
+k_decode_shared_wire(const uint8_t *__restrict__ wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *__restrict__ table,
+                     te_pre *__restrict__ rows, uint8_t *__restrict__ outs, uint8_t *__restrict__ proofs, int validate, uint32_t *__restrict__ flags) {
+  using Fq = typename S::Fq;
+  constexpr size_t L = S::POINT_LEN;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, n_pts = n_rows + n_outs;
+  if (g >= n_pts + n) return;
+  const bool is_row = g < n_rows, is_r = g >= n_pts;
+  const uint32_t j = g - n_pts;                                          // (of a proof)
+  const uint8_t *src = wire + (is_r ? L * n_pts + (L + 32) * j : L * g);
+  fp xm, ym, x, y; bool check;
+  int32_t st = decode_point_at<S>(src, validate, xm, ym, x, y, check);
+  uint8_t *dst = is_row ? table + 64 * (size_t)g : is_r ? proofs + 96 * (size_t)j : outs + 64 * (size_t)(g - n_rows);
+  fp_store_le(dst, x); fp_store_le(dst + 32, y);
+  if (is_r) fp_store_le(dst + 64, fp_load_le(src + L));
+  if (is_row) {
+    uint32_t *d = reinterpret_cast<uint32_t *>(rows + g);
+    fp_store(d, xm); fp_store(d + 8, ym);
+    if constexpr (S::SW_NATIVE) fp_store(d + 16, fp_zero());
+    else fp_store(d + 16, fp_mul<Fq>(fp_mul<Fq>(xm, ym), fp_const<Fq>(S::D)));
+  }
+  if (check && !point_in_subgroup<S>(xm, ym)) st = 2;
   if (st) atomicOr(flags, (uint32_t)FLAG_CURVE);
 }
 // few points with the subgroup test: FOUR lanes per point -- the decoding is computed alike by the four lanes, r P runs as one
@@ -1058,7 +1086,7 @@ template <class S>
 __global__ void __launch_bounds__(128)
 k_validate_xy(const uint8_t *__restrict__ base, uint32_t stride, uint32_t ppr, uint32_t nrec, int level, uint32_t *__restrict__ flags,
               int32_t *__restrict__ rec_status, const uint32_t *__restrict__ item_off, uint32_t n_items) {
-  using Fq = typename S::Fq; using Fr = typename S::Fr;
+  using Fq = typename S::Fq;
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nrec * ppr) return;
   uint32_t j = t / ppr; const uint32_t p = t - j * ppr;
@@ -1073,13 +1101,7 @@ k_validate_xy(const uint8_t *__restrict__ base, uint32_t stride, uint32_t ppr, u
   if (!bad) {
     fp xm = fp_to_mont<Fq>(x), ym = fp_to_mont<Fq>(y);
     bad = !te_on_curve<S>(xm, ym);
-    if (!bad && level >= 2) {
-      if constexpr (S::HAS_2DESCENT) bad = !te_in_subgroup_2descent<S>(ym);
-      else {
-        te_ext rp = te_smul<S>(te_make_pre<S>(xm, ym), fp_const<Fr>(Fr::P), Fr::BITS);
-        bad = !te_is_identity<S>(rp);
-      }
-    }
+    if (!bad && level >= 2) bad = !point_in_subgroup<S>(xm, ym);
   }
   if (bad) { atomicOr(flags, (uint32_t)FLAG_CURVE); if (rec_status) rec_status[j] = 2; }
 }
@@ -1245,6 +1267,13 @@ template <class S> void SingleOps<S>::validate_xy(const uint8_t *d_base, uint32_
 template <class S> void SingleOps<S>::decompress_strided(const uint8_t *d_in, uint32_t in_stride, uint32_t n, uint8_t *d_out, uint32_t out_stride, int validate, uint32_t *d_flags, hipStream_t st) {
   if (!n) return;
   hipLaunchKernelGGL(k_decompress_strided<S>, dim3((n + 127) / 128), dim3(128), 0, st, d_in, in_stride, n, d_out, out_stride, validate, d_flags);
+}
+template <class S> hipError_t SingleOps<S>::decode_shared_wire(const uint8_t *d_wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *d_table, te_pre_raw *d_rows,
+                                                               uint8_t *d_outs, uint8_t *d_proofs, int validate, uint32_t *d_flags, hipStream_t st) {
+  const uint32_t pts = n_rows + n_outs + n;
+  if (!pts) return hipSuccess;
+  hipLaunchKernelGGL(k_decode_shared_wire<S>, dim3((pts + 127) / 128), dim3(128), 0, st, d_wire, n_rows, n_outs, n, d_table, (te_pre *)d_rows, d_outs, d_proofs, validate, d_flags);
+  return hipGetLastError();
 }
 template <class S> void SingleOps<S>::compress(const uint8_t *d_in, uint32_t n, uint8_t *d_out, hipStream_t st) {
   if (!n) return;

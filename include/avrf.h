@@ -181,6 +181,34 @@ int avrf_thin_batch_stage_shared(avrf_ctx *ctx, size_t n, size_t n_shared, const
                                  const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs_xy,
                                  const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs);
 size_t avrf_thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared);
+/* The same batch from wire bytes, for a caller that holds its validator keys and slot inputs as the bytes it received.  With
+ * L = avrf_point_len(suite): shared is n_shared x L (`serialize_compressed` points), outputs sum(io_counts) x L, proofs
+ * n x (L + 32) laid out R || s (the Thin wire proof of avrf_thin_batch_stage_wire); pk_index, input_index, io_counts, ads and
+ * ad_lens exactly as in avrf_thin_batch_stage_shared.  avrf_thin_batch_verify_shared_wire is stage + avrf_thin_batch_run.
+ *   indices   checked on the host before anything is staged: a failure is AVRF_ERR_BAD_ARG and the context keeps what it had
+ *             staged.  avrf_pool_submit_shared_wire checks on the submitting thread, before a ticket exists.
+ *   decoding  one kernel launch per staging decodes EVERY table row -- referenced or not --, every output and every R, each
+ *             once: a row costs one square root however many items refer to it.  validate = 0: the point must decode
+ *             (Validate::No).  validate != 0: it must also be non-identity and in the prime-order subgroup (Validate::Yes,
+ *             src/lib.rs:410-433).  THIS DIFFERS FROM THE x || y FLAVOUR ABOVE: under validate != 0 an identity row is refused
+ *             even when nothing refers to it, because deserialising a key or an input with Validate::Yes refuses the identity.
+ *             With validate = 0 an identity row decodes; the run then refuses it (AVRF_INVALID_DATA) only if it is
+ *             referenced, as in the x || y flavour.
+ *   failure   a point that fails makes the stage call return AVRF_INVALID_DATA with nothing staged (a following run answers
+ *             as after a failed avrf_thin_batch_stage_wire); in the pool the verdict is AVRF_INVALID_DATA, which
+ *             avrf_pool_resubmit with from_host = 0 and the cycle mode repeat, while from_host = 1 stages again from the
+ *             eight host buffers.
+ *   after     the staged batch is a shared-table batch in every respect: term layout and avrf_thin_shared_n_terms as above,
+ *             every run entry point, the pool's wait / resubmit / cycle.  avrf_ctx_set_validation keeps acting on the staged
+ *             x || y points at every run, independently of `validate`. */
+int avrf_thin_batch_stage_shared_wire(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared,
+                                      const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs,
+                                      const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                      const uint8_t *proofs, int validate);
+int avrf_thin_batch_verify_shared_wire(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared,
+                                       const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs,
+                                       const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                       const uint8_t *proofs, int validate);
 
 /* ---- Ownership of host buffers; page-locked memory (SURVEY.md 8b "Ownership").
  * Every entry point copies what it needs out of the caller's buffers before it returns, EXCEPT avrf_pool_submit (below), whose
@@ -247,6 +275,13 @@ int avrf_pool_submit_wire(avrf_pool *pool, size_t n, const uint8_t *pks, const u
 int avrf_pool_submit_shared(avrf_pool *pool, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index,
                             const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts,
                             const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket);
+/* avrf_pool_submit_shared_wire (kind 1 pools): the same job from wire bytes, arguments and contract as
+ * avrf_thin_batch_stage_shared_wire above; ownership as avrf_pool_submit_shared: all eight host buffers stay untouched until the
+ * verdict is out, and are read again by every avrf_pool_resubmit with from_host = 1. */
+int avrf_pool_submit_shared_wire(avrf_pool *pool, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index,
+                                 const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
+                                 const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
+                                 uint64_t *ticket);
 int avrf_pool_wait(avrf_pool *pool, uint64_t ticket, int *status);
 int avrf_pool_resubmit(avrf_pool *pool, uint64_t ticket, int from_host, uint64_t *new_ticket);
 int avrf_pool_cycle(avrf_pool *pool, int from_host, uint64_t steps_block, double min_seconds, uint64_t max_steps, int expect_status,
