@@ -150,8 +150,23 @@ def thin_shared_n_terms(n, tot_io, n_shared):
     return f(C.c_size_t(n), C.c_size_t(tot_io), C.c_size_t(n_shared))
 
 
+SEGMENT_TERMS_MAX, SEGMENTS_PADDED_TERMS_MAX, SEGMENTS_WINDOWS_MAX = 8191, 1 << 20, 65535   # include/avrf.h AVRF_SEGMENT*
+
+
+def thin_segments_layout(seg_items, io_counts):
+    """Layout of a segmented Thin run (host arithmetic; no device needed): seg_items items per segment over the items whose I/O pair
+    counts are io_counts -> (L, padded terms, total terms, window bits), or ERR_BAD_ARG when the counts do not sum to
+    len(io_counts) or a limit of include/avrf.h is exceeded."""
+    seg_items, io_counts = list(seg_items), list(io_counts)
+    out = (C.c_uint64 * 4)()
+    st = lib().avrf_thin_segments_layout(C.c_size_t(len(io_counts)), C.c_size_t(len(seg_items)), _u32(seg_items), _u32(io_counts), out)
+    return tuple(out) if st == OK else st
+
+
 class Context:
     """One engine instance = suite + HIP stream + device workspace (avrf_ctx)."""
+
+    thin_segments_layout = staticmethod(thin_segments_layout)
 
     def __init__(self, suite=BANDERSNATCH_SHA512_ELL2, device=0):
         self._h = C.c_void_p()
@@ -224,6 +239,49 @@ class Context:
 
     def thin_batch_run(self):
         return lib().avrf_thin_batch_run(self._h)
+
+    # -- one verdict per segment of the staged Thin batch (include/avrf.h avrf_thin_batch_run_segments)
+    def thin_batch_run_segments(self, seg_items):
+        """seg_items: items per segment, consecutive, summing to the staged n -> list of statuses, or the refusal (ERR_BAD_ARG)."""
+        seg_items = list(seg_items)
+        out = (C.c_int32 * max(1, len(seg_items)))()
+        st = lib().avrf_thin_batch_run_segments(self._h, C.c_size_t(len(seg_items)), _u32(seg_items), out)
+        return list(out)[: len(seg_items)] if st == OK else st
+
+    def thin_batch_verify_segments(self, b, seg_items):
+        """stage + thin_batch_run_segments for a Batch."""
+        seg_items = list(seg_items)
+        out = (C.c_int32 * max(1, len(seg_items)))()
+        st = lib().avrf_thin_batch_verify_segments(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs,
+                                                   C.c_size_t(len(seg_items)), _u32(seg_items), out)
+        return list(out)[: len(seg_items)] if st == OK else st
+
+    def thin_batch_verify_segments_wire(self, b, seg_items, validate=1):
+        """The same for a Batch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes (compressed points)."""
+        seg_items = list(seg_items)
+        out = (C.c_int32 * max(1, len(seg_items)))()
+        st = lib().avrf_thin_batch_verify_segments_wire(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs,
+                                                        int(validate), C.c_size_t(len(seg_items)), _u32(seg_items), out)
+        return list(out)[: len(seg_items)] if st == OK else st
+
+    def thin_segment_terms(self, seg):
+        """(bases_xy, scalars) the last segmented run built for segment `seg`, as last_terms gives the plain run's."""
+        f = lib().avrf_thin_segment_terms
+        f.restype = C.c_size_t
+        k = f(self._h, C.c_size_t(seg), None, None)
+        bases, sc = (C.c_uint8 * max(1, 64 * k))(), (C.c_uint8 * max(1, 32 * k))()
+        assert f(self._h, C.c_size_t(seg), bases, sc) == k
+        return bytes(bases)[: 64 * k], bytes(sc)[: 32 * k]
+
+    def msm_segments(self, n_seg, bases_xy, scalars):
+        """n_seg independent MSMs of L = len(scalars) / 32 / n_seg terms in one call -> list of n_seg result points (x || y)."""
+        L = len(scalars) // 32 // n_seg if n_seg else 0
+        assert len(scalars) == 32 * n_seg * L and len(bases_xy) == 64 * n_seg * L
+        out = (C.c_uint8 * max(1, 64 * n_seg))()
+        st = lib().avrf_msm_te_segments(self._h, C.c_size_t(n_seg), C.c_size_t(L), _u8(bases_xy), _u8(scalars), out)
+        if st != OK:
+            raise AvrfError(f"avrf_msm_te_segments -> {st}")
+        return [bytes(out)[64 * v: 64 * v + 64] for v in range(n_seg)]
 
     def pedersen_batch_verify(self, items_ios_xy, ads, proofs):
         b = Batch.from_items(items_ios_xy, ads, proofs=proofs)

@@ -16,6 +16,8 @@
 #include "proto_dev.h"
 #include "vrf_batch.h"
 #include "thin_shared.h"
+#include "thin_seg.h"
+#include "host_pool.h"
 #include "suite_dispatch.h"
 #include <chrono>
 #include <optional>
@@ -755,6 +757,190 @@ int avrf_pedersen_batch_verify(avrf_ctx *c, size_t n, const uint8_t *ios_xy, con
                                const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   int st = avrf_pedersen_batch_stage(c, n, ios_xy, io_counts, ads, ad_lens, proofs);
   return st ? st : avrf_pedersen_batch_run(c);
+}
+
+// ---------------------------------------------------------------- one verdict per segment of the staged Thin batch (thin_seg.h)
+}  // extern "C"
+
+// The layout of n_seg thin::BatchVerifiers over consecutive runs of n staged items (include/avrf.h avrf_thin_segments_layout): item
+// offsets into *seg_off (n_seg + 1) when wanted, out = { L, n_seg L, sum of the term counts, window bits }; io_off: n + 1 prefix sums of
+// the items' pair counts.  AVRF_ERR_BAD_ARG when the counts do not sum to n or a limit is exceeded.
+static int seg_limits(size_t n_seg, uint64_t L, uint64_t out[4]) {
+  if (L > (uint64_t)AVRF_SEGMENT_TERMS_MAX || n_seg * L > (uint64_t)AVRF_SEGMENTS_PADDED_TERMS_MAX) return AVRF_ERR_BAD_ARG;
+  const uint64_t c = L ? (uint64_t)msm_segments_window_bits(L) : 0;
+  // (windows of a 256-bit scalar: no suite's are more; fewer than eight segments run one after the other, msm.h msm_te_segments)
+  if (n_seg >= 8 && L && n_seg * ((257 + c - 1) / c) > (uint64_t)AVRF_SEGMENTS_WINDOWS_MAX) return AVRF_ERR_BAD_ARG;
+  out[0] = L; out[1] = n_seg * L; out[3] = c;
+  return AVRF_OK;
+}
+static int seg_layout(size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_off, std::vector<uint32_t> *seg_off, uint64_t out[4]) {
+  if ((n_seg && !seg_items) || n_seg > 0x0fffffffULL || (n && !io_off)) return AVRF_ERR_BAD_ARG;
+  if (seg_off) seg_off->assign(n_seg + 1, (uint32_t)n);
+  uint64_t at = 0, L = 0, total = 0;
+  for (size_t v = 0; v < n_seg; v++) {
+    const uint64_t items = seg_items[v];
+    if (at + items > n) return AVRF_ERR_BAD_ARG;
+    if (seg_off) (*seg_off)[v] = (uint32_t)at;
+    const uint64_t n_v = items ? 2 * items + 2 * (uint64_t)(io_off[at + items] - io_off[at]) + 1 : 0;   // src/thin.rs:282-317; none for an empty segment
+    if (n_v > L) L = n_v;
+    total += n_v; at += items;
+  }
+  if (at != n) return AVRF_ERR_BAD_ARG;
+  out[2] = total;
+  return seg_limits(n_seg, L, out);
+}
+
+extern "C" {
+
+int avrf_thin_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_counts, uint64_t out[4]) {
+  if (!out || (n && !io_counts) || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  std::vector<uint32_t> io_off(n + 1);
+  uint64_t a = 0;
+  for (size_t j = 0; j < n; j++) { io_off[j] = (uint32_t)a; a += io_counts[j]; }
+  if (a > 0x1fffffffULL) return AVRF_ERR_BAD_ARG;
+  io_off[n] = (uint32_t)a;
+  return seg_layout(n, n_seg, seg_items, io_off.data(), nullptr, out);
+}
+
+int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  if (!c || ctx_busy(c) || c->staged_kind != Thin || c->n_shared || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
+  std::vector<uint32_t> seg_off; uint64_t lay[4];
+  if (int e = seg_layout(c->n, n_seg, seg_items, c->h_io.as<uint32_t>(), &seg_off, lay)) return e;
+  for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;          // what an empty segment keeps (src/thin.rs:262-264)
+  if (!n_seg || !c->n) return AVRF_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = c->n, L = (size_t)lay[0], padded = (size_t)lay[1];
+  const KindFacts &k = kind_facts(Thin);
+  HIP_TRY(c->d_seg_scalars.ensure(padded * 32)); HIP_TRY(c->d_seg_pre.ensure(padded * sizeof(te_pre_raw))); HIP_TRY(c->d_seg_wsz.ensure(n * 32));
+  HIP_TRY(c->d_seg_off.ensure((n_seg + 1) * 4)); HIP_TRY(c->d_seg_seeds.ensure(n_seg * sizeof(Seed64)));
+  // prepare once, for all segments: k_thin_prepare knows nothing about batches, and its records are contiguous per item
+  const double t0 = now_us();
+  if (int e = batch_begin(c, Thin)) return e;
+  c->run_phase = 0;                                                    // (the phases below are this call's own; an error leaves the context idle)
+  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
+  // The flag word is the batch's.  Only when it is set: which items raised it -- the prepare kernel's checks again, per item, and
+  // the validation with a status per item (the clean case pays nothing).
+  std::vector<int32_t> item_status;
+  if (*c->h_flags.as<uint32_t>()) {
+    item_status.resize(n);
+    HIP_TRY(c->d_status.ensure(n * 4));
+    HIP_TRY(hipMemsetAsync(c->d_status.p, 0, n * 4, c->stream));
+    AVRF_SEG(c->suite, item_flags(batch_of(c), c->d_status.as<int32_t>(), c->stream));
+    validate_staged(c, Thin, c->d_status.as<int32_t>());
+    HIP_TRY(hipMemcpyAsync(item_status.data(), c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
+  }
+  // the n_seg weight transcripts, each SUITE_ID || 0x50 || its own records (src/thin.rs:274-279), on the process's host pool
+  const double t1 = now_us();
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+  BatchDev b = batch_of(c);
+  std::vector<Seed64> seeds(n_seg);
+  if (!suite_host_weights(c->suite)) {
+    // counter-mode transcripts: sixteen messages at a time through the multi-buffer hash; a group builds its messages itself
+    const size_t recsz = k.record();
+    const uint8_t *rec = c->h_msg.as<uint8_t>() + pl;
+    c->h_seg_msg.resize(n_seg * pl + n * recsz);
+    parallel_for((n_seg + 15) / 16, [&](size_t g) {
+      WeightJob jobs[16]; WeightJob *pj[16]; int cnt = 0;
+      for (size_t v = 16 * g; v < n_seg && v < 16 * g + 16; v++, cnt++) {
+        const size_t first = seg_off[v], items = seg_off[v + 1] - first;
+        uint8_t *m = c->h_seg_msg.data() + v * pl + first * recsz;
+        memcpy(m, prefix, pl); memcpy(m + pl, rec + first * recsz, items * recsz);
+        jobs[cnt] = WeightJob::whole(m, pl + items * recsz); pj[cnt] = &jobs[cnt];
+      }
+      sha512_many(pj, cnt);
+      for (int i = 0; i < cnt; i++) seeds[16 * g + i] = seed_of(jobs[i].digest);
+    });
+    HIP_TRY(hipMemcpyAsync(c->d_seg_seeds.p, seeds.data(), n_seg * sizeof(Seed64), hipMemcpyHostToDevice, c->stream));
+  } else {
+    // sponge / SHA-256 transcripts: every segment's weight stream squeezed on the host, item j's 16 bytes at 16 j
+    c->h_weights.resize(n * k.weight);
+    parallel_for(n_seg, [&](size_t v) {
+      const size_t first = seg_off[v], items = seg_off[v + 1] - first;
+      if (!items) return;
+      with_suite(c->suite, [&](auto tag_) {
+        using S = typename decltype(tag_)::type;
+        std::conditional_t<S::XOF_SHAKE, HostShake128, HostSha256> h;
+        absorb_weight_message(h, prefix, pl, items, c->h_c.as<uint8_t>() + 16 * first, c->h_resp.data() + k.resp * first, k.resp);
+        h.squeeze_copy(c->h_weights.data() + k.weight * first, items * k.weight);
+      });
+    });
+    HIP_TRY(c->d_weights.ensure(n * k.weight));
+    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), n * k.weight, hipMemcpyHostToDevice, c->stream));
+    b.weights = c->d_weights.as<uint8_t>();
+  }
+  // terms into the padded layout (the padding scalars are zeroed on every run), then all segments' MSMs in one chain
+  const double t2 = now_us();
+  HIP_TRY(hipMemcpyAsync(c->d_seg_off.p, seg_off.data(), (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_seg_scalars.p, 0, padded * 32, c->stream));
+  AVRF_SEG(c->suite, thin_terms(b, c->d_seg_off.as<uint32_t>(), (uint32_t)n_seg, (uint32_t)L, c->d_seg_seeds.as<Seed64>(), c->d_c.as<uint32_t>(),
+                                c->d_z.as<uint32_t>(), c->d_seg_wsz.as<uint32_t>(), c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
+  const double t3 = now_us();
+  std::vector<HostExt> sums(n_seg);
+  if (int e = guarded([&] { return msm_te_segments(c->suite, c->d_seg_pre.as<te_pre_raw>(), c->d_seg_scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->stream, sums.data()) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  for (size_t v = 0; v < n_seg; v++) {
+    if (seg_off[v] == seg_off[v + 1]) continue;
+    status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322
+    for (size_t j = seg_off[v]; !item_status.empty() && j < seg_off[v + 1]; j++) if (item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // :266-271
+  }
+  c->seg_gen = c->stage_gen; c->seg_L = L; c->seg_off = std::move(seg_off);
+  // avrf_last_timing: prepare + its wait (and the attribution pass), the transcripts, the terms launches, the MSM chain with its wait
+  const double t4 = now_us();
+  c->timing[1] = t1 - t0; c->timing[2] = t2 - t1; c->timing[3] = t3 - t2; c->timing[4] = t4 - t3; c->timing[5] = 0; c->timing[0] = t4 - t0;
+  return AVRF_OK;
+}
+
+int avrf_thin_batch_verify_segments(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
+                                    const uint32_t *ad_lens, const uint8_t *proofs, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  int st = avrf_thin_batch_stage(c, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs);
+  return st ? st : avrf_thin_batch_run_segments(c, n_seg, seg_items, status_out);
+}
+int avrf_thin_batch_verify_segments_wire(avrf_ctx *c, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                                         const uint32_t *ad_lens, const uint8_t *proofs, int validate, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  int st = avrf_thin_batch_stage_wire(c, n, pks, ios, io_counts, ads, ad_lens, proofs, validate);
+  return st ? st : avrf_thin_batch_run_segments(c, n_seg, seg_items, status_out);
+}
+
+// the terms of one segment of the last segmented run, as avrf_batch_last_terms gives the plain run's
+size_t avrf_thin_segment_terms(avrf_ctx *c, size_t seg, uint8_t *bases_xy, uint8_t *scalars) {
+  if (!c || ctx_busy(c) || c->staged_kind != Thin || c->seg_gen != c->stage_gen || seg + 1 >= c->seg_off.size()) return 0;
+  if (hipSetDevice(c->device) != hipSuccess) return 0;
+  const uint32_t *io_off = c->h_io.as<uint32_t>();
+  const size_t first = c->seg_off[seg], items = c->seg_off[seg + 1] - first;
+  if (!items) return 0;
+  const size_t cnt = 2 * items + 2 * (size_t)(io_off[first + items] - io_off[first]) + 1, t0 = seg * c->seg_L;
+  if (scalars) { if (hipMemcpy(scalars, c->d_seg_scalars.as<uint8_t>() + 32 * t0, cnt * 32, hipMemcpyDeviceToHost) != hipSuccess) return 0; }
+  if (bases_xy) {
+    std::vector<te_pre_raw> pre(cnt);
+    if (hipMemcpy(pre.data(), c->d_seg_pre.as<te_pre_raw>() + t0, cnt * sizeof(te_pre_raw), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    for (size_t i = 0; i < cnt; i++) {
+      H256 x, y; memcpy(x.l, pre[i].w, 32); memcpy(y.l, pre[i].w + 8, 32);
+      with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; x = HostField<typename S::Fq>::from_mont(x); y = HostField<typename S::Fq>::from_mont(y); });
+      memcpy(bases_xy + 64 * i, x.l, 32); memcpy(bases_xy + 64 * i + 32, y.l, 32);
+    }
+  }
+  return cnt;
+}
+
+// n_seg independent MSMs of L terms through the segmented chain (msm.h msm_te_segments), beside avrf_msm_te
+int avrf_msm_te_segments(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy) {
+  if (!c || ctx_busy(c) || (n_seg && !out_xy) || (n_seg && L && (!bases_xy || !scalars)) || n_seg > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  uint64_t lay[4];
+  if (int e = seg_limits(n_seg, L, lay)) return e;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = n_seg * L;
+  for (size_t i = 0; i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
+  std::vector<HostExt> sums(n_seg);
+  if (n) {
+    if (int e = upload_bases_and_scalars(c, n, bases_xy, scalars, n * 32)) return e;
+    launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
+    HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  c->staged_kind = 0;
+  if (int e = guarded([&] { return msm_te_segments(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->stream, sums.data()) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
+  for (size_t v = 0; v < n_seg; v++) finish_point(c, sums[v], out_xy + 64 * v);
+  return AVRF_OK;
 }
 
 // ---------------------------------------------------------------- one batch split over several GPUs

@@ -78,6 +78,11 @@ struct avrf_ctx {
   avrf::DevBuf d_tabs;                               // per-item window tables of the independent prove / verify kernels
   avrf::DevBuf d_fixed; bool fixed_ready = false;   // fixed-base tables of G and BLINDING_BASE (provers, scalar_mul_base), built on first use
   avrf::PinBuf h_c, h_flags, h_io;
+  // the last segmented run of the staged batch (avrf_thin_batch_run_segments; thin_seg.h): terms of its own, n_seg * seg_L of them, so
+  // that the plain run's terms stay what they were; seg_off (n_seg + 1 item offsets) describes them while seg_gen == stage_gen
+  uint64_t seg_gen = 0; size_t seg_L = 0; std::vector<uint32_t> seg_off;
+  avrf::DevBuf d_seg_scalars, d_seg_pre, d_seg_wsz, d_seg_off, d_seg_seeds;
+  std::vector<uint8_t> h_seg_msg;   // the segments' weight-transcript messages, prefix || records each
   double timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int run_phase = 0;              // batch_begin / batch_hash / batch_end
   bool unit_weights = false;      // batch_launch: every item's weight is 1 (avrf_thin_verify runs ONE item as its own equation through the MSM path)

@@ -121,6 +121,14 @@ int msm_te_finish(int suite, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream
 // form: out[v] = sum_t s_{v,t} P_t.  Synchronises the stream.  Returns -1 when the shape is not the single-launch one.
 int msm_te_small_vectors(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, size_t n_vectors, MsmWorkspace &ws, hipStream_t stream,
                          HostExt *out);
+// n_seg independent MSMs in one chain: segment v is the L bases at d_pre + v * L with the L scalars at d_scalars + 8 v L, out[v] its
+// sum.  A zero scalar is never gathered, so segments shorter than L are padded with zero scalars and the padding bases need not be
+// initialised.  n_seg >= 8: one Pippenger chain of n_seg * nwin virtual windows with the Horner on the device; fewer: the single-MSM
+// path, once per segment.  Synchronises the stream.  Returns -1 (nothing launched) beyond the limits below.
+constexpr size_t MSM_SEG_TERMS_MAX = 8191;          // L: keeps nb <= 256, so one reduction kernel (k_bits_direct)
+constexpr size_t MSM_SEG_WINDOWS_MAX = 65535;       // n_seg * nwin: the sort kernels carry the virtual window in blockIdx.y
+int msm_te_segments(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out);
+int msm_segments_window_bits(size_t L);             // the window width msm_plan gives an L-term MSM (host arithmetic)
 bool msm_te_pending_supported(int suite);   // a caller's record is taken by the window-sum form of the chain only
 
 // G1 MSM over a short-Weierstrass curve (curve: 0 BLS12-381, 1 BN254): d_bases = n Montgomery affine

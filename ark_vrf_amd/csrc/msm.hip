@@ -241,10 +241,11 @@ k_plan(const uint32_t *__restrict__ win_tot, uint32_t vwin, uint32_t lanes_targe
 
 // remap_n != 0 (fixed-base tables): key position p = dw * remap_n + i refers to table entry dw * remap_stride + i
 // (or dw * remap_stride + bidx[v][i] when the vector names its own bases)
+// base_stride != 0 (segmented MSMs, msm_te_segments): vector w / nwin multiplies bases of its own, which start at (w / nwin) * base_stride
 __global__ void __launch_bounds__(256)
 k_scatter(const uint16_t *__restrict__ keys, uint32_t n, uint32_t tile_len, int c, const uint32_t *__restrict__ H,
           const uint32_t *__restrict__ offs, uint32_t *__restrict__ sorted, uint32_t remap_n, uint32_t remap_stride,
-          const uint32_t *__restrict__ bidx, uint32_t ntiles, uint32_t vwin) {
+          const uint32_t *__restrict__ bidx, uint32_t ntiles, uint32_t vwin, uint32_t nwin, uint32_t base_stride) {
   extern __shared__ uint32_t lds[];
   // XCD-aware placement: workgroups go round-robin over the 8 XCDs by linear id, and every XCD has its own L2.  All tiles of a
   // window run on ONE XCD (window w on XCD w mod 8), so the 4-byte scattered stores into that window's region of sorted[]
@@ -253,6 +254,7 @@ k_scatter(const uint16_t *__restrict__ keys, uint32_t n, uint32_t tile_len, int 
   const uint32_t nb = 1u << (c - 1);
   const uint32_t xcd = blockIdx.x & 7u, k = blockIdx.x >> 3, tile = k % ntiles, w = xcd + 8u * (k / ntiles);
   if (w >= vwin) return;
+  const uint32_t base0 = base_stride ? (w / nwin) * base_stride : 0u;   // (0 for every launch over shared bases: the stored index is i, as ever)
   const uint32_t *Hin = H + ((size_t)w * ntiles + tile) * nb;
   for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) lds[b] = offs[(size_t)w * nb + b] + Hin[b];
   __syncthreads();
@@ -262,7 +264,7 @@ k_scatter(const uint16_t *__restrict__ keys, uint32_t n, uint32_t tile_len, int 
     uint32_t key = kw[i], b = key & 0x7fffu;
     if (b) {
       uint32_t pos = atomicAdd(&lds[b - 1], 1u);
-      uint32_t idx = i;
+      uint32_t idx = i + base0;
       if (remap_n) {                                      // bidx: per-vector base indices (sparse MSMs over a shared table)
         uint32_t j = i % remap_n;
         idx = (i / remap_n) * remap_stride + (bidx ? bidx[(size_t)w * remap_n + j] : j);
@@ -506,6 +508,35 @@ k_horner(const uint32_t *__restrict__ bits, uint32_t nbits, uint32_t batch, uint
     acc = CV::add(acc, CV::load_acc(T + (size_t)i * CV::ACC_WORDS));
   }
   CV::store_acc(out + (size_t)b * CV::ACC_WORDS, acc);
+}
+
+// The same Horner for the segmented twisted-Edwards chain (msm_te_segments), a WAVE per MSM with a point spread over the four lanes of
+// a quad (te_quad.h).  A lane per MSM walks nbits one-lane doublings and additions one after the other, and a SIMD retires those no
+// faster for four waves than for sixty-four: 2.9 ms for 256 MSMs of 259 bit sums, two thirds of the whole segmented call.  Here quad q
+// of the wave folds the m = ceil(nbits / 16) bit sums from q m on (m two-round doublings and three-round additions), then a tree over
+// the quads shifts the upper half by s m doublings and adds it, s = 1, 2, 4, 8: 15 m doublings in a row -- the 2^252 of the top bits,
+// which no arrangement avoids -- but only four more additions.  All 64 lanes stay active throughout (the DPP moves of q_add / q_dbl
+// need whole quads); only quad 0's result is kept.
+template <class S>
+__global__ void __launch_bounds__(64)
+k_horner_quads(const uint32_t *__restrict__ bits, uint32_t nbits, uint32_t *__restrict__ out) {
+  const uint32_t v = blockIdx.x, q = threadIdx.x >> 2, j = threadIdx.x & 3, m = (nbits + 15) / 16;
+  const uint32_t *T = bits + (size_t)v * nbits * 32 + j * 8;          // coordinate j of te_ext x | y | t | z
+  fp acc = q_identity<S>(j);
+#pragma unroll 1
+  for (int i = (int)m - 1; i >= 0; i--) {
+    const uint32_t p = q * m + (uint32_t)i;
+    acc = q_dbl<S>(acc, j);
+    acc = q_add<S>(acc, p < nbits ? fp_load(T + (size_t)p * 32) : q_identity<S>(j), j);
+  }
+#pragma unroll 1
+  for (uint32_t s = 1; s < 16; s <<= 1) {
+    fp o = fp_shfl_down(acc, 4 * (int)s);                             // quad q + s (what the quads without such a partner compute is dropped)
+#pragma unroll 1
+    for (uint32_t d = 0; d < s * m; d++) o = q_dbl<S>(o, j);
+    acc = q_add<S>(acc, o, j);
+  }
+  if (q == 0) fp_store(out + (size_t)v * 32 + j * 8, acc);
 }
 
 // Fixed-base (table) batched MSMs have ONE bucket set per MSM: out[set] = sum_b b * B_b.  A group of 2^lps_log lanes
@@ -781,6 +812,7 @@ struct MsmLaunch {
   const uint32_t *d_base_idx = nullptr;  // sparse form (msm.h msm_g1_fixed_device)
   bool defer = false;                    // everything up to the copies back is enqueued, nothing is waited for: the caller collects later (msm_collect)
   int scalars_mont = 0;                  // the scalars are Montgomery limbs (msm.h msm_g1_fixed_device)
+  size_t base_stride = 0;                // segmented form (msm.h msm_te_segments): vector v multiplies bases [v * base_stride, v * base_stride + n); 0: shared bases
 };
 
 // Runs the whole device pipeline for one MSM and leaves the nwin*c bit sums T_p in rec.bits_host (accumulator layout of CV).
@@ -795,7 +827,7 @@ static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t
   MsmPlan p = msm_plan(n_in, scalar_bits);
   auto finish = [&]() { if (!o.defer) msm_collect(ws, rec, stream); };
   // (the G1 callers take eight or more vectors back as finished points -- device Horner below -- so they keep that form)
-  if (n_in <= MSM_TINY_TERMS && batch <= (CV::FIXED_TABLE ? (size_t)7 : MSM_TINY_VECTORS) && !table_c && !d_base_idx && !scalars_mont && msm_env().tiny) {
+  if (n_in <= MSM_TINY_TERMS && batch <= (CV::FIXED_TABLE ? (size_t)7 : MSM_TINY_VECTORS) && !table_c && !d_base_idx && !scalars_mont && !o.base_stride && msm_env().tiny) {
     p.c = 1; p.nwin = scalar_bits; p.nb = 1; p.lpb = 0;
     const size_t acc_b = (size_t)CV::ACC_WORDS * 4, nbits = (size_t)scalar_bits;
     ws.ensure(n_in, p, acc_b, batch, 256);
@@ -839,7 +871,7 @@ static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t
   hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, stream, ws.win_tot.as(), vwin, (uint32_t)lanes_target, (uint32_t)msm_env().per_min,
                      ws.lane_base.as(), ws.plan_dev.as());
   hipLaunchKernelGGL(k_scatter, dim3(8u * ((vwin + 7u) / 8u) * ntiles), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)n, tile_len, p.c, ws.hist.as(),
-                     ws.offsets.as(), ws.sorted.as(), remap_n, remap_stride, d_base_idx, ntiles, vwin);
+                     ws.offsets.as(), ws.sorted.as(), remap_n, remap_stride, d_base_idx, ntiles, vwin, (uint32_t)p.nwin, (uint32_t)o.base_stride);
   rec.ensure((size_t)vwin * 3 * acc_bytes);   // the window triples, which are all a caller's record is sent (the workspace's own is sized with `bits`)
   if (CV::ZERO_IS_IDENTITY) HIP_CHECK(hipMemsetAsync(ws.buckets.p, 0, (size_t)nbk * acc_bytes, stream));   // empty buckets
   HIP_CHECK(hipEventRecord(rec.ev0, stream));
@@ -904,8 +936,13 @@ static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t
                        p.c, h, (uint32_t)nbits, ws.bits.as());
   }
   if (batch >= 8) {                                        // device Horner: only `batch` points come back
-    hipLaunchKernelGGL(k_horner<CV>, dim3(((unsigned)batch + 63) / 64), dim3(64), 0, stream, ws.bits.as(), (uint32_t)(p.nwin * p.c),
-                       (uint32_t)batch, ws.rc.as());
+    bool quads = false;                                    // the segmented chain of a twisted-Edwards suite: a wave per MSM
+    if constexpr (CV::QUAD) if (o.base_stride) {
+      hipLaunchKernelGGL(k_horner_quads<typename CV::suite>, dim3((unsigned)batch), dim3(64), 0, stream, ws.bits.as(), (uint32_t)(p.nwin * p.c), ws.rc.as());
+      quads = true;
+    }
+    if (!quads) hipLaunchKernelGGL(k_horner<CV>, dim3(((unsigned)batch + 63) / 64), dim3(64), 0, stream, ws.bits.as(), (uint32_t)(p.nwin * p.c),
+                                   (uint32_t)batch, ws.rc.as());
     HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * acc_bytes, hipMemcpyDeviceToHost, stream));
   } else {
     HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, (size_t)nbits * acc_bytes, hipMemcpyDeviceToHost, stream));
@@ -976,6 +1013,39 @@ int msm_te_small_vectors(int suite, const te_pre_raw *d_pre, const uint32_t *d_s
   if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
   return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_small_vectors_impl<S>(d_pre, d_scalars, n, n_vectors, ws, stream, out); });
 }
+// n_seg independent MSMs of L terms each in ONE chain: vector v over bases of its own (MsmLaunch::base_stride), bucket sums by
+// k_bits_direct (L <= 8191 keeps nb <= 256), the Horner on the device, n_seg finished points back.  Fewer than MSM_SEG_CHAIN_MIN
+// vectors would take the chain's host-Horner form: they loop the single-MSM path instead.
+constexpr size_t MSM_SEG_CHAIN_MIN = 8;
+template <class S>
+static int msm_te_segments_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
+  using HT = HostTe<S>;
+  for (size_t v = 0; v < n_seg; v++) out[v] = HT::identity();
+  if (!L || !n_seg) return 0;
+  if (L > MSM_SEG_TERMS_MAX || n_seg * L > 0x7fffffffull) return -1;
+  if (n_seg < MSM_SEG_CHAIN_MIN) {
+    for (size_t v = 0; v < n_seg; v++) {
+      if (int e = msm_te_enqueue_impl<S>(d_pre + v * L, d_scalars + 8 * v * L, L, ws, ws.own, stream)) return e;
+      if (int e = msm_te_finish_impl<S>(ws, ws.own, stream, out + v)) return e;
+    }
+    return 0;
+  }
+  const MsmPlan p = msm_plan(L, S::Fr::BITS);
+  const size_t vwin = n_seg * (size_t)p.nwin;
+  // k_hist / k_scan_tiles take the virtual window as blockIdx.y; the sorted array is addressed by 32-bit entry offsets
+  if (vwin > MSM_SEG_WINDOWS_MAX || vwin * L >= 0xffff0000ull) return -1;
+  MsmLaunch o; o.batch = n_seg; o.scalar_stride = L; o.base_stride = L;
+  msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, L, S::Fr::BITS, ws, ws.own, stream, o);
+  ws.own.disarm();
+  const uint32_t *bh = ws.own.bits_host.as();
+  for (size_t v = 0; v < n_seg; v++) out[v] = HT::from_raw32(bh + v * 32);
+  return 0;
+}
+int msm_te_segments(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
+  if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
+  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_segments_impl<S>(d_pre, d_scalars, L, n_seg, ws, stream, out); });
+}
+int msm_segments_window_bits(size_t L) { return msm_plan(L, 256).c; }
 bool msm_te_pending_supported(int suite) {
   if (suite < 0 || suite >= AVRF_N_SUITES || !msm_env().window_sums) return false;
   return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)TeCurve<S>::WINDOW_SUMS; });

@@ -210,6 +210,63 @@ int avrf_thin_batch_verify_shared_wire(avrf_ctx *ctx, size_t n, size_t n_shared,
                                        const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
                                        const uint8_t *proofs, int validate);
 
+/* ---- thin::BatchVerifier over SEGMENTS of one staged batch: one verdict per group of items (src/thin.rs:188-326).
+ * n_seg independent BatchVerifiers over consecutive runs of the staged items -- segment v covers the next seg_items[v] items,
+ * the counts sum to n -- each with its own weight transcript (src/thin.rs:274-279 over ITS items only) and its own verdict, in
+ * one pass over the device: one prepare launch, one copy back, the n_seg transcripts hashed in groups, one terms pass, ONE MSM
+ * chain of n_seg * windows virtual windows, n_seg points back.  For a caller whose big batch failed (segments of a few hundred
+ * items locate the bad ones; avrf_thin_verify then runs on the failing segments only) and for a caller with many small
+ * batches (a block importer: one verdict per block).
+ *   statuses  status_out[v] is what avrf_thin_batch_verify answers for segment v's items alone: AVRF_OK,
+ *             AVRF_VERIFICATION_FAILURE or AVRF_INVALID_DATA; an empty segment is AVRF_OK (src/thin.rs:262-264).  An identity
+ *             key or I/O point, a non-canonical coordinate, a scalar >= r, or under avrf_ctx_set_validation 1 / 2 a point
+ *             that fails, marks ITS segment AVRF_INVALID_DATA and no other.  The call itself returns AVRF_OK whenever the
+ *             statuses were written.
+ *   limits    a segment has at most AVRF_SEGMENT_TERMS_MAX MSM terms (2 items + 2 pairs + 1); the padded layout at most
+ *             AVRF_SEGMENTS_PADDED_TERMS_MAX terms (n_seg * L, L = the longest segment's term count: about 1.7 KB of device
+ *             workspace per padded term at the narrowest window); n_seg * windows(L) at most AVRF_SEGMENTS_WINDOWS_MAX.
+ *   refusals  AVRF_ERR_BAD_ARG, with the context and its staged batch untouched and usable: counts that do not sum to n, a
+ *             limit exceeded, nothing staged, a Pedersen batch staged, a shared-table batch staged (its merged rows have no
+ *             per-segment meaning), a call between avrf_batch_run_begin and _end.
+ *   after     avrf_thin_batch_run on the same staging gives its usual verdict and avrf_batch_last_terms its usual terms: the
+ *             segmented terms live in buffers of their own.
+ *   terms     (avrf_thin_segment_terms; this layout is ABI) segment v's terms are those of avrf_batch_last_terms for a batch
+ *             of just its items, in the reference's order (src/thin.rs:287-317): R, pk, (O, I).., (G, g_v) last.
+ * avrf_thin_batch_run_segments works on the batch the context holds (avrf_thin_batch_stage / avrf_thin_batch_stage_wire);
+ * avrf_thin_batch_verify_segments / _wire are stage + run_segments with the arguments of avrf_thin_batch_verify / _wire (a
+ * staging error is returned as it is and no status is written).
+ * Runtime (tools/segments_bench.py; one context, 65 536 one-pair items resident): 256 segments of 256 items
+ * 2.43 ms (26.9-27.0 M items/s), 1 024 x 64 3.3 ms, 64 x 1 024 2.8 ms; the same 256 batches as separate pool submissions 33 ms.
+ * avrf_thin_verify on the same items, one verdict per ITEM, takes 2.35-2.39 ms: THE SEGMENTED CALL DOES NOT BEAT IT.  Use segments
+ * to locate a few bad items in a large batch (then avrf_thin_verify on the failing segments only) and for many small batches;
+ * use avrf_thin_verify when most items are suspect.  avrf_last_timing after a segmented run: [1] prepare + wait, [2] the
+ * transcripts, [3] terms launches, [4] MSM chain + wait, [0] their sum (microseconds). */
+enum {
+  AVRF_SEGMENT_TERMS_MAX = 8191,
+  AVRF_SEGMENTS_PADDED_TERMS_MAX = 1 << 20,
+  AVRF_SEGMENTS_WINDOWS_MAX = 65535
+};
+int avrf_thin_batch_run_segments(avrf_ctx *ctx, size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+int avrf_thin_batch_verify_segments(avrf_ctx *ctx, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy,
+                                    const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                    const uint8_t *proofs, size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+int avrf_thin_batch_verify_segments_wire(avrf_ctx *ctx, size_t n, const uint8_t *pks, const uint8_t *ios,
+                                         const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                         const uint8_t *proofs, int validate, size_t n_seg, const uint32_t *seg_items,
+                                         int32_t *status_out);
+/* The layout of a segmented run (src/thin.rs:188-326: term counts of n_seg BatchVerifiers), host arithmetic only, no device:
+ * out = { L, padded terms n_seg * L, total terms (the segments' own counts added up), window bits of the L-term MSMs }.
+ * io_counts has n entries.  AVRF_ERR_BAD_ARG when the counts do not sum to n or a limit above is exceeded. */
+int avrf_thin_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_counts, uint64_t out[4]);
+/* The MSM terms the last avrf_thin_batch_run_segments built for segment `seg` (src/thin.rs:188-326; tests): returns their
+ * number and fills bases_xy (count x 64) / scalars (count x 32) when given; 0 for an empty segment, without a segmented run on
+ * the current staging, or for a busy context. */
+size_t avrf_thin_segment_terms(avrf_ctx *ctx, size_t seg, uint8_t *bases_xy, uint8_t *scalars);
+/* n_seg independent msm_unchecked calls (src/thin.rs:319) of L terms each in one call, beside avrf_msm_te: segment v is
+ * bases_xy[v L ..], scalars[v L ..]; out_xy: n_seg x 64.  n_seg >= 8 runs as one chain, fewer as n_seg single MSMs.
+ * L <= AVRF_SEGMENT_TERMS_MAX and the other limits above, else AVRF_ERR_BAD_ARG. */
+int avrf_msm_te_segments(avrf_ctx *ctx, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy);
+
 /* ---- Ownership of host buffers; page-locked memory (SURVEY.md 8b "Ownership").
  * Every entry point copies what it needs out of the caller's buffers before it returns, EXCEPT avrf_pool_submit (below), whose
  * copies are left in flight.  From ordinary (pageable) memory a copy to the device goes through the runtime's bounce buffers

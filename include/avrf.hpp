@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 #include "avrf.h"
 
@@ -165,12 +166,49 @@ class BatchVerifier {
                                   packed_.ad_lens.data(), proofs_.data());
   }
   size_t len() const { return n_; }
+  // One verdict per segment (avrf_thin_batch_verify_segments): seg_items[v] consecutive pushed items each, summing to len(); what n_seg
+  // BatchVerifiers over those runs of items would answer (:188-326), in one pass over the device.  Throws when the call is refused.
+  std::vector<Status> verify_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_thin_batch_verify_segments(su_.ctx(), n_, pks_.data(), packed_.ios.data(), packed_.io_counts.data(), packed_.ads.data(), packed_.ad_lens.data(),
+                                        proofs_.data(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: thin verify segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+  // the same on the batch the context holds since the last verify() / verify_segments() (avrf_thin_batch_run_segments), e.g. finer
+  // segments over a segment that failed
+  std::vector<Status> run_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_thin_batch_run_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: thin run segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+  // the MSM terms of segment `seg` of the last segmented run (avrf_thin_segment_terms): bases x || y and scalars
+  std::pair<std::vector<uint8_t>, std::vector<uint8_t>> segment_terms(size_t seg) const {
+    const size_t k = avrf_thin_segment_terms(su_.ctx(), seg, nullptr, nullptr);
+    std::vector<uint8_t> bases(64 * k), scalars(32 * k);
+    if (k) avrf_thin_segment_terms(su_.ctx(), seg, bases.data(), scalars.data());
+    return {bases, scalars};
+  }
 
  private:
   const Suite &su_; size_t n_ = 0;
   std::vector<uint8_t> pks_, proofs_; detail::Packed packed_;
   friend class VerifierPool;
 };
+// { L, padded terms, total terms, window bits } of a segmented run (avrf_thin_segments_layout; host arithmetic): throws beyond the limits
+inline std::array<uint64_t, 4> segments_layout(const std::vector<uint32_t> &seg_items, const std::vector<uint32_t> &io_counts) {
+  std::array<uint64_t, 4> out{};
+  if (avrf_thin_segments_layout(io_counts.size(), seg_items.size(), seg_items.data(), io_counts.data(), out.data()) != AVRF_OK) throw std::invalid_argument("avrf: segments layout");
+  return out;
+}
+// n_seg independent msm_unchecked calls of L terms each (avrf_msm_te_segments): bases n_seg * L x 64, scalars n_seg * L x 32 -> n_seg points
+inline std::vector<Point> msm_segments(const Suite &su, size_t n_seg, size_t L, const std::vector<uint8_t> &bases_xy, const std::vector<uint8_t> &scalars) {
+  std::vector<uint8_t> out(64 * n_seg + 1);
+  if (bases_xy.size() != 64 * n_seg * L || scalars.size() != 32 * n_seg * L ||
+      avrf_msm_te_segments(su.ctx(), n_seg, L, bases_xy.data(), scalars.data(), out.data()) != AVRF_OK) throw std::invalid_argument("avrf: msm segments");
+  std::vector<Point> pts(n_seg);
+  for (size_t v = 0; v < n_seg; v++) std::copy(out.begin() + 64 * v, out.begin() + 64 * v + 64, pts[v].begin());
+  return pts;
+}
 
 // Many thin::BatchVerifier::verify calls in flight on one device (avrf_pool, include/avrf.h): submit() hands a filled
 // BatchVerifier over and returns a ticket at once, wait() blocks for that batch's verdict.  The BatchVerifier (its buffers)

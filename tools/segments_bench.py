@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""What the segmented Thin batch verifier (avrf_thin_batch_run_segments) gives against the calls it competes with, on one MI355X in one
+process: 65 536 one-pair items, the legs run alternately, three runs each; a run is the mean of ten calls after two warm-ups.
+    a  thin_batch_run_segments on the resident batch: 256 x 256, 1 024 x 64 and 64 x 1 024 items (and 256 x 256 from the host:
+       stage + run, what thin_verify pays too)
+    b  thin_verify on the same items: one verdict per item
+    c  the same 256 batches of 256 items as separate submissions through an avrf_pool with the headline's slots / lanes / threads
+       (from page-locked host buffers; and the pool's resident cycle over 144 such batches)
+    d  the plain thin_batch_run: one verdict for everything
+Per leg: items/s, and for the context's legs the k_accumulate milliseconds per call (avrf_kernel_stats) and the host-side stage times
+of the segmented call (avrf_last_timing: prepare + wait, transcripts, terms launches, MSM chain + wait).
+python tools/segments_bench.py [n] [--quick] [--legs=abcd] [--shape=ITEMS]
+    --legs: only these legs; --shape=256: of leg a only the segments of that many items (a kernel trace of one leg keeps its kernels apart)"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import oracle as orc  # noqa: E402
+from ark_vrf_amd import _native as nat  # noqa: E402
+
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+n = int(args[0]) if args else 65536
+QUICK = "--quick" in sys.argv
+SLOTS, LANES, THREADS, GROUP, DEPTH = 144, 12, 6, 8, 3
+REPS, CALLS, WARM = (1, 3, 1) if QUICK else (3, 10, 2)
+LEGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--legs=")), "abcd")
+SHAPE = next((int(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--shape=")), None)
+SHAPES = [(n // k, k) for k in (256, 64, 1024) if SHAPE in (None, k)]             # (segments, items per segment)
+
+
+def accum(ctx, reset):
+    ms, cnt = C.c_double(0), C.c_uint64(0)
+    nat.lib().avrf_kernel_stats(ctx._h, 1 if reset else 0, C.byref(ms), C.byref(cnt), None)
+    return ms.value, cnt.value
+
+
+def timed(ctx, call):
+    """mean seconds of CALLS calls after WARM warm-ups; k_accumulate ms and launches per call"""
+    for _ in range(WARM):
+        call()
+    accum(ctx, True)
+    t0 = time.perf_counter()
+    for _ in range(CALLS):
+        call()
+    sec = (time.perf_counter() - t0) / CALLS
+    ms, cnt = accum(ctx, True)
+    return sec, ms / CALLS, cnt / CALLS
+
+
+def main():
+    assert nat.set_blocking_sync(0, True) == 0
+    ctx = nat.Context(0)
+    b = orc.gen_batch(0, 0, n, threads=16)
+    batch = nat.Batch(n, b["ios_xy"], b["io_counts"], b["ads"], b["ad_lens"], pks_xy=b["pks_xy"], proofs=b["proofs"])
+    status = (C.c_int32 * n)()
+    out = dict(n=n, reps=REPS, calls=CALLS, warmups=WARM, pool=dict(slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH), runs=[])
+
+    def record(leg, sec, items=n, **kw):
+        run = dict(leg=leg, items_per_sec=round(items / sec), ms_per_call=round(1e3 * sec, 4), **kw)
+        out["runs"].append(run)
+        print(json.dumps(run), flush=True)
+
+    # leg c's batches: 256 items each, page-locked; one pool for the separate submissions and the resident cycle
+    per = 256
+    small = []
+    off = [0]
+    for ln in b["ad_lens"]:
+        off.append(off[-1] + ln)
+    for k in range(n // per):
+        lo, hi = k * per, (k + 1) * per
+        small.append(nat.PinnedBatch(per, b["ios_xy"][128 * lo: 128 * hi], [1] * per, b["ads"][off[lo]: off[hi]], b["ad_lens"][lo: hi],
+                                     pks_xy=b["pks_xy"][64 * lo: 64 * hi], proofs=b["proofs"][96 * lo: 96 * hi]))
+    pool = nat.Pool(0, kind=1, slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH) if "c" in LEGS else None
+
+    def pool_submissions():
+        tk = []
+        for i, sb in enumerate(small):
+            if i >= SLOTS:
+                assert pool.wait(tk[i - SLOTS]) == 0                              # a slot comes free
+            tk.append(pool.submit(sb))
+        for t in tk[max(0, len(tk) - SLOTS):]:
+            assert pool.wait(t) == 0
+
+    try:
+        for rep in range(REPS):
+            assert ctx.thin_batch_stage(batch) == 0
+            for n_seg, k in SHAPES if "a" in LEGS else []:                         # a: resident
+                segs = [k] * n_seg
+                assert ctx.thin_batch_run_segments(segs) == [0] * n_seg
+                sec, ms, cnt = timed(ctx, lambda: ctx.thin_batch_run_segments(segs))
+                tm = ctx.last_timing()
+                record("a %d x %d" % (n_seg, k), sec, rep=rep, accumulate_ms=round(ms, 4), accumulate_launches=cnt,
+                       stage_us=dict(prepare=round(tm[1]), transcripts=round(tm[2]), terms=round(tm[3]), msm=round(tm[4])))
+            if "d" in LEGS:
+                sec, ms, cnt = timed(ctx, lambda: ctx.thin_batch_run())
+                record("d plain run", sec, rep=rep, accumulate_ms=round(ms, 4), accumulate_launches=cnt)
+            if "a" in LEGS and SHAPE in (None, 256):
+                segs = [256] * (n // 256)
+                sec, ms, cnt = timed(ctx, lambda: ctx.thin_batch_verify_segments(batch, segs))
+                record("a 256 x 256 from host", sec, rep=rep, accumulate_ms=round(ms, 4))
+            if "b" in LEGS:
+                sec, _, _ = timed(ctx, lambda: ctx.thin_verify_into(batch, status))
+                assert not any(status)
+                record("b thin_verify", sec, rep=rep)
+            if "c" not in LEGS:
+                continue
+            for _ in range(WARM):                                                  # c
+                pool_submissions()
+            t0 = time.perf_counter()
+            for _ in range(CALLS):
+                pool_submissions()
+            record("c pool, %d submissions of %d" % (len(small), per), (time.perf_counter() - t0) / CALLS, rep=rep)
+            tk = [pool.submit(sb) for sb in small[:SLOTS]]
+            assert all(pool.wait(t) == 0 for t in tk)
+            pool.cycle(steps_block=SLOTS, min_seconds=0.1, expect=0)
+            done, mism, sec = pool.cycle(steps_block=SLOTS, min_seconds=0.3 if QUICK else 1.0, expect=0)
+            assert mism == 0
+            record("c pool, resident cycle of %d-item batches" % per, sec / done, items=per, rep=rep)
+        legs = {}
+        for r in out["runs"]:
+            legs.setdefault(r["leg"], []).append(r["items_per_sec"])
+        out["ranges"] = {leg: [min(v), max(v)] for leg, v in legs.items()}
+    finally:
+        if pool:
+            pool.close()
+        for sb in small:
+            sb.close()
+        ctx.close()
+    print(json.dumps(out["ranges"], indent=1))
+
+
+if __name__ == "__main__":
+    main()
