@@ -243,25 +243,22 @@ class Context:
     # -- one verdict per segment of the staged Thin batch (include/avrf.h avrf_thin_batch_run_segments)
     def thin_batch_run_segments(self, seg_items):
         """seg_items: items per segment, consecutive, summing to the staged n -> list of statuses, or the refusal (ERR_BAD_ARG)."""
-        seg_items = list(seg_items)
-        out = (C.c_int32 * max(1, len(seg_items)))()
-        st = lib().avrf_thin_batch_run_segments(self._h, C.c_size_t(len(seg_items)), _u32(seg_items), out)
-        return list(out)[: len(seg_items)] if st == OK else st
+        return self._segments(seg_items, lib().avrf_thin_batch_run_segments)
 
     def thin_batch_verify_segments(self, b, seg_items):
         """stage + thin_batch_run_segments for a Batch."""
-        seg_items = list(seg_items)
-        out = (C.c_int32 * max(1, len(seg_items)))()
-        st = lib().avrf_thin_batch_verify_segments(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs,
-                                                   C.c_size_t(len(seg_items)), _u32(seg_items), out)
-        return list(out)[: len(seg_items)] if st == OK else st
+        return self._segments(seg_items, lib().avrf_thin_batch_verify_segments, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
 
     def thin_batch_verify_segments_wire(self, b, seg_items, validate=1):
         """The same for a Batch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes (compressed points)."""
+        return self._segments(seg_items, lib().avrf_thin_batch_verify_segments_wire, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens,
+                              b.proofs, int(validate))
+
+    def _segments(self, seg_items, call, *args):
+        """call(ctx, *args, n_seg, seg_items, status_out) -> the list of n_seg statuses, or the refusal."""
         seg_items = list(seg_items)
         out = (C.c_int32 * max(1, len(seg_items)))()
-        st = lib().avrf_thin_batch_verify_segments_wire(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs,
-                                                        int(validate), C.c_size_t(len(seg_items)), _u32(seg_items), out)
+        st = call(self._h, *args, C.c_size_t(len(seg_items)), _u32(seg_items), out)
         return list(out)[: len(seg_items)] if st == OK else st
 
     def thin_segment_terms(self, seg):
@@ -439,14 +436,16 @@ class PinnedBatch:
     """A Batch whose buffers live in page-locked host memory (avrf_host_alloc): staging copies from it are DMA transfers."""
 
     def __init__(self, n, ios_xy, io_counts, ads, ad_lens, pks_xy=None, proofs=None):
+        self._pin_all(n, dict(ios_xy=ios_xy, ads=ads, pks_xy=pks_xy, proofs=proofs), dict(io_counts=io_counts, ad_lens=ad_lens))
+
+    def _pin_all(self, n, byte_fields, u32_fields):
+        """n and one pinned attribute per field (None stays None); the u32 fields are lists of counts or indices."""
         self.n = n
         self._ptrs = []
-        self.ios_xy = self._pin(bytes(ios_xy))
-        self.io_counts = self._pin(bytes(_u32(io_counts)))
-        self.ads = self._pin(bytes(ads))
-        self.ad_lens = self._pin(bytes(_u32(ad_lens)))
-        self.pks_xy = self._pin(bytes(pks_xy)) if pks_xy is not None else None
-        self.proofs = self._pin(bytes(proofs)) if proofs is not None else None
+        for name, v in byte_fields.items():
+            setattr(self, name, self._pin(bytes(v)) if v is not None else None)
+        for name, v in u32_fields.items():
+            setattr(self, name, self._pin(bytes(_u32(v))))
 
     def _pin(self, data):
         p = C.c_void_p()
@@ -473,10 +472,9 @@ class PinnedSharedBatch(PinnedBatch):
     """A SharedBatch whose buffers live in page-locked host memory."""
 
     def __init__(self, n, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs):
-        self.n, self.n_shared = n, len(bytes(shared_xy)) // 64
-        self._ptrs = []
-        self.shared_xy, self.outputs_xy, self.ads, self.proofs = (self._pin(bytes(v)) for v in (shared_xy, outputs_xy, ads, proofs))
-        self.pk_index, self.input_index, self.io_counts, self.ad_lens = (self._pin(bytes(_u32(v))) for v in (pk_index, input_index, io_counts, ad_lens))
+        self.n_shared = len(bytes(shared_xy)) // 64
+        self._pin_all(n, dict(shared_xy=shared_xy, outputs_xy=outputs_xy, ads=ads, proofs=proofs),
+                      dict(pk_index=pk_index, input_index=input_index, io_counts=io_counts, ad_lens=ad_lens))
 
     args = SharedBatch.args
 
@@ -515,41 +513,30 @@ class Pool:
     def set_validation(self, level):
         return lib().avrf_pool_set_validation(self._h, int(level))
 
-    def submit(self, b):
-        """b: Batch or PinnedBatch.  Returns the ticket."""
+    def _submit(self, symbol, b, *args):
+        """One of the avrf_pool_submit* calls for batch object b -> the ticket; b is kept while the pool may read its buffers."""
         t = C.c_uint64(0)
-        st = lib().avrf_pool_submit(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, C.byref(t))
+        st = getattr(lib(), symbol)(self._h, *args, C.byref(t))
         if st != OK:
-            raise AvrfError(f"avrf_pool_submit -> {st}")
+            raise AvrfError(f"{symbol} -> {st}")
         self._keep[t.value] = b
         return t.value
+
+    def submit(self, b):
+        """b: Batch or PinnedBatch.  Returns the ticket."""
+        return self._submit("avrf_pool_submit", b, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
 
     def submit_shared(self, b):
         """b: SharedBatch (a kind 1 pool).  Returns the ticket."""
-        t = C.c_uint64(0)
-        st = lib().avrf_pool_submit_shared(self._h, *b.args(), C.byref(t))
-        if st != OK:
-            raise AvrfError(f"avrf_pool_submit_shared -> {st}")
-        self._keep[t.value] = b
-        return t.value
+        return self._submit("avrf_pool_submit_shared", b, *b.args())
 
     def submit_shared_wire(self, b, validate=1):
         """b: SharedWireBatch / PinnedSharedWireBatch (a kind 1 pool).  Returns the ticket."""
-        t = C.c_uint64(0)
-        st = lib().avrf_pool_submit_shared_wire(self._h, *b.args(), int(validate), C.byref(t))
-        if st != OK:
-            raise AvrfError(f"avrf_pool_submit_shared_wire -> {st}")
-        self._keep[t.value] = b
-        return t.value
+        return self._submit("avrf_pool_submit_shared_wire", b, *b.args(), int(validate))
 
     def submit_wire(self, b, validate=1):
         """b: a Batch / PinnedBatch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes (compressed points)"""
-        t = C.c_uint64(0)
-        st = lib().avrf_pool_submit_wire(self._h, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, int(validate), C.byref(t))
-        if st != OK:
-            raise AvrfError(f"avrf_pool_submit_wire -> {st}")
-        self._keep[t.value] = b
-        return t.value
+        return self._submit("avrf_pool_submit_wire", b, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, int(validate))
 
     def wait(self, ticket):
         s = C.c_int(0)

@@ -162,15 +162,22 @@ void avrf_ctx_destroy(avrf_ctx *c) {
   delete c;                                                            // (~avrf_ctx, capi_internal.h: the order things go in)
 }
 
-// MSM over the first n terms of the context's lane (c->L->d_pre, c->L->d_scalars) on its stream, waited for.  What the engine
-// refuses is AVRF_ERR_BAD_ARG, a failed HIP call or allocation AVRF_ERR_NO_DEVICE (guarded).
+}  // extern "C"
+// A call into the MSM engine (msm.h): what the engine refuses is AVRF_ERR_BAD_ARG, a failed HIP call or allocation AVRF_ERR_NO_DEVICE (guarded).
+template <class F> static int msm_guarded(F f) { return guarded([&] { return f() ? (int)AVRF_ERR_BAD_ARG : 0; }); }
+// MSM over the first n terms of the context's lane (c->L->d_pre, c->L->d_scalars) on its stream, waited for
 static int lane_msm(avrf_ctx *c, size_t n, HostExt *r) {
-  return guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; });
+  return msm_guarded([&] { return msm_te_device(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, r); });
 }
 // the same for nv scalar vectors over the lane's first n bases through the single-launch form (msm.h msm_te_small_vectors): r[v]
 static int lane_msm_vectors(avrf_ctx *c, size_t n, size_t nv, HostExt *r) {
-  return guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, nv, c->L->ws, c->stream, r) ? (int)AVRF_ERR_BAD_ARG : 0; });
+  return msm_guarded([&] { return msm_te_small_vectors(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), n, nv, c->L->ws, c->stream, r); });
 }
+// n_seg independent MSMs of L terms each over arrays of the context's, through the segmented chain (msm.h msm_te_segments): sums[v]
+static int lane_msm_segments(avrf_ctx *c, const DevBuf &d_pre, const DevBuf &d_scalars, size_t L, size_t n_seg, HostExt *sums) {
+  return msm_guarded([&] { return msm_te_segments(c->suite, d_pre.as<te_pre_raw>(), d_scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->stream, sums); });
+}
+extern "C" {
 
 static int finish_point(avrf_ctx *c, const HostExt &r, uint8_t out_xy[64]) {
   with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; HostTe<S>::to_affine_bytes(r, out_xy); });
@@ -243,16 +250,13 @@ int avrf_g1_msm(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *s
     launch_g1_bases(curve, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream);
     HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
-  if (int e = guarded([&] { return msm_g1_device(curve, c->L->d_pre.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, out_xy) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = msm_guarded([&] { return msm_g1_device(curve, c->L->d_pre.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(), n, c->L->ws, c->stream, out_xy); })) return e;
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   return AVRF_OK;
 }
 
 // ---------------------------------------------------------------- staging
 
-// kind: a ProofKind (proof_kind.h: Thin pks + 96-byte proofs, Pedersen 256-byte proofs, Tiny 48); proofs/pks/sks may be NULL for provers
-// wait = false (pool.hip): the copies are left in flight on c->stream -- from buffers of avrf_host_alloc they are DMA transfers
-// that cost no host time; the caller's buffers must stay untouched until the batch's verdict is out
 }  // extern "C"
 namespace avrf {
 // HOST_WEIGHTS is exactly "the transcript is not the counter-mode SHA-512 one" (batch_seed squeezes a sponge's or SHA-256's stream)
@@ -292,7 +296,15 @@ static int ensure_terms(avrf_ctx *c) {
   return AVRF_OK;
 }
 
-// The opening both stagers share: argument checks (`args_ok`: the flavour's own), state reset, prefix sums of io_counts / ad_lens into h_io
+// off[0 .. n]: the prefix sums of n counts, the total into *total; false when the total is over `limit`
+static bool prefix_sums(const uint32_t *counts, size_t n, uint32_t *off, uint64_t limit, uint64_t *total) {
+  uint64_t a = 0;
+  for (size_t j = 0; j < n; j++) { off[j] = (uint32_t)a; a += counts[j]; }
+  off[n] = (uint32_t)a; *total = a;
+  return a <= limit;
+}
+
+// The opening every flavour shares: argument checks (`args_ok`: the flavour's own), state reset, prefix sums of io_counts / ad_lens into h_io
 // with their limits, offsets and `ads` copied -- and between them the I/O pairs when they come as x || y.  n == 0 stages the empty batch.
 static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8_t *ios, bool ios_xy, const uint32_t *io_counts,
                       const uint8_t *ads, const uint32_t *ad_lens) {
@@ -305,10 +317,8 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
   HIP_TRY(c->h_io.ensure((n + 1) * 8));
   uint32_t *io_off = c->h_io.as<uint32_t>(), *ad_off = io_off + (n + 1);
   uint64_t a = 0, b = 0;
-  for (size_t j = 0; j < n; j++) { io_off[j] = (uint32_t)a; ad_off[j] = (uint32_t)b; a += io_counts[j]; b += ad_lens[j]; }
-  if (a > 0x1fffffffULL || b > 0x7fffffffULL) return AVRF_ERR_BAD_ARG;
+  if (!prefix_sums(io_counts, n, io_off, 0x1fffffffULL, &a) || !prefix_sums(ad_lens, n, ad_off, 0x7fffffffULL, &b)) return AVRF_ERR_BAD_ARG;
   if ((a && !ios) || (b && !ads)) return AVRF_ERR_BAD_ARG;
-  io_off[n] = (uint32_t)a; ad_off[n] = (uint32_t)b;
   c->tot_io = (size_t)a;
   HIP_TRY(c->d_io_off.ensure((n + 1) * 4)); HIP_TRY(c->d_ad_off.ensure((n + 1) * 4));
   HIP_TRY(c->d_ios.ensure(a * 128 + 16)); HIP_TRY(c->d_ads.ensure(b + 16));
@@ -318,7 +328,7 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
   if (b) HIP_TRY(hipMemcpyAsync(c->d_ads.p, ads, b, hipMemcpyHostToDevice, c->stream));
   return AVRF_OK;
 }
-// The close both stagers share for a batch VERIFIER: the host copy of the responses (item 0's at `resp`, `stride` apart) for a sponge
+// The close every flavour shares for a batch VERIFIER: the host copy of the responses (item 0's at `resp`, `stride` apart) for a sponge
 // transcript, which absorbs them on the host (counter-mode ones hash the device's records); the term count; the buffers the run writes.
 static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t stride) {
   const size_t n = c->n, rsz = kind_facts(kind).resp;
@@ -332,163 +342,136 @@ static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t str
   return c->lane_owner ? ensure_terms(c) : (int)AVRF_OK;
 }
 
-int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
-              const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait) {
-  if (int e = stage_open(c, kind, n, true, ios_xy, true, io_counts, ads, ad_lens)) return e;
-  if (n == 0) return AVRF_OK;
-  const size_t psz = kind_facts(kind).xy_proof();
-  if (pks_xy) { HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(hipMemcpyAsync(c->d_pks.p, pks_xy, n * 64, hipMemcpyHostToDevice, c->stream)); }
-  if (sks) { HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(hipMemcpyAsync(c->d_sks.p, sks, n * 32, hipMemcpyHostToDevice, c->stream)); }
-  if (proofs) {
-    HIP_TRY(c->d_proofs.ensure(n * psz)); HIP_TRY(hipMemcpyAsync(c->d_proofs.p, proofs, n * psz, hipMemcpyHostToDevice, c->stream));
-    if (kind == Tiny) { HIP_TRY(hipStreamSynchronize(c->stream)); c->staged_kind = kind; return AVRF_OK; }   // Tiny: no batch verifier
-    if (int e = stage_verifier(c, kind, proofs + kind_facts(kind).resp_at_xy(), psz)) return e;
-  }
-  if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
-  c->staged_kind = kind;
-  return AVRF_OK;
-}
-// Thin over a table of shared points (include/avrf.h; thin_shared.h): the table, the indices, the outputs and the proofs go up; the
-// device gathers the rows into the plain staged layout, converts each row once and sorts the references by row -- the host only checks
-// the indices.  What the staging leaves is reused by every run of it (resident reruns, the pool's resubmission without host sources).
-bool shared_indices_ok(size_t n, size_t n_shared, const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts) {
-  if (!n) return true;
-  if (!n_shared || n_shared > 0x0fffffffULL || n > 0x0fffffffULL || !pk_index || !io_counts) return false;
+bool shared_indices_ok(const BatchSource &s) {
+  if (!s.n) return true;
+  if (!s.n_shared || s.n_shared > 0x0fffffffULL || s.n > 0x0fffffffULL || !s.pk_index || !s.io_counts) return false;
   uint64_t a = 0; uint32_t over = 0;
-  for (size_t j = 0; j < n; j++) { over |= pk_index[j] >= n_shared; a += io_counts[j]; }
-  if (over || a > 0x1fffffffULL || (a && (!input_index || !outputs_xy))) return false;
-  for (size_t k = 0; k < a; k++) over |= input_index[k] >= n_shared;
+  for (size_t j = 0; j < s.n; j++) { over |= s.pk_index[j] >= s.n_shared; a += s.io_counts[j]; }
+  if (over || a > 0x1fffffffULL || (a && (!s.input_index || !s.outputs))) return false;
+  for (size_t k = 0; k < a; k++) over |= s.input_index[k] >= s.n_shared;
   return !over;
 }
-int ctx_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
-                     const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait) {
-  const bool args_ok = !n || (shared_xy && proofs && shared_indices_ok(n, n_shared, pk_index, input_index, outputs_xy, io_counts));   // (refused before anything is staged)
-  if (int e = stage_open(c, Thin, n, args_ok, outputs_xy, false, io_counts, ads, ad_lens)) return e;
-  if (n == 0) return AVRF_OK;
-  const size_t a = c->tot_io, nc = n + a;
-  HIP_TRY(c->d_table.ensure(n_shared * 64)); HIP_TRY(c->d_table_idx.ensure(nc * 4)); HIP_TRY(c->d_table_outs.ensure(a * 64 + 16));
-  HIP_TRY(c->d_table_rows.ensure(n_shared * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(n_shared, nc) * 4));
-  HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(c->d_proofs.ensure(n * 96));
-  HIP_TRY(hipMemcpyAsync(c->d_table.p, shared_xy, n_shared * 64, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_table_idx.p, pk_index, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (a) {
-    HIP_TRY(hipMemcpyAsync(c->d_table_idx.as<uint32_t>() + n, input_index, a * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_table_outs.p, outputs_xy, a * 64, hipMemcpyHostToDevice, c->stream));
+
+// What ctx_stage enqueues behind stage_open for a batch of n > 0 items, and its close.  The payload is the flavour's own:
+//   x || y        keys, secrets and proofs (each where given) go to the buffers the kernels read;
+//   wire          (src/thin.rs:78-94, src/pedersen.rs:106-134 deserialise, then `push`) the caller's serialize_compressed
+//                 bytes go to d_misc as they are (keys | I/O points | proofs), every point is decompressed (validate: + not the identity,
+//                 + prime-order subgroup, src/lib.rs:410-433) STRAIGHT INTO the staged x || y buffers and the proofs' scalars are copied
+//                 beside their points -- no decompressed byte crosses PCIe or a host core;
+//   shared        (thin_shared.h) the table, the indices, the outputs and the proofs go up; shared_plan gathers the rows into the plain
+//                 staged layout and sorts the references by row, rows_pre converts each row once -- the host only checks the indices;
+//   shared + wire rows | outputs | proofs go to d_misc and ONE kernel does all the decoding (vrf_single.hip k_decode_shared_wire): every
+//                 row, referenced or not, once to d_table (x || y) and d_table_rows (te_pre, what rows_pre leaves), every output to
+//                 d_table_outs, every R || s to d_proofs.  What decodes is canonical, so the plan's range flag stays clear.
+// A wire point that fails raises the decode flag (d_status -> h_flags[2]): AVRF_INVALID_DATA here, before any equation (as the
+// reference's deserialisation would), or from batch_collect when nothing was waited for (wire_pending).  What a shared staging
+// leaves is reused by every run of it (resident reruns, the pool's resubmission without host sources).
+static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
+  const KindFacts &k = kind_facts(s.kind);
+  const bool shared = s.n_shared != 0;
+  const size_t n = s.n, a = c->tot_io, nc = n + a, ns = s.n_shared, psz = k.xy_proof();
+  const size_t L = s.wire ? (size_t)point_len_of(c->suite) : 0, plen = k.wire_proof(L);
+  const size_t w_pks = shared ? ns * L : k.pk ? n * L : 0, w_ios = shared ? a * L : 2 * a * L, w_pr = n * plen;   // the wire bytes in d_misc
+  uint8_t *dw = nullptr; uint32_t *d_flag = nullptr, *h_flag = c->h_flags.as<uint32_t>() + 2, *plan = nullptr;
+  if (shared) {
+    HIP_TRY(c->d_table.ensure(ns * 64)); HIP_TRY(c->d_table_idx.ensure(nc * 4)); HIP_TRY(c->d_table_outs.ensure(a * 64 + 16));
+    HIP_TRY(c->d_table_rows.ensure(ns * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(ns, nc) * 4));
+    plan = c->d_table_plan.as<uint32_t>();
   }
-  HIP_TRY(hipMemcpyAsync(c->d_proofs.p, proofs, n * 96, hipMemcpyHostToDevice, c->stream));
-  uint32_t *plan = c->d_table_plan.as<uint32_t>(), *flag = shared_plan_flag(plan, n_shared, nc);
-  HIP_TRY(hipMemsetAsync(flag, 0, 4, c->stream));
-  HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)n_shared, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)n, (uint32_t)a,
-                      c->d_pks.as<uint8_t>(), c->d_ios.as<uint8_t>(), plan, c->stream));
-  HIP_TRY(AVRF_SHARED(c->suite, rows_pre(c->d_table.as<uint8_t>(), (uint32_t)n_shared, c->d_table_rows.as<te_pre_raw>(), flag, c->stream)));
-  c->n_shared = n_shared;
-  if (int e = stage_verifier(c, Thin, proofs + kind_facts(Thin).resp_at_xy(), 96)) { c->n_shared = 0; return e; }
+  if (shared || s.wire) { HIP_TRY(c->d_proofs.ensure(n * psz)); if (shared || k.pk) HIP_TRY(c->d_pks.ensure(n * 64)); }
+  if (s.wire) {
+    HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
+    dw = c->d_misc.as<uint8_t>(); d_flag = c->d_status.as<uint32_t>();
+  }
+  auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
+  if (shared && s.wire) {
+    HIP_TRY(up(dw, s.table, w_pks));
+    if (w_ios) HIP_TRY(up(dw + w_pks, s.outputs, w_ios));
+    HIP_TRY(up(dw + w_pks + w_ios, s.proofs, w_pr));
+    HIP_TRY(up(c->d_table_idx.p, s.pk_index, n * 4));
+    if (a) HIP_TRY(up(c->d_table_idx.as<uint32_t>() + n, s.input_index, a * 4));
+  } else if (shared) {
+    HIP_TRY(up(c->d_table.p, s.table, ns * 64));
+    HIP_TRY(up(c->d_table_idx.p, s.pk_index, n * 4));
+    if (a) { HIP_TRY(up(c->d_table_idx.as<uint32_t>() + n, s.input_index, a * 4)); HIP_TRY(up(c->d_table_outs.p, s.outputs, a * 64)); }
+    HIP_TRY(up(c->d_proofs.p, s.proofs, n * psz));
+  } else if (s.wire) {
+    if (w_pks) HIP_TRY(up(dw, s.pks, w_pks));
+    if (w_ios) HIP_TRY(up(dw + w_pks, s.ios, w_ios));
+    HIP_TRY(up(dw + w_pks + w_ios, s.proofs, w_pr));
+  } else {
+    if (s.pks) { HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(up(c->d_pks.p, s.pks, n * 64)); }
+    if (s.sks) { HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(up(c->d_sks.p, s.sks, n * 32)); }
+    if (s.proofs) { HIP_TRY(c->d_proofs.ensure(n * psz)); HIP_TRY(up(c->d_proofs.p, s.proofs, n * psz)); }
+  }
+  if (s.wire) HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
+  if (shared) HIP_TRY(hipMemsetAsync(shared_plan_flag(plan, ns, nc), 0, 4, c->stream));
+  if (s.wire) {
+    const uint8_t *dpr = dw + w_pks + w_ios;
+    if (shared)
+      HIP_TRY(AVRF_SINGLE(c->suite, decode_shared_wire(dw, (uint32_t)ns, (uint32_t)a, (uint32_t)n, c->d_table.as<uint8_t>(), c->d_table_rows.as<te_pre_raw>(),
+                                                       c->d_table_outs.as<uint8_t>(), c->d_proofs.as<uint8_t>(), s.validate, d_flag, c->stream)));
+    else {
+      if (k.pk) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, s.validate, d_flag, c->stream));
+      AVRF_SINGLE(c->suite, decompress_strided(dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>(), 64, s.validate, d_flag, c->stream));
+      for (size_t p = 0; p < k.points; p++)
+        AVRF_SINGLE(c->suite, decompress_strided(dpr + L * p, (uint32_t)plen, (uint32_t)n, c->d_proofs.as<uint8_t>() + 64 * p, (uint32_t)psz, s.validate, d_flag, c->stream));
+      HIP_TRY(hipMemcpy2DAsync(c->d_proofs.as<uint8_t>() + 64 * k.points, psz, dpr + L * k.points, plen, k.tail, n, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (shared) {
+    HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)ns, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)n, (uint32_t)a,
+                        c->d_pks.as<uint8_t>(), c->d_ios.as<uint8_t>(), plan, c->stream));
+    if (!s.wire) HIP_TRY(AVRF_SHARED(c->suite, rows_pre(c->d_table.as<uint8_t>(), (uint32_t)ns, c->d_table_rows.as<te_pre_raw>(), shared_plan_flag(plan, ns, nc), c->stream)));
+    c->n_shared = ns;
+  }
+  if (s.proofs && s.kind != Tiny)                                      // (Tiny has no batch verifier, and a prover stages no proofs)
+    if (int e = stage_verifier(c, s.kind, s.proofs + (s.wire ? k.resp_at_wire(L) : k.resp_at_xy()), s.wire ? plen : psz)) return e;
+  if (s.wire && !wait) { c->wire_pending = true; return AVRF_OK; }
   if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
-  c->staged_kind = Thin;
+  if (s.wire) { HIP_TRY(hipGetLastError()); if (*h_flag) return AVRF_INVALID_DATA; }
   return AVRF_OK;
 }
-// The wire flavour of the batch verifiers' staging (src/thin.rs:78-94, src/pedersen.rs:106-134 deserialise, then
-// `push`): the caller's `serialize_compressed` bytes go to the device as they are, every point is decompressed (validate: + not the
-// identity, + prime-order subgroup, src/lib.rs:410-433) STRAIGHT INTO the context's staged x || y buffers, the proofs' scalars are
-// copied beside their points -- no decompressed byte crosses PCIe or a host core.  A point that fails makes the batch InvalidData
-// here, before any equation (as the reference's deserialisation would).  kind Thin (pk, R || s), Pedersen (Yb, R, Ok || s || sb).
-// wait = false (pool.hip): nothing is waited for -- the flag is read by batch_collect once the stream's work has completed
-int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
-                   const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait) {
-  const bool args_ok = (kind == Thin || kind == Pedersen) && (!n || (proofs && (kind != Thin || pks)));
-  if (int e = stage_open(c, kind, n, args_ok, ios, false, io_counts, ads, ad_lens)) return e;
-  if (n == 0) return AVRF_OK;
-  const KindFacts &k = kind_facts(kind);
-  const size_t L = (size_t)point_len_of(c->suite), a = c->tot_io, ppts = k.points, plen = k.wire_proof(L), psz = k.xy_proof();
-  const size_t w_pks = k.pk ? n * L : 0, w_ios = 2 * a * L, w_pr = n * plen;
-  HIP_TRY(c->d_proofs.ensure(n * psz));
-  if (k.pk) HIP_TRY(c->d_pks.ensure(n * 64));
-  HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
-  uint8_t *dw = c->d_misc.as<uint8_t>();
-  if (w_pks) HIP_TRY(hipMemcpyAsync(dw, pks, w_pks, hipMemcpyHostToDevice, c->stream));
-  if (w_ios) HIP_TRY(hipMemcpyAsync(dw + w_pks, ios, w_ios, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dw + w_pks + w_ios, proofs, w_pr, hipMemcpyHostToDevice, c->stream));
-  uint32_t *d_flag = c->d_status.as<uint32_t>(), *h_flag = c->h_flags.as<uint32_t>() + 2;
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
-  if (k.pk) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, validate, d_flag, c->stream));
-  AVRF_SINGLE(c->suite, decompress_strided(dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>(), 64, validate, d_flag, c->stream));
-  const uint8_t *dpr = dw + w_pks + w_ios;
-  for (size_t p = 0; p < ppts; p++)
-    AVRF_SINGLE(c->suite, decompress_strided(dpr + L * p, (uint32_t)plen, (uint32_t)n, c->d_proofs.as<uint8_t>() + 64 * p, (uint32_t)psz, validate, d_flag, c->stream));
-  HIP_TRY(hipMemcpy2DAsync(c->d_proofs.as<uint8_t>() + 64 * ppts, psz, dpr + L * ppts, plen, k.tail, n, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  if (int e = stage_verifier(c, kind, proofs + k.resp_at_wire(L), plen)) return e;
-  if (!wait) { c->wire_pending = true; c->staged_kind = kind; return AVRF_OK; }
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  if (*h_flag) return AVRF_INVALID_DATA;
-  c->staged_kind = kind;
-  return AVRF_OK;
-}
-// The two together: a shared-table Thin batch whose table, outputs and proofs come as wire bytes.  The bytes go to d_misc (rows | outputs |
-// proofs, three copies) and ONE kernel does all the decoding (vrf_single.hip k_decode_shared_wire): every row, referenced or not, once to
-// d_table (x || y) and d_table_rows (te_pre, what rows_pre leaves after ctx_stage_shared), every output to d_table_outs, every R || s to
-// d_proofs.  shared_plan then runs on d_table as it does after ctx_stage_shared, and the batch is a shared-table batch to every run entry
-// point.  What decodes is canonical, so the plan's range flag stays clear; a point that fails raises the decode flag of ctx_stage_wire
-// (d_status -> h_flags[2]): AVRF_INVALID_DATA here, or from batch_collect when nothing was waited for (wire_pending).
-int ctx_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
-                          const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
-                          int validate, bool wait) {
-  const bool args_ok = !n || (shared && proofs && shared_indices_ok(n, n_shared, pk_index, input_index, outputs, io_counts));   // (refused before anything is staged)
-  if (int e = stage_open(c, Thin, n, args_ok, outputs, false, io_counts, ads, ad_lens)) return e;
-  if (n == 0) return AVRF_OK;
-  const KindFacts &k = kind_facts(Thin);
-  const size_t L = (size_t)point_len_of(c->suite), a = c->tot_io, nc = n + a, plen = k.wire_proof(L);
-  const size_t w_rows = n_shared * L, w_outs = a * L, w_pr = n * plen;
-  HIP_TRY(c->d_table.ensure(n_shared * 64)); HIP_TRY(c->d_table_idx.ensure(nc * 4)); HIP_TRY(c->d_table_outs.ensure(a * 64 + 16));
-  HIP_TRY(c->d_table_rows.ensure(n_shared * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(n_shared, nc) * 4));
-  HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(c->d_proofs.ensure(n * k.xy_proof()));
-  HIP_TRY(c->d_misc.ensure(w_rows + w_outs + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
-  uint8_t *dw = c->d_misc.as<uint8_t>();
-  HIP_TRY(hipMemcpyAsync(dw, shared, w_rows, hipMemcpyHostToDevice, c->stream));
-  if (w_outs) HIP_TRY(hipMemcpyAsync(dw + w_rows, outputs, w_outs, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(dw + w_rows + w_outs, proofs, w_pr, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_table_idx.p, pk_index, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (a) HIP_TRY(hipMemcpyAsync(c->d_table_idx.as<uint32_t>() + n, input_index, a * 4, hipMemcpyHostToDevice, c->stream));
-  uint32_t *d_flag = c->d_status.as<uint32_t>(), *h_flag = c->h_flags.as<uint32_t>() + 2;
-  uint32_t *plan = c->d_table_plan.as<uint32_t>();
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
-  HIP_TRY(hipMemsetAsync(shared_plan_flag(plan, n_shared, nc), 0, 4, c->stream));
-  HIP_TRY(AVRF_SINGLE(c->suite, decode_shared_wire(dw, (uint32_t)n_shared, (uint32_t)a, (uint32_t)n, c->d_table.as<uint8_t>(), c->d_table_rows.as<te_pre_raw>(),
-                                                   c->d_table_outs.as<uint8_t>(), c->d_proofs.as<uint8_t>(), validate, d_flag, c->stream)));
-  HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)n_shared, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)n, (uint32_t)a,
-                      c->d_pks.as<uint8_t>(), c->d_ios.as<uint8_t>(), plan, c->stream));
-  c->n_shared = n_shared;
-  if (int e = stage_verifier(c, Thin, proofs + k.resp_at_wire(L), plen)) { c->n_shared = 0; return e; }
-  if (!wait) { c->wire_pending = true; c->staged_kind = Thin; return AVRF_OK; }
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
-  if (*h_flag) { c->n_shared = 0; return AVRF_INVALID_DATA; }
-  c->staged_kind = Thin;
-  return AVRF_OK;
+
+// kind: a ProofKind (proof_kind.h: Thin pks + 96-byte proofs, Pedersen 256-byte proofs, Tiny 48).  wait = false (pool.hip): the copies are
+// left in flight on c->stream -- from buffers of avrf_host_alloc they are DMA transfers that cost no host time; the caller's buffers must
+// stay untouched until the batch's verdict is out.  The flavour's argument check refuses before anything staged is touched; every later
+// failure leaves nothing staged (staged_kind == 0) and no shared table.
+int ctx_stage(avrf_ctx *c, const BatchSource &s, bool wait) {
+  const bool shared = s.n_shared != 0;
+  const bool args_ok = (!s.wire || s.kind == Thin || s.kind == Pedersen) && (!shared || s.kind == Thin) &&
+                       (!s.n || (shared ? s.table && s.proofs && shared_indices_ok(s) : !s.wire || (s.proofs && (s.kind != Thin || s.pks))));
+  if (int e = stage_open(c, s.kind, s.n, args_ok, shared ? s.outputs : s.ios, !shared && !s.wire, s.io_counts, s.ads, s.ad_lens)) return e;
+  if (s.n == 0) return AVRF_OK;
+  const int st = stage_payload(c, s, wait);
+  if (st) c->n_shared = 0; else c->staged_kind = s.kind;
+  return st;
 }
 }  // namespace avrf
 extern "C" {
 int avrf_thin_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                                const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
   if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  return avrf::ctx_stage_wire(c, Thin, n, pks, ios, io_counts, ads, ad_lens, proofs, validate, true);
+  return ctx_stage(c, wire_source(plain_source(Thin, n, pks, ios, io_counts, ads, ad_lens, proofs), validate), true);
 }
 int avrf_pedersen_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                                    const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
   if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  return avrf::ctx_stage_wire(c, Pedersen, n, nullptr, ios, io_counts, ads, ad_lens, proofs, validate, true);
+  return ctx_stage(c, wire_source(plain_source(Pedersen, n, nullptr, ios, io_counts, ads, ad_lens, proofs), validate), true);
 }
 
 int avrf_thin_batch_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
                                  const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
-  return ctx_stage_shared(c, n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs, true);
+  if (n && !n_shared) return AVRF_ERR_BAD_ARG;                         // (no table: a source with n_shared == 0 is a plain one)
+  return ctx_stage(c, shared_source(n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs), true);
 }
 size_t avrf_thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared) { return thin_shared_n_terms(n, tot_io, n_shared); }
 int avrf_thin_batch_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
                                       const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
                                       int validate) {
-  if (!c || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
-  return ctx_stage_shared_wire(c, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, validate, true);
+  if (!c || ctx_busy(c) || (n && !n_shared)) return AVRF_ERR_BAD_ARG;
+  return ctx_stage(c, wire_source(shared_source(n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs), validate), true);
 }
 int avrf_thin_batch_verify_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
                                        const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
@@ -500,12 +483,12 @@ int avrf_thin_batch_verify_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, c
 int avrf_thin_batch_stage(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && (!pks_xy || !proofs)) return AVRF_ERR_BAD_ARG;
-  return ctx_stage(c, Thin, n, nullptr, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, true);
+  return ctx_stage(c, plain_source(Thin, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs), true);
 }
 int avrf_pedersen_batch_stage(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts,
                               const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && !proofs) return AVRF_ERR_BAD_ARG;
-  return ctx_stage(c, Pedersen, n, nullptr, nullptr, ios_xy, io_counts, ads, ad_lens, proofs, true);
+  return ctx_stage(c, plain_source(Pedersen, n, nullptr, ios_xy, io_counts, ads, ad_lens, proofs), true);
 }
 
 // ---- the weight transcripts of the contexts in flight, hashed together (host_sha512_mb.h)
@@ -630,7 +613,7 @@ int batch_begin(avrf_ctx *c, int kind) {
 int batch_collect(avrf_ctx *c, int kind) {
   if (!c || c->staged_kind != kind || c->run_phase != 1) return AVRF_ERR_BAD_ARG;
   if (c->n && *c->h_flags.as<uint32_t>()) { c->run_phase = 0; return AVRF_INVALID_DATA; }   // src/thin.rs:266-271, src/pedersen.rs:348-353
-  if (c->wire_pending) {                                               // staged from wire bytes without waiting (ctx_stage_wire): a point that failed to decode / validate
+  if (c->wire_pending) {                                               // staged from wire bytes without waiting (ctx_stage): a point that failed to decode / validate
     c->wire_pending = false;
     if (c->n && c->h_flags.as<uint32_t>()[2]) { c->run_phase = 0; c->staged_kind = 0; return AVRF_INVALID_DATA; }
   }
@@ -641,20 +624,25 @@ int batch_collect(avrf_ctx *c, int kind) {
 // digest.  Sponge / SHA-256 transcripts (Shake128Transcript: the weights are the sponge's OUTPUT STREAM, 16 bytes per item, 32 for
 // Pedersen -- sequential, so the host squeezes it and the terms kernel reads it from HBM instead of deriving block j / 4 from a
 // seed; HashTranscript<Sha256> of the test suite takes the same route): the stream goes to c->h_weights and the digest is not used.
+// squeeze_weights is that transcript over `items` staged items from `first` -- one BatchVerifier's: absorbed from h_c / h_resp at `first`,
+// squeezed into h_weights (sized by the caller) at `first`; the segmented run calls it once per segment.
+static void squeeze_weights(avrf_ctx *c, int kind, size_t first, size_t items) {
+  const KindFacts &k = kind_facts(kind);
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+  with_suite(c->suite, [&](auto tag_) {
+    using S = typename decltype(tag_)::type;
+    std::conditional_t<S::XOF_SHAKE, HostShake128, HostSha256> h;
+    absorb_weight_message(h, prefix, pl, items, c->h_c.as<uint8_t>() + 16 * first, c->h_resp.data() + k.resp * first, k.resp);
+    h.squeeze_copy(c->h_weights.data() + k.weight * first, items * k.weight);
+  });
+}
 int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]) {
   const size_t n = c->n;
   memset(digest, 0, 64);
   if (!n) return AVRF_OK;
   if (suite_host_weights(c->suite)) {
-    const KindFacts &k = kind_facts(kind);
-    uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
-    c->h_weights.resize(n * k.weight);
-    with_suite(c->suite, [&](auto tag_) {
-      using S = typename decltype(tag_)::type;
-      std::conditional_t<S::XOF_SHAKE, HostShake128, HostSha256> h;
-      absorb_weight_message(h, prefix, pl, n, c->h_c.as<uint8_t>(), c->h_resp.data(), k.resp);
-      h.squeeze_copy(c->h_weights.data(), n * k.weight);
-    });
+    c->h_weights.resize(n * kind_facts(kind).weight);
+    squeeze_weights(c, kind, 0, n);
     return AVRF_OK;
   }
   WeightJob job = WeightJob::whole(c->h_msg.as<uint8_t>(), c->h_msg_len);
@@ -685,7 +673,7 @@ int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]) {
   const double t2 = now_us();
   launch_terms(c, kind, b, seed_of(digest), 0, c->L->d_scalars.as<uint32_t>());
   const double t3 = now_us();
-  if (int e = guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->chain(), c->stream) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = msm_guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->chain(), c->stream); })) return e;
   c->timing[3] = t3 - t2;
   c->run_msm_us = now_us() - t3;
   c->run_phase = 2;
@@ -699,7 +687,7 @@ int batch_end(avrf_ctx *c, int kind) {
   HIP_TRY(hipSetDevice(c->device));
   const double t3 = now_us();
   HostExt r;
-  if (int e = guarded([&] { return msm_te_finish(c->suite, c->L->ws, c->chain(), c->stream, &r) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = msm_guarded([&] { return msm_te_finish(c->suite, c->L->ws, c->chain(), c->stream, &r); })) return e;
   double t4 = now_us();
   int st = point_is_identity(c, r) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
   double t5 = now_us();
@@ -762,6 +750,22 @@ int avrf_pedersen_batch_verify(avrf_ctx *c, size_t n, const uint8_t *ios_xy, con
 // ---------------------------------------------------------------- one verdict per segment of the staged Thin batch (thin_seg.h)
 }  // extern "C"
 
+// `count` MSM terms of the context's device back to the host, each where wanted: the bases as canonical x || y, the scalars as they are.
+// Returns count, 0 when a copy failed.
+static size_t terms_to_host(avrf_ctx *c, const te_pre_raw *d_pre, const uint8_t *d_scalars, size_t count, uint8_t *bases_xy, uint8_t *scalars) {
+  if (scalars) { if (hipMemcpy(scalars, d_scalars, count * 32, hipMemcpyDeviceToHost) != hipSuccess) return 0; }
+  if (bases_xy) {
+    std::vector<te_pre_raw> pre(count);
+    if (hipMemcpy(pre.data(), d_pre, count * sizeof(te_pre_raw), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    for (size_t i = 0; i < count; i++) {
+      H256 x, y; memcpy(x.l, pre[i].w, 32); memcpy(y.l, pre[i].w + 8, 32);
+      with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; x = HostField<typename S::Fq>::from_mont(x); y = HostField<typename S::Fq>::from_mont(y); });
+      memcpy(bases_xy + 64 * i, x.l, 32); memcpy(bases_xy + 64 * i + 32, y.l, 32);
+    }
+  }
+  return count;
+}
+
 // The layout of n_seg thin::BatchVerifiers over consecutive runs of n staged items (include/avrf.h avrf_thin_segments_layout): item
 // offsets into *seg_off (n_seg + 1) when wanted, out = { L, n_seg L, sum of the term counts, window bits }; io_off: n + 1 prefix sums of
 // the items' pair counts.  AVRF_ERR_BAD_ARG when the counts do not sum to n or a limit is exceeded.
@@ -781,7 +785,7 @@ static int seg_layout(size_t n, size_t n_seg, const uint32_t *seg_items, const u
     const uint64_t items = seg_items[v];
     if (at + items > n) return AVRF_ERR_BAD_ARG;
     if (seg_off) (*seg_off)[v] = (uint32_t)at;
-    const uint64_t n_v = items ? 2 * items + 2 * (uint64_t)(io_off[at + items] - io_off[at]) + 1 : 0;   // src/thin.rs:282-317; none for an empty segment
+    const uint64_t n_v = items ? n_terms(Thin, items, io_off[at + items] - io_off[at]) : 0;   // none for an empty segment
     if (n_v > L) L = n_v;
     total += n_v; at += items;
   }
@@ -794,11 +798,8 @@ extern "C" {
 
 int avrf_thin_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_counts, uint64_t out[4]) {
   if (!out || (n && !io_counts) || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
-  std::vector<uint32_t> io_off(n + 1);
-  uint64_t a = 0;
-  for (size_t j = 0; j < n; j++) { io_off[j] = (uint32_t)a; a += io_counts[j]; }
-  if (a > 0x1fffffffULL) return AVRF_ERR_BAD_ARG;
-  io_off[n] = (uint32_t)a;
+  std::vector<uint32_t> io_off(n + 1); uint64_t a;
+  if (!prefix_sums(io_counts, n, io_off.data(), 0x1fffffffULL, &a)) return AVRF_ERR_BAD_ARG;
   return seg_layout(n, n_seg, seg_items, io_off.data(), nullptr, out);
 }
 
@@ -855,16 +856,7 @@ int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_
   } else {
     // sponge / SHA-256 transcripts: every segment's weight stream squeezed on the host, item j's 16 bytes at 16 j
     c->h_weights.resize(n * k.weight);
-    parallel_for(n_seg, [&](size_t v) {
-      const size_t first = seg_off[v], items = seg_off[v + 1] - first;
-      if (!items) return;
-      with_suite(c->suite, [&](auto tag_) {
-        using S = typename decltype(tag_)::type;
-        std::conditional_t<S::XOF_SHAKE, HostShake128, HostSha256> h;
-        absorb_weight_message(h, prefix, pl, items, c->h_c.as<uint8_t>() + 16 * first, c->h_resp.data() + k.resp * first, k.resp);
-        h.squeeze_copy(c->h_weights.data() + k.weight * first, items * k.weight);
-      });
-    });
+    parallel_for(n_seg, [&](size_t v) { if (seg_off[v + 1] != seg_off[v]) squeeze_weights(c, Thin, seg_off[v], seg_off[v + 1] - seg_off[v]); });
     HIP_TRY(c->d_weights.ensure(n * k.weight));
     HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), n * k.weight, hipMemcpyHostToDevice, c->stream));
     b.weights = c->d_weights.as<uint8_t>();
@@ -877,7 +869,7 @@ int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_
                                 c->d_z.as<uint32_t>(), c->d_seg_wsz.as<uint32_t>(), c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
   const double t3 = now_us();
   std::vector<HostExt> sums(n_seg);
-  if (int e = guarded([&] { return msm_te_segments(c->suite, c->d_seg_pre.as<te_pre_raw>(), c->d_seg_scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->stream, sums.data()) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm_segments(c, c->d_seg_pre, c->d_seg_scalars, L, n_seg, sums.data())) return e;
   for (size_t v = 0; v < n_seg; v++) {
     if (seg_off[v] == seg_off[v + 1]) continue;
     status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322
@@ -908,18 +900,8 @@ size_t avrf_thin_segment_terms(avrf_ctx *c, size_t seg, uint8_t *bases_xy, uint8
   const uint32_t *io_off = c->h_io.as<uint32_t>();
   const size_t first = c->seg_off[seg], items = c->seg_off[seg + 1] - first;
   if (!items) return 0;
-  const size_t cnt = 2 * items + 2 * (size_t)(io_off[first + items] - io_off[first]) + 1, t0 = seg * c->seg_L;
-  if (scalars) { if (hipMemcpy(scalars, c->d_seg_scalars.as<uint8_t>() + 32 * t0, cnt * 32, hipMemcpyDeviceToHost) != hipSuccess) return 0; }
-  if (bases_xy) {
-    std::vector<te_pre_raw> pre(cnt);
-    if (hipMemcpy(pre.data(), c->d_seg_pre.as<te_pre_raw>() + t0, cnt * sizeof(te_pre_raw), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    for (size_t i = 0; i < cnt; i++) {
-      H256 x, y; memcpy(x.l, pre[i].w, 32); memcpy(y.l, pre[i].w + 8, 32);
-      with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; x = HostField<typename S::Fq>::from_mont(x); y = HostField<typename S::Fq>::from_mont(y); });
-      memcpy(bases_xy + 64 * i, x.l, 32); memcpy(bases_xy + 64 * i + 32, y.l, 32);
-    }
-  }
-  return cnt;
+  const size_t t0 = seg * c->seg_L;
+  return terms_to_host(c, c->d_seg_pre.as<te_pre_raw>() + t0, c->d_seg_scalars.as<uint8_t>() + 32 * t0, n_terms(Thin, items, io_off[first + items] - io_off[first]), bases_xy, scalars);
 }
 
 // n_seg independent MSMs of L terms through the segmented chain (msm.h msm_te_segments), beside avrf_msm_te
@@ -937,7 +919,7 @@ int avrf_msm_te_segments(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bas
     HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
   c->staged_kind = 0;
-  if (int e = guarded([&] { return msm_te_segments(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->stream, sums.data()) ? (int)AVRF_ERR_BAD_ARG : 0; })) return e;
+  if (int e = lane_msm_segments(c, c->L->d_pre, c->L->d_scalars, L, n_seg, sums.data())) return e;
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   for (size_t v = 0; v < n_seg; v++) finish_point(c, sums[v], out_xy + 64 * v);
   return AVRF_OK;
@@ -1050,18 +1032,7 @@ int avrf_points_sum(int suite, size_t k, const uint8_t *points_xy, uint8_t out_x
 size_t avrf_batch_last_terms(avrf_ctx *c, uint8_t *bases_xy, uint8_t *scalars) {
   if (!c || !c->staged_kind || !c->n_terms || ctx_busy(c)) return 0;
   if (hipSetDevice(c->device) != hipSuccess) return 0;
-  size_t k = c->n_terms;
-  if (scalars) { if (hipMemcpy(scalars, c->L->d_scalars.p, k * 32, hipMemcpyDeviceToHost) != hipSuccess) return 0; }
-  if (bases_xy) {
-    std::vector<te_pre_raw> pre(k);
-    if (hipMemcpy(pre.data(), c->L->d_pre.p, k * sizeof(te_pre_raw), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    for (size_t i = 0; i < k; i++) {
-      H256 x, y; memcpy(x.l, pre[i].w, 32); memcpy(y.l, pre[i].w + 8, 32);
-      with_suite(c->suite, [&](auto tag) { using S = typename decltype(tag)::type; x = HostField<typename S::Fq>::from_mont(x); y = HostField<typename S::Fq>::from_mont(y); });
-      memcpy(bases_xy + 64 * i, x.l, 32); memcpy(bases_xy + 64 * i + 32, y.l, 32);
-    }
-  }
-  return k;
+  return terms_to_host(c, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint8_t>(), c->n_terms, bases_xy, scalars);
 }
 
 void avrf_last_timing(avrf_ctx *c, double out[8]) {
@@ -1223,7 +1194,9 @@ template <class One, class Wave, class Lane>
 static int item_call(avrf_ctx *c, const ItemCall &k, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy,
                      const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, One one, Wave wave, Lane lane) {
   // Tiny waits for its staging copies; Thin and Pedersen leave them in flight (the call waits for the stream before it returns)
-  int st = ctx_stage(c, k.kind, n, sks, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, k.kind == Tiny);
+  BatchSource src = plain_source(k.kind, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs);
+  src.sks = sks;
+  int st = ctx_stage(c, src, k.kind == Tiny);
   if (st || !n) return st;
   const size_t psz = kind_facts(k.kind).xy_proof();
   if (k.prover) {

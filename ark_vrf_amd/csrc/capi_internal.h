@@ -95,22 +95,39 @@ struct avrf_ctx {
 
 namespace avrf {
 struct WeightJob;
-// Staging, then the phases of a staged batch's run, shared by the three-call ABI (capi.hip) and the pool's workers (pool.hip).  `kind` is
-// a ProofKind (sizes: proof_kind.h).  The stagers share opening and close and differ in the payload: x || y arrays, or wire bytes decompressed on the device.
+// Where a batch comes from: the caller's host arrays, named for what they hold.  The x || y flavours read pks / ios / proofs as
+// affine coordinates; `wire` ones as serialize_compressed bytes, decoded on the device (validate: + not the identity, + subgroup).
+// n_shared != 0: Thin over a table of shared points (include/avrf.h) -- `table` rows, the items' keys and inputs as indices into
+// it, the `outputs` beside them -- and pks / ios are not read.
+struct BatchSource {
+  int kind = 0; size_t n = 0;       // a ProofKind (sizes: proof_kind.h)
+  bool wire = false; int validate = 0;
+  const uint8_t *sks = nullptr, *pks = nullptr, *ios = nullptr; const uint32_t *io_counts = nullptr;
+  const uint8_t *ads = nullptr; const uint32_t *ad_lens = nullptr; const uint8_t *proofs = nullptr;   // proofs / pks / sks may be NULL for provers
+  size_t n_shared = 0; const uint8_t *table = nullptr; const uint32_t *pk_index = nullptr, *input_index = nullptr; const uint8_t *outputs = nullptr;
+};
+// how the entry points fill one from their argument lists: x || y arrays, a table with indices, and either as wire bytes
+inline BatchSource plain_source(int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                                const uint32_t *ad_lens, const uint8_t *proofs) {
+  BatchSource s;
+  s.kind = kind; s.n = n; s.pks = pks; s.ios = ios; s.io_counts = io_counts; s.ads = ads; s.ad_lens = ad_lens; s.proofs = proofs;
+  return s;
+}
+inline BatchSource shared_source(size_t n, size_t n_shared, const uint8_t *table, const uint32_t *pk_index, const uint32_t *input_index,
+                                 const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
+  BatchSource s = plain_source(Thin, n, nullptr, nullptr, io_counts, ads, ad_lens, proofs);
+  s.n_shared = n_shared; s.table = table; s.pk_index = pk_index; s.input_index = input_index; s.outputs = outputs;
+  return s;
+}
+inline BatchSource wire_source(BatchSource s, int validate) { s.wire = true; s.validate = validate; return s; }
+// Staging, then the phases of a staged batch's run, shared by the three-call ABI (capi.hip) and the pool's workers (pool.hip).  One stager
+// over a source: opening and close are shared, the payload (what is copied, what decodes it) is the flavour's.  wait = false (pool.hip):
+// nothing is waited for, and a wire source's decode flag is read by batch_collect.
 int ctx_create(int suite, int device, bool lane_owner, avrf_ctx **out);
-int ctx_stage(avrf_ctx *c, int kind, size_t n, const uint8_t *sks, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
-              const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait);
-// Thin over a table of shared points (include/avrf.h); shared_indices_ok is the host's index check (every index < n_shared; outputs present), which
-// ctx_stage_shared makes itself and the pool makes on the submitting thread as well
-bool shared_indices_ok(size_t n, size_t n_shared, const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts);
-int ctx_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
-                     const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, bool wait);
-int ctx_stage_wire(avrf_ctx *c, int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
-                   const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool wait);   // serialize_compressed bytes in, decompressed on the device
-// both: the table, the outputs and R || s as wire bytes, all decoded by one kernel launch; then a shared-table batch like ctx_stage_shared's
-int ctx_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
-                          const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
-                          int validate, bool wait);
+int ctx_stage(avrf_ctx *c, const BatchSource &src, bool wait);
+// the host's check of a shared-table source (every index < n_shared; outputs present), which ctx_stage makes itself and the pool makes on
+// the submitting thread as well
+bool shared_indices_ok(const BatchSource &src);
 int batch_begin(avrf_ctx *c, int kind);                               // validation + prepare kernel + copies back enqueued on c->stream
 int batch_collect(avrf_ctx *c, int kind);                             // (c->stream's work has completed) AVRF_INVALID_DATA for a refused item
 bool suite_host_weights(int suite);                                   // sponge / SHA-256 transcript: batch_seed squeezes the weight stream itself (no seed)

@@ -41,25 +41,19 @@ size_t sum_counts(const uint32_t *c, size_t n) { size_t t = 0; for (size_t i = 0
 // shared by the thin / tiny / pedersen wire verifiers: kind is a ProofKind, its layouts those of proof_kind.h
 // pp0_xy / pp0_st (optional): xy and decode status of every item's FIRST proof point (the Pedersen key commitment Yb, which
 // ring::Verifier also needs as the ring proof's instance) -- so that a caller does not decompress it a second time
-// (Until the single-launch MSM -- msm.hip k_msm_tiny_bits -- a "batch" of <= 64 items went through the per-item
-// verifiers here, 0.6 ms against 1.5 ms for the Pippenger chain on one item; the batch verifier now takes 0.30 ms for one item,
-// 0.32 for eight, 0.46 for 64, against 0.52-0.55 ms per per-item call, so a batch is a batch whatever its size: SMALL_BATCH = 0.)
-constexpr size_t SMALL_BATCH = 0;
 // The two phases of a wire verification, separate so that a caller can run the verification proper beside other work (the ring
 // half of avrf_ring_vrf_verify): wire_prepare decompresses (and validates) every point and lays the proofs out in the x || y form;
 // wire_finish runs the verifier and folds the points' decode statuses into the items' statuses.
 struct WirePrep {
-  int kind = 0; bool batch = false, small = false; size_t n = 0, tot = 0, ppts = 0;
+  int kind = 0; bool batch = false; size_t n = 0, tot = 0, ppts = 0;
   const uint32_t *io_counts = nullptr, *ad_lens = nullptr; const uint8_t *ads = nullptr;
-  std::vector<uint8_t> xy, px; std::vector<int32_t> pst, small_status;
+  std::vector<uint8_t> xy, px; std::vector<int32_t> pst;
   const uint8_t *x_pks = nullptr, *x_ios = nullptr;
 };
 int wire_prepare(avrf_ctx *ctx, int kind, bool batch, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                  const uint32_t *ad_lens, const uint8_t *proofs, int validate, bool have_status_out, WirePrep &w,
                  std::vector<uint8_t> *pp0_xy = nullptr, std::vector<int32_t> *pp0_st = nullptr) {
   const KindFacts &k = kind_facts(kind);
-  w.small = batch && n <= SMALL_BATCH && kind != Tiny;
-  if (w.small) { w.small_status.assign(n ? n : 1, 0); batch = false; have_status_out = true; }
   if (!ctx || (n && (!io_counts || !ad_lens || !proofs)) || (n && k.pk && !pks) || (!batch && n && !have_status_out)) return AVRF_ERR_BAD_ARG;
   w.kind = kind; w.batch = batch; w.n = n; w.io_counts = io_counts; w.ad_lens = ad_lens; w.ads = ads;
   if (!n) return AVRF_OK;
@@ -90,7 +84,6 @@ int wire_prepare(avrf_ctx *ctx, int kind, bool batch, size_t n, const uint8_t *p
 int wire_finish(avrf_ctx *ctx, WirePrep &w, int32_t *status_out) {
   const size_t n = w.n, tot = w.tot, ppts = w.ppts; const int kind = w.kind;
   if (!n) return AVRF_OK;
-  if (w.small) status_out = w.small_status.data();
   if (w.batch) {
     if (kind == Thin) return avrf_thin_batch_verify(ctx, n, w.x_pks, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data());
     return avrf_pedersen_batch_verify(ctx, n, w.x_ios, w.io_counts, w.ads, w.ad_lens, w.px.data());
@@ -107,11 +100,6 @@ int wire_finish(avrf_ctx *ctx, WirePrep &w, int32_t *status_out) {
   for (size_t j = 0; j < n; j++) { for (size_t k = 0; k < 2 * (size_t)w.io_counts[j]; k++) if (pst[at + io_at + k]) status_out[j] = AVRF_INVALID_DATA; io_at += 2 * w.io_counts[j]; }
   at += 2 * tot;
   for (size_t p = 0; p < ppts; p++) for (size_t j = 0; j < n; j++) if (pst[at + p * n + j]) status_out[j] = AVRF_INVALID_DATA;
-  if (w.small) {                                                       // BatchVerifier's verdict: InvalidData before VerificationFailure
-    int worst = AVRF_OK;
-    for (size_t j = 0; j < n; j++) { if (status_out[j] == AVRF_INVALID_DATA) return AVRF_INVALID_DATA; if (status_out[j]) worst = AVRF_VERIFICATION_FAILURE; }
-    return worst;
-  }
   return AVRF_OK;
 }
 int verify_wire(avrf_ctx *ctx, int kind, bool batch, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,

@@ -13,9 +13,10 @@
 //     chains, folds finished ones (host_te.h) -- all from completion events, sleeping in the driver only when idle;
 //   * inputs are read where the caller put them: from buffers of avrf_host_alloc the staging copies are DMA transfers that
 //     overlap the other batches' kernels and cost no host time (include/avrf.h "Ownership").
-// Verdicts are those of avrf_thin_batch_run / avrf_pedersen_batch_run: the workers call the same stagers and phases (capi_internal.h:
-// ctx_stage / ctx_stage_wire, batch_begin / _collect / _seed / _launch / _end; grouped hashing through sha512_many), each
-// under `guarded` -- a failed HIP call or allocation inside a worker becomes the batch's status, never an exception off the thread.
+// Verdicts are those of avrf_thin_batch_run / avrf_pedersen_batch_run: a slot keeps the BatchSource it was submitted with, and the
+// workers call the same stager and phases (capi_internal.h: ctx_stage over that source, whatever its flavour; batch_begin / _collect /
+// _seed / _launch / _end; grouped hashing through sha512_many), each under `guarded` -- a failed HIP call or allocation inside a
+// worker becomes the batch's status, never an exception off the thread.
 #include "capi_internal.h"
 #include "suite_dispatch.h"
 #include "host_sha512_mb.h"
@@ -38,7 +39,6 @@ struct Slot {
   avrf_ctx *c = nullptr;          // a lane-less context: staged buffers, challenges, records, pinned transcript
   std::atomic<int> state{S_FREE};
   bool has_batch = false;         // the buffers hold a staged batch (it can be run again without its host sources)
-  bool wire = false; int validate = 0;   // the host sources are serialize_compressed bytes (avrf_pool_submit_wire): decompressed on the device while staging
   bool from_host = false;         // stage from the host sources before the run
   bool resident_invalid = false;  // the staged bytes did not decode / validate (a wire batch): runs from the resident state answer InvalidData again
   uint64_t ticket = 0;
@@ -47,12 +47,7 @@ struct Slot {
   Lane *lane = nullptr;
   MsmChain pend;                  // the record of the slot's MSM chain (several chains queue on one lane)
   uint64_t seq = 0;               // order in which the worker enqueued the slot's current phase (oldest is waited for first)
-  size_t n = 0;
-  const uint8_t *pks = nullptr, *ios = nullptr, *ads = nullptr, *proofs = nullptr;
-  const uint32_t *io_counts = nullptr, *ad_lens = nullptr;
-  // the host sources are a table of shared points (avrf_pool_submit_shared): pks = the table, ios = the outputs, and the indices into the table
-  // (with `wire` as well -- avrf_pool_submit_shared_wire -- table, outputs and proofs are wire bytes: ctx_stage_shared_wire)
-  bool shared = false; size_t n_shared = 0; const uint32_t *pk_index = nullptr, *input_index = nullptr;
+  BatchSource src;                // the host sources, as submitted (the caller keeps them alive while the slot may stage from them)
   uint8_t digest[64];
   // the event, the record, then the context: it has no stream or workspace of its own and is detached from the pool's lane before it dies
   ~Slot() {
@@ -121,7 +116,7 @@ struct Run {
   }
   // (a wire batch whose points did not decode leaves no usable staged state -- batch_collect drops it -- but the slot still "holds" that
   // batch: resubmission and cycle mode from the resident state must give the same verdict, not a bad-argument error)
-  static void latch(Slot &S, int status) { if (S.wire && status == AVRF_INVALID_DATA) S.resident_invalid = true; }
+  static void latch(Slot &S, int status) { if (S.src.wire && status == AVRF_INVALID_DATA) S.resident_invalid = true; }
 
   void begin(Slot &S) {
     const double t0 = thread_cpu_us();
@@ -132,10 +127,7 @@ struct Run {
     if (!S.from_host && S.resident_invalid) { W.cpu_us[0] += thread_cpu_us() - t0; done(S, AVRF_INVALID_DATA); return; }
     if (S.from_host) {
       S.resident_invalid = false;
-      if (S.shared && S.wire) st = guarded([&] { return ctx_stage_shared_wire(c, S.n, S.n_shared, S.pks, S.pk_index, S.input_index, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, S.validate, /*wait=*/false); });
-      else if (S.shared) st = guarded([&] { return ctx_stage_shared(c, S.n, S.n_shared, S.pks, S.pk_index, S.input_index, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
-      else if (S.wire) st = guarded([&] { return ctx_stage_wire(c, P->kind, S.n, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, S.validate, /*wait=*/false); });
-      else st = guarded([&] { return ctx_stage(c, P->kind, S.n, nullptr, S.pks, S.ios, S.io_counts, S.ads, S.ad_lens, S.proofs, /*wait=*/false); });
+      st = guarded([&] { return ctx_stage(c, S.src, /*wait=*/false); });
       S.has_batch = st == AVRF_OK;
     }
     if (st == AVRF_OK) st = guarded([&] { return batch_begin(c, P->kind); });
@@ -318,40 +310,11 @@ int avrf_pool_set_validation(avrf_pool *P, int level) {
   return AVRF_OK;
 }
 
-struct SharedSource { size_t n_shared; const uint32_t *pk_index, *input_index; };   // pool_submit: pks_xy is the table, ios_xy the outputs
-static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
-                       const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate, const SharedSource *shared = nullptr);
-int avrf_pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
-                     const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket) {
-  return pool_submit(P, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs, ticket, false, 0);
-}
-// the same job from the reference's wire bytes (`serialize_compressed` points, proofs as CanonicalSerialize writes them): the
-// points are decompressed -- validate != 0: and checked for non-identity and prime-order-subgroup membership -- on the device
-// while the batch is staged; a point that fails makes the batch's verdict AVRF_INVALID_DATA
-int avrf_pool_submit_wire(avrf_pool *P, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
-                          const uint32_t *ad_lens, const uint8_t *proofs, int validate, uint64_t *ticket) {
-  return pool_submit(P, n, pks, ios, io_counts, ads, ad_lens, proofs, ticket, true, validate);
-}
-// the same job over a table of shared points (include/avrf.h avrf_thin_batch_stage_shared); the indices are checked here, on the calling
-// thread, before a ticket exists
-int avrf_pool_submit_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
-                            const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
-                            uint64_t *ticket) {
-  if (!P || P->kind != Thin || !shared_indices_ok(n, n_shared, pk_index, input_index, outputs_xy, io_counts)) return AVRF_ERR_BAD_ARG;
-  const SharedSource src{n_shared, pk_index, input_index};
-  return pool_submit(P, n, shared_xy, outputs_xy, io_counts, ads, ad_lens, proofs, ticket, false, 0, &src);
-}
-// both: the table, the outputs and the proofs as wire bytes (include/avrf.h avrf_thin_batch_stage_shared_wire); indices checked here as above
-int avrf_pool_submit_shared_wire(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
-                                 const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
-                                 int validate, uint64_t *ticket) {
-  if (!P || P->kind != Thin || !shared_indices_ok(n, n_shared, pk_index, input_index, outputs, io_counts)) return AVRF_ERR_BAD_ARG;
-  const SharedSource src{n_shared, pk_index, input_index};
-  return pool_submit(P, n, shared, outputs, io_counts, ads, ad_lens, proofs, ticket, true, validate, &src);
-}
-static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
-                       const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket, bool wire, int validate, const SharedSource *shared) {
-  if (!P || !ticket || (n && (!proofs || !io_counts || !ad_lens)) || (n && kind_facts(P->kind).pk && !pks_xy)) return AVRF_ERR_BAD_ARG;
+// A free slot of the least loaded worker takes the source (waiting for one while batches are running).  What every flavour needs is
+// checked here, on the calling thread, before a ticket exists; the shared ones check their indices there as well.
+static int pool_submit(avrf_pool *P, const BatchSource &src, uint64_t *ticket) {
+  const uint8_t *keys = src.n_shared ? src.table : src.pks;
+  if (!P || !ticket || (src.n && (!src.proofs || !src.io_counts || !src.ad_lens)) || (src.n && kind_facts(P->kind).pk && !keys)) return AVRF_ERR_BAD_ARG;
   std::unique_lock<std::mutex> lk(P->m);
   if (P->cycling) return AVRF_ERR_BAD_ARG;
   for (;;) {
@@ -364,9 +327,8 @@ static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint
     }
     if (best >= 0) {
       Slot &S = P->slots[best];
-      S.n = n; S.pks = pks_xy; S.ios = ios_xy; S.io_counts = io_counts; S.ads = ads; S.ad_lens = ad_lens; S.proofs = proofs;
-      S.shared = shared != nullptr; S.n_shared = shared ? shared->n_shared : 0; S.pk_index = shared ? shared->pk_index : nullptr; S.input_index = shared ? shared->input_index : nullptr;
-      S.from_host = true; S.wire = wire; S.validate = validate; S.resident_invalid = false; S.ticket = P->next_ticket++; S.status = 0;
+      S.src = src;
+      S.from_host = true; S.resident_invalid = false; S.ticket = P->next_ticket++; S.status = 0;
       S.state = S_SUBMITTED;
       *ticket = S.ticket;
       P->cv_work.notify_all();
@@ -375,6 +337,36 @@ static int pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint
     if (!any_running) return AVRF_ERR_BAD_ARG;                         // every slot holds an uncollected verdict: avrf_pool_wait first
     P->cv_done.wait(lk);
   }
+}
+int avrf_pool_submit(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
+                     const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket) {
+  if (!P) return AVRF_ERR_BAD_ARG;
+  return pool_submit(P, plain_source(P->kind, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs), ticket);
+}
+// the same job from the reference's wire bytes (`serialize_compressed` points, proofs as CanonicalSerialize writes them): the
+// points are decompressed -- validate != 0: and checked for non-identity and prime-order-subgroup membership -- on the device
+// while the batch is staged; a point that fails makes the batch's verdict AVRF_INVALID_DATA
+int avrf_pool_submit_wire(avrf_pool *P, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                          const uint32_t *ad_lens, const uint8_t *proofs, int validate, uint64_t *ticket) {
+  if (!P) return AVRF_ERR_BAD_ARG;
+  return pool_submit(P, wire_source(plain_source(P->kind, n, pks, ios, io_counts, ads, ad_lens, proofs), validate), ticket);
+}
+// the same job over a table of shared points (include/avrf.h avrf_thin_batch_stage_shared); the indices are checked here, on the calling
+// thread, before a ticket exists
+int avrf_pool_submit_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
+                            const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                            uint64_t *ticket) {
+  const BatchSource src = shared_source(n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs);
+  if (!P || P->kind != Thin || !shared_indices_ok(src)) return AVRF_ERR_BAD_ARG;
+  return pool_submit(P, src, ticket);
+}
+// both: the table, the outputs and the proofs as wire bytes (include/avrf.h avrf_thin_batch_stage_shared_wire); indices checked here as above
+int avrf_pool_submit_shared_wire(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                                 const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                                 int validate, uint64_t *ticket) {
+  const BatchSource src = wire_source(shared_source(n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs), validate);
+  if (!P || P->kind != Thin || !shared_indices_ok(src)) return AVRF_ERR_BAD_ARG;
+  return pool_submit(P, src, ticket);
 }
 
 int avrf_pool_wait(avrf_pool *P, uint64_t ticket, int *status) {
