@@ -163,10 +163,20 @@ def thin_segments_layout(seg_items, io_counts):
     return tuple(out) if st == OK else st
 
 
+def pedersen_segments_layout(n, seg_items):
+    """Layout of a segmented Pedersen run over n items (host arithmetic; no device needed; five terms per item and two per
+    segment whatever the pair counts) -> (L, padded terms, total terms, window bits), or ERR_BAD_ARG as above."""
+    seg_items = list(seg_items)
+    out = (C.c_uint64 * 4)()
+    st = lib().avrf_pedersen_segments_layout(C.c_size_t(n), C.c_size_t(len(seg_items)), _u32(seg_items), out)
+    return tuple(out) if st == OK else st
+
+
 class Context:
     """One engine instance = suite + HIP stream + device workspace (avrf_ctx)."""
 
     thin_segments_layout = staticmethod(thin_segments_layout)
+    pedersen_segments_layout = staticmethod(pedersen_segments_layout)
 
     def __init__(self, suite=BANDERSNATCH_SHA512_ELL2, device=0):
         self._h = C.c_void_p()
@@ -263,7 +273,27 @@ class Context:
 
     def thin_segment_terms(self, seg):
         """(bases_xy, scalars) the last segmented run built for segment `seg`, as last_terms gives the plain run's."""
-        f = lib().avrf_thin_segment_terms
+        return self._segment_terms(lib().avrf_thin_segment_terms, seg)
+
+    # -- the same over the staged Pedersen batch (include/avrf.h avrf_pedersen_batch_run_segments)
+    def pedersen_batch_run_segments(self, seg_items):
+        """seg_items: items per segment, consecutive, summing to the staged n -> list of statuses, or the refusal (ERR_BAD_ARG)."""
+        return self._segments(seg_items, lib().avrf_pedersen_batch_run_segments)
+
+    def pedersen_batch_verify_segments(self, b, seg_items):
+        """stage + pedersen_batch_run_segments for a Batch."""
+        return self._segments(seg_items, lib().avrf_pedersen_batch_verify_segments, C.c_size_t(b.n), b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
+
+    def pedersen_batch_verify_segments_wire(self, b, seg_items, validate=1):
+        """The same for a Batch whose ios_xy / proofs fields hold the WIRE bytes (compressed points)."""
+        return self._segments(seg_items, lib().avrf_pedersen_batch_verify_segments_wire, C.c_size_t(b.n), b.ios_xy, b.io_counts, b.ads, b.ad_lens,
+                              b.proofs, int(validate))
+
+    def pedersen_segment_terms(self, seg):
+        """(bases_xy, scalars) the last segmented Pedersen run built for segment `seg`."""
+        return self._segment_terms(lib().avrf_pedersen_segment_terms, seg)
+
+    def _segment_terms(self, f, seg):
         f.restype = C.c_size_t
         k = f(self._h, C.c_size_t(seg), None, None)
         bases, sc = (C.c_uint8 * max(1, 64 * k))(), (C.c_uint8 * max(1, 32 * k))()

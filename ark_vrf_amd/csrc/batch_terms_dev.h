@@ -1,8 +1,9 @@
 // batch_terms_dev.h -- what the terms kernels of the batch verifiers share (vrf_batch.hip k_thin_terms / k_ped_terms / k_g_final,
-// thin_shared.hip k_thin_terms_shared / k_shared_merge), each stated once:
+// thin_shared.hip k_thin_terms_shared / k_shared_merge, thin_seg.hip's segmented kernels of both kinds), each stated once:
 //   fp_from_u128, emit_term : a 128-bit little-endian value as a field element; one MSM term (plain scalar + precomputed base)
 //   block_sum               : the sum of an Fr value over a block, in LDS
 //   thin_item               : the per-item arithmetic of thin::BatchVerifier::verify, src/thin.rs:287-313, over a sink for its terms
+//   ped_item                : the per-item arithmetic of pedersen::BatchVerifier::verify, src/pedersen.rs:369-410, over a sink likewise
 //   base_term               : the shared-base term (G or BLINDING_BASE, -(sum of the blocks' partials)), src/thin.rs:303,316-317
 #pragma once
 #include "proto_dev.h"
@@ -65,6 +66,35 @@ AVRF_DI fp thin_item(const BatchDev &b, const Seed64 &seed, uint64_t j0, const u
     out.input(j, io0, i, fp_neg<Fr>(fp_mul<Fr>(ws, z)), p);                             // (I_i, -w s z_i)
   }
   return ws;
+}
+
+// Item j of pedersen::BatchVerifier::verify (src/pedersen.rs:369-410): its five terms go to `out`, a struct with one inline function
+//   term(j, k, scalar_plain, xy)      k = 0 (O, t c)   1 (Ok, t)   2 (I, -t s)   3 (Yb, u c)   4 (R, u)
+// (O, I: the item's merged pair, merged_xy + 128 j, k_ped_prepare); what the item adds to the scalars of G and BLINDING_BASE, u s
+// (returned) and u sb (usb), comes back in Montgomery form (:409-410).
+template <class S, class Out>
+AVRF_DI fp ped_item(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *__restrict__ c_in, const uint8_t *__restrict__ merged_xy,
+                    uint32_t j, const Out &out, fp &usb) {
+  using Fr = typename S::Fr;
+  // 32 squeezed bytes per item: t = bytes[0..16], u = bytes[16..32]   (:373-381)
+  // (j0: global index of the shard's first item when one batch is split over several GPUs)
+  fp t_plain, u_plain;
+  if (b.weights) { t_plain = fp_from_u128(reinterpret_cast<const uint32_t *>(b.weights + 32 * (size_t)j)); u_plain = fp_from_u128(reinterpret_cast<const uint32_t *>(b.weights + 32 * (size_t)j + 16)); }
+  else {
+    ShaReader rd; for (int i = 0; i < 8; i++) rd.seed[i] = seed.w[i]; rd.have = 0;
+    t_plain = xof128(rd, (uint32_t)(2 * (j0 + j))); u_plain = xof128(rd, (uint32_t)(2 * (j0 + j) + 1));
+  }
+  fp tt = fp_to_mont<Fr>(t_plain), uu = fp_to_mont<Fr>(u_plain);
+  fp c = fp_to_mont<Fr>(fp_from_u128(c_in + 4 * (size_t)j));
+  const uint8_t *pr = b.proofs + 256 * (size_t)j, *mo = merged_xy + 128 * (size_t)j;
+  fp s = fp_to_mont<Fr>(fp_load_le(pr + 192)), sb = fp_to_mont<Fr>(fp_load_le(pr + 224));
+  out.term(j, 0, fp_from_mont<Fr>(fp_mul<Fr>(tt, c)), mo + 64);                    // (O, t c)      :392-393
+  out.term(j, 1, t_plain, pr + 128);                                               // (Ok, t)       :395-396
+  out.term(j, 2, fp_from_mont<Fr>(fp_neg<Fr>(fp_mul<Fr>(tt, s))), mo);             // (I, -t s)     :398-399
+  out.term(j, 3, fp_from_mont<Fr>(fp_mul<Fr>(uu, c)), pr);                         // (Yb, u c)     :402-403
+  out.term(j, 4, u_plain, pr + 64);                                                // (R, u)        :405-406
+  const fp us = fp_mul<Fr>(uu, s); usb = fp_mul<Fr>(uu, sb);                       // :409-410
+  return us;
 }
 
 // g = -(sum of the nparts partials); term t_last = (G, g), or (BLINDING_BASE, g) for which_base 1   (thin.rs:303,316-317).

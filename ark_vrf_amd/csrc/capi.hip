@@ -747,7 +747,7 @@ int avrf_pedersen_batch_verify(avrf_ctx *c, size_t n, const uint8_t *ios_xy, con
   return st ? st : avrf_pedersen_batch_run(c);
 }
 
-// ---------------------------------------------------------------- one verdict per segment of the staged Thin batch (thin_seg.h)
+// ---------------------------------------------------------------- one verdict per segment of the staged Thin or Pedersen batch (thin_seg.h)
 }  // extern "C"
 
 // `count` MSM terms of the context's device back to the host, each where wanted: the bases as canonical x || y, the scalars as they are.
@@ -766,9 +766,10 @@ static size_t terms_to_host(avrf_ctx *c, const te_pre_raw *d_pre, const uint8_t 
   return count;
 }
 
-// The layout of n_seg thin::BatchVerifiers over consecutive runs of n staged items (include/avrf.h avrf_thin_segments_layout): item
-// offsets into *seg_off (n_seg + 1) when wanted, out = { L, n_seg L, sum of the term counts, window bits }; io_off: n + 1 prefix sums of
-// the items' pair counts.  AVRF_ERR_BAD_ARG when the counts do not sum to n or a limit is exceeded.
+// The layout of n_seg BatchVerifiers of `kind` over consecutive runs of n staged items (include/avrf.h avrf_thin_segments_layout,
+// avrf_pedersen_segments_layout): item offsets into *seg_off (n_seg + 1) when wanted, out = { L, n_seg L, sum of the term counts, window
+// bits }; io_off: n + 1 prefix sums of the items' pair counts (Thin only: a Pedersen item has five terms whatever its pairs).
+// AVRF_ERR_BAD_ARG when the counts do not sum to n or a limit is exceeded.
 static int seg_limits(size_t n_seg, uint64_t L, uint64_t out[4]) {
   if (L > (uint64_t)AVRF_SEGMENT_TERMS_MAX || n_seg * L > (uint64_t)AVRF_SEGMENTS_PADDED_TERMS_MAX) return AVRF_ERR_BAD_ARG;
   const uint64_t c = L ? (uint64_t)msm_segments_window_bits(L) : 0;
@@ -777,15 +778,15 @@ static int seg_limits(size_t n_seg, uint64_t L, uint64_t out[4]) {
   out[0] = L; out[1] = n_seg * L; out[3] = c;
   return AVRF_OK;
 }
-static int seg_layout(size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_off, std::vector<uint32_t> *seg_off, uint64_t out[4]) {
-  if ((n_seg && !seg_items) || n_seg > 0x0fffffffULL || (n && !io_off)) return AVRF_ERR_BAD_ARG;
+static int seg_layout(int kind, size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_off, std::vector<uint32_t> *seg_off, uint64_t out[4]) {
+  if ((n_seg && !seg_items) || n_seg > 0x0fffffffULL || (kind == Thin && n && !io_off)) return AVRF_ERR_BAD_ARG;
   if (seg_off) seg_off->assign(n_seg + 1, (uint32_t)n);
   uint64_t at = 0, L = 0, total = 0;
   for (size_t v = 0; v < n_seg; v++) {
     const uint64_t items = seg_items[v];
     if (at + items > n) return AVRF_ERR_BAD_ARG;
     if (seg_off) (*seg_off)[v] = (uint32_t)at;
-    const uint64_t n_v = items ? n_terms(Thin, items, io_off[at + items] - io_off[at]) : 0;   // none for an empty segment
+    const uint64_t n_v = items ? n_terms(kind, items, kind == Thin ? io_off[at + items] - io_off[at] : 0) : 0;   // none for an empty segment
     if (n_v > L) L = n_v;
     total += n_v; at += items;
   }
@@ -800,23 +801,43 @@ int avrf_thin_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items,
   if (!out || (n && !io_counts) || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   std::vector<uint32_t> io_off(n + 1); uint64_t a;
   if (!prefix_sums(io_counts, n, io_off.data(), 0x1fffffffULL, &a)) return AVRF_ERR_BAD_ARG;
-  return seg_layout(n, n_seg, seg_items, io_off.data(), nullptr, out);
+  return seg_layout(Thin, n, n_seg, seg_items, io_off.data(), nullptr, out);
+}
+int avrf_pedersen_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, uint64_t out[4]) {
+  if (!out || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  return seg_layout(Pedersen, n, n_seg, seg_items, nullptr, nullptr, out);
+}
+}  // extern "C"
+
+// The segmented run of either batch verifier (include/avrf.h avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments).  What the
+// kind decides: the record and weight sizes (kind_facts), the scratch per item, the terms and flags launches, n_terms in seg_layout.
+static void launch_seg_terms(avrf_ctx *c, int kind, const BatchDev &b, size_t n_seg, size_t L) {
+  const uint32_t *off = c->d_seg_off.as<uint32_t>(); const Seed64 *seeds = c->d_seg_seeds.as<Seed64>();
+  if (kind == Thin) AVRF_SEG(c->suite, thin_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_seg_wsz.as<uint32_t>(),
+                                                  c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
+  else AVRF_SEG(c->suite, ped_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_seg_wsz.as<uint32_t>(),
+                                    c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
+}
+static void launch_seg_item_flags(avrf_ctx *c, int kind, const BatchDev &b) {
+  if (kind == Thin) AVRF_SEG(c->suite, item_flags(b, c->d_status.as<int32_t>(), c->stream));
+  else AVRF_SEG(c->suite, ped_item_flags(b, c->d_status.as<int32_t>(), c->stream));
 }
 
-int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
-  if (!c || ctx_busy(c) || c->staged_kind != Thin || c->n_shared || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
+static int run_segments(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  if (!c || ctx_busy(c) || c->staged_kind != kind || c->n_shared || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
   std::vector<uint32_t> seg_off; uint64_t lay[4];
-  if (int e = seg_layout(c->n, n_seg, seg_items, c->h_io.as<uint32_t>(), &seg_off, lay)) return e;
-  for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;          // what an empty segment keeps (src/thin.rs:262-264)
+  if (int e = seg_layout(kind, c->n, n_seg, seg_items, c->h_io.as<uint32_t>(), &seg_off, lay)) return e;
+  for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;          // what an empty segment keeps (src/thin.rs:262-264, src/pedersen.rs:343-345)
   if (!n_seg || !c->n) return AVRF_OK;
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = c->n, L = (size_t)lay[0], padded = (size_t)lay[1];
-  const KindFacts &k = kind_facts(Thin);
-  HIP_TRY(c->d_seg_scalars.ensure(padded * 32)); HIP_TRY(c->d_seg_pre.ensure(padded * sizeof(te_pre_raw))); HIP_TRY(c->d_seg_wsz.ensure(n * 32));
+  const KindFacts &k = kind_facts(kind);
+  // (scratch per item: Thin's w s z0, Pedersen's u s and u sb)
+  HIP_TRY(c->d_seg_scalars.ensure(padded * 32)); HIP_TRY(c->d_seg_pre.ensure(padded * sizeof(te_pre_raw))); HIP_TRY(c->d_seg_wsz.ensure(n * (kind == Thin ? 32 : 64)));
   HIP_TRY(c->d_seg_off.ensure((n_seg + 1) * 4)); HIP_TRY(c->d_seg_seeds.ensure(n_seg * sizeof(Seed64)));
-  // prepare once, for all segments: k_thin_prepare knows nothing about batches, and its records are contiguous per item
+  // prepare once, for all segments: the prepare kernels know nothing about batches, and their records are contiguous per item
   const double t0 = now_us();
-  if (int e = batch_begin(c, Thin)) return e;
+  if (int e = batch_begin(c, kind)) return e;
   c->run_phase = 0;                                                    // (the phases below are this call's own; an error leaves the context idle)
   HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
   // The flag word is the batch's.  Only when it is set: which items raised it -- the prepare kernel's checks again, per item, and
@@ -826,12 +847,12 @@ int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_
     item_status.resize(n);
     HIP_TRY(c->d_status.ensure(n * 4));
     HIP_TRY(hipMemsetAsync(c->d_status.p, 0, n * 4, c->stream));
-    AVRF_SEG(c->suite, item_flags(batch_of(c), c->d_status.as<int32_t>(), c->stream));
-    validate_staged(c, Thin, c->d_status.as<int32_t>());
+    launch_seg_item_flags(c, kind, batch_of(c));
+    validate_staged(c, kind, c->d_status.as<int32_t>());
     HIP_TRY(hipMemcpyAsync(item_status.data(), c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
   }
-  // the n_seg weight transcripts, each SUITE_ID || 0x50 || its own records (src/thin.rs:274-279), on the process's host pool
+  // the n_seg weight transcripts, each SUITE_ID || 0x50 || its own records (src/thin.rs:274-279, src/pedersen.rs:361-367), on the process's host pool
   const double t1 = now_us();
   uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
   BatchDev b = batch_of(c);
@@ -854,9 +875,9 @@ int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_
     });
     HIP_TRY(hipMemcpyAsync(c->d_seg_seeds.p, seeds.data(), n_seg * sizeof(Seed64), hipMemcpyHostToDevice, c->stream));
   } else {
-    // sponge / SHA-256 transcripts: every segment's weight stream squeezed on the host, item j's 16 bytes at 16 j
+    // sponge / SHA-256 transcripts: every segment's weight stream squeezed on the host, item j's 16 (Pedersen: 32) bytes at 16 (32) j
     c->h_weights.resize(n * k.weight);
-    parallel_for(n_seg, [&](size_t v) { if (seg_off[v + 1] != seg_off[v]) squeeze_weights(c, Thin, seg_off[v], seg_off[v + 1] - seg_off[v]); });
+    parallel_for(n_seg, [&](size_t v) { if (seg_off[v + 1] != seg_off[v]) squeeze_weights(c, kind, seg_off[v], seg_off[v + 1] - seg_off[v]); });
     HIP_TRY(c->d_weights.ensure(n * k.weight));
     HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), n * k.weight, hipMemcpyHostToDevice, c->stream));
     b.weights = c->d_weights.as<uint8_t>();
@@ -865,15 +886,14 @@ int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_
   const double t2 = now_us();
   HIP_TRY(hipMemcpyAsync(c->d_seg_off.p, seg_off.data(), (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_seg_scalars.p, 0, padded * 32, c->stream));
-  AVRF_SEG(c->suite, thin_terms(b, c->d_seg_off.as<uint32_t>(), (uint32_t)n_seg, (uint32_t)L, c->d_seg_seeds.as<Seed64>(), c->d_c.as<uint32_t>(),
-                                c->d_z.as<uint32_t>(), c->d_seg_wsz.as<uint32_t>(), c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
+  launch_seg_terms(c, kind, b, n_seg, L);
   const double t3 = now_us();
   std::vector<HostExt> sums(n_seg);
   if (int e = lane_msm_segments(c, c->d_seg_pre, c->d_seg_scalars, L, n_seg, sums.data())) return e;
   for (size_t v = 0; v < n_seg; v++) {
     if (seg_off[v] == seg_off[v + 1]) continue;
-    status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322
-    for (size_t j = seg_off[v]; !item_status.empty() && j < seg_off[v + 1]; j++) if (item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // :266-271
+    status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
+    for (size_t j = seg_off[v]; !item_status.empty() && j < seg_off[v + 1]; j++) if (item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // src/thin.rs:266-271, src/pedersen.rs:348-353
   }
   c->seg_gen = c->stage_gen; c->seg_L = L; c->seg_off = std::move(seg_off);
   // avrf_last_timing: prepare + its wait (and the attribution pass), the transcripts, the terms launches, the MSM chain with its wait
@@ -881,6 +901,22 @@ int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_
   c->timing[1] = t1 - t0; c->timing[2] = t2 - t1; c->timing[3] = t3 - t2; c->timing[4] = t4 - t3; c->timing[5] = 0; c->timing[0] = t4 - t0;
   return AVRF_OK;
 }
+// the terms of one segment of the last segmented run, as avrf_batch_last_terms gives the plain run's
+static size_t segment_terms(avrf_ctx *c, int kind, size_t seg, uint8_t *bases_xy, uint8_t *scalars) {
+  if (!c || ctx_busy(c) || c->staged_kind != kind || c->seg_gen != c->stage_gen || seg + 1 >= c->seg_off.size()) return 0;
+  if (hipSetDevice(c->device) != hipSuccess) return 0;
+  const uint32_t *io_off = c->h_io.as<uint32_t>();
+  const size_t first = c->seg_off[seg], items = c->seg_off[seg + 1] - first;
+  if (!items) return 0;
+  const size_t t0 = seg * c->seg_L;
+  return terms_to_host(c, c->d_seg_pre.as<te_pre_raw>() + t0, c->d_seg_scalars.as<uint8_t>() + 32 * t0,
+                       n_terms(kind, items, kind == Thin ? io_off[first + items] - io_off[first] : 0), bases_xy, scalars);
+}
+
+extern "C" {
+
+int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) { return run_segments(c, Thin, n_seg, seg_items, status_out); }
+int avrf_pedersen_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) { return run_segments(c, Pedersen, n_seg, seg_items, status_out); }
 
 int avrf_thin_batch_verify_segments(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
                                     const uint32_t *ad_lens, const uint8_t *proofs, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
@@ -893,16 +929,19 @@ int avrf_thin_batch_verify_segments_wire(avrf_ctx *c, size_t n, const uint8_t *p
   return st ? st : avrf_thin_batch_run_segments(c, n_seg, seg_items, status_out);
 }
 
-// the terms of one segment of the last segmented run, as avrf_batch_last_terms gives the plain run's
-size_t avrf_thin_segment_terms(avrf_ctx *c, size_t seg, uint8_t *bases_xy, uint8_t *scalars) {
-  if (!c || ctx_busy(c) || c->staged_kind != Thin || c->seg_gen != c->stage_gen || seg + 1 >= c->seg_off.size()) return 0;
-  if (hipSetDevice(c->device) != hipSuccess) return 0;
-  const uint32_t *io_off = c->h_io.as<uint32_t>();
-  const size_t first = c->seg_off[seg], items = c->seg_off[seg + 1] - first;
-  if (!items) return 0;
-  const size_t t0 = seg * c->seg_L;
-  return terms_to_host(c, c->d_seg_pre.as<te_pre_raw>() + t0, c->d_seg_scalars.as<uint8_t>() + 32 * t0, n_terms(Thin, items, io_off[first + items] - io_off[first]), bases_xy, scalars);
+int avrf_pedersen_batch_verify_segments(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                        const uint8_t *proofs, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  int st = avrf_pedersen_batch_stage(c, n, ios_xy, io_counts, ads, ad_lens, proofs);
+  return st ? st : avrf_pedersen_batch_run_segments(c, n_seg, seg_items, status_out);
 }
+int avrf_pedersen_batch_verify_segments_wire(avrf_ctx *c, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                             const uint8_t *proofs, int validate, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  int st = avrf_pedersen_batch_stage_wire(c, n, ios, io_counts, ads, ad_lens, proofs, validate);
+  return st ? st : avrf_pedersen_batch_run_segments(c, n_seg, seg_items, status_out);
+}
+
+size_t avrf_thin_segment_terms(avrf_ctx *c, size_t seg, uint8_t *bases_xy, uint8_t *scalars) { return segment_terms(c, Thin, seg, bases_xy, scalars); }
+size_t avrf_pedersen_segment_terms(avrf_ctx *c, size_t seg, uint8_t *bases_xy, uint8_t *scalars) { return segment_terms(c, Pedersen, seg, bases_xy, scalars); }
 
 // n_seg independent MSMs of L terms through the segmented chain (msm.h msm_te_segments), beside avrf_msm_te
 int avrf_msm_te_segments(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy) {

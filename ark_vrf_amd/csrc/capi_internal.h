@@ -78,8 +78,9 @@ struct avrf_ctx {
   avrf::DevBuf d_tabs;                               // per-item window tables of the independent prove / verify kernels
   avrf::DevBuf d_fixed; bool fixed_ready = false;   // fixed-base tables of G and BLINDING_BASE (provers, scalar_mul_base), built on first use
   avrf::PinBuf h_c, h_flags, h_io;
-  // the last segmented run of the staged batch (avrf_thin_batch_run_segments; thin_seg.h): terms of its own, n_seg * seg_L of them, so
-  // that the plain run's terms stay what they were; seg_off (n_seg + 1 item offsets) describes them while seg_gen == stage_gen
+  // the last segmented run of the staged batch (avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments; thin_seg.h): terms of its
+  // own, n_seg * seg_L of them, so that the plain run's terms stay what they were; seg_off (n_seg + 1 item offsets) describes them while
+  // seg_gen == stage_gen.  d_seg_wsz: per-item scratch of the terms kernel (Thin w s z0, n x 32 bytes; Pedersen u s and u sb, n x 64)
   uint64_t seg_gen = 0; size_t seg_L = 0; std::vector<uint32_t> seg_off;
   avrf::DevBuf d_seg_scalars, d_seg_pre, d_seg_wsz, d_seg_off, d_seg_seeds;
   std::vector<uint8_t> h_seg_msg;   // the segments' weight-transcript messages, prefix || records each

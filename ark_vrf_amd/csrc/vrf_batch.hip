@@ -5,6 +5,8 @@
 //                     vrf_transcript_base :159-173, DelinearizeScalars :335-369, challenge :270-280)
 //   k_thin_terms   : the per-item part of thin::BatchVerifier::verify, src/thin.rs:287-313 (thin_item, batch_terms_dev.h)
 //   k_g_final      : the shared-generator term, src/thin.rs:303,316-317 (base_term, batch_terms_dev.h)
+//   k_ped_prepare  : pedersen::BatchItem::new, src/pedersen.rs:276-293
+//   k_ped_terms    : the per-item part of pedersen::BatchVerifier::verify, src/pedersen.rs:369-410 (ped_item, batch_terms_dev.h)
 // One lane per batch item; SHA-512 state in VGPRs (sha512_dev.h); scalar-field products in
 // 8 x u32 Montgomery form (fp256.h).
 #include "vrf_batch.h"
@@ -172,7 +174,13 @@ k_ped_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint8_t *__restrict__ me
   if (f) atomicOr(flags, f);
 }
 
-// per-item part of pedersen::BatchVerifier::verify, src/pedersen.rs:369-410
+// k_ped_terms' sink of ped_item's terms: item j's five at 5 j + k
+template <class S> struct PlainPedTerms {
+  uint32_t *__restrict__ scalars; te_pre *__restrict__ pre;
+  AVRF_DI void term(uint32_t j, uint32_t k, const fp &sc_plain, const uint8_t *xy) const { emit_term<S>(scalars, pre, 5 * j + k, sc_plain, xy); }
+};
+
+// per-item part of pedersen::BatchVerifier::verify, src/pedersen.rs:369-410 (ped_item, batch_terms_dev.h)
 template <class S>
 __global__ void __launch_bounds__(128)
 k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c_in, const uint8_t *__restrict__ merged_xy,
@@ -181,27 +189,7 @@ k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c
   __shared__ fp red[128];
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   fp us = fp_zero(), usb = fp_zero();
-  if (j < b.n) {
-    // 32 squeezed bytes per item: t = bytes[0..16], u = bytes[16..32]   (:373-381)
-    // (j0: global index of the shard's first item when one batch is split over several GPUs)
-    fp t_plain, u_plain;
-    if (b.weights) { t_plain = fp_from_u128(reinterpret_cast<const uint32_t *>(b.weights + 32 * (size_t)j)); u_plain = fp_from_u128(reinterpret_cast<const uint32_t *>(b.weights + 32 * (size_t)j + 16)); }
-    else {
-      ShaReader rd; for (int i = 0; i < 8; i++) rd.seed[i] = seed.w[i]; rd.have = 0;
-      t_plain = xof128(rd, (uint32_t)(2 * (j0 + j))); u_plain = xof128(rd, (uint32_t)(2 * (j0 + j) + 1));
-    }
-    fp tt = fp_to_mont<Fr>(t_plain), uu = fp_to_mont<Fr>(u_plain);
-    fp c = fp_to_mont<Fr>(fp_from_u128(c_in + 4 * (size_t)j));
-    const uint8_t *pr = b.proofs + 256 * (size_t)j, *mo = merged_xy + 128 * (size_t)j;
-    fp s = fp_to_mont<Fr>(fp_load_le(pr + 192)), sb = fp_to_mont<Fr>(fp_load_le(pr + 224));
-    uint32_t k = 5 * j;
-    emit_term<S>(scalars, pre, k, fp_from_mont<Fr>(fp_mul<Fr>(tt, c)), mo + 64);                    // (O, t c)      :388-389
-    emit_term<S>(scalars, pre, k + 1, t_plain, pr + 128);                                            // (Ok, t)       :391-392
-    emit_term<S>(scalars, pre, k + 2, fp_from_mont<Fr>(fp_neg<Fr>(fp_mul<Fr>(tt, s))), mo);         // (I, -t s)     :394-395
-    emit_term<S>(scalars, pre, k + 3, fp_from_mont<Fr>(fp_mul<Fr>(uu, c)), pr);                     // (Yb, u c)     :398-399
-    emit_term<S>(scalars, pre, k + 4, u_plain, pr + 64);                                             // (R, u)        :401-402
-    us = fp_mul<Fr>(uu, s); usb = fp_mul<Fr>(uu, sb);                                                // :405-406
-  }
+  if (j < b.n) us = ped_item<S>(b, seed, j0, c_in, merged_xy, j, PlainPedTerms<S>{scalars, pre}, usb);
   const fp gsum = block_sum<Fr, 128>(us, red);
   if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, gsum);
   __syncthreads();

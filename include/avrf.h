@@ -267,6 +267,48 @@ size_t avrf_thin_segment_terms(avrf_ctx *ctx, size_t seg, uint8_t *bases_xy, uin
  * L <= AVRF_SEGMENT_TERMS_MAX and the other limits above, else AVRF_ERR_BAD_ARG. */
 int avrf_msm_te_segments(avrf_ctx *ctx, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy);
 
+/* ---- pedersen::BatchVerifier over SEGMENTS of one staged batch (src/pedersen.rs:303-426): the five calls above for the Pedersen
+ * verifier, with the same meaning, limits and refusals.  n_seg independent BatchVerifiers over consecutive runs of the staged
+ * Pedersen items, each with its own weight transcript (SUITE_ID || 0x50 || c || s || sb of ITS items, src/pedersen.rs:361-367;
+ * 32 weight bytes per item, t then u, :373-381) and its own verdict: one prepare launch, one copy back, the transcripts hashed
+ * sixteen at a time, one terms pass, ONE MSM chain.
+ *   statuses  status_out[v] is what avrf_pedersen_batch_verify answers for segment v's items alone; an empty segment is AVRF_OK
+ *             (src/pedersen.rs:343-345).  An identity key commitment Yb or supplied I/O point (:348-353; the MERGED pair of an
+ *             item without pairs is the identity legitimately, :264-267), a non-canonical coordinate, s or sb >= r, or under
+ *             avrf_ctx_set_validation 1 / 2 a point that fails, marks ITS segment AVRF_INVALID_DATA and no other.
+ *   layout    (avrf_pedersen_segment_terms; ABI) segment v covers the staged items [seg_off[v], seg_off[v + 1]) and has
+ *             n_v = 5 items + 2 terms at [v L, v L + n_v) of arrays of n_seg L terms, L the largest n_v, in the reference's order
+ *             (src/pedersen.rs:383-418): per item O, Ok, I, Yb, R, then (G, -sum u s), then (B, -sum u sb) last -- the terms of
+ *             avrf_batch_last_terms for a batch of just its items.  Scalars behind n_v are zero and their bases unwritten; an
+ *             empty segment has no terms.
+ *   limits    the three above through the same check: 5 items + 2 <= AVRF_SEGMENT_TERMS_MAX makes 1 637 items (8 187 terms) the
+ *             longest Pedersen segment.
+ *   refusals  AVRF_ERR_BAD_ARG with the staging untouched: nothing staged, a Thin batch staged (and avrf_thin_batch_run_segments
+ *             refuses a Pedersen one), counts that do not sum to n, a limit exceeded, a call between avrf_batch_run_begin and
+ *             _end.  avrf_pedersen_batch_run afterwards gives its usual verdict and avrf_batch_last_terms its usual terms.
+ * avrf_last_timing keeps the slots of the Thin call.
+ * Runtime (tools/segments_bench.py --kind=pedersen; one context, 65 536 one-pair items resident):
+ * 256 segments of 256 items 2.57-2.66 ms (24.6-25.5 M items/s), 1 024 x 64 3.5-3.7 ms, 64 x 1 024 3.0-3.9 ms; the same 256 batches as
+ * separate pool submissions 41-52 ms (15-20 x slower).  avrf_pedersen_verify on the same items, one verdict per ITEM and staged
+ * from the host, takes 2.83-3.42 ms: ON A RESIDENT BATCH THE SEGMENTED CALL BEATS IT (ranges apart, 20 % between the means); staged
+ * from the host on every call (avrf_pedersen_batch_verify_segments, 3.25-3.30 ms) it does not.  Use segments for many small
+ * batches and to locate a few bad items in a batch the context already holds (then avrf_pedersen_verify on the failing segments
+ * only); use avrf_pedersen_verify when the items come from the host and most are suspect. */
+int avrf_pedersen_batch_run_segments(avrf_ctx *ctx, size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+int avrf_pedersen_batch_verify_segments(avrf_ctx *ctx, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts,
+                                        const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, size_t n_seg,
+                                        const uint32_t *seg_items, int32_t *status_out);
+int avrf_pedersen_batch_verify_segments_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios, const uint32_t *io_counts,
+                                             const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
+                                             size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+/* The layout of a segmented Pedersen run (src/pedersen.rs:303-426: 5 items + 2 terms per BatchVerifier whatever the pair counts, so
+ * no io_counts), host arithmetic only: out as avrf_thin_segments_layout.  AVRF_ERR_BAD_ARG when the counts do not sum to n or a
+ * limit is exceeded. */
+int avrf_pedersen_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, uint64_t out[4]);
+/* The MSM terms the last avrf_pedersen_batch_run_segments built for segment `seg` (src/pedersen.rs:303-426; tests), as
+ * avrf_thin_segment_terms. */
+size_t avrf_pedersen_segment_terms(avrf_ctx *ctx, size_t seg, uint8_t *bases_xy, uint8_t *scalars);
+
 /* ---- Ownership of host buffers; page-locked memory (SURVEY.md 8b "Ownership").
  * Every entry point copies what it needs out of the caller's buffers before it returns, EXCEPT avrf_pool_submit (below), whose
  * copies are left in flight.  From ordinary (pageable) memory a copy to the device goes through the runtime's bounce buffers

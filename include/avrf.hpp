@@ -278,11 +278,52 @@ class BatchVerifier {
     return avrf_pedersen_batch_verify(su_.ctx(), n_, packed_.ios.data(), packed_.io_counts.data(), packed_.ads.data(),
                                       packed_.ad_lens.data(), proofs_.data());
   }
+  size_t len() const { return n_; }
+  // One verdict per segment (avrf_pedersen_batch_verify_segments): seg_items[v] consecutive pushed items each, summing to len(); what
+  // n_seg BatchVerifiers over those runs of items would answer (:303-426), in one pass over the device.  Throws when the call is refused.
+  std::vector<Status> verify_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_pedersen_batch_verify_segments(su_.ctx(), n_, packed_.ios.data(), packed_.io_counts.data(), packed_.ads.data(), packed_.ad_lens.data(),
+                                            proofs_.data(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen verify segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+  // the same on the batch the context holds since the last verify() / verify_segments() (avrf_pedersen_batch_run_segments)
+  std::vector<Status> run_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_pedersen_batch_run_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen run segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+  // the MSM terms of segment `seg` of the last segmented run (avrf_pedersen_segment_terms): bases x || y and scalars
+  std::pair<std::vector<uint8_t>, std::vector<uint8_t>> segment_terms(size_t seg) const {
+    const size_t k = avrf_pedersen_segment_terms(su_.ctx(), seg, nullptr, nullptr);
+    std::vector<uint8_t> bases(64 * k), scalars(32 * k);
+    if (k) avrf_pedersen_segment_terms(su_.ctx(), seg, bases.data(), scalars.data());
+    return {bases, scalars};
+  }
 
  private:
   const Suite &su_; size_t n_ = 0;
   std::vector<uint8_t> proofs_; detail::Packed packed_;
 };
+// { L, padded terms, total terms, window bits } of a segmented run over n items (avrf_pedersen_segments_layout; host arithmetic): throws
+// beyond the limits
+inline std::array<uint64_t, 4> segments_layout(size_t n, const std::vector<uint32_t> &seg_items) {
+  std::array<uint64_t, 4> out{};
+  if (avrf_pedersen_segments_layout(n, seg_items.size(), seg_items.data(), out.data()) != AVRF_OK) throw std::invalid_argument("avrf: segments layout");
+  return out;
+}
+// One verdict per segment from the reference's byte strings (avrf_pedersen_batch_verify_segments_wire): ios holds the items' compressed
+// (input || output) pairs back to back, proofs n serialised proofs, ads the additional data back to back.  Throws when an item does
+// not decode (AVRF_INVALID_DATA from staging) or the call is refused.
+inline std::vector<Status> verify_segments_wire(const Suite &su, const std::vector<uint8_t> &ios, const std::vector<uint32_t> &io_counts, const std::vector<uint8_t> &ads,
+                                                const std::vector<uint32_t> &ad_lens, const std::vector<uint8_t> &proofs, int validate,
+                                                const std::vector<uint32_t> &seg_items) {
+  std::vector<int32_t> st(seg_items.size() + 1);
+  if (io_counts.size() != ad_lens.size() ||
+      avrf_pedersen_batch_verify_segments_wire(su.ctx(), io_counts.size(), ios.data(), io_counts.data(), ads.data(), ad_lens.data(), proofs.data(), validate,
+                                               seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen verify segments (wire)");
+  return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+}
 
 }  // namespace pedersen
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""What the segmented Thin batch verifier (avrf_thin_batch_run_segments) gives against the calls it competes with, on one MI355X in one
-process: 65 536 one-pair items, the legs run alternately, three runs each; a run is the mean of ten calls after two warm-ups.
+"""What a segmented batch verifier (avrf_thin_batch_run_segments; avrf_pedersen_batch_run_segments with --kind=pedersen, whose legs
+call the Pedersen twin of every entry point named below) gives against the calls it competes with, on one MI355X in one process:
+65 536 one-pair items, the legs run alternately, three runs each; a run is the mean of ten calls after two warm-ups.
     a  thin_batch_run_segments on the resident batch: 256 x 256, 1 024 x 64 and 64 x 1 024 items (and 256 x 256 from the host:
        stage + run, what thin_verify pays too)
     b  thin_verify on the same items: one verdict per item
@@ -9,8 +10,9 @@ process: 65 536 one-pair items, the legs run alternately, three runs each; a run
     d  the plain thin_batch_run: one verdict for everything
 Per leg: items/s, and for the context's legs the k_accumulate milliseconds per call (avrf_kernel_stats) and the host-side stage times
 of the segmented call (avrf_last_timing: prepare + wait, transcripts, terms launches, MSM chain + wait).
-python tools/segments_bench.py [n] [--quick] [--legs=abcd] [--shape=ITEMS]
-    --legs: only these legs; --shape=256: of leg a only the segments of that many items (a kernel trace of one leg keeps its kernels apart)"""
+python tools/segments_bench.py [n] [--quick] [--legs=abcd] [--shape=ITEMS] [--kind=thin|pedersen]
+    --legs: only these legs; --shape=256: of leg a only the segments of that many items (a kernel trace of one leg keeps its kernels apart)
+    --kind=pedersen: the same legs over the Pedersen verifier (avrf_pedersen_batch_run_segments, avrf_pedersen_verify, a kind 2 pool)"""
 import ctypes as C
 import json
 import os
@@ -30,6 +32,9 @@ REPS, CALLS, WARM = (1, 3, 1) if QUICK else (3, 10, 2)
 LEGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--legs=")), "abcd")
 SHAPE = next((int(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--shape=")), None)
 SHAPES = [(n // k, k) for k in (256, 64, 1024) if SHAPE in (None, k)]             # (segments, items per segment)
+KIND = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--kind=")), "thin")
+# per kind: the oracle's and the pool's kind ids, the x || y proof size, whether items carry a public key (KIND is also the Context methods' prefix)
+ORC_KIND, POOL_KIND, PROOF, HAS_PK = {"thin": (0, 1, 96, True), "pedersen": (1, 2, 256, False)}[KIND]
 
 
 def accum(ctx, reset):
@@ -54,10 +59,13 @@ def timed(ctx, call):
 def main():
     assert nat.set_blocking_sync(0, True) == 0
     ctx = nat.Context(0)
-    b = orc.gen_batch(0, 0, n, threads=16)
-    batch = nat.Batch(n, b["ios_xy"], b["io_counts"], b["ads"], b["ad_lens"], pks_xy=b["pks_xy"], proofs=b["proofs"])
+    b = orc.gen_batch(0, ORC_KIND, n, threads=16)
+    pks = (lambda lo, hi: b["pks_xy"][64 * lo: 64 * hi]) if HAS_PK else (lambda lo, hi: None)
+    batch = nat.Batch(n, b["ios_xy"], b["io_counts"], b["ads"], b["ad_lens"], pks_xy=pks(0, n), proofs=b["proofs"])
     status = (C.c_int32 * n)()
-    out = dict(n=n, reps=REPS, calls=CALLS, warmups=WARM, pool=dict(slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH), runs=[])
+    stage, run, run_segments, verify_segments, verify_into = (getattr(ctx, KIND + "_" + m) for m in
+                                                              ("batch_stage", "batch_run", "batch_run_segments", "batch_verify_segments", "verify_into"))
+    out = dict(kind=KIND, n=n, reps=REPS, calls=CALLS, warmups=WARM, pool=dict(slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH), runs=[])
 
     def record(leg, sec, items=n, **kw):
         run = dict(leg=leg, items_per_sec=round(items / sec), ms_per_call=round(1e3 * sec, 4), **kw)
@@ -73,8 +81,8 @@ def main():
     for k in range(n // per):
         lo, hi = k * per, (k + 1) * per
         small.append(nat.PinnedBatch(per, b["ios_xy"][128 * lo: 128 * hi], [1] * per, b["ads"][off[lo]: off[hi]], b["ad_lens"][lo: hi],
-                                     pks_xy=b["pks_xy"][64 * lo: 64 * hi], proofs=b["proofs"][96 * lo: 96 * hi]))
-    pool = nat.Pool(0, kind=1, slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH) if "c" in LEGS else None
+                                     pks_xy=pks(lo, hi), proofs=b["proofs"][PROOF * lo: PROOF * hi]))
+    pool = nat.Pool(0, kind=POOL_KIND, slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH) if "c" in LEGS else None
 
     def pool_submissions():
         tk = []
@@ -87,25 +95,25 @@ def main():
 
     try:
         for rep in range(REPS):
-            assert ctx.thin_batch_stage(batch) == 0
+            assert stage(batch) == 0
             for n_seg, k in SHAPES if "a" in LEGS else []:                         # a: resident
                 segs = [k] * n_seg
-                assert ctx.thin_batch_run_segments(segs) == [0] * n_seg
-                sec, ms, cnt = timed(ctx, lambda: ctx.thin_batch_run_segments(segs))
+                assert run_segments(segs) == [0] * n_seg
+                sec, ms, cnt = timed(ctx, lambda: run_segments(segs))
                 tm = ctx.last_timing()
                 record("a %d x %d" % (n_seg, k), sec, rep=rep, accumulate_ms=round(ms, 4), accumulate_launches=cnt,
                        stage_us=dict(prepare=round(tm[1]), transcripts=round(tm[2]), terms=round(tm[3]), msm=round(tm[4])))
             if "d" in LEGS:
-                sec, ms, cnt = timed(ctx, lambda: ctx.thin_batch_run())
+                sec, ms, cnt = timed(ctx, lambda: run())
                 record("d plain run", sec, rep=rep, accumulate_ms=round(ms, 4), accumulate_launches=cnt)
             if "a" in LEGS and SHAPE in (None, 256):
                 segs = [256] * (n // 256)
-                sec, ms, cnt = timed(ctx, lambda: ctx.thin_batch_verify_segments(batch, segs))
+                sec, ms, cnt = timed(ctx, lambda: verify_segments(batch, segs))
                 record("a 256 x 256 from host", sec, rep=rep, accumulate_ms=round(ms, 4))
             if "b" in LEGS:
-                sec, _, _ = timed(ctx, lambda: ctx.thin_verify_into(batch, status))
+                sec, _, _ = timed(ctx, lambda: verify_into(batch, status))
                 assert not any(status)
-                record("b thin_verify", sec, rep=rep)
+                record("b %s_verify" % KIND, sec, rep=rep)
             if "c" not in LEGS:
                 continue
             for _ in range(WARM):                                                  # c
