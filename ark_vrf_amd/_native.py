@@ -150,6 +150,50 @@ def thin_shared_n_terms(n, tot_io, n_shared):
     return f(C.c_size_t(n), C.c_size_t(tot_io), C.c_size_t(n_shared))
 
 
+class PedersenSharedBatch:
+    """A Pedersen batch over a table of shared inputs in the C-ABI layout (include/avrf.h avrf_pedersen_batch_stage_shared): shared_xy
+    n_shared x 64, input_index one row per I/O pair (item-major), outputs_xy one point per pair, proofs n x 256."""
+
+    def __init__(self, n, shared_xy, input_index, outputs_xy, io_counts, ads, ad_lens, proofs):
+        self.n = n
+        self.n_shared = len(shared_xy if isinstance(shared_xy, C.Array) else bytes(shared_xy)) // 64
+        self.shared_xy, self.outputs_xy, self.ads, self.proofs = _u8(shared_xy), _u8(outputs_xy), _u8(ads), _u8(proofs)
+        self.input_index, self.io_counts, self.ad_lens = _u32(input_index), _u32(io_counts), _u32(ad_lens)
+
+    def args(self):
+        return (C.c_size_t(self.n), C.c_size_t(self.n_shared), self.shared_xy, self.input_index, self.outputs_xy,
+                self.io_counts, self.ads, self.ad_lens, self.proofs)
+
+
+class PedersenSharedWireBatch(PedersenSharedBatch):
+    """A PedersenSharedBatch from wire bytes (avrf_pedersen_batch_stage_shared_wire): `shared` n_shared x L and `outputs` one L-byte
+    compressed point per pair, proofs n x (3 L + 64) laid out Yb || R || Ok || s || sb; L = Context.point_len of the suite."""
+
+    def __init__(self, n, shared, input_index, outputs, io_counts, ads, ad_lens, proofs, L=32):
+        PedersenSharedBatch.__init__(self, n, shared, input_index, outputs, io_counts, ads, ad_lens, proofs)
+        self.n_shared = len(shared if isinstance(shared, C.Array) else bytes(shared)) // L
+
+
+def dedup_inputs(ios_xy):
+    """An expanded Pedersen batch's pairs -> (shared_xy, input_index, outputs_xy): the byte-wise distinct inputs (the first 64 of
+    every 128 bytes of ios_xy), the row of every pair's input, and the outputs on their own.  No pairs: an empty table."""
+    shared, _, input_index, outputs = dedup_points(b"", ios_xy)
+    return shared, input_index, outputs
+
+
+def dedup_inputs_wire(ios, L=32):
+    """dedup_inputs on compressed points: ios pairs of L-byte points (input || output) -> (shared, input_index, outputs)."""
+    shared, _, input_index, outputs = dedup_points_wire(b"", ios, L)
+    return shared, input_index, outputs
+
+
+def pedersen_shared_n_terms(n, n_shared):
+    """Terms of the MSM a shared-table Pedersen batch builds, 4 n + n_shared + 2 (host arithmetic; no device needed)."""
+    f = lib().avrf_pedersen_shared_n_terms
+    f.restype = C.c_size_t
+    return f(C.c_size_t(n), C.c_size_t(n_shared))
+
+
 SEGMENT_TERMS_MAX, SEGMENTS_PADDED_TERMS_MAX, SEGMENTS_WINDOWS_MAX = 8191, 1 << 20, 65535   # include/avrf.h AVRF_SEGMENT*
 
 
@@ -249,6 +293,17 @@ class Context:
 
     def thin_batch_run(self):
         return lib().avrf_thin_batch_run(self._h)
+
+    def pedersen_batch_stage_shared(self, b):
+        """b: PedersenSharedBatch.  Staged for pedersen_batch_run / batch_run_begin .. / last_terms like a plain batch."""
+        return lib().avrf_pedersen_batch_stage_shared(self._h, *b.args())
+
+    def pedersen_batch_stage_shared_wire(self, b, validate=1):
+        """b: PedersenSharedWireBatch.  INVALID_DATA when a row, an output or a proof point does not decode (validate: or fails Validate::Yes)."""
+        return lib().avrf_pedersen_batch_stage_shared_wire(self._h, *b.args(), int(validate))
+
+    def pedersen_batch_verify_shared_wire(self, b, validate=1):
+        return lib().avrf_pedersen_batch_verify_shared_wire(self._h, *b.args(), int(validate))
 
     # -- one verdict per segment of the staged Thin batch (include/avrf.h avrf_thin_batch_run_segments)
     def thin_batch_run_segments(self, seg_items):
@@ -517,6 +572,25 @@ class PinnedSharedWireBatch(PinnedSharedBatch):
         self.n_shared = len(bytes(shared)) // L
 
 
+class PinnedPedersenSharedBatch(PinnedBatch):
+    """A PedersenSharedBatch whose buffers live in page-locked host memory."""
+
+    def __init__(self, n, shared_xy, input_index, outputs_xy, io_counts, ads, ad_lens, proofs):
+        self.n_shared = len(bytes(shared_xy)) // 64
+        self._pin_all(n, dict(shared_xy=shared_xy, outputs_xy=outputs_xy, ads=ads, proofs=proofs),
+                      dict(input_index=input_index, io_counts=io_counts, ad_lens=ad_lens))
+
+    args = PedersenSharedBatch.args
+
+
+class PinnedPedersenSharedWireBatch(PinnedPedersenSharedBatch):
+    """A PedersenSharedWireBatch whose buffers live in page-locked host memory."""
+
+    def __init__(self, n, shared, input_index, outputs, io_counts, ads, ad_lens, proofs, L=32):
+        PinnedPedersenSharedBatch.__init__(self, n, shared, input_index, outputs, io_counts, ads, ad_lens, proofs)
+        self.n_shared = len(bytes(shared)) // L
+
+
 class Pool:
     """avrf_pool: many BatchVerifier::verify jobs in flight on one device (include/avrf.h).  kind 1 thin, 2 pedersen."""
 
@@ -563,6 +637,14 @@ class Pool:
     def submit_shared_wire(self, b, validate=1):
         """b: SharedWireBatch / PinnedSharedWireBatch (a kind 1 pool).  Returns the ticket."""
         return self._submit("avrf_pool_submit_shared_wire", b, *b.args(), int(validate))
+
+    def submit_pedersen_shared(self, b):
+        """b: PedersenSharedBatch / PinnedPedersenSharedBatch (a kind 2 pool).  Returns the ticket."""
+        return self._submit("avrf_pool_submit_pedersen_shared", b, *b.args())
+
+    def submit_pedersen_shared_wire(self, b, validate=1):
+        """b: PedersenSharedWireBatch / PinnedPedersenSharedWireBatch (a kind 2 pool).  Returns the ticket."""
+        return self._submit("avrf_pool_submit_pedersen_shared_wire", b, *b.args(), int(validate))
 
     def submit_wire(self, b, validate=1):
         """b: a Batch / PinnedBatch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes (compressed points)"""

@@ -1,5 +1,5 @@
 // batch_terms_dev.h -- what the terms kernels of the batch verifiers share (vrf_batch.hip k_thin_terms / k_ped_terms / k_g_final,
-// thin_shared.hip k_thin_terms_shared / k_shared_merge, thin_seg.hip's segmented kernels of both kinds), each stated once:
+// thin_shared.hip k_thin_terms_shared / k_ped_terms_shared / k_shared_merge, thin_seg.hip's segmented kernels of both kinds), each stated once:
 //   fp_from_u128, emit_term : a 128-bit little-endian value as a field element; one MSM term (plain scalar + precomputed base)
 //   block_sum               : the sum of an Fr value over a block, in LDS
 //   thin_item               : the per-item arithmetic of thin::BatchVerifier::verify, src/thin.rs:287-313, over a sink for its terms

@@ -292,7 +292,7 @@ void sha512_many(WeightJob *const *jobs, int k) {
 // d_scalars / d_pre / d_gpart of the context's lane for the staged batch's n_terms
 static int ensure_terms(avrf_ctx *c) {
   HIP_TRY(c->L->d_scalars.ensure(c->n_terms * 32)); HIP_TRY(c->L->d_pre.ensure(c->n_terms * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(((c->n + 127) / 128) * 64 + 64));
-  if (c->n_shared) HIP_TRY(c->L->d_shared.ensure(shared_scratch_words(c->n + c->tot_io) * 4));
+  if (c->n_shared) HIP_TRY(c->L->d_shared.ensure(shared_scratch_words(c->n_contrib) * 4));
   return AVRF_OK;
 }
 
@@ -312,7 +312,7 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
   if (n && (!io_counts || !ad_lens)) return AVRF_ERR_BAD_ARG;
   if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->n_shared = 0; c->stage_gen++; c->wire_pending = false;
+  c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->n_shared = 0; c->n_contrib = 0; c->stage_gen++; c->wire_pending = false;
   if (n == 0) { c->staged_kind = kind; return AVRF_OK; }
   HIP_TRY(c->h_io.ensure((n + 1) * 8));
   uint32_t *io_off = c->h_io.as<uint32_t>(), *ad_off = io_off + (n + 1);
@@ -336,17 +336,18 @@ static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t str
     c->h_resp.resize(n * rsz);
     for (size_t j = 0; j < n; j++) memcpy(&c->h_resp[rsz * j], resp + stride * j, rsz);
   }
-  c->n_terms = c->n_shared ? thin_shared_n_terms(n, c->tot_io, c->n_shared) : n_terms(kind, n, c->tot_io);
+  c->n_terms = c->n_shared ? shared_n_terms(kind, n, c->tot_io, c->n_shared) : n_terms(kind, n, c->tot_io);
   HIP_TRY(c->d_c.ensure(n * 16)); HIP_TRY(c->h_c.ensure(n * 16));
-  HIP_TRY(c->d_z.ensure(z_bytes(kind, n, c->tot_io)));
+  HIP_TRY(c->d_z.ensure(z_bytes(kind, n, c->tot_io, c->n_shared != 0)));
   return c->lane_owner ? ensure_terms(c) : (int)AVRF_OK;
 }
 
 bool shared_indices_ok(const BatchSource &s) {
   if (!s.n) return true;
-  if (!s.n_shared || s.n_shared > 0x0fffffffULL || s.n > 0x0fffffffULL || !s.pk_index || !s.io_counts) return false;
+  const bool keys = kind_facts(s.kind).pk;                             // (a Pedersen item has no key: input_index alone)
+  if (!s.n_shared || s.n_shared > 0x0fffffffULL || s.n > 0x0fffffffULL || (keys && !s.pk_index) || !s.io_counts) return false;
   uint64_t a = 0; uint32_t over = 0;
-  for (size_t j = 0; j < s.n; j++) { over |= s.pk_index[j] >= s.n_shared; a += s.io_counts[j]; }
+  for (size_t j = 0; j < s.n; j++) { if (keys) over |= s.pk_index[j] >= s.n_shared; a += s.io_counts[j]; }
   if (over || a > 0x1fffffffULL || (a && (!s.input_index || !s.outputs))) return false;
   for (size_t k = 0; k < a; k++) over |= s.input_index[k] >= s.n_shared;
   return !over;
@@ -362,14 +363,16 @@ bool shared_indices_ok(const BatchSource &s) {
 //                 staged layout and sorts the references by row, rows_pre converts each row once -- the host only checks the indices;
 //   shared + wire rows | outputs | proofs go to d_misc and ONE kernel does all the decoding (vrf_single.hip k_decode_shared_wire): every
 //                 row, referenced or not, once to d_table (x || y) and d_table_rows (te_pre, what rows_pre leaves), every output to
-//                 d_table_outs, every R || s to d_proofs.  What decodes is canonical, so the plan's range flag stays clear.
+//                 d_table_outs, every R || s to d_proofs (Pedersen: k_decode_ped_shared_wire, Yb, R, Ok and s || sb of every proof).
+//                 What decodes is canonical, so the plan's range flag stays clear.
+//   A Pedersen source over a table has no keys: its references are the tot_io inputs alone (nk = 0 below; thin_shared.h "Pedersen").
 // A wire point that fails raises the decode flag (d_status -> h_flags[2]): AVRF_INVALID_DATA here, before any equation (as the
 // reference's deserialisation would), or from batch_collect when nothing was waited for (wire_pending).  What a shared staging
 // leaves is reused by every run of it (resident reruns, the pool's resubmission without host sources).
 static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
   const KindFacts &k = kind_facts(s.kind);
   const bool shared = s.n_shared != 0;
-  const size_t n = s.n, a = c->tot_io, nc = n + a, ns = s.n_shared, psz = k.xy_proof();
+  const size_t n = s.n, a = c->tot_io, nk = shared && k.pk ? n : 0, nc = nk + a, ns = s.n_shared, psz = k.xy_proof();   // nk: references to key rows
   const size_t L = s.wire ? (size_t)point_len_of(c->suite) : 0, plen = k.wire_proof(L);
   const size_t w_pks = shared ? ns * L : k.pk ? n * L : 0, w_ios = shared ? a * L : 2 * a * L, w_pr = n * plen;   // the wire bytes in d_misc
   uint8_t *dw = nullptr; uint32_t *d_flag = nullptr, *h_flag = c->h_flags.as<uint32_t>() + 2, *plan = nullptr;
@@ -378,7 +381,7 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
     HIP_TRY(c->d_table_rows.ensure(ns * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(ns, nc) * 4));
     plan = c->d_table_plan.as<uint32_t>();
   }
-  if (shared || s.wire) { HIP_TRY(c->d_proofs.ensure(n * psz)); if (shared || k.pk) HIP_TRY(c->d_pks.ensure(n * 64)); }
+  if (shared || s.wire) { HIP_TRY(c->d_proofs.ensure(n * psz)); if (k.pk) HIP_TRY(c->d_pks.ensure(n * 64)); }
   if (s.wire) {
     HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
     dw = c->d_misc.as<uint8_t>(); d_flag = c->d_status.as<uint32_t>();
@@ -388,12 +391,12 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
     HIP_TRY(up(dw, s.table, w_pks));
     if (w_ios) HIP_TRY(up(dw + w_pks, s.outputs, w_ios));
     HIP_TRY(up(dw + w_pks + w_ios, s.proofs, w_pr));
-    HIP_TRY(up(c->d_table_idx.p, s.pk_index, n * 4));
-    if (a) HIP_TRY(up(c->d_table_idx.as<uint32_t>() + n, s.input_index, a * 4));
+    if (nk) HIP_TRY(up(c->d_table_idx.p, s.pk_index, nk * 4));
+    if (a) HIP_TRY(up(c->d_table_idx.as<uint32_t>() + nk, s.input_index, a * 4));
   } else if (shared) {
     HIP_TRY(up(c->d_table.p, s.table, ns * 64));
-    HIP_TRY(up(c->d_table_idx.p, s.pk_index, n * 4));
-    if (a) { HIP_TRY(up(c->d_table_idx.as<uint32_t>() + n, s.input_index, a * 4)); HIP_TRY(up(c->d_table_outs.p, s.outputs, a * 64)); }
+    if (nk) HIP_TRY(up(c->d_table_idx.p, s.pk_index, nk * 4));
+    if (a) { HIP_TRY(up(c->d_table_idx.as<uint32_t>() + nk, s.input_index, a * 4)); HIP_TRY(up(c->d_table_outs.p, s.outputs, a * 64)); }
     HIP_TRY(up(c->d_proofs.p, s.proofs, n * psz));
   } else if (s.wire) {
     if (w_pks) HIP_TRY(up(dw, s.pks, w_pks));
@@ -408,7 +411,10 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
   if (shared) HIP_TRY(hipMemsetAsync(shared_plan_flag(plan, ns, nc), 0, 4, c->stream));
   if (s.wire) {
     const uint8_t *dpr = dw + w_pks + w_ios;
-    if (shared)
+    if (shared && s.kind == Pedersen)
+      HIP_TRY(AVRF_SINGLE(c->suite, decode_ped_shared_wire(dw, (uint32_t)ns, (uint32_t)a, (uint32_t)n, c->d_table.as<uint8_t>(), c->d_table_rows.as<te_pre_raw>(),
+                                                           c->d_table_outs.as<uint8_t>(), c->d_proofs.as<uint8_t>(), s.validate, d_flag, c->stream)));
+    else if (shared)
       HIP_TRY(AVRF_SINGLE(c->suite, decode_shared_wire(dw, (uint32_t)ns, (uint32_t)a, (uint32_t)n, c->d_table.as<uint8_t>(), c->d_table_rows.as<te_pre_raw>(),
                                                        c->d_table_outs.as<uint8_t>(), c->d_proofs.as<uint8_t>(), s.validate, d_flag, c->stream)));
     else {
@@ -421,10 +427,10 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
     HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   }
   if (shared) {
-    HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)ns, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)n, (uint32_t)a,
+    HIP_TRY(shared_plan(c->d_table.as<uint8_t>(), (uint32_t)ns, c->d_table_idx.as<uint32_t>(), c->d_table_outs.as<uint8_t>(), (uint32_t)nk, (uint32_t)a,
                         c->d_pks.as<uint8_t>(), c->d_ios.as<uint8_t>(), plan, c->stream));
     if (!s.wire) HIP_TRY(AVRF_SHARED(c->suite, rows_pre(c->d_table.as<uint8_t>(), (uint32_t)ns, c->d_table_rows.as<te_pre_raw>(), shared_plan_flag(plan, ns, nc), c->stream)));
-    c->n_shared = ns;
+    c->n_shared = ns; c->n_contrib = nc;
   }
   if (s.proofs && s.kind != Tiny)                                      // (Tiny has no batch verifier, and a prover stages no proofs)
     if (int e = stage_verifier(c, s.kind, s.proofs + (s.wire ? k.resp_at_wire(L) : k.resp_at_xy()), s.wire ? plen : psz)) return e;
@@ -440,12 +446,12 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
 // failure leaves nothing staged (staged_kind == 0) and no shared table.
 int ctx_stage(avrf_ctx *c, const BatchSource &s, bool wait) {
   const bool shared = s.n_shared != 0;
-  const bool args_ok = (!s.wire || s.kind == Thin || s.kind == Pedersen) && (!shared || s.kind == Thin) &&
+  const bool args_ok = (!s.wire || s.kind == Thin || s.kind == Pedersen) && (!shared || s.kind == Thin || s.kind == Pedersen) &&
                        (!s.n || (shared ? s.table && s.proofs && shared_indices_ok(s) : !s.wire || (s.proofs && (s.kind != Thin || s.pks))));
   if (int e = stage_open(c, s.kind, s.n, args_ok, shared ? s.outputs : s.ios, !shared && !s.wire, s.io_counts, s.ads, s.ad_lens)) return e;
   if (s.n == 0) return AVRF_OK;
   const int st = stage_payload(c, s, wait);
-  if (st) c->n_shared = 0; else c->staged_kind = s.kind;
+  if (st) c->n_shared = c->n_contrib = 0; else c->staged_kind = s.kind;
   return st;
 }
 }  // namespace avrf
@@ -464,20 +470,46 @@ int avrf_pedersen_batch_stage_wire(avrf_ctx *c, size_t n, const uint8_t *ios, co
 int avrf_thin_batch_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
                                  const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
   if (n && !n_shared) return AVRF_ERR_BAD_ARG;                         // (no table: a source with n_shared == 0 is a plain one)
-  return ctx_stage(c, shared_source(n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs), true);
+  return ctx_stage(c, shared_source(Thin, n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs), true);
 }
 size_t avrf_thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared) { return thin_shared_n_terms(n, tot_io, n_shared); }
 int avrf_thin_batch_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
                                       const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
                                       int validate) {
   if (!c || ctx_busy(c) || (n && !n_shared)) return AVRF_ERR_BAD_ARG;
-  return ctx_stage(c, wire_source(shared_source(n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs), validate), true);
+  return ctx_stage(c, wire_source(shared_source(Thin, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs), validate), true);
 }
 int avrf_thin_batch_verify_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
                                        const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
                                        int validate) {
   if (int e = avrf_thin_batch_stage_shared_wire(c, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, validate)) return e;
   return avrf_thin_batch_run(c);
+}
+
+// Pedersen over a table of shared inputs (include/avrf.h).  n_shared == 0 is a table nothing can refer to: legal exactly when no item has a
+// pair, and then the batch IS a plain one (ped_no_pairs: every io_count 0) and is staged as one.
+static bool ped_no_pairs(size_t n, const uint32_t *io_counts) {
+  if (n && !io_counts) return false;
+  uint32_t any = 0;
+  for (size_t j = 0; j < n; j++) any |= io_counts[j];
+  return !any;
+}
+int avrf_pedersen_batch_stage_shared(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *input_index, const uint8_t *outputs_xy,
+                                     const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
+  if (n && !proofs) return AVRF_ERR_BAD_ARG;
+  if (n && !n_shared && !ped_no_pairs(n, io_counts)) return AVRF_ERR_BAD_ARG;
+  return ctx_stage(c, shared_source(Pedersen, n, n_shared, shared_xy, nullptr, input_index, outputs_xy, io_counts, ads, ad_lens, proofs), true);
+}
+size_t avrf_pedersen_shared_n_terms(size_t n, size_t n_shared) { return ped_shared_n_terms(n, n_shared); }
+int avrf_pedersen_batch_stage_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *input_index, const uint8_t *outputs,
+                                          const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
+  if (!c || ctx_busy(c) || (n && !n_shared && !ped_no_pairs(n, io_counts))) return AVRF_ERR_BAD_ARG;
+  return ctx_stage(c, wire_source(shared_source(Pedersen, n, n_shared, shared, nullptr, input_index, outputs, io_counts, ads, ad_lens, proofs), validate), true);
+}
+int avrf_pedersen_batch_verify_shared_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *input_index, const uint8_t *outputs,
+                                           const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
+  if (int e = avrf_pedersen_batch_stage_shared_wire(c, n, n_shared, shared, input_index, outputs, io_counts, ads, ad_lens, proofs, validate)) return e;
+  return avrf_pedersen_batch_run(c);
 }
 
 int avrf_thin_batch_stage(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
@@ -562,19 +594,23 @@ static Seed64 seed_of(const uint8_t digest[64]) {
 // The run's check flags start clear -- or, over a shared table, from what staging found in it (a non-canonical coordinate in any row)
 static hipError_t reset_flags(avrf_ctx *c) {
   if (!c->n_shared) return hipMemsetAsync(c->d_flags.p, 0, 4, c->stream);
-  return hipMemcpyAsync(c->d_flags.p, shared_plan_flag(c->d_table_plan.as<uint32_t>(), c->n_shared, c->n + c->tot_io), 4, hipMemcpyDeviceToDevice, c->stream);
+  return hipMemcpyAsync(c->d_flags.p, shared_plan_flag(c->d_table_plan.as<uint32_t>(), c->n_shared, c->n_contrib), 4, hipMemcpyDeviceToDevice, c->stream);
 }
 static void launch_prepare(avrf_ctx *c, int kind, const BatchDev &b) {
   if (kind == Thin) AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
-  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->stream));
+  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->n_shared != 0, c->stream));
 }
 static void launch_terms(avrf_ctx *c, int kind, const BatchDev &b, const Seed64 &seed, uint64_t first, uint32_t *d_scalars) {
   if (kind == Thin && c->n_shared)
     AVRF_SHARED(c->suite, thin_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(),
-                                     shared_plan_view(c->d_table_plan.as<uint32_t>(), c->d_table_rows.as<te_pre_raw>(), c->n_shared, c->n + c->tot_io),
+                                     shared_plan_view(c->d_table_plan.as<uint32_t>(), c->d_table_rows.as<te_pre_raw>(), c->n_shared, c->n_contrib),
                                      (uint32_t)c->tot_io, c->L->d_shared.as<uint32_t>(), d_scalars, c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), c->stream));
   else if (kind == Thin) AVRF_BATCH(c->suite, thin_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), d_scalars,
                                                     c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
+  else if (c->n_shared)
+    AVRF_SHARED(c->suite, ped_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(),
+                                    shared_plan_view(c->d_table_plan.as<uint32_t>(), c->d_table_rows.as<te_pre_raw>(), c->n_shared, c->n_contrib),
+                                    c->L->d_shared.as<uint32_t>(), d_scalars, c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), c->stream));
   else AVRF_BATCH(c->suite, ped_terms(b, seed, first, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), d_scalars,
                                       c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
 }

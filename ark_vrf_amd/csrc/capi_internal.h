@@ -47,7 +47,7 @@ struct Lane : LaneStream {
   int queued = 0;                 // chains enqueued and not yet collected (pool.hip)
   MsmWorkspace ws;
   DevBuf d_scalars, d_pre, d_gpart;
-  DevBuf d_shared;                // a shared-table Thin batch: the row scalars' contributions and partial sums of the chain being built (thin_shared.h)
+  DevBuf d_shared;                // a shared-table batch: the row scalars' contributions and partial sums of the chain being built (thin_shared.h)
 };
 
 }  // namespace avrf
@@ -66,9 +66,10 @@ struct avrf_ctx {
   int staged_kind = 0;            // 0 none, else the ProofKind staged (proof_kind.h)
   size_t n = 0, tot_io = 0, n_terms = 0;
   avrf::DevBuf d_pks, d_ios, d_io_off, d_ads, d_ad_off, d_proofs, d_sks;
-  // a Thin batch staged over a table of shared points (avrf_thin_batch_stage_shared; thin_shared.h): n_shared rows, 0 for a plain staging.
+  // a Thin or Pedersen batch staged over a table of shared points (avrf_thin_batch_stage_shared, avrf_pedersen_batch_stage_shared;
+  // thin_shared.h): n_shared rows, 0 for a plain staging; n_contrib references (proof_kind.h shared_n_contrib).
   // d_pks / d_ios hold the gathered rows, so that the prepare kernel runs as on a plain batch; the terms come from the table and the plan.
-  size_t n_shared = 0;
+  size_t n_shared = 0, n_contrib = 0;
   avrf::DevBuf d_table, d_table_idx, d_table_outs, d_table_rows, d_table_plan;
   std::vector<uint8_t> h_resp;    // host copy of the response scalars (s [, sb]) for the weight transcript (sponge transcripts only)
   avrf::DevBuf d_rec; avrf::PinBuf h_msg;     // counter-mode transcripts: the records written by the prepare kernel, and prefix || records on the host
@@ -98,8 +99,8 @@ namespace avrf {
 struct WeightJob;
 // Where a batch comes from: the caller's host arrays, named for what they hold.  The x || y flavours read pks / ios / proofs as
 // affine coordinates; `wire` ones as serialize_compressed bytes, decoded on the device (validate: + not the identity, + subgroup).
-// n_shared != 0: Thin over a table of shared points (include/avrf.h) -- `table` rows, the items' keys and inputs as indices into
-// it, the `outputs` beside them -- and pks / ios are not read.
+// n_shared != 0: over a table of shared points (include/avrf.h) -- `table` rows, the items' keys (Thin) and inputs as indices into
+// it, the `outputs` beside them -- and pks / ios are not read.  A Pedersen source has no pk_index.
 struct BatchSource {
   int kind = 0; size_t n = 0;       // a ProofKind (sizes: proof_kind.h)
   bool wire = false; int validate = 0;
@@ -114,9 +115,9 @@ inline BatchSource plain_source(int kind, size_t n, const uint8_t *pks, const ui
   s.kind = kind; s.n = n; s.pks = pks; s.ios = ios; s.io_counts = io_counts; s.ads = ads; s.ad_lens = ad_lens; s.proofs = proofs;
   return s;
 }
-inline BatchSource shared_source(size_t n, size_t n_shared, const uint8_t *table, const uint32_t *pk_index, const uint32_t *input_index,
+inline BatchSource shared_source(int kind, size_t n, size_t n_shared, const uint8_t *table, const uint32_t *pk_index, const uint32_t *input_index,
                                  const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs) {
-  BatchSource s = plain_source(Thin, n, nullptr, nullptr, io_counts, ads, ad_lens, proofs);
+  BatchSource s = plain_source(kind, n, nullptr, nullptr, io_counts, ads, ad_lens, proofs);
   s.n_shared = n_shared; s.table = table; s.pk_index = pk_index; s.input_index = input_index; s.outputs = outputs;
   return s;
 }

@@ -356,7 +356,7 @@ int avrf_pool_submit_wire(avrf_pool *P, size_t n, const uint8_t *pks, const uint
 int avrf_pool_submit_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *pk_index, const uint32_t *input_index,
                             const uint8_t *outputs_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
                             uint64_t *ticket) {
-  const BatchSource src = shared_source(n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs);
+  const BatchSource src = shared_source(Thin, n, n_shared, shared_xy, pk_index, input_index, outputs_xy, io_counts, ads, ad_lens, proofs);
   if (!P || P->kind != Thin || !shared_indices_ok(src)) return AVRF_ERR_BAD_ARG;
   return pool_submit(P, src, ticket);
 }
@@ -364,9 +364,26 @@ int avrf_pool_submit_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8
 int avrf_pool_submit_shared_wire(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
                                  const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
                                  int validate, uint64_t *ticket) {
-  const BatchSource src = wire_source(shared_source(n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs), validate);
+  const BatchSource src = wire_source(shared_source(Thin, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs), validate);
   if (!P || P->kind != Thin || !shared_indices_ok(src)) return AVRF_ERR_BAD_ARG;
   return pool_submit(P, src, ticket);
+}
+// the Pedersen pool's shared-table jobs (include/avrf.h avrf_pedersen_batch_stage_shared / _shared_wire): no pk_index; checked as above.
+// (n_shared == 0: legal when no item has a pair, and then a plain source -- shared_indices_ok refuses every other empty table)
+static int pool_submit_ped_shared(avrf_pool *P, BatchSource src, uint64_t *ticket) {
+  if (!P || P->kind != Pedersen || (src.n && src.n_shared && !src.table)) return AVRF_ERR_BAD_ARG;
+  if (!src.n_shared) { for (size_t j = 0; src.io_counts && j < src.n; j++) if (src.io_counts[j]) return AVRF_ERR_BAD_ARG; }
+  else if (!shared_indices_ok(src)) return AVRF_ERR_BAD_ARG;
+  return pool_submit(P, src, ticket);
+}
+int avrf_pool_submit_pedersen_shared(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared_xy, const uint32_t *input_index, const uint8_t *outputs_xy,
+                                     const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket) {
+  return pool_submit_ped_shared(P, shared_source(Pedersen, n, n_shared, shared_xy, nullptr, input_index, outputs_xy, io_counts, ads, ad_lens, proofs), ticket);
+}
+int avrf_pool_submit_pedersen_shared_wire(avrf_pool *P, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *input_index, const uint8_t *outputs,
+                                          const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
+                                          uint64_t *ticket) {
+  return pool_submit_ped_shared(P, wire_source(shared_source(Pedersen, n, n_shared, shared, nullptr, input_index, outputs, io_counts, ads, ad_lens, proofs), validate), ticket);
 }
 
 int avrf_pool_wait(avrf_pool *P, uint64_t ticket, int *status) {

@@ -29,8 +29,14 @@ constexpr const KindFacts &kind_facts(int kind) { return KIND_FACTS[kind]; }
 constexpr size_t n_terms(int kind, size_t n, size_t tot_io) { return kind == Thin ? 2 * n + 2 * tot_io + 1 : 5 * n + 2; }
 // Thin over a table of n_shared points (include/avrf.h avrf_thin_batch_stage_shared): R per item, O per I/O pair, one term per row, G
 constexpr size_t thin_shared_n_terms(size_t n, size_t tot_io, size_t n_shared) { return n + tot_io + n_shared + 1; }
+// Pedersen over a table of n_shared inputs (avrf_pedersen_batch_stage_shared): O, Ok, Yb, R per item, one term per row, G, BLINDING_BASE
+constexpr size_t ped_shared_n_terms(size_t n, size_t n_shared) { return 4 * n + n_shared + 2; }
+constexpr size_t shared_n_terms(int kind, size_t n, size_t tot_io, size_t n_shared) { return kind == Thin ? thin_shared_n_terms(n, tot_io, n_shared) : ped_shared_n_terms(n, n_shared); }
+// the references of a shared-table batch, one per contribution to a row's scalar: Thin every key and every input, Pedersen the inputs
+constexpr size_t shared_n_contrib(int kind, size_t n, size_t tot_io) { return (KIND_FACTS[kind].pk ? n : 0) + tot_io; }
 // what the prepare kernel leaves the terms kernel besides the challenges: Thin z_{j,i} (16 bytes per I/O pair), Pedersen the merged pair
-constexpr size_t z_bytes(int kind, size_t n, size_t tot_io) { return kind == Thin ? tot_io * 16 + 16 : n * 128; }
+// -- over a shared table (k_ped_prepare<S, true>) only its output half, and z_{j,i} (16 bytes per I/O pair) behind the n slots
+constexpr size_t z_bytes(int kind, size_t n, size_t tot_io, bool shared = false) { return kind == Thin ? tot_io * 16 + 16 : n * 128 + (shared ? tot_io * 16 + 16 : 0); }
 
 static_assert(kind_facts(Thin).xy_proof() == 96 && kind_facts(Pedersen).xy_proof() == 256 && kind_facts(Tiny).xy_proof() == 48, "x || y proofs");
 static_assert(kind_facts(Thin).wire_proof(32) == 64 && kind_facts(Pedersen).wire_proof(32) == 160 && kind_facts(Tiny).wire_proof(32) == 48, "wire proofs");

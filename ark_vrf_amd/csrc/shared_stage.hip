@@ -1,5 +1,6 @@
-// shared_stage.hip -- the suite-independent staging of a Thin batch over a table of shared points (thin_shared.h): the plain staged
-// layout gathered from the table, and the counting sort of the n + tot_io references by row (32-bit integer atomics on counters only).
+// shared_stage.hip -- the suite-independent staging of a Thin or Pedersen batch over a table of shared points (thin_shared.h): the plain staged
+// layout gathered from the table, and the counting sort of the references by row (32-bit integer atomics on counters only).  Thin: n keys
+// and tot_io inputs; Pedersen: the tot_io inputs alone (n = 0 here, and a batch whose items have no pairs leaves every row unreferenced).
 #include "thin_shared.h"
 #include "fpn.h"
 
@@ -88,12 +89,12 @@ k_shared_place(const uint32_t *__restrict__ idx, uint32_t n_shared, uint32_t n_c
 hipError_t shared_plan(const uint8_t *d_table, uint32_t n_shared, const uint32_t *d_idx, const uint8_t *d_outputs, uint32_t n, uint32_t tot_io,
                        uint8_t *d_pks, uint8_t *d_ios, uint32_t *d_plan, hipStream_t st) {
   const uint32_t nc = n + tot_io;
-  if (!nc || !n_shared) return hipSuccess;
+  if (!n_shared) return hipSuccess;
   uint32_t *cursor = d_plan, *row_off = d_plan + (n_shared + 1), *pos = row_off + (n_shared + 1), *slot_row = pos + nc;
   if (hipError_t e = hipMemsetAsync(cursor, 0, (size_t)(n_shared + 1) * 4, st)) return e;
-  hipLaunchKernelGGL(k_shared_gather, dim3((nc + 255) / 256), dim3(256), 0, st, d_table, n_shared, d_idx, d_outputs, n, tot_io, d_pks, d_ios, cursor);
+  if (nc) hipLaunchKernelGGL(k_shared_gather, dim3((nc + 255) / 256), dim3(256), 0, st, d_table, n_shared, d_idx, d_outputs, n, tot_io, d_pks, d_ios, cursor);
   hipLaunchKernelGGL(k_shared_scan, dim3(1), dim3(1024), 0, st, cursor, row_off, n_shared);
-  hipLaunchKernelGGL(k_shared_place, dim3((nc + 255) / 256), dim3(256), 0, st, d_idx, n_shared, nc, cursor, pos, slot_row);
+  if (nc) hipLaunchKernelGGL(k_shared_place, dim3((nc + 255) / 256), dim3(256), 0, st, d_idx, n_shared, nc, cursor, pos, slot_row);
   return hipGetLastError();                                             // (a launch that was refused)
 }
 

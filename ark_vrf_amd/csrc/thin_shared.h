@@ -18,6 +18,12 @@
 //     contrib[pos[.]]; k_shared_lanes sums equal contiguous shares of SHARED_SHARE slots per lane -- rows inside a share are
 //     finished there, a row that crosses a share boundary leaves partials; k_shared_merge adds the partials of each such row
 //     (min(lanes, T) units, four per block, 256 threads on each cut row) and the generator term.  Three launches whatever the distribution of the references.
+//
+// Pedersen (avrf_pedersen_batch_stage_shared): an item has no key, so the references are the tot_io inputs alone (C = tot_io, t = k for
+// I/O pair k) and the table holds inputs only.  The reference already merges G and BLINDING_BASE (src/pedersen.rs:387-418); an item's
+// input term is -t s I_merged = sum_i (-t s z_i) I_i (merge_ios, common.rs:389-419), so each pair adds -t s z_i to its row and the MSM has
+// 4 n + T + 2 terms instead of 5 n + 2.  Same plan, same k_shared_lanes; k_ped_terms_shared is the ped_item caller and k_shared_merge<S, 2>
+// writes both base terms.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,6 +49,7 @@ struct SharedPlan {
 };
 
 // Gather + counting sort of a staging (suite-independent: shared_stage.hip).  idx: pk_index (n) then input_index (tot_io); plan: shared_plan_words.
+// n: the items that reference a KEY row -- 0 for a Pedersen batch, whose references are the tot_io inputs alone (d_pks is then not touched).
 // An index >= n_shared is the host's to refuse; the kernels clamp it so that no read leaves the table.
 // (a refused memset or launch comes back as its error, so that a failed plan is never reported as a good staging)
 hipError_t shared_plan(const uint8_t *d_table, uint32_t n_shared, const uint32_t *d_idx, const uint8_t *d_outputs, uint32_t n, uint32_t tot_io,
@@ -59,6 +66,10 @@ template <class S> struct SharedOps {
   // terms in the layout of include/avrf.h: (R_j, w_j) at j + io_off[j], (O_ji, w c z_i) behind it, row r at n + tot_io + r, (G, g) last
   static void thin_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint32_t *d_z, const SharedPlan &p,
                          uint32_t tot_io, uint32_t *d_scratch, uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, hipStream_t st);
+  // Pedersen: item j's four terms at 4 j, row r at 4 n + r, (G, .) and (BLINDING_BASE, .) last.  d_merged: what k_ped_prepare<S, true> left
+  // (merged outputs, then the z_i); d_gpart: 2 x ceil(n / 128) partials as BatchOps::ped_terms.  p.n_contrib = tot_io.
+  static void ped_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint8_t *d_merged, const SharedPlan &p,
+                        uint32_t *d_scratch, uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, hipStream_t st);
 };
 #define AVRF_SHARED(suite, CALL) with_suite((suite), [&](auto tag_) { return SharedOps<typename decltype(tag_)::type>::CALL; })
 

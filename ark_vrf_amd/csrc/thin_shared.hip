@@ -1,6 +1,8 @@
 // thin_shared.hip -- the device side of thin::BatchVerifier over a table of shared points (thin_shared.h).
 //
 //   k_shared_pre                     : every table row once to te_pre, through the suite's own te_make_pre
+//   k_ped_terms_shared               : ped_item (batch_terms_dev.h; src/pedersen.rs:369-410), as k_ped_terms: the four terms on the item's own points;
+//                                      the input scalars -t s z_i go to contrib[pos[.]] (thin_shared.h "Pedersen")
 //   k_thin_terms_shared              : thin_item (batch_terms_dev.h; src/thin.rs:287-313), as k_thin_terms of vrf_batch.hip: the R and
 //                                      output terms; the key and input scalars go to contrib[pos[.]] in Montgomery form
 //   k_shared_lanes / k_shared_merge  : the segmented sum of contrib in Fr -> the T row terms; the generator term (src/thin.rs:303,316-317)
@@ -55,6 +57,44 @@ k_thin_terms_shared(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__rest
   if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, sum);
 }
 
+// k_ped_terms_shared's sink of ped_item's terms: item j's (O, t c), (Ok, t), (Yb, u c), (R, u) at 4 j + {0, 1, 2, 3}.  Term 2, (I, -t s),
+// is not emitted: the merged input is sum z_i I_i (common.rs:389-419), so -t s z_i goes to the row of pair i's input -- contrib[pos[io0 + i]]
+// in Montgomery form, z_0 = 1 and z_i (i >= 1) as k_ped_prepare<S, true> left them behind the merged outputs.
+template <class S> struct PedSharedTerms {
+  uint32_t *__restrict__ scalars; te_pre *__restrict__ pre; const uint32_t *__restrict__ io_off; const uint32_t *__restrict__ z_in;
+  const uint32_t *__restrict__ pos; uint32_t *__restrict__ contrib;
+  using Fr = typename S::Fr;
+  AVRF_DI void term(uint32_t j, uint32_t k, const fp &sc_plain, const uint8_t *xy) const {
+    if (k != 2) { emit_term<S>(scalars, pre, 4 * j + (k > 2 ? k - 1 : k), sc_plain, xy); return; }
+    const uint32_t io0 = io_off[j], m = io_off[j + 1] - io0;
+    if (!m) return;                                                     // no pair: the merged input is the identity (pedersen.rs:264-267)
+    const fp ts = fp_to_mont<Fr>(sc_plain);
+    fp_store(contrib + 8 * (size_t)pos[io0], ts);
+    for (uint32_t i = 1; i < m; i++)
+      fp_store(contrib + 8 * (size_t)pos[io0 + i], fp_mul<Fr>(ts, fp_to_mont<Fr>(fp_from_u128(z_in + 4 * (size_t)(io0 + i)))));
+  }
+};
+
+// per-item part of pedersen::BatchVerifier::verify over a table of shared inputs (ped_item, batch_terms_dev.h), as k_ped_terms of vrf_batch.hip
+template <class S>
+__global__ void __launch_bounds__(128)
+k_ped_terms_shared(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c_in, const uint8_t *__restrict__ merged_xy,
+                   const uint32_t *__restrict__ pos, uint32_t *__restrict__ contrib, uint32_t *__restrict__ scalars, te_pre *__restrict__ pre,
+                   uint32_t *__restrict__ gpart, uint32_t *__restrict__ bpart) {
+  using Fr = typename S::Fr;
+  __shared__ fp red[128];
+  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  fp us = fp_zero(), usb = fp_zero();
+  if (j < b.n)
+    us = ped_item<S>(b, seed, j0, c_in, merged_xy, j,
+                     PedSharedTerms<S>{scalars, pre, b.io_off, reinterpret_cast<const uint32_t *>(merged_xy + 128 * (size_t)b.n), pos, contrib}, usb);
+  const fp gsum = block_sum<Fr, 128>(us, red);
+  if (threadIdx.x == 0) fp_store(gpart + 8 * (size_t)blockIdx.x, gsum);
+  __syncthreads();
+  const fp bsum = block_sum<Fr, 128>(usb, red);
+  if (threadIdx.x == 0) fp_store(bpart + 8 * (size_t)blockIdx.x, bsum);
+}
+
 enum : uint32_t { SHARED_NO_ROW = 0xffffffffu };
 
 // Lane l sums slots [l SHARE, (l + 1) SHARE) in slot order, whatever rows they belong to.  A run of one row's slots that begins
@@ -95,15 +135,22 @@ k_shared_lanes(SharedPlan p, const uint32_t *__restrict__ contrib, uint32_t *__r
 // all its 256 threads add one cut row's partials (four independent running sums per thread, then a tree in LDS), so that ONE row of
 // all 131 072 references -- 16 384 partials -- costs each thread 64 additions.  A unit is a ROW when there are no more rows than
 // lanes (the shared case: a cut row is known from row_off alone), else a LANE (tail_row says whether it left a tail): min(lanes, T)
-// units.  The last block is the generator term (base_term, as k_g_final).
-template <class S>
+// units.  The last block is the generator term (base_term, as k_g_final); NBASE = 2 (Pedersen): the last two are (G, .) at t0 + T from gpart
+// and (BLINDING_BASE, .) at t0 + T + 1 from the nparts partials behind it.
+template <class S, int NBASE = 1>
 __global__ void __launch_bounds__(256)
 k_shared_merge(SharedPlan p, const uint32_t *__restrict__ part, const uint32_t *__restrict__ tail_row, uint32_t n_units, int by_row,
                const uint32_t *__restrict__ gpart, uint32_t nparts, uint32_t *__restrict__ scalars, te_pre *__restrict__ pre, uint32_t t0) {
   using Fr = typename S::Fr;
   __shared__ fp red[256];
   const uint32_t tid = threadIdx.x;
+  if constexpr (NBASE == 1) {
   if (blockIdx.x == gridDim.x - 1) { base_term<S, true>(gpart, nparts, scalars, pre, t0 + p.n_shared, 0, red); return; }   // (G, g), rolled as below
+  } else if (blockIdx.x + NBASE >= gridDim.x) {
+    const uint32_t w = blockIdx.x + NBASE - gridDim.x;                  // 0: G, 1: BLINDING_BASE
+    base_term<S, true>(gpart + 8 * (size_t)nparts * w, nparts, scalars, pre, t0 + p.n_shared + w, (int)w, red);
+    return;
+  }
   for (uint32_t i = 0; i < 4; i++) {                                    // (everything that decides control flow below is block-uniform)
     const uint32_t u = blockIdx.x * 4 + i;
     if (u >= n_units) break;
@@ -150,6 +197,19 @@ template <class S> void SharedOps<S>::thin_terms(const BatchDev &b, const Seed64
   const int by_row = p.n_shared <= nl;
   const uint32_t units = by_row ? p.n_shared : nl;
   hipLaunchKernelGGL(k_shared_merge<S>, dim3((units + 3) / 4 + 1), dim3(256), 0, st, p, part, tail_row, units, by_row, d_gpart, g.x, d_scalars, (te_pre *)d_pre, t0);
+}
+template <class S> void SharedOps<S>::ped_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint8_t *d_merged, const SharedPlan &p,
+                                                uint32_t *d_scratch, uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, hipStream_t st) {
+  if (!b.n) return;
+  const uint32_t nl = (uint32_t)shared_lanes(p.n_contrib), t0 = 4 * b.n;
+  uint32_t *contrib = d_scratch, *part = contrib + 8 * (size_t)p.n_contrib, *tail_row = part + 16 * (size_t)nl;
+  dim3 g((b.n + 127) / 128), blk(128);
+  hipLaunchKernelGGL(k_ped_terms_shared<S>, g, blk, 0, st, b, seed, j0, d_c, d_merged, p.pos, contrib, d_scalars, (te_pre *)d_pre, d_gpart, d_gpart + 8 * (size_t)g.x);
+  const uint32_t work = nl > p.n_shared ? nl : p.n_shared;
+  if (work) hipLaunchKernelGGL(k_shared_lanes<S>, dim3((work + 255) / 256), dim3(256), 0, st, p, contrib, part, tail_row, d_scalars, (te_pre *)d_pre, t0);
+  const int by_row = p.n_shared <= nl;
+  const uint32_t units = by_row ? p.n_shared : nl;
+  hipLaunchKernelGGL((k_shared_merge<S, 2>), dim3((units + 3) / 4 + 2), dim3(256), 0, st, p, part, tail_row, units, by_row, d_gpart, g.x, d_scalars, (te_pre *)d_pre, t0);
 }
 template struct SharedOps<suite_by_id<AVRF_TU_SUITE>::type>;
 

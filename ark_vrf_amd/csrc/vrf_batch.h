@@ -21,8 +21,9 @@ template <class S> struct BatchOps {
   // seed.  n_terms = 2 n + 2 tot_io + 1.
   static void thin_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint32_t *d_z,
                          uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, uint32_t n_terms, hipStream_t st);
-  // pedersen::BatchItem::new (src/pedersen.rs:276-293) and the (5N+2)-term MSM of :369-418.
-  static void ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, hipStream_t st);
+  // pedersen::BatchItem::new (src/pedersen.rs:276-293) and the (5N+2)-term MSM of :369-418.  shared: the k_ped_prepare<S, true> variant
+  // for a batch over a table of shared inputs -- the merged output only, and the z_i behind the n slots of d_merged (proof_kind.h z_bytes)
+  static void ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, bool shared, hipStream_t st);
   static void ped_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint8_t *d_merged,
                         uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, uint32_t n_terms, hipStream_t st);
 };
@@ -70,6 +71,9 @@ template <class S> struct SingleOps {
   // every point into d_table (x || y) + d_rows (te_pre), d_outs, d_proofs (x || y || s, 96 apart); FLAG_CURVE in *d_flags for a failing point
   static hipError_t decode_shared_wire(const uint8_t *d_wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *d_table, te_pre_raw *d_rows,
                                        uint8_t *d_outs, uint8_t *d_proofs, int validate, uint32_t *d_flags, hipStream_t st);
+  // the Pedersen sibling (k_decode_ped_shared_wire): proofs Yb || R || Ok || s || sb on the wire, x || y proofs 256 apart in d_proofs
+  static hipError_t decode_ped_shared_wire(const uint8_t *d_wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *d_table, te_pre_raw *d_rows,
+                                           uint8_t *d_outs, uint8_t *d_proofs, int validate, uint32_t *d_flags, hipStream_t st);
   static void output_hash(const uint8_t *d_in, uint32_t n, uint32_t len, uint8_t *d_out, hipStream_t st);   // Output::hash, src/lib.rs:605-609
   static void secret_from_seed(const uint8_t *d_seeds, uint32_t n, uint8_t *d_sk, uint32_t *d_flags, hipStream_t st);   // Secret::from_seed, src/lib.rs:346-369
 };

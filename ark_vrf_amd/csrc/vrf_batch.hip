@@ -122,7 +122,10 @@ k_g_final(const uint32_t *__restrict__ gpart, uint32_t nparts, uint32_t *__restr
 
 // pedersen::BatchItem::new (src/pedersen.rs:276-293): challenge c_j and the merged I/O pair
 // (written as canonical xy to merged_xy[j], 128 bytes) for every item.
-template <class S>
+// SHARED (a batch over a table of shared inputs, thin_shared.h): the inputs stay rows of the table, so the merged INPUT is never
+// computed or written -- only the merged output (merged_xy + 128 j + 64, where ped_item reads it) and, behind the n slots, the
+// delinearisation scalars z_i, i >= 1, of every multi-pair item (16 bytes at merged_xy + 128 n + 16 (io0 + i); z_0 = 1 is not stored).
+template <class S, bool SHARED>
 __global__ void __launch_bounds__(128)
 k_ped_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint8_t *__restrict__ merged_xy, uint32_t *__restrict__ flags) {
   using Fr = typename S::Fr;
@@ -133,7 +136,30 @@ k_ped_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint8_t *__restrict__ me
   suite_tr<S> t; uint32_t f = 0;
   tr_base<S>(t, DS_PEDERSEN, false, nullptr, ios, m, b.ads + ad0, adl, &f);   // io identity -> io_identity flag (:278)
   uint8_t *mo = merged_xy + 128 * (size_t)j;
-  if (m == 1) {
+  if constexpr (SHARED) {
+    if (m == 1) {
+      const uint4 *src = reinterpret_cast<const uint4 *>(ios + 64); uint4 *dst = reinterpret_cast<uint4 *>(mo + 64);
+#pragma unroll
+      for (int i = 0; i < 4; i++) dst[i] = src[i];
+    } else if (m == 0) {
+      fp zero = fp_zero(), one = fp_zero(); one.v[0] = S::SW_NATIVE ? 0 : 1;
+      fp_store_le(mo + 64, zero); fp_store_le(mo + 96, one);
+    } else {                                                                   // merge_ios' output half; the z_i go to the terms kernel
+      auto dseed = delin_seed(t);
+      uint32_t *z_out = reinterpret_cast<uint32_t *>(merged_xy + 128 * (size_t)b.n);
+      te_ext om = te_identity<S>();
+      for (uint32_t i = 0; i < m; i++) {
+        te_pre po = pre_from_xy<S>(ios + 128 * (size_t)i + 64);
+        if (i == 0) om = te_madd<S>(om, po);
+        else {
+          fp z = xof128(dseed, i - 1);
+          *reinterpret_cast<uint4 *>(z_out + 4 * (size_t)(io0 + i)) = make_uint4(z.v[0], z.v[1], z.v[2], z.v[3]);
+          om = te_add<S>(om, te_smul<S>(po, z, 128));
+        }
+      }
+      store_xy<S>(mo + 64, te_to_aff<S>(om));
+    }
+  } else if (m == 1) {
     const uint4 *src = reinterpret_cast<const uint4 *>(ios); uint4 *dst = reinterpret_cast<uint4 *>(mo);
 #pragma unroll
     for (int i = 0; i < 8; i++) dst[i] = src[i];
@@ -197,10 +223,11 @@ k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c
   if (threadIdx.x == 0) fp_store(bpart + 8 * (size_t)blockIdx.x, bsum);
 }
 
-template <class S> void BatchOps<S>::ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, hipStream_t st) {
+template <class S> void BatchOps<S>::ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, bool shared, hipStream_t st) {
   if (!b.n) return;
   dim3 g((b.n + 127) / 128), blk(128);
-  hipLaunchKernelGGL(k_ped_prepare<S>, g, blk, 0, st, b, d_c, d_merged, d_flags);
+  if (shared) hipLaunchKernelGGL((k_ped_prepare<S, true>), g, blk, 0, st, b, d_c, d_merged, d_flags);
+  else hipLaunchKernelGGL((k_ped_prepare<S, false>), g, blk, 0, st, b, d_c, d_merged, d_flags);
 }
 template <class S> void BatchOps<S>::ped_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint8_t *d_merged,
                                                uint32_t *d_scalars, te_pre_raw *d_pre, uint32_t *d_gpart, uint32_t n_terms, hipStream_t st) {

@@ -1023,6 +1023,35 @@ k_decode_shared_wire(const uint8_t *__restrict__ wire, uint32_t n_rows, uint32_t
   if (check && !point_in_subgroup<S>(xm, ym)) st = 2;
   if (st) atomicOr(flags, (uint32_t)FLAG_CURVE);
 }
+// The Pedersen sibling (avrf_pedersen_batch_stage_shared_wire): `wire` holds the n_rows rows and the n_outs outputs as above, then the n proofs
+// Yb || R || Ok || s || sb (3 L + 64 bytes).  Thread g takes one point: row g, output g - n_rows, or point q = (g - n_pts) % 3 of proof
+// j = (g - n_pts) / 3, which goes to proofs + 256 j + 64 q; the lane of Yb copies s || sb behind the three points.  Rows, failing points and
+// the subgroup test as in k_decode_shared_wire.
+template <class S>
+__global__ void __launch_bounds__(128)
+k_decode_ped_shared_wire(const uint8_t *__restrict__ wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *__restrict__ table,
+                         te_pre *__restrict__ rows, uint8_t *__restrict__ outs, uint8_t *__restrict__ proofs, int validate, uint32_t *__restrict__ flags) {
+  using Fq = typename S::Fq;
+  constexpr size_t L = S::POINT_LEN, PLEN = 3 * L + 64;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, n_pts = n_rows + n_outs;
+  if (g >= n_pts + 3 * n) return;
+  const bool is_row = g < n_rows, is_pr = g >= n_pts;
+  const uint32_t j = (g - n_pts) / 3, q = (g - n_pts) % 3;               // (of a proof)
+  const uint8_t *src = wire + (is_pr ? L * n_pts + PLEN * j + L * q : L * g);
+  fp xm, ym, x, y; bool check;
+  int32_t st = decode_point_at<S>(src, validate, xm, ym, x, y, check);
+  uint8_t *dst = is_row ? table + 64 * (size_t)g : is_pr ? proofs + 256 * (size_t)j + 64 * q : outs + 64 * (size_t)(g - n_rows);
+  fp_store_le(dst, x); fp_store_le(dst + 32, y);
+  if (is_pr && q == 0) { fp_store_le(dst + 192, fp_load_le(src + 3 * L)); fp_store_le(dst + 224, fp_load_le(src + 3 * L + 32)); }
+  if (is_row) {
+    uint32_t *d = reinterpret_cast<uint32_t *>(rows + g);
+    fp_store(d, xm); fp_store(d + 8, ym);
+    if constexpr (S::SW_NATIVE) fp_store(d + 16, fp_zero());
+    else fp_store(d + 16, fp_mul<Fq>(fp_mul<Fq>(xm, ym), fp_const<Fq>(S::D)));
+  }
+  if (check && !point_in_subgroup<S>(xm, ym)) st = 2;
+  if (st) atomicOr(flags, (uint32_t)FLAG_CURVE);
+}
 // few points with the subgroup test: FOUR lanes per point -- the decoding is computed alike by the four lanes, r P runs as one
 // quad scalar multiplication (te_quad.h: 85 windows of three doublings and an addition, 0.6 ms instead of 1.7 ms on one lane)
 template <class S>
@@ -1273,6 +1302,13 @@ template <class S> hipError_t SingleOps<S>::decode_shared_wire(const uint8_t *d_
   const uint32_t pts = n_rows + n_outs + n;
   if (!pts) return hipSuccess;
   hipLaunchKernelGGL(k_decode_shared_wire<S>, dim3((pts + 127) / 128), dim3(128), 0, st, d_wire, n_rows, n_outs, n, d_table, (te_pre *)d_rows, d_outs, d_proofs, validate, d_flags);
+  return hipGetLastError();
+}
+template <class S> hipError_t SingleOps<S>::decode_ped_shared_wire(const uint8_t *d_wire, uint32_t n_rows, uint32_t n_outs, uint32_t n, uint8_t *d_table, te_pre_raw *d_rows,
+                                                                   uint8_t *d_outs, uint8_t *d_proofs, int validate, uint32_t *d_flags, hipStream_t st) {
+  const uint32_t pts = n_rows + n_outs + 3 * n;
+  if (!pts) return hipSuccess;
+  hipLaunchKernelGGL(k_decode_ped_shared_wire<S>, dim3((pts + 127) / 128), dim3(128), 0, st, d_wire, n_rows, n_outs, n, d_table, (te_pre *)d_rows, d_outs, d_proofs, validate, d_flags);
   return hipGetLastError();
 }
 template <class S> void SingleOps<S>::compress(const uint8_t *d_in, uint32_t n, uint8_t *d_out, hipStream_t st) {

@@ -301,6 +301,80 @@ int avrf_pedersen_batch_verify_segments(avrf_ctx *ctx, size_t n, const uint8_t *
 int avrf_pedersen_batch_verify_segments_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios, const uint32_t *io_counts,
                                              const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
                                              size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+/* ---- pedersen::BatchVerifier over a table of shared INPUTS.
+ * The Pedersen proof is the half of a ring-VRF proof that runs here, and the ticket workload makes tens of thousands of them over
+ * the same two or three VRF inputs.  The reference merges the two bases every item shares, G and BLINDING_BASE, into one MSM term
+ * each (src/pedersen.rs:387-418); here the inputs get the same treatment: the scalars of a row's references are added in the scalar
+ * field on the device, which leaves sum scalar * base, and so the verdict, unchanged.  The MSM has 4 n + n_shared + 2 terms instead
+ * of 5 n + 2, an item carries four points instead of five, and it sends a 4-byte index instead of 64 bytes of input.
+ *
+ * The arguments are those of avrf_thin_batch_stage_shared without pk_index (a Pedersen item has no public key): shared_xy is
+ * n_shared x 64 (x || y); input_index[k] is the row that is the input of I/O pair k (k runs over sum(io_counts), item-major);
+ * outputs_xy: sum(io_counts) x 64; proofs: n x 256 as in avrf_pedersen_batch_stage.  A row may be referenced any number of times
+ * or not at all.
+ *
+ * A batch staged this way runs through every run entry point unchanged (avrf_pedersen_batch_run, avrf_batch_run_begin / _hash /
+ * _end, avrf_pedersen_batch_challenges / _partial, avrf_batch_last_terms; the pool's wait / resubmit, both from_host values, /
+ * cycle), and its verdict is the one avrf_pedersen_batch_verify gives for the EXPANDED batch, every index replaced by its row;
+ * AVRF_OK for the empty batch.
+ *   checks    a REFERENCED identity row is AVRF_INVALID_DATA (io_identity, src/pedersen.rs:278,348-353), an unreferenced one is
+ *             fine; a non-canonical coordinate in ANY row is AVRF_INVALID_DATA.  Under avrf_ctx_set_validation /
+ *             avrf_pool_set_validation 1 or 2 the table is validated once per row (not once per reference), the outputs and the
+ *             proof points as in a plain batch.
+ *   no pairs  an item without pairs is legal: its merged pair is the identity legitimately (:264-267) and it contributes to no
+ *             row.  n_shared == 0 is accepted exactly when sum(io_counts) == 0; nothing is shared then and the batch is staged as
+ *             avrf_pedersen_batch_stage stages it (plain 5 n + 2 terms, segments allowed).
+ *   indices   an index >= n_shared is AVRF_ERR_BAD_ARG, found on the host before anything is staged: the context keeps what it
+ *             had staged.  avrf_pool_submit_pedersen_shared checks on the submitting thread, before a ticket exists.  No kernel
+ *             reads outside the table whatever the indices say.
+ *   terms     (avrf_batch_last_terms; this layout is ABI) item j has four terms at 4 j + k: k = 0 (O_merged, t c), 1 (Ok, t),
+ *             2 (Yb, u c), 3 (R, u).  Row r is at 4 n + r with the scalar  - sum of t_j s_j z_ji over the pairs whose input is r
+ *             (mod r_order), z_j0 = 1 and z_ji, i >= 1, the item's delinearisation scalars (src/utils/common.rs:345-363,389-419);
+ *             0 for a row nothing refers to.  (G, -sum u s) is at 4 n + n_shared and (BLINDING_BASE, -sum u sb) last.
+ *             avrf_pedersen_shared_n_terms = 4 n + n_shared + 2 (host arithmetic only, no device needed).
+ *   pairs     the merged input of an item with several pairs is sum z_i I_i, so its term -t s I_merged IS the contributions
+ *             -t s z_i to the pairs' rows (the reference's own linearity); the merged OUTPUT stays one term per item.
+ *   segments  avrf_pedersen_batch_run_segments refuses a shared-table staging (AVRF_ERR_BAD_ARG: the merged rows have no
+ *             per-segment meaning); avrf_pedersen_batch_run afterwards still answers.
+ *   restaging a later avrf_pedersen_batch_stage on the same context gives the plain 5 n + 2 terms again; a failed shared staging
+ *             leaves nothing staged.
+ * Measured (tools/shared_bench.py --kind=pedersen; kind 2 pool, 65 536 one-pair items over 3 inputs): resident
+ * 134.7-138.6 M items/s against 108.6-112.6 for avrf_pool_submit in the same process (1.24 x, ranges apart); from page-locked host
+ * buffers 94.2-95.6 against 82.6-91.9 (1.07 x, ranges apart by little).  USE THE PLAIN CALL WHEN NOTHING IS SHARED: with every input
+ * its own row (T = n) the term count is the plain one; resident runs are level (112.2-120.8 against 110.4-111.6) and staging the
+ * table from the host costs a tenth of the throughput (80.9-85.8 against 89.9-91.8 M items/s, 0.90 x). */
+int avrf_pedersen_batch_stage_shared(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared_xy,
+                                     const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts,
+                                     const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs);
+size_t avrf_pedersen_shared_n_terms(size_t n, size_t n_shared);
+/* The same batch from wire bytes.  With L = avrf_point_len(suite): shared is n_shared x L (`serialize_compressed` points), outputs
+ * sum(io_counts) x L, proofs n x (3 L + 64) laid out Yb || R || Ok || s || sb (the Pedersen wire proof of
+ * avrf_pedersen_batch_stage_wire); input_index, io_counts, ads and ad_lens exactly as in avrf_pedersen_batch_stage_shared.
+ * avrf_pedersen_batch_verify_shared_wire is stage + avrf_pedersen_batch_run.
+ *   indices   checked on the host before anything is staged: a failure is AVRF_ERR_BAD_ARG and the context keeps what it had
+ *             staged.  avrf_pool_submit_pedersen_shared_wire checks on the submitting thread, before a ticket exists.
+ *   decoding  one kernel launch per staging decodes EVERY table row -- referenced or not --, every output and the three points of
+ *             every proof, each once: a row costs one square root however many items refer to it, and an item four square roots
+ *             instead of five.  validate = 0: the point must decode (Validate::No).  validate != 0: it must also be non-identity
+ *             and in the prime-order subgroup (Validate::Yes, src/lib.rs:410-433).  AS IN THE THIN CALL, THIS DIFFERS FROM THE
+ *             x || y FLAVOUR: under validate != 0 an identity row is refused even when nothing refers to it.  With validate = 0 an
+ *             identity row decodes; the run then refuses it only if it is referenced.  As in avrf_pedersen_batch_stage_wire,
+ *             validate != 0 refuses an item without pairs, because its Ok is the identity.
+ *   failure   a point that fails makes the stage call return AVRF_INVALID_DATA with nothing staged; in the pool the verdict is
+ *             AVRF_INVALID_DATA, which avrf_pool_resubmit with from_host = 0 and the cycle mode repeat, while from_host = 1
+ *             stages again from the seven host buffers.
+ *   after     the staged batch is a shared-table batch in every respect: term layout and avrf_pedersen_shared_n_terms as above,
+ *             every run entry point, the pool's wait / resubmit / cycle.  avrf_ctx_set_validation keeps acting on the staged
+ *             x || y points at every run, independently of `validate`.
+ * Measured (tools/shared_wire_bench.py --kind=pedersen, validate = 1, from page-locked host buffers, same pool and items):
+ * 57.8-58.6 M items/s against 41.3-46.0 for avrf_pool_submit_wire (1.34 x, ranges apart): four points decoded per item instead of
+ * five and 4/5 of the MSM terms.  The x || y flavour of the same batch runs 93.6-96.4. */
+int avrf_pedersen_batch_stage_shared_wire(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared,
+                                          const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
+                                          const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate);
+int avrf_pedersen_batch_verify_shared_wire(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared,
+                                           const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
+                                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate);
 /* The layout of a segmented Pedersen run (src/pedersen.rs:303-426: 5 items + 2 terms per BatchVerifier whatever the pair counts, so
  * no io_counts), host arithmetic only: out as avrf_thin_segments_layout.  AVRF_ERR_BAD_ARG when the counts do not sum to n or a
  * limit is exceeded. */
@@ -381,6 +455,18 @@ int avrf_pool_submit_shared_wire(avrf_pool *pool, size_t n, size_t n_shared, con
                                  const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
                                  const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
                                  uint64_t *ticket);
+/* avrf_pool_submit_pedersen_shared / _shared_wire (kind 2 pools; a kind 1 pool refuses them, as avrf_pool_submit_shared / _shared_wire
+ * refuse a kind 2 pool): the Pedersen jobs over a table of shared inputs, arguments and contract as avrf_pedersen_batch_stage_shared /
+ * _shared_wire above.  All seven host buffers must stay untouched until the verdict is out, and are read again by every
+ * avrf_pool_resubmit with from_host = 1.  The indices, and a missing outputs or input_index where there are I/O pairs, are refused
+ * here, before a ticket exists.  Resubmission and the cycle mode reuse the gathered rows and the plan. */
+int avrf_pool_submit_pedersen_shared(avrf_pool *pool, size_t n, size_t n_shared, const uint8_t *shared_xy,
+                                     const uint32_t *input_index, const uint8_t *outputs_xy, const uint32_t *io_counts,
+                                     const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, uint64_t *ticket);
+int avrf_pool_submit_pedersen_shared_wire(avrf_pool *pool, size_t n, size_t n_shared, const uint8_t *shared,
+                                          const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
+                                          const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
+                                          uint64_t *ticket);
 int avrf_pool_wait(avrf_pool *pool, uint64_t ticket, int *status);
 int avrf_pool_resubmit(avrf_pool *pool, uint64_t ticket, int from_host, uint64_t *new_ticket);
 int avrf_pool_cycle(avrf_pool *pool, int from_host, uint64_t steps_block, double min_seconds, uint64_t max_steps, int expect_status,

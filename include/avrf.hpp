@@ -305,6 +305,56 @@ class BatchVerifier {
   const Suite &su_; size_t n_ = 0;
   std::vector<uint8_t> proofs_; detail::Packed packed_;
 };
+// pedersen::BatchVerifier over a table of shared inputs (avrf_pedersen_batch_stage_shared): push() keeps one row per byte-wise distinct
+// input and an index per I/O pair, so that an MSM of 4 n + T + 2 terms (shared_n_terms) answers what BatchVerifier::verify answers for
+// the same items.  With no pair pushed at all the table is empty and the batch runs as a plain one.
+class SharedBatchVerifier {
+ public:
+  explicit SharedBatchVerifier(const Suite &su) : su_(su) {}
+  void push(const std::vector<VrfIo> &ios, const std::string &ad, const Proof &proof) {
+    for (const VrfIo &io : ios) {
+      uint32_t r = 0;
+      for (; r < rows_.size() / 64; r++) if (std::equal(io.input.begin(), io.input.end(), rows_.begin() + 64 * r)) break;
+      if (r == rows_.size() / 64) rows_.insert(rows_.end(), io.input.begin(), io.input.end());
+      input_index_.push_back(r);
+      outputs_.insert(outputs_.end(), io.output.begin(), io.output.end());
+    }
+    io_counts_.push_back((uint32_t)ios.size());
+    ads_.insert(ads_.end(), ad.begin(), ad.end()); ad_lens_.push_back((uint32_t)ad.size());
+    uint8_t pr[256]; to_wire(proof, pr); proofs_.insert(proofs_.end(), pr, pr + 256); n_++;
+  }
+  Status verify() const {
+    if (int e = avrf_pedersen_batch_stage_shared(su_.ctx(), n_, n_shared(), rows_.data(), input_index_.data(), outputs_.data(), io_counts_.data(),
+                                                 ads_.data(), ad_lens_.data(), proofs_.data())) return e;
+    return avrf_pedersen_batch_run(su_.ctx());
+  }
+  size_t len() const { return n_; }
+  size_t n_shared() const { return rows_.size() / 64; }
+  size_t n_terms() const { return avrf_pedersen_shared_n_terms(n_, n_shared()); }
+
+ private:
+  const Suite &su_; size_t n_ = 0;
+  std::vector<uint8_t> rows_, outputs_, ads_, proofs_; std::vector<uint32_t> input_index_, io_counts_, ad_lens_;
+};
+// the same from the reference's byte strings (avrf_pedersen_batch_verify_shared_wire): shared holds n_shared compressed points, outputs one per
+// I/O pair, proofs n serialised proofs.  AVRF_INVALID_DATA when a point does not decode (validate != 0: or fails Validate::Yes).
+inline Status verify_shared_wire(const Suite &su, size_t n_shared, const std::vector<uint8_t> &shared, const std::vector<uint32_t> &input_index, const std::vector<uint8_t> &outputs,
+                                 const std::vector<uint32_t> &io_counts, const std::vector<uint8_t> &ads, const std::vector<uint32_t> &ad_lens,
+                                 const std::vector<uint8_t> &proofs, int validate) {
+  if (io_counts.size() != ad_lens.size()) throw std::invalid_argument("avrf: pedersen verify shared (wire)");
+  return avrf_pedersen_batch_verify_shared_wire(su.ctx(), io_counts.size(), n_shared, shared.data(), input_index.data(), outputs.data(),
+                                                io_counts.data(), ads.data(), ad_lens.data(), proofs.data(), validate);
+}
+// staging alone (avrf_pedersen_batch_stage_shared_wire), for a caller that runs the batch through avrf_batch_run_begin / _hash / _end
+inline Status stage_shared_wire(const Suite &su, size_t n_shared, const std::vector<uint8_t> &shared, const std::vector<uint32_t> &input_index, const std::vector<uint8_t> &outputs,
+                                const std::vector<uint32_t> &io_counts, const std::vector<uint8_t> &ads, const std::vector<uint32_t> &ad_lens,
+                                const std::vector<uint8_t> &proofs, int validate) {
+  if (io_counts.size() != ad_lens.size()) throw std::invalid_argument("avrf: pedersen stage shared (wire)");
+  return avrf_pedersen_batch_stage_shared_wire(su.ctx(), io_counts.size(), n_shared, shared.data(), input_index.data(), outputs.data(),
+                                               io_counts.data(), ads.data(), ad_lens.data(), proofs.data(), validate);
+}
+// The pool's jobs over a table of shared inputs are the C calls avrf_pool_submit_pedersen_shared / avrf_pool_submit_pedersen_shared_wire
+// on a kind 2 pool (include/avrf.h): the pool has no C++ wrapper.
 // { L, padded terms, total terms, window bits } of a segmented run over n items (avrf_pedersen_segments_layout; host arithmetic): throws
 // beyond the limits
 inline std::array<uint64_t, 4> segments_layout(size_t n, const std::vector<uint32_t> &seg_items) {

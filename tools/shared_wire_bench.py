@@ -7,8 +7,10 @@ Three arms run alternately in this one process and this one pool, three times ea
     shared_wire  avrf_pool_submit_shared_wire: the 1 027 rows once, then R and the output of every item (two per item)
     shared       avrf_pool_submit_shared on x || y points, nothing to decode: for context
 Prints items/s per run, then per arm the runs and their median, the plain-wire arm's spread (max - min) and the ratios.
-python tools/shared_wire_bench.py [n] [--quick] [--only=ARM]
-    --quick: one short run per arm; --only=wire | shared_wire | shared: that arm alone (a kernel trace of one arm)"""
+python tools/shared_wire_bench.py [n] [--quick] [--only=ARM] [--kind=thin|pedersen]
+    --quick: one short run per arm; --only=wire | shared_wire | shared: that arm alone (a kernel trace of one arm)
+    --kind=pedersen: the Pedersen verifier in a kind 2 pool over 3 inputs (avrf_pool_submit_pedersen_shared_wire: the 3 rows once, then the
+                 output and Yb, R, Ok of every item -- four points per item against the plain wire call's five)"""
 import json
 import os
 import sys
@@ -17,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from ark_vrf_amd import _native as nat  # noqa: E402
-from shared_bench import shared_items  # noqa: E402   (the items of its T = 1027 table; it reads the same [n] from the command line)
+from shared_bench import PED, shared_items  # noqa: E402   (the items of its T = 1027 / T = 3 table; it reads the same [n] and --kind from the command line)
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(args[0]) if args else 65536
@@ -35,6 +37,19 @@ def batches(ctx):
     b = shared_items(ctx, 1024, 3)
     L = ctx.point_len
     pks, ios = ctx.points_compress(b["pks_xy"]), ctx.points_compress(b["ios_xy"])
+    if PED:
+        pts = ctx.points_compress(b"".join(b["proofs"][256 * j: 256 * j + 192] for j in range(n)))
+        proofs = b"".join(pts[3 * L * j: 3 * L * (j + 1)] + b["proofs"][256 * j + 192: 256 * j + 256] for j in range(n))
+        rows, input_index, outputs = nat.dedup_inputs_wire(ios, L)
+        rows_xy, input_index_xy, outputs_xy = nat.dedup_inputs(b["ios_xy"])
+        assert len(rows) // L == len(rows_xy) // 64 <= 3
+        return {
+            "wire": (nat.PinnedBatch(n, ios, b["io_counts"], b["ads"], b["ad_lens"], proofs=proofs), lambda pool, x: pool.submit_wire(x, validate=VALIDATE)),
+            "shared_wire": (nat.PinnedPedersenSharedWireBatch(n, rows, input_index, outputs, b["io_counts"], b["ads"], b["ad_lens"], proofs, L),
+                            lambda pool, x: pool.submit_pedersen_shared_wire(x, validate=VALIDATE)),
+            "shared": (nat.PinnedPedersenSharedBatch(n, rows_xy, input_index_xy, outputs_xy, b["io_counts"], b["ads"], b["ad_lens"], b["proofs"]),
+                       lambda pool, x: pool.submit_pedersen_shared(x)),
+        }
     r = ctx.points_compress(b"".join(b["proofs"][96 * j: 96 * j + 64] for j in range(n)))
     proofs = b"".join(r[L * j: L * j + L] + b["proofs"][96 * j + 64: 96 * j + 96] for j in range(n))
     rows, pk_index, input_index, outputs = nat.dedup_points_wire(pks, ios, L)
@@ -57,9 +72,9 @@ def main():
     arms = batches(ctx)
     ctx.close()
     run_arms = [a for a in ARMS if ONLY in (None, a)]
-    out = dict(n=n, n_shared=arms["shared_wire"][0].n_shared, validate=VALIDATE, pool=dict(slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH),
+    out = dict(n=n, kind="pedersen" if PED else "thin", n_shared=arms["shared_wire"][0].n_shared, validate=VALIDATE, pool=dict(slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH),
                reps=REPS, min_seconds=MIN_S, runs=[])
-    pool = nat.Pool(0, kind=1, slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH)
+    pool = nat.Pool(0, kind=2 if PED else 1, slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH)
     try:
         for rep in range(-1, REPS):                                               # rep -1: warm-up of every arm, not recorded
             for arm in run_arms:                                                  # alternately: every slot takes the arm's batch, then the cycle stages it again and again
@@ -86,7 +101,8 @@ def main():
             out["shared_wire_over_wire"] = round(sw["median"] / w["median"], 4)
             out["shared_wire_over_shared"] = round(sw["median"] / out["shared"]["median"], 4)
             out["not_below_wire_by_more_than_its_spread"] = sw["median"] >= w["median"] - w["spread"]
-            out["reaches_70M"] = sw["median"] >= 70e6
+            if not PED:
+                out["reaches_70M"] = sw["median"] >= 70e6
     finally:
         pool.close()
         for batch, _ in arms.values():
