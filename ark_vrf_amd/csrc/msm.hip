@@ -635,7 +635,9 @@ struct MsmEnv {
   int c = 0, per_min = 8, wsum_wps = 0, occ = 0, tile = 0; bool window_sums = true, tiny = true;
   size_t wsum_blk_max = 64;          // fixed-base launches of at most this many bucket sets take the workgroup-per-set weighted sum
   MsmEnv() {
-    if (const char *e = getenv("AVRF_MSM_C")) { int v = atoi(e); if (v >= 3 && v <= 15) c = v; }
+    // 4 .. 15, the range of msm_plan's own choices; anything else leaves the choice to msm_plan (below 4 the window-sum form's host fold
+    // -- 2^4 between P1 and P2 -- no longer fits a window; above 15 a bucket no longer fits a key)
+    if (const char *e = getenv("AVRF_MSM_C")) { int v = atoi(e); if (v >= 4 && v <= 15) c = v; }
     if (const char *e = getenv("AVRF_MSM_OCC")) { int v = atoi(e); if (v >= 1 && v <= 8) occ = v; }   // resident k_accumulate waves per SIMD to fill
     if (const char *e = getenv("AVRF_MSM_TILE")) { int v = atoi(e); if (v >= 1024 && v <= (1 << 22)) tile = v; }       // keys per sort workgroup of a batched launch
     if (const char *e = getenv("AVRF_MSM_PER_MIN")) { int v = atoi(e); if (v >= 1 && v <= 4096) per_min = v; }

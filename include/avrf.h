@@ -517,7 +517,7 @@ void avrf_last_timing(avrf_ctx *ctx, double out[8]);
 
 /* Device-side timing of the dominant kernel (MSM bucket accumulation), measured with HIP events
  * recorded on the context's stream around every launch since the last reset: total milliseconds,
- * number of launches, and the plan of the last MSM {window bits c, windows, buckets/window, lanes/bucket}. */
+ * number of launches, and the plan of the last MSM {window bits c, windows, buckets/window, entries/lane}. */
 int avrf_kernel_stats(avrf_ctx *ctx, int reset, double *accum_ms_total, uint64_t *accum_launches, int32_t plan[4]);
 
 /* ---- Independent items (the per-item Prover / Verifier traits).  Two device forms behind every entry point below, same

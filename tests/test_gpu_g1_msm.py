@@ -43,6 +43,21 @@ def test_random(env, suite, n):
 
 
 @pytest.mark.parametrize("suite", [0, 1])
+@pytest.mark.parametrize("n", [4097, 8193])
+def test_random_above_the_srs(env, suite, n):
+    """more terms than the SRS files have points: 257 of them, each many times.  4 097 terms run nb = 256, 8 193 the first nb = 512 --
+    k_rowcol / k_bits with more than a wave per row.  The expected point is the big-int MSM over the 257 distinct bases, every base's
+    scalars added mod r first (as many terms one by one take several seconds in Python)."""
+    s, srs, ctx = env[suite]
+    rng = random.Random(100 * suite + n)
+    pts = [srs.g1[i % 257] for i in range(n)]
+    ks = [rng.randrange(s.r) for _ in range(n)]
+    got = ctx.g1_msm(b"".join(le(s, P) for P in pts), b"".join(k.to_bytes(32, "little") for k in ks))
+    folded = [sum(ks[i::257]) % s.r for i in range(257)]
+    assert got == le(s, R.g1_affine(s.p, R.g1_msm(s.p, srs.g1[:257], folded)))
+
+
+@pytest.mark.parametrize("suite", [0, 1])
 def test_exceptional_cases(env, suite):
     s, srs, ctx = env[suite]
     rng = random.Random(9 + suite)

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def ctxs():
     from ark_vrf_amd import _native as nat
-    return {s: nat.Context(s) for s in (0, 1)}
+    return {s: nat.Context(s) for s in (0, 1, orc.SECP256R1)}
 
 
 @pytest.mark.parametrize("suite", [0, 1])
@@ -24,6 +24,24 @@ def test_msm_random(ctxs, suite, n):
     bases = b"".join(pts[i % len(pts)] for i in range(n)) if n else b""
     sc = b"".join(rand_scalar(rng, suite) for _ in range(n))
     assert ctxs[suite].msm(bases, sc) == (orc.msm(suite, bases, sc) if n else IDENTITY_XY)
+
+
+_BASES257 = {}
+
+
+@pytest.mark.parametrize("suite", [0, orc.SECP256R1])
+@pytest.mark.parametrize("n", [8191, 8192, 8193, 16391, 32769, 65537])
+def test_msm_plan_boundaries(ctxs, suite, n):
+    """sizes on the steps of msm_plan's width (lg = 12 | 13, 14 | 15, 15 | 16: both sides of its lg >= 16 branch, and c = 11 by both
+    routes), on the sort tile's boundary (8 192 keys) and in its third, partial tile; twisted Edwards and the native short-Weierstrass
+    suite.  Which width runs is msm_plan's business: tests/test_gpu_msm_plans.py compares every width with the oracle."""
+    if suite not in _BASES257:
+        _BASES257[suite] = rand_points_xy(random.Random(257 + suite), suite, 257)
+    rng = random.Random(3000 * suite + n)
+    pts = _BASES257[suite]
+    bases = b"".join(pts[i % 257] for i in range(n))
+    sc = b"".join(rand_scalar(rng, suite) for _ in range(n))
+    assert ctxs[suite].msm(bases, sc) == orc.msm(suite, bases, sc)
 
 
 @pytest.mark.parametrize("suite", [0, 1])

@@ -170,10 +170,10 @@ def engine_case(c, suite, n_seg, L, seed):
 
 
 @pytest.mark.parametrize("suite", [0, 1])
-@pytest.mark.parametrize("n_seg,L", [(8, 5), (8, 300), (8, 1025), (8, 4100), (9, 2049), (3, 300), (3, 2100)])
+@pytest.mark.parametrize("n_seg,L", [(8, 5), (8, 300), (8, 600), (8, 1025), (8, 4100), (9, 2049), (3, 300), (3, 2100)])
 def test_msm_segments(ctxs, suite, n_seg, L):
-    """window widths 4 (L = 5), 5, 7 (1 025), 8 (2 049: nine segments) and 9 (4 100: nb = 256, the widest); three segments take the
-    looped single-MSM route, through the single-launch form (300 terms) and through the Pippenger chain (2 100)"""
+    """window widths 4 (L = 5), 5 (300), 6 (600), 7 (1 025), 8 (2 049: nine segments) and 9 (4 100: nb = 256, the widest); three segments
+    take the looped single-MSM route, through the single-launch form (300 terms) and through the Pippenger chain (2 100)"""
     engine_case(ctxs[suite], suite, n_seg, L, 100 * n_seg + L)
 
 
