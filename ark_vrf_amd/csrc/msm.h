@@ -65,15 +65,25 @@ struct MsmPlan {
 };
 MsmPlan msm_plan(size_t n, int scalar_bits);
 
-// What ONE enqueued launch chain sends back to the host: the results (bit sums, window triples or finished points, in the accumulator
-// layout of the curve policy), the device's plan and the timing events of the dominant kernel.  Every workspace has one of its own,
-// which serves a lane that runs one chain at a time.  A caller that queues several chains behind each other on one lane (stream +
-// workspace; the device-side workspace is reused in stream order) hands in a record per chain instead: pool.hip gives every slot one.
+// What the tail of a chain left in MsmChain::bits_host, vector after vector: `per` bit sums T_p (sum_p 2^p T_p), `per` window triples
+// (W_w = P1 + 2^4 P2 + 2^lg P3, sum_w 2^(c w) W_w) or one finished point.  Set with the tail's copy back only; read by msm.hip msm_fold.
+struct MsmResult {
+  enum Form { NONE, BIT_SUMS, WINDOW_TRIPLES, POINTS } form = NONE;
+  size_t vectors = 0;            // scalar vectors (independent MSMs) of the chain
+  size_t per = 0;                // entries per vector: bit sums or windows (POINTS: 1)
+  size_t words = 0;              // u32 words per point (accumulator layout of the curve policy)
+  int lg = 0;                    // WINDOW_TRIPLES: the scale 2^lg of a triple's third point
+  size_t stride() const { return per * (form == WINDOW_TRIPLES ? 3 : 1); }   // points per vector
+};
+// What ONE enqueued launch chain sends back to the host: the results and their description, the device's plan and the timing events of
+// the dominant kernel.  Every workspace has one of its own, which serves a lane that runs one chain at a time.  A caller that queues
+// several chains behind each other on one lane (stream + workspace; the device-side workspace is reused in stream order) hands in a
+// record per chain instead: pool.hip gives every slot one.
 struct MsmChain {
   PinMem bits_host, plan_host;   // results | 64 bytes: copy of the workspace's plan_dev
   DevEvent ev0, ev1;             // bracket the dominant kernel (k_accumulate) on the launch stream
-  MsmPlan plan = {0, 0, 0, 0}; int ret = 0;
-  int wsum_lg = 4;               // scale 2^lg of the third point of a window triple (TE window sums)
+  MsmPlan plan = {0, 0, 0, 0};
+  MsmResult res;                 // what bits_host holds once the chain is collected
   size_t n = 0;
   bool armed = false;            // enqueued and not collected yet (msm_te_enqueue / msm_te_finish)
   void ensure(size_t bytes);     // the events, the plan words and room for `bytes` of results (grow-only)
@@ -107,7 +117,7 @@ struct MsmWorkspace {
 };
 
 // MSM of n precomputed device points (Montgomery form) with n plain 256-bit scalars (8 x u32 LE,
-// already < r), on `stream`.  Result: extended point on the host.  suite: 0 Bandersnatch, 1 Baby-JubJub.
+// already < r), on `stream`.  Result: extended point on the host.  suite: an id of include/avrf.h (0 .. AVRF_N_SUITES - 1).
 int msm_te_device(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n,
                   MsmWorkspace &ws, hipStream_t stream, HostExt *out);
 // the same in two halves: msm_te_enqueue launches the whole kernel chain and the copies back on `stream` and returns without
@@ -135,7 +145,7 @@ bool msm_te_pending_supported(int suite);   // a caller's record is taken by the
 // points (2 * Fq words each, (0,0) = infinity), d_scalars = n plain 256-bit scalars (< r).
 // out_xy: canonical affine x || y little-endian (2 * FQ_BYTES), all-zero for the point at infinity.
 // batch > 1: `batch` scalar vectors over the same bases (vector b starts at element b * scalar_stride; 0 = n),
-// `batch` results in out_xy.
+// `batch` results in out_xy.  Eight or more vectors without a window table stay correct through the host fold (no device Horner for G1); nothing calls it so.
 int msm_g1_device(int curve, const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
                   size_t batch = 1, size_t scalar_stride = 0);
 // Fixed-base form for MSMs over one shared base set (the KZG SRS): build_g1_table fills

@@ -24,8 +24,8 @@
 //   k_wsum_blk / k_wsum   weighted bucket sum sum_b b*B_b of one window (or of one fixed-base bucket set) by
 //                a workgroup / a group of lanes: 2 additions per bucket + a suffix scan
 //   k_rowcol, k_bits, k_bits_direct, k_horner   the bit-decomposition reduction sum_b b*B_b = sum_k 2^k T_k, kept for
-//                G1 MSMs without a window table (ring_proof::index, the verifier's MSMs)
-//   host         Horner over the window sums (nwin * (c doublings + 1 addition))
+//                G1 MSMs without a window table (ring_proof::index, the verifier's MSMs) and for segmented launches
+//   host         msm_fold: Horner over what the chain's tail left (window triples, bit sums), or the finished points as they are
 //
 // Fixed-base mode (G1 only): the bases are a window table T[w][i] = 2^(c w) P_i, so ALL windows of a scalar vector
 // share one bucket set; `batch` vectors over the same table run as `batch` bucket sets in one launch chain.
@@ -369,7 +369,6 @@ k_accumulate(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ so
   AC::store_part(part + (slot0 + b) * AC::PART_WORDS, acc);
 }
 
-template <class T> struct type_tag { using type = T; };
 template <class CV> AVRF_DI typename CV::acc_t wave_sum(typename CV::acc_t acc);
 
 // Bucket `slot` = v * nb + b holds entries [offs, offs + cnt): they were accumulated by lanes lf..ll of window v, whose partials
@@ -717,7 +716,6 @@ template <class CV> static AccShape accumulate_shape() {
   }
   return cache[dev];
 }
-template <class CV> static size_t accumulate_lanes() { return accumulate_shape<CV>().lanes; }
 
 // AVRF_MSM_POISON=1 (debugging): fresh workspace memory is filled with 0xA5 bytes, so that a kernel that reads what no kernel wrote fails
 // every time instead of depending on what the allocator hands back
@@ -817,207 +815,212 @@ struct MsmLaunch {
   size_t base_stride = 0;                // segmented form (msm.h msm_te_segments): vector v multiplies bases [v * base_stride, v * base_stride + n); 0: shared bases
 };
 
-// Runs the whole device pipeline for one MSM and leaves the nwin*c bit sums T_p in rec.bits_host (accumulator layout of CV).
-// `rec` is the record the chain reports to: the workspace's own or a caller's (single-launch and window-sum forms only).
-// Returns the number of bit sums per vector (vector b's sums start at b * that).  Throws HipFailure when a HIP call fails.
-template <class CV>
-static int msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n_in, int scalar_bits, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream,
-                      const MsmLaunch &o = MsmLaunch()) {
-  const size_t batch = o.batch, scalar_stride = o.scalar_stride ? o.scalar_stride : n_in;
-  const int table_c = o.table_c, scalars_mont = o.scalars_mont;
-  const uint32_t *const d_base_idx = o.d_base_idx;
-  MsmPlan p = msm_plan(n_in, scalar_bits);
-  auto finish = [&]() { if (!o.defer) msm_collect(ws, rec, stream); };
-  // (the G1 callers take eight or more vectors back as finished points -- device Horner below -- so they keep that form)
-  if (n_in <= MSM_TINY_TERMS && batch <= (CV::FIXED_TABLE ? (size_t)7 : MSM_TINY_VECTORS) && !table_c && !d_base_idx && !scalars_mont && !o.base_stride && msm_env().tiny) {
-    p.c = 1; p.nwin = scalar_bits; p.nb = 1; p.lpb = 0;
-    const size_t acc_b = (size_t)CV::ACC_WORDS * 4, nbits = (size_t)scalar_bits;
-    ws.ensure(n_in, p, acc_b, batch, 256);
-    rec.ensure(batch * nbits * acc_b); rec.plan_host.as()[0] = 0; rec.plan = p;
-    HIP_CHECK(hipEventRecord(rec.ev0, stream));
-    unsigned threads = 64; while (threads < n_in && threads < 256) threads <<= 1;           // a power of two of waves: the LDS butterfly halves it
-    hipLaunchKernelGGL(k_msm_tiny_bits<CV>, dim3((unsigned)nbits, (unsigned)batch), dim3(threads), (threads / 64) * acc_b, stream, d_bases, d_scalars, (uint32_t)n_in,
-                       (uint32_t)scalar_stride, ws.bits.as());
-    HIP_CHECK(hipEventRecord(rec.ev1, stream));
-    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, batch * nbits * acc_b, hipMemcpyDeviceToHost, stream));
-    finish();
-    return (int)nbits;
-  }
-  const size_t lanes_target = accumulate_lanes<CV>();
-  size_t n = n_in;
-  uint32_t remap_n = 0, remap_stride = 0;
-  dim3 b256(256);
-  int dig_nwin = p.nwin;
-  if (table_c) {
-    dig_nwin = (scalar_bits + 1 + table_c - 1) / table_c;
-    p.c = table_c; p.nb = 1 << (table_c - 1); p.nwin = 1;
-    n = n_in * (size_t)dig_nwin;                                        // one window of n_in * dig_nwin keys per vector
-    remap_n = (uint32_t)n_in; remap_stride = (uint32_t)o.table_stride;
-  }
-  // fixed-base mode: the reduction kernels run over CV::red (G1: general additions on the unsaturated limbs, buckets in raw limbs)
-  using RV = typename CV::red;
-  const bool red = CV::FIXED_TABLE && table_c != 0;
-  const size_t acc_bytes = (size_t)(red ? (int)RV::ACC_WORDS : (int)CV::ACC_WORDS) * 4;
-  const uint32_t vwin = (uint32_t)(p.nwin * batch);
-  const size_t lanes_max = lanes_target + vwin + 256;                   // sum_v ceil(tot_v / per) <= total / per + vwin
-  if ((size_t)vwin * n >= 0xffff0000ull) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // 32-bit entry offsets
-  ws.ensure(n, p, acc_bytes, batch, lanes_max, (size_t)CV::accum::PART_WORDS * 4);
-  const uint32_t nbk = vwin * p.nb;
-  const uint32_t tile_len = tile_len_for(n, vwin), ntiles = (uint32_t)((n + tile_len - 1) / tile_len);
+// The five chains of msm_device, named by what ends them; msm_tail is the one place that decides between them.
+enum class MsmTail { SINGLE_LAUNCH, WINDOW_TRIPLES, TABLE_WSUM, DEVICE_HORNER, HOST_BITS };
+template <class CV> static MsmTail msm_tail(size_t n, const MsmLaunch &o) {
+  const bool plain = !o.table_c && !o.d_base_idx && !o.scalars_mont && !o.base_stride;
+  if (plain && n <= MSM_TINY_TERMS && o.batch <= MSM_TINY_VECTORS && msm_env().tiny) return MsmTail::SINGLE_LAUNCH;   // k_msm_tiny_bits alone: bit sums
+  if (CV::WINDOW_SUMS && o.batch == 1 && msm_env().window_sums) return MsmTail::WINDOW_TRIPLES;                        // three points per window
+  if (CV::FIXED_TABLE && o.table_c) return MsmTail::TABLE_WSUM;                       // one weighted sum per bucket set: a finished point per vector
+  if (!CV::FIXED_TABLE && o.base_stride) return MsmTail::DEVICE_HORNER;   // segmented (msm_te_segments only: G1 does not build this tail's kernels): device bit sums and Horner
+  return MsmTail::HOST_BITS;                                                          // k_rowcol / k_bits: the bit sums of every vector
+}
+// what the stages of one chain share: the lane, the record, the launch and, for the general chain, the plan with the sizes derived from it
+struct MsmRun {
+  MsmWorkspace &ws; MsmChain &rec; hipStream_t stream; const MsmLaunch &o;
+  MsmPlan p;
+  size_t n;                    // keys per virtual window (fixed-base mode: n_in * digit windows)
+  uint32_t vwin, nbk;          // virtual windows (nwin per vector) | buckets of all of them
+  size_t acc_bytes;            // one accumulator of the reduction kernels
+  uint32_t tile_len, ntiles;   // keys per sort workgroup | sort workgroups per virtual window
+};
+// the one way results leave the device: the copy back and, with it, the description of what the copy carries
+static void copy_back(MsmChain &rec, const DevMem &from, const MsmResult &res, hipStream_t stream) {
+  rec.res = res;
+  HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, from.p, res.vectors * res.stride() * res.words * 4, hipMemcpyDeviceToHost, stream));
+}
+template <class CV> static void chain_single_launch(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, int scalar_bits, MsmRun &r) {
+  r.p.c = 1; r.p.nwin = scalar_bits; r.p.nb = 1; r.p.lpb = 0;
+  const size_t acc_b = (size_t)CV::ACC_WORDS * 4, nbits = (size_t)scalar_bits;
+  r.ws.ensure(n, r.p, acc_b, r.o.batch, 256);
+  r.rec.ensure(r.o.batch * nbits * acc_b); r.rec.plan_host.as()[0] = 0; r.rec.plan = r.p;
+  HIP_CHECK(hipEventRecord(r.rec.ev0, r.stream));
+  unsigned threads = 64; while (threads < n && threads < 256) threads <<= 1;           // a power of two of waves: the LDS butterfly halves it
+  hipLaunchKernelGGL(k_msm_tiny_bits<CV>, dim3((unsigned)nbits, (unsigned)r.o.batch), dim3(threads), (threads / 64) * acc_b, r.stream, d_bases, d_scalars, (uint32_t)n,
+                     (uint32_t)(r.o.scalar_stride ? r.o.scalar_stride : n), r.ws.bits.as());
+  HIP_CHECK(hipEventRecord(r.rec.ev1, r.stream));
+  copy_back(r.rec, r.ws.bits, MsmResult{MsmResult::BIT_SUMS, r.o.batch, nbits, (size_t)CV::ACC_WORDS}, r.stream);
+}
+// the sort: digits -> keys, per-tile histograms, offsets, the lanes' plan, entries grouped by (virtual window, bucket) in ws.sorted
+static void chain_sort(const uint32_t *d_scalars, size_t n_in, int dig_nwin, size_t lanes_target, const MsmRun &r) {
+  MsmWorkspace &ws = r.ws; const MsmLaunch &o = r.o; const MsmPlan &p = r.p; hipStream_t stream = r.stream;
+  const dim3 b256(256);
   const size_t lds_bytes = (size_t)p.nb * 4;
-  hipLaunchKernelGGL(k_digits, dim3((unsigned)((n_in + 255) / 256), (unsigned)batch), b256, 0, stream, d_scalars, (uint32_t)n_in, (uint32_t)scalar_stride,
-                     p.c, dig_nwin, ws.keys.as<uint16_t>(), scalars_mont);
-  hipLaunchKernelGGL(k_hist, dim3(ntiles, vwin), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)n, tile_len, p.c, ws.hist.as());
-  hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)((p.nb + 255) / 256), vwin), b256, 0, stream, ws.hist.as(), ntiles, p.c, ws.cnts.as());
-  hipLaunchKernelGGL(k_scan_offs, dim3(vwin), dim3(1024), 0, stream, ws.cnts.as(), (uint32_t)n, p.c, ws.offsets.as(), ws.win_tot.as());
-  hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, stream, ws.win_tot.as(), vwin, (uint32_t)lanes_target, (uint32_t)msm_env().per_min,
+  // fixed-base mode: key (window w, term i) gathers table entry w * table_stride + i
+  const uint32_t remap_n = o.table_c ? (uint32_t)n_in : 0, remap_stride = o.table_c ? (uint32_t)o.table_stride : 0;
+  hipLaunchKernelGGL(k_digits, dim3((unsigned)((n_in + 255) / 256), (unsigned)o.batch), b256, 0, stream, d_scalars, (uint32_t)n_in,
+                     (uint32_t)(o.scalar_stride ? o.scalar_stride : n_in), p.c, dig_nwin, ws.keys.as<uint16_t>(), o.scalars_mont);
+  hipLaunchKernelGGL(k_hist, dim3(r.ntiles, r.vwin), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)r.n, r.tile_len, p.c, ws.hist.as());
+  hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)((p.nb + 255) / 256), r.vwin), b256, 0, stream, ws.hist.as(), r.ntiles, p.c, ws.cnts.as());
+  hipLaunchKernelGGL(k_scan_offs, dim3(r.vwin), dim3(1024), 0, stream, ws.cnts.as(), (uint32_t)r.n, p.c, ws.offsets.as(), ws.win_tot.as());
+  hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, stream, ws.win_tot.as(), r.vwin, (uint32_t)lanes_target, (uint32_t)msm_env().per_min,
                      ws.lane_base.as(), ws.plan_dev.as());
-  hipLaunchKernelGGL(k_scatter, dim3(8u * ((vwin + 7u) / 8u) * ntiles), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)n, tile_len, p.c, ws.hist.as(),
-                     ws.offsets.as(), ws.sorted.as(), remap_n, remap_stride, d_base_idx, ntiles, vwin, (uint32_t)p.nwin, (uint32_t)o.base_stride);
-  rec.ensure((size_t)vwin * 3 * acc_bytes);   // the window triples, which are all a caller's record is sent (the workspace's own is sized with `bits`)
-  if (CV::ZERO_IS_IDENTITY) HIP_CHECK(hipMemsetAsync(ws.buckets.p, 0, (size_t)nbk * acc_bytes, stream));   // empty buckets
-  HIP_CHECK(hipEventRecord(rec.ev0, stream));
-  hipLaunchKernelGGL(k_accumulate<CV>, dim3((unsigned)((lanes_max + 255) / 256)), b256, accumulate_shape<CV>().lds, stream, d_bases, ws.sorted.as(),
-                     ws.offsets.as(), ws.win_tot.as(), ws.lane_base.as(), ws.plan_dev.as(), vwin, (uint32_t)p.nb, (uint32_t)n, ws.part.as());
-  HIP_CHECK(hipEventRecord(rec.ev1, stream));
-  auto bucket_sums = [&](auto tag) {
-    using BV = typename decltype(tag)::type;
-    hipLaunchKernelGGL(k_bucket_sum<BV>, dim3((nbk + 255) / 256), b256, 0, stream, ws.offsets.as(), ws.cnts.as(), ws.lane_base.as(), ws.plan_dev.as(), nbk,
-                       (uint32_t)p.nb, (uint32_t)n, ws.part.as(), ws.buckets.as(), ws.heavy.as());
-    hipLaunchKernelGGL(k_heavy_sum<BV>, dim3(nbk < 1024 ? nbk : 1024), b256, 4 * acc_bytes, stream, ws.offsets.as(), ws.cnts.as(), ws.lane_base.as(),
-                       ws.plan_dev.as(), (uint32_t)p.nb, (uint32_t)n, ws.part.as(), ws.buckets.as(), ws.heavy.as());
-  };
-  if (red) bucket_sums(type_tag<RV>{}); else bucket_sums(type_tag<CV>{});
-  HIP_CHECK(hipMemcpyAsync(rec.plan_host.p, ws.plan_dev.p, 8, hipMemcpyDeviceToHost, stream));
-  rec.plan = p;
-  if constexpr (CV::WINDOW_SUMS) if (batch == 1 && msm_env().window_sums) {
-    // weighted bucket sum of every window with the four-lanes-per-point kernels (te_quad.h): three points per window come
-    // back; the host folds them into its window Horner (scales 1, 2^4, 16 m), so the device does no doublings at all
-    const uint32_t nb = (uint32_t)p.nb;
-    const uint32_t wpw = nb >= 256 ? 16u : 1u, m = nb >= 256 ? nb / 256 : (nb >= 16 ? nb / 16 : 1u);
-    const uint32_t nwaves = vwin * wpw;
-    hipLaunchKernelGGL(k_wsum_q1<typename CV::suite>, dim3((nwaves + 3) / 4), b256, 0, stream, ws.buckets.as(), nb, m, wpw, nwaves, ws.rc.as());
-    hipLaunchKernelGGL(k_wsum_q2<typename CV::suite>, dim3(vwin), dim3(64), 0, stream, ws.rc.as(), wpw, ws.bits.as());
-    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, (size_t)vwin * 3 * acc_bytes, hipMemcpyDeviceToHost, stream));
-    rec.wsum_lg = 4; while ((1u << rec.wsum_lg) < 16 * m) rec.wsum_lg++;
-    finish();
-    return -(int)vwin;                                       // negative: bits_host holds window triples, not bit sums
-  }
-  if (!ws.owns(rec)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // a caller's record is taken by the window-sum form only
-  const int h = (p.c - 1) / 2;
-  const uint32_t tasks = (1u << h) + ((uint32_t)p.nb >> h);
-  const int nbits = (int)vwin * p.c;
-  if constexpr (CV::FIXED_TABLE) if (table_c) {   // one bucket set per MSM: weighted sum in one kernel, no bit sums
-    uint32_t wps = 1;                                      // waves per bucket set when the launch has few sets
-    // (a wave per set does the least work per bucket -- 2.5 adds against 4.4 with four waves -- and measured faster as
-    // soon as a few hundred sets are in flight; the workgroup form is for the handful of sets of a single proof)
-    // (round 3 re-check with 512-set launches, which fill only half the SIMDs with one wave per set: two waves per set 12.4 k proofs/s,
-    // four 11.9 k against 12.6-12.7 k -- with several contexts in flight the idle SIMDs are not idle, total work decides)
-    const uint32_t wps_max = batch <= msm_env().wsum_blk_max ? 4 : 1;
-    while (wps < wps_max && (uint32_t)p.nb >= 64 * wps * 2) wps *= 2;
-    if (wps > 1) {
-      hipLaunchKernelGGL(k_wsum_blk<RV>, dim3((unsigned)batch), dim3(64 * wps), (size_t)wps * 2 * acc_bytes, stream, ws.buckets.as(),
-                         (uint32_t)p.nb, ws.rc.as());
-    } else {
-      uint32_t lps_log = 6;                                // lanes per bucket set: enough waves to cover the chip, <= nb
-      while (lps_log > 2 && (batch << (lps_log - 1)) >= 2048 * 64) lps_log--;
-      while ((1u << lps_log) > (uint32_t)p.nb) lps_log--;
-      hipLaunchKernelGGL(k_wsum<RV>, dim3((unsigned)(((batch << lps_log) + 255) / 256)), b256, 0, stream, ws.buckets.as(), (uint32_t)p.nb,
-                         (uint32_t)batch, lps_log, ws.rc.as());
-    }
-    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * (size_t)RV::OUT_WORDS * 4, hipMemcpyDeviceToHost, stream));
-    finish();
-    return p.c;
-  }
-  if (p.nb <= 256 && batch >= 8) {
-    hipLaunchKernelGGL(k_bits_direct<CV>, dim3(((unsigned)nbits + 127) / 128), dim3(128), 0, stream, ws.buckets.as(), p.c, (uint32_t)nbits, ws.bits.as());
+  hipLaunchKernelGGL(k_scatter, dim3(8u * ((r.vwin + 7u) / 8u) * r.ntiles), b256, lds_bytes, stream, ws.keys.as<uint16_t>(), (uint32_t)r.n, r.tile_len, p.c, ws.hist.as(),
+                     ws.offsets.as(), ws.sorted.as(), remap_n, remap_stride, o.d_base_idx, r.ntiles, r.vwin, (uint32_t)p.nwin, (uint32_t)o.base_stride);
+}
+template <class BV> static void bucket_sums(const MsmRun &r) {
+  hipLaunchKernelGGL(k_bucket_sum<BV>, dim3((r.nbk + 255) / 256), dim3(256), 0, r.stream, r.ws.offsets.as(), r.ws.cnts.as(), r.ws.lane_base.as(), r.ws.plan_dev.as(), r.nbk,
+                     (uint32_t)r.p.nb, (uint32_t)r.n, r.ws.part.as(), r.ws.buckets.as(), r.ws.heavy.as());
+  hipLaunchKernelGGL(k_heavy_sum<BV>, dim3(r.nbk < 1024 ? r.nbk : 1024), dim3(256), 4 * r.acc_bytes, r.stream, r.ws.offsets.as(), r.ws.cnts.as(), r.ws.lane_base.as(),
+                     r.ws.plan_dev.as(), (uint32_t)r.p.nb, (uint32_t)r.n, r.ws.part.as(), r.ws.buckets.as(), r.ws.heavy.as());
+}
+// the accumulation (bracketed by the record's events), the bucket sums into ws.buckets and the plan's copy back
+// (red: the reduction kernels run over CV::red -- G1 in fixed-base mode: general additions on the unsaturated limbs, buckets in raw limbs)
+template <class CV> static void chain_accumulate(const uint32_t *d_bases, size_t lanes_max, bool red, const MsmRun &r) {
+  r.rec.ensure((size_t)r.vwin * 3 * r.acc_bytes);   // the window triples, which are all a caller's record is sent (the workspace's own is sized with `bits`)
+  if (CV::ZERO_IS_IDENTITY) HIP_CHECK(hipMemsetAsync(r.ws.buckets.p, 0, (size_t)r.nbk * r.acc_bytes, r.stream));   // empty buckets
+  HIP_CHECK(hipEventRecord(r.rec.ev0, r.stream));
+  hipLaunchKernelGGL(k_accumulate<CV>, dim3((unsigned)((lanes_max + 255) / 256)), dim3(256), accumulate_shape<CV>().lds, r.stream, d_bases, r.ws.sorted.as(),
+                     r.ws.offsets.as(), r.ws.win_tot.as(), r.ws.lane_base.as(), r.ws.plan_dev.as(), r.vwin, (uint32_t)r.p.nb, (uint32_t)r.n, r.ws.part.as());
+  HIP_CHECK(hipEventRecord(r.rec.ev1, r.stream));
+  if (red) bucket_sums<typename CV::red>(r); else bucket_sums<CV>(r);
+  HIP_CHECK(hipMemcpyAsync(r.rec.plan_host.p, r.ws.plan_dev.p, 8, hipMemcpyDeviceToHost, r.stream));
+  r.rec.plan = r.p;
+}
+// weighted bucket sum of every window with the four-lanes-per-point kernels (te_quad.h): three points per window come
+// back; the host folds them into its window Horner (scales 1, 2^4, 16 m), so the device does no doublings at all
+template <class CV> static void tail_window_triples(const MsmRun &r) {
+  const uint32_t nb = (uint32_t)r.p.nb;
+  const uint32_t wpw = nb >= 256 ? 16u : 1u, m = nb >= 256 ? nb / 256 : (nb >= 16 ? nb / 16 : 1u), nwaves = r.vwin * wpw;
+  hipLaunchKernelGGL(k_wsum_q1<typename CV::suite>, dim3((nwaves + 3) / 4), dim3(256), 0, r.stream, r.ws.buckets.as(), nb, m, wpw, nwaves, r.ws.rc.as());
+  hipLaunchKernelGGL(k_wsum_q2<typename CV::suite>, dim3(r.vwin), dim3(64), 0, r.stream, r.ws.rc.as(), wpw, r.ws.bits.as());
+  int lg = 4; while ((1u << lg) < 16 * m) lg++;
+  copy_back(r.rec, r.ws.bits, MsmResult{MsmResult::WINDOW_TRIPLES, 1, r.vwin, (size_t)CV::ACC_WORDS, lg}, r.stream);
+}
+// one bucket set per MSM: weighted sum in one kernel, no bit sums
+template <class CV> static void tail_table_wsum(const MsmRun &r) {
+  using RV = typename CV::red;
+  const size_t batch = r.o.batch; const uint32_t nb = (uint32_t)r.p.nb;
+  uint32_t wps = 1;                                      // waves per bucket set when the launch has few sets
+  // (a wave per set does the least work per bucket -- 2.5 adds against 4.4 with four waves -- and measured faster as
+  // soon as a few hundred sets are in flight; the workgroup form is for the handful of sets of a single proof)
+  // (round 3 re-check with 512-set launches, which fill only half the SIMDs with one wave per set: two waves per set 12.4 k proofs/s,
+  // four 11.9 k against 12.6-12.7 k -- with several contexts in flight the idle SIMDs are not idle, total work decides)
+  const uint32_t wps_max = batch <= msm_env().wsum_blk_max ? 4 : 1;
+  while (wps < wps_max && nb >= 64 * wps * 2) wps *= 2;
+  if (wps > 1) {
+    hipLaunchKernelGGL(k_wsum_blk<RV>, dim3((unsigned)batch), dim3(64 * wps), (size_t)wps * 2 * r.acc_bytes, r.stream, r.ws.buckets.as(), nb, r.ws.rc.as());
   } else {
-    hipLaunchKernelGGL(k_rowcol<CV>, dim3(((size_t)vwin * tasks * 64 + 255) / 256), b256, 0, stream, ws.buckets.as(), p.c, h,
-                       vwin * tasks, ws.rc.as());
-    hipLaunchKernelGGL(k_bits<CV>, dim3(((size_t)nbits * 64 + 255) / 256), b256, 0, stream, ws.buckets.as(), ws.rc.as(),
-                       p.c, h, (uint32_t)nbits, ws.bits.as());
+    uint32_t lps_log = 6;                                // lanes per bucket set: enough waves to cover the chip, <= nb
+    while (lps_log > 2 && (batch << (lps_log - 1)) >= 2048 * 64) lps_log--;
+    while ((1u << lps_log) > nb) lps_log--;
+    hipLaunchKernelGGL(k_wsum<RV>, dim3((unsigned)(((batch << lps_log) + 255) / 256)), dim3(256), 0, r.stream, r.ws.buckets.as(), nb, (uint32_t)batch, lps_log, r.ws.rc.as());
   }
-  if (batch >= 8) {                                        // device Horner: only `batch` points come back
-    bool quads = false;                                    // the segmented chain of a twisted-Edwards suite: a wave per MSM
-    if constexpr (CV::QUAD) if (o.base_stride) {
-      hipLaunchKernelGGL(k_horner_quads<typename CV::suite>, dim3((unsigned)batch), dim3(64), 0, stream, ws.bits.as(), (uint32_t)(p.nwin * p.c), ws.rc.as());
-      quads = true;
+  copy_back(r.rec, r.ws.rc, MsmResult{MsmResult::POINTS, batch, 1, (size_t)RV::OUT_WORDS}, r.stream);
+}
+// the bit sums T_k (sum_b b B_b = sum_k 2^k T_k) of every virtual window into ws.bits, rows and columns of the bucket grid first
+template <class CV> static void rowcol_bits(const MsmRun &r) {
+  const int c = r.p.c, h = (c - 1) / 2;
+  const uint32_t tasks = (1u << h) + ((uint32_t)r.p.nb >> h), nbits = r.vwin * (uint32_t)c;
+  hipLaunchKernelGGL(k_rowcol<CV>, dim3(((size_t)r.vwin * tasks * 64 + 255) / 256), dim3(256), 0, r.stream, r.ws.buckets.as(), c, h, r.vwin * tasks, r.ws.rc.as());
+  hipLaunchKernelGGL(k_bits<CV>, dim3(((size_t)nbits * 64 + 255) / 256), dim3(256), 0, r.stream, r.ws.buckets.as(), r.ws.rc.as(), c, h, nbits, r.ws.bits.as());
+}
+// segmented launch: the bit sums in one kernel while a window's buckets allow it, the Horner on the device, only `batch` points come back
+template <class CV> static void tail_device_horner(const MsmRun &r) {
+  const uint32_t nbits = r.vwin * (uint32_t)r.p.c, vbits = (uint32_t)(r.p.nwin * r.p.c), batch = (uint32_t)r.o.batch;
+  if (r.p.nb <= 256) hipLaunchKernelGGL(k_bits_direct<CV>, dim3((nbits + 127) / 128), dim3(128), 0, r.stream, r.ws.buckets.as(), r.p.c, nbits, r.ws.bits.as());
+  else rowcol_bits<CV>(r);
+  if constexpr (CV::QUAD) hipLaunchKernelGGL(k_horner_quads<typename CV::suite>, dim3(batch), dim3(64), 0, r.stream, r.ws.bits.as(), vbits, r.ws.rc.as());   // a wave per MSM (te_quad.h)
+  else hipLaunchKernelGGL(k_horner<CV>, dim3((batch + 63) / 64), dim3(64), 0, r.stream, r.ws.bits.as(), vbits, batch, r.ws.rc.as());                      // a lane per MSM
+  copy_back(r.rec, r.ws.rc, MsmResult{MsmResult::POINTS, batch, 1, (size_t)CV::ACC_WORDS}, r.stream);
+}
+// Enqueues the device pipeline of o.batch MSMs: the single launch, or sort, accumulation and the tail msm_tail picks; collects it unless
+// o.defer.  `rec`: the workspace's own record or a caller's (single-launch and window-sum forms only).  Throws HipFailure when a HIP call fails.
+template <class CV>
+static void msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n_in, int scalar_bits, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream,
+                       const MsmLaunch &o = MsmLaunch()) {
+  const MsmTail tail = msm_tail<CV>(n_in, o);
+  MsmRun r{ws, rec, stream, o, msm_plan(n_in, scalar_bits), n_in};
+  if (tail == MsmTail::SINGLE_LAUNCH) chain_single_launch<CV>(d_bases, d_scalars, n_in, scalar_bits, r);
+  else {
+    MsmPlan &p = r.p;
+    int dig_nwin = p.nwin;
+    if (o.table_c) {
+      dig_nwin = (scalar_bits + 1 + o.table_c - 1) / o.table_c;
+      p.c = o.table_c; p.nb = 1 << (o.table_c - 1); p.nwin = 1;
+      r.n = n_in * (size_t)dig_nwin;                                      // one window of n_in * dig_nwin keys per vector
     }
-    if (!quads) hipLaunchKernelGGL(k_horner<CV>, dim3(((unsigned)batch + 63) / 64), dim3(64), 0, stream, ws.bits.as(), (uint32_t)(p.nwin * p.c),
-                                   (uint32_t)batch, ws.rc.as());
-    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * acc_bytes, hipMemcpyDeviceToHost, stream));
-  } else {
-    HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.bits.p, (size_t)nbits * acc_bytes, hipMemcpyDeviceToHost, stream));
+    const bool red = tail == MsmTail::TABLE_WSUM;
+    r.acc_bytes = (size_t)(red ? (int)CV::red::ACC_WORDS : (int)CV::ACC_WORDS) * 4;
+    r.vwin = (uint32_t)(p.nwin * o.batch); r.nbk = r.vwin * p.nb;
+    const size_t lanes_target = accumulate_shape<CV>().lanes, lanes_max = lanes_target + r.vwin + 256;   // sum_v ceil(tot_v / per) <= total / per + vwin
+    if ((size_t)r.vwin * r.n >= 0xffff0000ull) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // 32-bit entry offsets
+    ws.ensure(r.n, p, r.acc_bytes, o.batch, lanes_max, (size_t)CV::accum::PART_WORDS * 4);
+    r.tile_len = tile_len_for(r.n, r.vwin); r.ntiles = (uint32_t)((r.n + r.tile_len - 1) / r.tile_len);
+    chain_sort(d_scalars, n_in, dig_nwin, lanes_target, r);
+    chain_accumulate<CV>(d_bases, lanes_max, red, r);
+    if (tail != MsmTail::WINDOW_TRIPLES && !ws.owns(rec)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // a caller's record is taken by the window-sum form only
+    if constexpr (CV::WINDOW_SUMS) if (tail == MsmTail::WINDOW_TRIPLES) tail_window_triples<CV>(r);
+    if constexpr (CV::FIXED_TABLE) if (tail == MsmTail::TABLE_WSUM) tail_table_wsum<CV>(r);
+    if constexpr (!CV::FIXED_TABLE) if (tail == MsmTail::DEVICE_HORNER) tail_device_horner<CV>(r);
+    if (tail == MsmTail::HOST_BITS) { rowcol_bits<CV>(r); copy_back(r.rec, ws.bits, MsmResult{MsmResult::BIT_SUMS, o.batch, (size_t)(p.nwin * p.c), (size_t)CV::ACC_WORDS}, r.stream); }
   }
-  finish();
-  return p.nwin * p.c;
+  if (!o.defer) msm_collect(ws, rec, stream);
+}
+// Vector v of a COLLECTED record as a point of the host group HG (HostTe<S> or HostG1<C>), according to the form the chain's tail left.
+template <class HG> static auto msm_fold(const MsmChain &rec, size_t v) {
+  const MsmResult &r = rec.res;
+  const uint32_t *bh = rec.bits_host.as() + v * r.stride() * r.words;
+  auto acc = HG::identity();
+  auto step = [&](int dbls, size_t i) { while (dbls-- > 0) acc = HG::dbl(acc); acc = HG::add(acc, HG::from_raw32(bh + i * r.words)); };   // acc = 2^dbls acc + point i
+  const int c = rec.plan.c, lg = r.lg;
+  if (r.form == MsmResult::POINTS) return HG::from_raw32(bh);
+  if (r.form == MsmResult::BIT_SUMS) for (size_t i = r.per; i-- > 0;) step(1, i);                       // bit sums T_p: sum_p 2^p T_p
+  else for (size_t w = r.per; w-- > 0;) { step(c - lg, 3 * w + 2); step(lg - 4, 3 * w + 1); step(4, 3 * w); }   // window triples: W_w = P1 + 2^4 P2 + 2^lg P3; sum_w 2^(c w) W_w
+  return acc;
 }
 
 template <class S>
 static int msm_te_enqueue_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
-  rec.n = n; rec.ret = 0; rec.armed = true;
+  rec.n = n; rec.armed = true;
   MsmLaunch o; o.defer = true;
-  if (n) rec.ret = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, rec, stream, o);
+  if (n) msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, rec, stream, o);
   return 0;
 }
 template <class S>
 static int msm_te_finish_impl(MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out) {
-  using HT = HostTe<S>;
-  *out = HT::identity();
+  *out = HostTe<S>::identity();
   if (!rec.armed) return -1;                              // nothing was enqueued (or another call consumed the chain): an error, never the identity
   rec.disarm();
   if (rec.n == 0) return 0;
   msm_collect(ws, rec, stream);
-  const int nbits = rec.ret, c = rec.plan.c, lg = rec.wsum_lg; const uint32_t *bh = rec.bits_host.as();
-  HostExt acc = HT::identity();
-  if (nbits < 0) {                                        // window triples: W_w = P1 + 2^4 P2 + 2^lg P3; sum_w 2^(c w) W_w
-    for (int w = -nbits - 1; w >= 0; w--) {
-      for (int k = 0; k < c - lg; k++) acc = HT::dbl(acc);
-      acc = HT::add(acc, HT::from_raw32(bh + ((size_t)w * 3 + 2) * 32));
-      for (int k = 0; k < lg - 4; k++) acc = HT::dbl(acc);
-      acc = HT::add(acc, HT::from_raw32(bh + ((size_t)w * 3 + 1) * 32));
-      for (int k = 0; k < 4; k++) acc = HT::dbl(acc);
-      acc = HT::add(acc, HT::from_raw32(bh + (size_t)w * 3 * 32));
-    }
-  } else for (int i = nbits - 1; i >= 0; i--) {           // bit sums T_p: sum_p 2^p T_p
-    acc = HT::dbl(acc);
-    acc = HT::add(acc, HT::from_raw32(bh + (size_t)i * 32));
-  }
-  *out = acc;
+  *out = msm_fold<HostTe<S>>(rec, 0);
   return 0;
 }
 
+template <class F> static int te_call(int suite, F f) { return suite < 0 || suite >= AVRF_N_SUITES ? -1 : with_suite(suite, f); }   // a suite id out of range answers -1
 int msm_te_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
-  if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
-  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_enqueue_impl<S>(d_pre, d_scalars, n, ws, rec, stream); });
+  return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_enqueue_impl<S>(d_pre, d_scalars, n, ws, rec, stream); });
 }
 int msm_te_finish(int suite, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out) {
-  if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
-  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_finish_impl<S>(ws, rec, stream, out); });
+  return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_finish_impl<S>(ws, rec, stream, out); });
 }
 template <class S>
 static int msm_te_small_vectors_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, size_t nv, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
-  using HT = HostTe<S>;
   if (!n || n > MSM_TINY_TERMS || !nv || nv > MSM_TINY_VECTORS || !msm_env().tiny) return -1;
   MsmLaunch o; o.batch = nv; o.scalar_stride = n;
-  const int nbits = msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, ws.own, stream, o);
+  msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, n, S::Fr::BITS, ws, ws.own, stream, o);
   ws.own.disarm();
-  const uint32_t *bh = ws.own.bits_host.as();
-  parallel_for(nv, [&](size_t v) {                          // the vectors' Horners side by side (sum_p 2^p T_p)
-    HostExt acc = HT::identity();
-    for (int i = nbits - 1; i >= 0; i--) { acc = HT::dbl(acc); acc = HT::add(acc, HT::from_raw32(bh + ((size_t)v * nbits + i) * 32)); }
-    out[v] = acc;
-  });
+  parallel_for(nv, [&](size_t v) { out[v] = msm_fold<HostTe<S>>(ws.own, v); });   // the vectors' Horners side by side
   return 0;
 }
 int msm_te_small_vectors(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t n, size_t n_vectors, MsmWorkspace &ws, hipStream_t stream,
                          HostExt *out) {
-  if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
-  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_small_vectors_impl<S>(d_pre, d_scalars, n, n_vectors, ws, stream, out); });
+  return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_small_vectors_impl<S>(d_pre, d_scalars, n, n_vectors, ws, stream, out); });
 }
 // n_seg independent MSMs of L terms each in ONE chain: vector v over bases of its own (MsmLaunch::base_stride), bucket sums by
 // k_bits_direct (L <= 8191 keeps nb <= 256), the Horner on the device, n_seg finished points back.  Fewer than MSM_SEG_CHAIN_MIN
-// vectors would take the chain's host-Horner form: they loop the single-MSM path instead.
+// vectors loop the single-MSM path instead; the threshold has not been measured, and this is the one place it is written.
 constexpr size_t MSM_SEG_CHAIN_MIN = 8;
 template <class S>
 static int msm_te_segments_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
@@ -1039,13 +1042,11 @@ static int msm_te_segments_impl(const te_pre_raw *d_pre, const uint32_t *d_scala
   MsmLaunch o; o.batch = n_seg; o.scalar_stride = L; o.base_stride = L;
   msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, L, S::Fr::BITS, ws, ws.own, stream, o);
   ws.own.disarm();
-  const uint32_t *bh = ws.own.bits_host.as();
-  for (size_t v = 0; v < n_seg; v++) out[v] = HT::from_raw32(bh + v * 32);
+  for (size_t v = 0; v < n_seg; v++) out[v] = msm_fold<HT>(ws.own, v);
   return 0;
 }
 int msm_te_segments(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
-  if (suite < 0 || suite >= AVRF_N_SUITES) return -1;
-  return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_segments_impl<S>(d_pre, d_scalars, L, n_seg, ws, stream, out); });
+  return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_segments_impl<S>(d_pre, d_scalars, L, n_seg, ws, stream, out); });
 }
 int msm_segments_window_bits(size_t L) { return msm_plan(L, 256).c; }
 bool msm_te_pending_supported(int suite) {
@@ -1177,30 +1178,21 @@ void build_g1_table(int curve, const uint32_t *d_bases, size_t n, int c, int nwi
   HIP_CHECK(tmp.release());
 }
 
-template <class C>
-static int msm_g1_impl(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy, const MsmLaunch &o) {
+// The G1 tail: every vector of the collected record to a point, all of them to affine bytes.
+template <class C> static void g1_results(const MsmChain &rec, size_t batch, uint8_t *out_xy) {
   using HG = HostG1<C>;
-  constexpr size_t OUT = 8 * C::Fq::N;                    // bytes of one affine result
-  const size_t batch = o.batch; const int table_c = o.table_c;
-  int nbits = n ? msm_device<G1Curve<C>>(d_bases, d_scalars, n, C::Fr::BITS, ws, ws.own, stream, o) : 0;
   std::vector<typename HG::Pt> res(batch);
-  // (a few vectors without the device Horner: their bit-sum Horners -- nbits doublings and additions each -- run side by side)
-  auto fold = [&](size_t b) {
-    typename HG::Pt acc = HG::identity();
-    if (batch >= 8 || table_c) acc = HG::from_raw32(ws.own.bits_host.as() + b * 4 * C::Fq::N);      // Horner already done on the device
-    else if (n) {
-      const uint32_t *bh = ws.own.bits_host.as() + b * (size_t)nbits * 4 * C::Fq::N;
-      for (int i = nbits - 1; i >= 0; i--) {
-        acc = HG::dbl(acc);
-        acc = HG::add(acc, HG::from_raw32(bh + (size_t)i * 4 * C::Fq::N));
-      }
-    }
-    res[b] = acc;
-  };
-  if (batch >= 2 && batch < 8 && !table_c) parallel_for(batch, fold);
+  auto fold = [&](size_t b) { res[b] = msm_fold<HG>(rec, b); };
+  // (a few vectors of bit sums: their Horners -- as many doublings and additions as a vector has bit sums -- run side by side)
+  if (rec.res.form == MsmResult::BIT_SUMS && batch >= 2) parallel_for(batch, fold);
   else for (size_t b = 0; b < batch; b++) fold(b);
   HG::to_affine_bytes_batch(res.data(), batch, out_xy);
-  (void)OUT;
+}
+template <class C>
+static int msm_g1_impl(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy, const MsmLaunch &o) {
+  if (!n) { memset(out_xy, 0, o.batch * 8 * C::Fq::N); return 0; }   // no terms: the point at infinity (all-zero x || y) for every vector
+  msm_device<G1Curve<C>>(d_bases, d_scalars, n, C::Fr::BITS, ws, ws.own, stream, o);
+  g1_results<C>(ws.own, o.batch, out_xy);
   return 0;
 }
 
@@ -1561,7 +1553,7 @@ k_direct_reduce(const uint32_t *__restrict__ part, uint32_t lpv, uint32_t *__res
 template <class C>
 static int msm_g1_direct_impl(const G1DirectTable &t, const uint32_t *d_scalars, size_t n, size_t scalar_stride, MsmWorkspace &ws, hipStream_t stream,
                               uint8_t *out_xy, size_t batch, int scalars_mont, const uint32_t *d_base_idx) {
-  using CV = G1Curve<C>; using RV = typename CV::red; using HG = HostG1<C>;
+  using CV = G1Curve<C>; using RV = typename CV::red;
   if (!n || !batch) return -1;
   const size_t rows = (size_t)t.rows, E = n * rows;
   if (E * batch >= 0xffff0000ull || (!d_base_idx && n > t.n)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};
@@ -1584,13 +1576,11 @@ static int msm_g1_direct_impl(const G1DirectTable &t, const uint32_t *d_scalars,
                      (uint32_t)E, (uint32_t)lpv, (uint32_t)per, (uint32_t)batch, ws.part.as());
   HIP_CHECK(hipEventRecord(rec.ev1, stream));
   hipLaunchKernelGGL(k_direct_reduce<RV>, dim3((unsigned)batch), dim3(64), 0, stream, ws.part.as(), (uint32_t)lpv, ws.rc.as());
-  HIP_CHECK(hipMemcpyAsync(rec.bits_host.p, ws.rc.p, batch * (size_t)RV::OUT_WORDS * 4, hipMemcpyDeviceToHost, stream));
+  copy_back(rec, ws.rc, MsmResult{MsmResult::POINTS, batch, 1, (size_t)RV::OUT_WORDS}, stream);
   rec.plan_host.as()[0] = (uint32_t)per;
   rec.plan = p;
   msm_collect(ws, rec, stream);
-  std::vector<typename HG::Pt> res(batch);
-  for (size_t b = 0; b < batch; b++) res[b] = HG::from_raw32(rec.bits_host.as() + b * 4 * C::Fq::N);
-  HG::to_affine_bytes_batch(res.data(), batch, out_xy);
+  g1_results<C>(rec, batch, out_xy);
   return 0;
 }
 int msm_g1_direct_device(const G1DirectTable &t, const uint32_t *d_scalars, size_t n, size_t scalar_stride, MsmWorkspace &ws, hipStream_t stream,

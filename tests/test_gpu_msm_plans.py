@@ -3,7 +3,7 @@ window widths c = 4 .. 15, entries per lane 1 .. 4 096, the window-sum and the b
 tiny sizes -- each on inputs built for it (tests/msm_plan_inputs.py, conditions checked by tests/test_msm_plan_inputs_host.py),
 through five chains: avrf_msm_te on Bandersnatch, Baby-JubJub and secp256r1 (the native short-Weierstrass suite), avrf_g1_msm on
 BLS12-381 and BN254 -- and, beside them, avrf_msm_te_segments on Bandersnatch (the batched tail: k_bits_direct or k_rowcol / k_bits,
-the device Horner).
+the device Horner) and the ring commitment of both pairing suites down the general chain (three G1 vectors in one call).
 
 The engine reads its knobs once per process, so a case is one fresh child (tests/msm_plan_child.py) with the knobs in its
 environment; the child reports every result and the plan avrf_kernel_stats gives after it.  A result must equal the reference byte
@@ -25,12 +25,13 @@ import pytest
 import msm_plan_inputs as mpi
 import oracle as orc
 from oracle import ring_py as R
-from helpers import IDENTITY_XY, R_ORDER, rand_points_xy
+from helpers import IDENTITY_XY, R_ORDER, rand_points_xy, xy
 
 pytestmark = pytest.mark.gpu
 
 CHILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "msm_plan_child.py")
 SRS = {0: "bls12-381-srs-2-11-uncompressed-zcash.bin", 1: "bn254-testing-2-9-uncompressed.bin"}
+RING_VECTORS = {0: "bandersnatch_sha-512_ell2_ring.json", 1: "baby-jubjub_sha-512_tai_ring.json"}
 FIELD = {0: 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001,
          1: 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001,
          7: 0xffffffff00000001000000000000000000000000ffffffffffffffffffffffff}
@@ -106,7 +107,7 @@ def world(golden_dir, tmp_path_factory):
     """-> ({kind of case: its case file, written once}, {kind: {set: expected bytes}}, {kind: {set: (terms per MSM, MSMs, bits of the
     group order, the scalars)}})"""
     chains = {"te0": TeChain(0), "te1": TeChain(1), "te7": TeChain(7), "g1_0": G1Chain(0, golden_dir), "g1_1": G1Chain(1, golden_dir)}
-    sets, want, shape = ({"mix": {}, "small": {}, "tiles3": {}} for _ in range(3))
+    sets, want, shape = ({"mix": {}, "small": {}, "tiles3": {}, "ring": {}} for _ in range(3))
 
     def put(kind, name, ch, terms, n_seg=1, **kw):
         L = len(terms) // n_seg
@@ -124,6 +125,14 @@ def world(golden_dir, tmp_path_factory):
     # the segmented call on the first SEG_N x SEG_L terms of Bandersnatch's mix: every segment against the oracle on its terms alone
     put("mix", "te0_segments", chains["te0"], mpi.mix_terms(chains["te0"].r, SEED)[0][:SEG_N * SEG_L], n_seg=SEG_N)
     sets["mix"]["te0_segments"].update(call="msm_segments", n_seg=SEG_N)
+    # the ring commitment of the first reference ring vector of each pairing suite: three KZG commits of 512 terms in one G1 call
+    for i, vec in RING_VECTORS.items():
+        with open(os.path.join(golden_dir, vec)) as f:
+            v = json.load(f)[0]
+        raw = bytes.fromhex(v["ring_pks"])
+        keys = b"".join(xy(i, raw[k: k + 32]) for k in range(0, len(raw), 32))
+        sets["ring"]["g1_%d" % i] = dict(call="ring_commit", suite=i, srs=os.path.join(golden_dir, SRS[i]), keys=keys.hex())
+        want["ring"]["g1_%d" % i] = bytes.fromhex(v["ring_pks_com"])
     d = tmp_path_factory.mktemp("msm_plans")
     files = {}
     for kind, v in sets.items():
@@ -225,6 +234,16 @@ def test_occupancy(world, occ):
 def test_general_chain_at_tiny_sizes(world):
     """AVRF_MSM_TINY=0: 1, 2, 5, 64 and 300 terms down the general chain -- lanes with empty shares, windows without entries, c = 4"""
     check(world, "small", {"AVRF_MSM_TINY": "0"})
+
+
+def test_g1_three_vectors_general_chain(world):
+    """AVRF_MSM_TINY=0 sends the ring commitment's G1 call -- 3 scalar vectors over 512 SRS points, inside the single launch by default --
+    down the general chain (c = 6): bit sums of every vector come back and their Horners run side by side on the host.  The
+    commitment must be the reference vector's"""
+    got, want, _ = run_case(world, "ring", {"AVRF_MSM_TINY": "0"})
+    for name, g in got.items():
+        assert "error" not in g, (name, g)
+        assert bytes.fromhex(g["out"]) == want[name], name
 
 
 def test_three_tiles_default_environment(world):

@@ -165,15 +165,19 @@ def engine_case(c, suite, n_seg, L, seed):
     with ThreadPoolExecutor(max_workers=8) as ex:
         want = list(ex.map(lambda v: orc.msm(suite, bases[v], scalars[v]), range(n_seg)))
     assert got == want
-    assert got[1] == IDENTITY_XY                                                  # all scalars zero: the identity encoding
+    assert got[1] == (bytes(64) if suite == orc.SECP256R1 else IDENTITY_XY)       # all scalars zero: the suite's identity encoding
     return got
 
 
-@pytest.mark.parametrize("suite", [0, 1])
-@pytest.mark.parametrize("n_seg,L", [(8, 5), (8, 300), (8, 600), (8, 1025), (8, 4100), (9, 2049), (3, 300), (3, 2100)])
+SEG_SHAPES = [(8, 5), (8, 300), (8, 600), (8, 1025), (8, 4100), (9, 2049), (3, 300), (3, 2100)]
+
+
+@pytest.mark.parametrize("n_seg,L,suite", [(n, L, s) for s in (0, 1) for n, L in SEG_SHAPES] + [(8, 5, orc.SECP256R1), (8, 300, orc.SECP256R1)])
 def test_msm_segments(ctxs, suite, n_seg, L):
     """window widths 4 (L = 5), 5 (300), 6 (600), 7 (1 025), 8 (2 049: nine segments) and 9 (4 100: nb = 256, the widest); three segments
-    take the looped single-MSM route, through the single-launch form (300 terms) and through the Pippenger chain (2 100)"""
+    take the looped single-MSM route, through the single-launch form (300 terms) and through the Pippenger chain (2 100).  secp256r1, the
+    native short-Weierstrass suite, at widths 4 and 5: the generic device Horner (k_horner) behind k_bits_direct, where the
+    twisted-Edwards suites take k_horner_quads"""
     engine_case(ctxs[suite], suite, n_seg, L, 100 * n_seg + L)
 
 
