@@ -219,8 +219,8 @@ template <class C> struct HostPairing {
     }
     return r;
   }
-  // prod_i e(P_i, Q_i) == 1 with the Q_i given as line tables
-  static bool product_is_one_lines(const El *px, const El *py, const bool *pinf, const G2Lines *tabs, int n) {
+  // the Miller product prod_i f_(t-1, Q_i)(P_i) with the Q_i given as line tables (no final exponentiation)
+  static F12 miller_lines(const El *px, const El *py, const bool *pinf, const G2Lines *tabs, int n) {
     F12 f = f12_one();
     std::vector<size_t> pos(n, 0);
     for (int bit = C::ATE_LOOP_BITS - 2; bit >= 0; bit--) {
@@ -233,14 +233,18 @@ template <class C> struct HostPairing {
           f = f12_mul_line(f, tabs[i].c[k], f2_neg(f2_scale(tabs[i].lam[k], px[i])), py[i]);
         }
     }
-    return f12_is_one(final_exp(f));
+    return f;
+  }
+  // prod_i e(P_i, Q_i) == 1 with the Q_i given as line tables
+  static bool product_is_one_lines(const El *px, const El *py, const bool *pinf, const G2Lines *tabs, int n) {
+    return f12_is_one(final_exp(miller_lines(px, py, pinf, tabs, n)));
   }
 
   // the same with one Miller loop per pair, each on its own thread of `pf` (pf(n, fn) runs fn(0..n-1)): a pair then pays its own
   // squarings of f, but for the verifier's two pairs the loop takes 63 squarings + 69 line products on the critical path
   // instead of 63 + 138 (a lone verification is a latency case: 1.04 -> 0.85 ms for the check)
   template <class ParFor>
-  static bool product_is_one_lines_par(const El *px, const El *py, const bool *pinf, const G2Lines *tabs, int n, ParFor pf) {
+  static F12 miller_lines_par(const El *px, const El *py, const bool *pinf, const G2Lines *tabs, int n, ParFor pf) {
     std::vector<F12> fs(n);
     pf((size_t)n, [&](size_t i) {
       F12 f = f12_one();
@@ -257,11 +261,15 @@ template <class C> struct HostPairing {
     });
     F12 f = fs[0];
     for (int i = 1; i < n; i++) f = f12_mul(f, fs[i]);
-    return f12_is_one(final_exp(f));
+    return f;
+  }
+  template <class ParFor>
+  static bool product_is_one_lines_par(const El *px, const El *py, const bool *pinf, const G2Lines *tabs, int n, ParFor pf) {
+    return f12_is_one(final_exp(miller_lines_par(px, py, pinf, tabs, n, pf)));
   }
 
-  // prod_i e(P_i, Q_i) == 1 ?   P_i affine G1 (Montgomery x, y; inf flag), Q_i affine G2 on the twist
-  static bool product_is_one(const El *px, const El *py, const bool *pinf, const G2 *q, int n) {
+  // the Miller product prod_i f_(t-1, Q_i)(P_i):   P_i affine G1 (Montgomery x, y; inf flag), Q_i affine G2 on the twist
+  static F12 miller(const El *px, const El *py, const bool *pinf, const G2 *q, int n) {
     std::vector<F2> rx(n), ry(n);
     std::vector<bool> live(n);
     for (int i = 0; i < n; i++) { live[i] = !pinf[i] && !q[i].inf; rx[i] = q[i].x; ry[i] = q[i].y; }
@@ -298,8 +306,11 @@ template <class C> struct HostPairing {
         }
       }
     }
-    F12 out = final_exp(f);                                          // f^((p^12 - 1) / r)
-    return f12_is_one(out);
+    return f;
+  }
+  // prod_i e(P_i, Q_i) == 1 ?
+  static bool product_is_one(const El *px, const El *py, const bool *pinf, const G2 *q, int n) {
+    return f12_is_one(final_exp(miller(px, py, pinf, q, n)));           // f^((p^12 - 1) / r) up to a power coprime to r
   }
 
   // affine G2 arithmetic on the twist (y^2 = x^3 + b'), only for tau * g2 when an SRS is generated (Kzg::setup)

@@ -90,3 +90,60 @@ def test_rejects_noncanonical_coordinate(env):
     bad = (s.p).to_bytes(48, "little") + (1).to_bytes(48, "little")
     with pytest.raises(nat.AvrfError, match="-> 2"):
         pairing_check(setup, [bad], [le_xy(s, srs.g1[0])])
+
+
+# ---- the device route (more than 16 checks) at the shapes k_pairing_check treats specially: a partial last wave, whose dead groups repeat the
+# last item, and points at infinity, whose pairs the groups of one wave skip independently.  Expected verdicts follow from the SRS relations.
+
+def _kinds(srs, p):
+    """(A, B, verdict) of the five kinds of check: e(A, g2) e(B, tau g2) == 1 with A = tau^(i+1) g1"""
+    g = srs.g1
+    neg = lambda P: (P[0], (-P[1]) % p)
+    return [lambda i: (None, None, 1), lambda i: (None, neg(g[0]), 0), lambda i: (g[0], None, 0),
+            lambda i: (g[1 + i % 40], neg(g[i % 40]), 1), lambda i: (g[1 + i % 40], neg(g[1 + i % 40]), 0)]
+
+
+@pytest.mark.parametrize("n", [17, 18, 19, 21])
+@pytest.mark.parametrize("suite", [0, 1])
+def test_device_route_partial_last_wave(env, suite, n):
+    """n is no multiple of four: the last wave has 1, 2, 3 and 1 live groups, and the last live item's verdict differs from its predecessor's
+    (the dead groups compute the last item again: a verdict written by one of them, or an index off by one, shows)."""
+    from ark_vrf_amd.ring import pairing_check
+    ctx, setup, srs = env[suite]
+    s = R.SUITES[suite]
+    true, broken = _kinds(srs, s.p)[3:]
+    items = [(true if (i % 3 != 1) == (n % 2 == 1) else broken)(i) for i in range(n - 2)]
+    items += [true(n - 2), broken(n - 1)] if n % 2 else [broken(n - 2), true(n - 1)]
+    want = [v for _, _, v in items]
+    assert want[-1] != want[-2] and 0 < sum(want) < n
+    assert pairing_check(setup, [le_xy(s, a) for a, _, _ in items], [le_xy(s, b) for _, b, _ in items]) == want
+
+
+@pytest.mark.parametrize("suite", [0, 1])
+def test_device_route_points_at_infinity(env, suite):
+    """(inf, inf), (inf, -g1), (g1, inf), true and broken relations in turn: any four consecutive items, so every wave, hold four different
+    kinds, and the groups of a wave skip different pairs of the Miller loop."""
+    from ark_vrf_amd.ring import pairing_check
+    ctx, setup, srs = env[suite]
+    s = R.SUITES[suite]
+    kinds = _kinds(srs, s.p)
+    items = [kinds[i % 5](i) for i in range(21)]
+    want = [v for _, _, v in items]
+    assert want[:5] == [1, 0, 0, 1, 0]
+    assert pairing_check(setup, [le_xy(s, a) for a, _, _ in items], [le_xy(s, b) for _, b, _ in items]) == want
+
+
+@pytest.mark.parametrize("suite", [0, 1])
+def test_host_and_device_routes_agree(env, suite):
+    """the same 16 checks alone (at most 16: the host pool) and inside a list of 20 (the device kernel): same verdicts, the expected ones"""
+    from ark_vrf_amd.ring import pairing_check
+    ctx, setup, srs = env[suite]
+    s = R.SUITES[suite]
+    kinds = _kinds(srs, s.p)
+    items = [kinds[(3 * i + i // 5) % 5](i) for i in range(20)]
+    enc = lambda its: ([le_xy(s, a) for a, _, _ in its], [le_xy(s, b) for _, b, _ in its])
+    want = [v for _, _, v in items]
+    assert len({(3 * i + i // 5) % 5 for i in range(2, 18)}) == 5
+    host = pairing_check(setup, *enc(items[2:18]))
+    dev = pairing_check(setup, *enc(items))
+    assert host == want[2:18] and dev == want and dev[2:18] == host
