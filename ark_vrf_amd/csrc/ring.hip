@@ -4,17 +4,19 @@
 //
 // Split of the work: proofs are proved in lockstep chunks.  On the device: the witness columns
 // (expanded from their sparse description), all NTTs, the constraint aggregation on the 4N domain, quotient,
-// evaluations, linearisation and opening quotients (k_ring_* / k_ntt_* below) and every KZG commitment as a batched
+// evaluations, linearisation and opening quotients (k_ring_* / k_ntt_*, ring_dev.h) and every KZG commitment as a batched
 // fixed-base MSM (msm.hip) over window tables of the SRS -- the four witness columns in the Lagrange basis, where
 // they are sparse -- and (round 4) the <= 254 twisted-Edwards additions of every proof's witness accumulator with their
 // batch normalisation (k_ring_witness_acc).  On host threads between the device rounds: only the Fiat-Shamir transcript
 // (SHAKE128).  Verification: transcript replay and scalars on the
 // host pool, two G1 MSMs on the device, one 2-pairing check on the host (host_pairing.h).
+// The host arithmetic of both -- transcript schedule, G1 codec, proof layout, the verifier's reduction of an item to scalars -- is
+// host_ring.h; this file keeps the handles, the table registry, setup, key, the prover's rounds, the verifier's stages and the exports.
 #include "../../include/avrf.h"
-#include "te.h"
-#include "te_quad.h"
+#include "ring_dev.h"
 #include "host_g1.h"
 #include "host_pairing.h"
+#include "host_ring.h"
 #include "host_te.h"
 #include "msm.h"
 #include "pairing.h"
@@ -42,499 +44,23 @@ namespace avrf {
 // a failed HIP call unwinds to the extern "C" entry point (guarded(), capi_internal.h), which returns AVRF_ERR_NO_DEVICE
 #define HIP_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw avrf::HipFailure{e_, __FILE__, __LINE__}; } while (0)
 
-// ------------------------------------------------------------------------------------------------
-// device NTT over Fr of the pairing curve (radix-2, stages fused through LDS; batch of equal sizes);
-// tw[k] = w^k (Montgomery), k < n/2
-
-template <class F>
-__global__ void k_ntt_bitrev(uint32_t *__restrict__ data, uint32_t n, int logn, uint32_t batch) {
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t b = t / n, i = t - b * n;
-  if (b >= batch) return;
-  uint32_t j = __brev(i) >> (32 - logn);
-  if (i < j) {
-    uint32_t *p = data + ((size_t)b * n + i) * 8, *q = data + ((size_t)b * n + j) * 8;
-    fp x = fp_load(p), y = fp_load(q);
-    fp_store(p, y); fp_store(q, x);
+// AVRF_RING_TRACE: the phases of a prove or verify call on stderr, one line per lap(): wall time since the last lap and, for the
+// prover, the PROCESS's CPU time of the phase, workers included.  `RingTrace lap(...); lap("phase");`
+struct RingTrace {
+  static bool on() { static const bool t = getenv("AVRF_RING_TRACE") != nullptr; return t; }
+  static double now(clockid_t c) { struct timespec ts; clock_gettime(c, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+  const char *who; size_t n; bool cpu; double t_prev, c_prev;
+  RingTrace(const char *who_, size_t n_, bool cpu_) : who(who_), n(n_), cpu(cpu_) { restart(); }
+  void restart() { t_prev = now(CLOCK_MONOTONIC); c_prev = cpu ? now(CLOCK_PROCESS_CPUTIME_ID) : 0; }
+  double wall_ms() const { return now(CLOCK_MONOTONIC) - t_prev; }
+  void operator()(const char *what) {
+    if (!on()) return;
+    const double t = now(CLOCK_MONOTONIC), c = cpu ? now(CLOCK_PROCESS_CPUTIME_ID) : 0;
+    if (cpu) fprintf(stderr, "  %s[%zu] %-32s %8.3f ms wall %8.3f ms cpu\n", who, n, what, t - t_prev, c - c_prev);
+    else fprintf(stderr, "  %s[%zu] %-28s %8.3f ms\n", who, n, what, t - t_prev);
+    t_prev = t; c_prev = c;
   }
-}
-template <class F>
-__global__ void k_ntt_scale(uint32_t *__restrict__ data, uint32_t total, fp k) {
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  uint32_t *p = data + (size_t)t * 8;
-  fp_store(p, fp_mul<F>(fp_load(p), k));
-}
-
-// Up to 8 consecutive butterfly stages [s0, s1) on a tile held in LDS: 2^(s1-s0) rows with row stride 2^s0 elements
-// times 2^cols_log adjacent columns (<= 256 elements, whole 128-byte lines when s0 > 0).  A size-2^13 transform is
-// 2 passes over HBM instead of 13.  brev_load: the tile is gathered from the bit-reversed positions of `src` (another
-// buffer, `src_n` <= n valid elements per vector, the rest read as zero -- zero-extension of a shorter coefficient
-// vector costs nothing); otherwise src == dst is read in place.  do_scale: multiply by `scale` on the way out.
-template <class F>
-__global__ void __launch_bounds__(128)
-k_ntt_fused(const uint32_t *__restrict__ src, uint32_t src_n, uint32_t *__restrict__ dst, uint32_t n, int logn, int s0, int s1, uint32_t cols_log,
-            const uint32_t *__restrict__ tw, int brev_load, fp scale, int do_scale) {
-  __shared__ uint32_t sh[256 * 8];
-  const uint32_t cols = 1u << cols_log, tile = (1u << (s1 - s0)) << cols_log;
-  const uint32_t tiles_per_vec = n / tile, b = blockIdx.x / tiles_per_vec, t = blockIdx.x - b * tiles_per_vec;
-  const uint32_t low_groups = (1u << s0) >> cols_log;
-  const uint32_t hi = t / low_groups, lo = t - hi * low_groups;
-  const uint32_t base = (hi << s1) + (lo << cols_log);
-  for (uint32_t e = threadIdx.x; e < tile; e += blockDim.x) {
-    const uint32_t i = base + ((e >> cols_log) << s0) + (e & (cols - 1));
-    fp v;
-    if (brev_load) { const uint32_t j = __brev(i) >> (32 - logn); v = j < src_n ? fp_load(src + ((size_t)b * src_n + j) * 8) : fp_zero(); }
-    else v = fp_load(src + ((size_t)b * n + i) * 8);
-    fp_store(sh + e * 8, v);
-  }
-  __syncthreads();
-  // (the twiddles are read from global memory inside the butterflies: preloading the tile - cols <= 255 twiddles of a pass into a
-  // second 8 KB of LDS measured slower -- 559 us against 400 us per launch in the 2 048-proof profile, proofs/s unchanged)
-  for (int s = s0; s < s1; s++) {
-    const int hl = s - s0;                                             // half = 2^hl rows
-    for (uint32_t j = threadIdx.x; j < tile / 2; j += blockDim.x) {
-      const uint32_t c = j & (cols - 1), jr = j >> cols_log;
-      const uint32_t grp = jr >> hl, pos = jr & ((1u << hl) - 1);
-      const uint32_t r0 = (grp << (hl + 1)) + pos, r1 = r0 + (1u << hl);
-      const uint32_t pg = (pos << s0) + (lo << cols_log) + c;          // position inside the stage's global group
-      const fp w = fp_load(tw + ((size_t)pg << (logn - 1 - s)) * 8);
-      uint32_t *p = sh + ((r0 << cols_log) + c) * 8, *q = sh + ((r1 << cols_log) + c) * 8;
-      const fp u = fp_load(p), v = fp_mul<F>(fp_load(q), w);
-      fp_store(p, fp_add<F>(u, v)); fp_store(q, fp_sub<F>(u, v));
-    }
-    __syncthreads();
-  }
-  for (uint32_t e = threadIdx.x; e < tile; e += blockDim.x) {
-    const uint32_t i = base + ((e >> cols_log) << s0) + (e & (cols - 1));
-    fp v = fp_load(sh + e * 8);
-    if (do_scale) v = fp_mul<F>(v, scale);
-    fp_store(dst + ((size_t)b * n + i) * 8, v);
-  }
-}
-
-// (i)NTT of `batch` vectors of size n (tw = powers of the root or of its inverse; scale = 1/n for the inverse).
-// src == dst: in place (a bit-reversal pass first).  Otherwise dst = NTT(zero-extended src), src vectors of src_n <= n.
-template <class F>
-static void ntt_launch2(const uint32_t *d_src, uint32_t src_n, uint32_t *d_dst, uint32_t n, const uint32_t *d_tw, uint32_t batch, const fp *scale, hipStream_t st) {
-  int logn = 0; while ((1u << logn) < n) logn++;
-  const bool inplace = d_src == d_dst;
-  if (inplace) hipLaunchKernelGGL(k_ntt_bitrev<F>, dim3(((size_t)n * batch + 255) / 256), dim3(256), 0, st, d_dst, n, logn, batch);
-  fp one; memset(&one, 0, sizeof one);
-  for (int s0 = 0; s0 < logn;) {
-    int s1 = s0 + 8 < logn ? s0 + 8 : logn;
-    if (s1 < logn && logn - s1 < 3) s1 = logn - 3 > s0 ? logn - 3 : s1;   // keep the last pass at >= 3 stages
-    uint32_t cols_log = 8 - (uint32_t)(s1 - s0); if ((int)cols_log > s0) cols_log = (uint32_t)s0;
-    const uint32_t tile = (1u << (s1 - s0)) << cols_log;
-    const bool last = s1 == logn;
-    hipLaunchKernelGGL(k_ntt_fused<F>, dim3((unsigned)((size_t)(n / tile) * batch)), dim3(tile / 2 < 128 ? (tile / 2 ? tile / 2 : 1) : 128), 0, st,
-                       (s0 == 0 && !inplace) ? d_src : (const uint32_t *)d_dst, src_n, d_dst, n, logn, s0, s1, cols_log, d_tw,
-                       (s0 == 0 && !inplace) ? 1 : 0, (last && scale) ? *scale : one, (last && scale) ? 1 : 0);
-    s0 = s1;
-  }
-}
-template <class F>
-static void ntt_launch(uint32_t *d_data, uint32_t n, const uint32_t *d_tw, uint32_t batch, const fp *scale, hipStream_t st) {
-  ntt_launch2<F>(d_data, n, d_data, n, d_tw, batch, scale, st);
-}
-
-// ------------------------------------------------------------------------------------------------
-// PIOP constraint aggregation on the 4N domain: one lane per domain point.
-// e4 = evaluations of bits | ip_acc | acc_x | acc_y (4 x M), fixed4 = points.x | points.y | selector
-// (3 x M), l4 = L_first | L_last (2 x M), tw4[k] = w4^k (k < M/2; w4^(M/2) = -1).
-struct RingConsts { fp alpha[7]; fp w_last, seedx, seedy, resx, resy; };
-
-template <class S>
-__global__ void __launch_bounds__(256)
-k_ring_constraints(const uint32_t *__restrict__ e4, const uint32_t *__restrict__ fixed4, const uint32_t *__restrict__ l4,
-                   const uint32_t *__restrict__ tw4, const RingConsts *__restrict__ consts, uint32_t M, uint32_t *__restrict__ out) {
-  using F = typename S::Fq;
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M) return;
-  const uint32_t proof = blockIdx.y;                                  // one proof per grid row
-  e4 += (size_t)proof * 4 * M * 8; out += (size_t)proof * M * 8;
-  const RingConsts &c = consts[proof];
-  const uint32_t is = (i + 4) & (M - 1);                              // column(wX) on the 4N domain
-  auto at = [&](const uint32_t *base, uint32_t col, uint32_t idx) { return fp_load(base + ((size_t)col * M + idx) * 8); };
-  const fp one = fp_one<F>();
-  const fp b = at(e4, 0, i), ip = at(e4, 1, i), x1 = at(e4, 2, i), y1 = at(e4, 3, i);
-  const fp ips = at(e4, 1, is), x3 = at(e4, 2, is), y3 = at(e4, 3, is);
-  const fp x2 = at(fixed4, 0, i), y2 = at(fixed4, 1, i), sel = at(fixed4, 2, i);
-  const fp lf = at(l4, 0, i), ll = at(l4, 1, i);
-  fp xi = fp_load(tw4 + (size_t)(i & (M / 2 - 1)) * 8);
-  if (i >= M / 2) xi = fp_neg<F>(xi);
-  const fp nl = fp_sub<F>(xi, c.w_last), omb = fp_sub<F>(one, b);
-  const fp x1y1 = fp_mul<F>(x1, y1), x2y2 = fp_mul<F>(x2, y2);
-  fp c0 = fp_mul<F>(fp_sub<F>(fp_sub<F>(ips, ip), fp_mul<F>(sel, b)), nl);
-  fp t1 = fp_add<F>(fp_mul<F>(y1, y2), mul_a<S>(fp_mul<F>(x1, x2)));
-  fp c1 = fp_mul<F>(fp_add<F>(fp_mul<F>(b, fp_sub<F>(fp_sub<F>(fp_mul<F>(x3, t1), x1y1), x2y2)), fp_mul<F>(omb, fp_sub<F>(x3, x1))), nl);
-  fp t2 = fp_sub<F>(fp_mul<F>(x1, y2), fp_mul<F>(x2, y1));
-  fp c2 = fp_mul<F>(fp_add<F>(fp_mul<F>(b, fp_add<F>(fp_sub<F>(fp_mul<F>(y3, t2), x1y1), x2y2)), fp_mul<F>(omb, fp_sub<F>(y3, y1))), nl);
-  fp c3 = fp_mul<F>(b, omb);
-  fp c4 = fp_add<F>(fp_mul<F>(lf, fp_sub<F>(x1, c.seedx)), fp_mul<F>(ll, fp_sub<F>(x1, c.resx)));
-  fp c5 = fp_add<F>(fp_mul<F>(lf, fp_sub<F>(y1, c.seedy)), fp_mul<F>(ll, fp_sub<F>(y1, c.resy)));
-  fp c6 = fp_add<F>(fp_mul<F>(lf, ip), fp_mul<F>(ll, fp_sub<F>(ip, one)));
-  fp s = fp_mul<F>(c.alpha[0], c0);
-  s = fp_add<F>(s, fp_mul<F>(c.alpha[1], c1)); s = fp_add<F>(s, fp_mul<F>(c.alpha[2], c2)); s = fp_add<F>(s, fp_mul<F>(c.alpha[3], c3));
-  s = fp_add<F>(s, fp_mul<F>(c.alpha[4], c4)); s = fp_add<F>(s, fp_mul<F>(c.alpha[5], c5)); s = fp_add<F>(s, fp_mul<F>(c.alpha[6], c6));
-  fp_store(out + (size_t)i * 8, s);
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// per-proof polynomial rounds of the prover on the device; grid.y / blockIdx = proof.
-// All vectors are Montgomery Fr, 8 words per element.
-
-struct Fp3 { fp v[3]; };
-
-template <class F> AVRF_DI fp fp_pow_u32(fp a, uint32_t e) {
-  fp r = fp_one<F>();
-  while (e) { if (e & 1) r = fp_mul<F>(r, a); e >>= 1; if (e) a = fp_sqr<F>(a); }
-  return r;
-}
-// sum over the 256 lanes of a workgroup (sh: 256 x 8 words); result valid in every lane
-template <class F> AVRF_DI fp block_sum256(fp v, uint32_t *sh) {
-  const uint32_t t = threadIdx.x;
-  __syncthreads();
-  fp_store(sh + t * 8, v);
-  __syncthreads();
-  for (uint32_t s = 128; s > 0; s >>= 1) {
-    if (t < s) fp_store(sh + t * 8, fp_add<F>(fp_load(sh + t * 8), fp_load(sh + (t + s) * 8)));
-    __syncthreads();
-  }
-  return fp_load(sh);
-}
-// value at x of the length-len polynomial c: lane t takes coefficients [t*L, (t+1)*L)
-template <class F> AVRF_DI fp block_eval256(const uint32_t *c, uint32_t len, const fp &x, uint32_t *sh) {
-  const uint32_t t = threadIdx.x, L = (len + 255) / 256;
-  uint32_t lo = t * L, hi = lo + L; if (hi > len) hi = len;
-  fp h = fp_zero();
-  for (uint32_t i = hi; i > lo; i--) h = fp_add<F>(fp_mul<F>(h, x), fp_load(c + (size_t)(i - 1) * 8));
-  if (lo < hi) h = fp_mul<F>(h, fp_pow_u32<F>(x, lo));
-  return block_sum256<F>(h, sh);
-}
-
-// quotient: q = agg * Z / (X^N - 1) with Z = X^3 + z2 X^2 + z1 X + z0 (the three zk rows), agg of length M = 4N:
-// t[k] = sum_m z[m] agg[k-m];  q[i] = sum_{j >= 1} t[i + jN]   (exact division: the remainder is zero)
-template <class F>
-__global__ void __launch_bounds__(256)
-k_ring_quotient(const uint32_t *__restrict__ agg, uint32_t N, uint32_t qlen, Fp3 z, uint32_t *__restrict__ q) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, M = 4 * N;
-  if (i >= qlen) return;
-  const uint32_t *a = agg + (size_t)blockIdx.y * M * 8;
-  fp acc = fp_zero();
-  for (uint32_t k = i + N; k <= M + 2; k += N) {
-    if (k < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[0], fp_load(a + (size_t)k * 8)));
-    if (k >= 1 && k - 1 < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[1], fp_load(a + (size_t)(k - 1) * 8)));
-    if (k >= 2 && k - 2 < M) acc = fp_add<F>(acc, fp_mul<F>(z.v[2], fp_load(a + (size_t)(k - 2) * 8)));
-    if (k >= 3 && k - 3 < M) acc = fp_add<F>(acc, fp_load(a + (size_t)(k - 3) * 8));
-  }
-  fp_store(q + ((size_t)blockIdx.y * qlen + i) * 8, acc);
-}
-
-// ev[proof][c] = poly_c(zeta_proof), c: px | py | sel (fixed, shared) | bits | ip | ax | ay (coef: proof x 4 x N)
-template <class F>
-__global__ void __launch_bounds__(256)
-k_ring_evals(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ fixed, const uint32_t *__restrict__ zeta, uint32_t N,
-             uint32_t *__restrict__ ev) {
-  __shared__ uint32_t sh[256 * 8];
-  const uint32_t c = blockIdx.x, p = blockIdx.y;
-  const uint32_t *poly = c < 3 ? fixed + (size_t)c * N * 8 : coef + ((size_t)p * 4 + (c - 3)) * N * 8;
-  fp v = block_eval256<F>(poly, N, fp_load(zeta + (size_t)p * 8), sh);
-  if (threadIdx.x == 0) fp_store(ev + ((size_t)p * 7 + c) * 8, v);
-}
-
-// linearisation polynomial lin = f0 ip + f1 ax + f2 ay (f from the evaluations, A.7 step 6) and lin(zeta w)
-template <class S>
-__global__ void __launch_bounds__(256)
-k_ring_lin(const uint32_t *__restrict__ coef, const RingConsts *__restrict__ consts, const uint32_t *__restrict__ zeta,
-           const uint32_t *__restrict__ ev, fp w, uint32_t N, uint32_t *__restrict__ lin, uint32_t *__restrict__ lin_zw) {
-  using F = typename S::Fq;
-  __shared__ uint32_t sh[256 * 8];
-  const uint32_t p = blockIdx.x, t = threadIdx.x;
-  const RingConsts &c = consts[p];
-  const uint32_t *e = ev + (size_t)p * 7 * 8;
-  const fp z = fp_load(zeta + (size_t)p * 8), one = fp_one<F>();
-  const fp x2 = fp_load(e), y2 = fp_load(e + 8), b = fp_load(e + 24), x1 = fp_load(e + 40), y1 = fp_load(e + 48);
-  const fp nlz = fp_sub<F>(z, c.w_last), omb = fp_sub<F>(one, b);
-  const fp k1 = fp_add<F>(fp_mul<F>(b, fp_add<F>(fp_mul<F>(y1, y2), mul_a<S>(fp_mul<F>(x1, x2)))), omb);
-  const fp k2 = fp_add<F>(fp_mul<F>(b, fp_sub<F>(fp_mul<F>(x1, y2), fp_mul<F>(x2, y1))), omb);
-  const fp f0 = fp_mul<F>(nlz, c.alpha[0]), f1 = fp_mul<F>(nlz, fp_mul<F>(c.alpha[1], k1)), f2 = fp_mul<F>(nlz, fp_mul<F>(c.alpha[2], k2));
-  const uint32_t *ip = coef + ((size_t)p * 4 + 1) * N * 8, *ax = ip + (size_t)N * 8, *ay = ax + (size_t)N * 8;
-  uint32_t *out = lin + (size_t)p * N * 8;
-  for (uint32_t i = t; i < N; i += 256)
-    fp_store(out + (size_t)i * 8, fp_add<F>(fp_add<F>(fp_mul<F>(f0, fp_load(ip + (size_t)i * 8)), fp_mul<F>(f1, fp_load(ax + (size_t)i * 8))),
-                                            fp_mul<F>(f2, fp_load(ay + (size_t)i * 8))));
-  __syncthreads();
-  fp v = block_eval256<F>(out, N, fp_mul<F>(z, w), sh);
-  if (t == 0) fp_store(lin_zw + (size_t)p * 8, v);
-}
-
-// aggregated opening polynomial at zeta: sum_c nu_c poly_c + nu_7 q   (length qlen; the 7 columns have length N)
-template <class F>
-__global__ void __launch_bounds__(256)
-k_ring_aggz(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ fixed, const uint32_t *__restrict__ q, const uint32_t *__restrict__ nu,
-            uint32_t N, uint32_t qlen, uint32_t *__restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
-  if (i >= qlen) return;
-  const uint32_t *nup = nu + (size_t)p * 8 * 8;
-  fp acc = fp_mul<F>(fp_load(nup + 7 * 8), fp_load(q + ((size_t)p * qlen + i) * 8));
-  if (i < N) {
-    for (int c = 0; c < 3; c++) acc = fp_add<F>(acc, fp_mul<F>(fp_load(nup + c * 8), fp_load(fixed + ((size_t)c * N + i) * 8)));
-    for (int c = 0; c < 4; c++) acc = fp_add<F>(acc, fp_mul<F>(fp_load(nup + (3 + c) * 8), fp_load(coef + (((size_t)p * 4 + c) * N + i) * 8)));
-  }
-  fp_store(out + ((size_t)p * qlen + i) * 8, acc);
-}
-
-// out = (c(X) - c(z)) / (X - z), z = zs[proof] * zmul: out[i-1] = A_i = c[i] + z A_{i+1}.  Lane t owns indices
-// [t*L, (t+1)*L); the carry into a chunk comes from a suffix scan of the chunk values with multiplier z^L.
-template <class F>
-__global__ void __launch_bounds__(256)
-k_ring_divlin(const uint32_t *__restrict__ in, uint32_t in_stride, uint32_t len, const uint32_t *__restrict__ zs, fp zmul,
-              uint32_t *__restrict__ out, uint32_t out_stride) {
-  __shared__ uint32_t sh[256 * 8];
-  const uint32_t p = blockIdx.x, t = threadIdx.x, L = (len + 255) / 256;
-  const uint32_t *c = in + (size_t)p * in_stride * 8;
-  uint32_t *o = out + (size_t)p * out_stride * 8;
-  const fp z = fp_mul<F>(fp_load(zs + (size_t)p * 8), zmul);
-  uint32_t lo = t * L, hi = lo + L; if (hi > len) hi = len; if (lo > len) lo = len;
-  fp h = fp_zero();
-  for (uint32_t i = hi; i > lo; i--) h = fp_add<F>(fp_mul<F>(h, z), fp_load(c + (size_t)(i - 1) * 8));
-  // carry[t] = sum_{t' > t} h_{t'} z^(L (t' - t - 1)):  start from h_{t+1}, then Hillis-Steele with z^(L d)
-  fp_store(sh + t * 8, h);
-  __syncthreads();
-  fp A = t + 1 < 256 ? fp_load(sh + (t + 1) * 8) : fp_zero();
-  fp mul = fp_pow_u32<F>(z, L);
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    __syncthreads();
-    fp_store(sh + t * 8, A);
-    __syncthreads();
-    if (t + d < 256) A = fp_add<F>(A, fp_mul<F>(mul, fp_load(sh + (t + d) * 8)));
-    mul = fp_sqr<F>(mul);
-  }
-  for (uint32_t i = hi; i > lo; i--) {
-    A = fp_add<F>(fp_load(c + (size_t)(i - 1) * 8), fp_mul<F>(A, z));
-    if (i >= 2) fp_store(o + (size_t)(i - 2) * 8, A);
-  }
-}
-
-// Witness columns from their sparse description (A.7 step 1): pos = sorted rows with bit 1 (<= 256 per proof,
-// padded), vals = the cnt+1 successive accumulator points (x | y), kidx = the signer's row, zk = the values of the
-// last 3 rows of each column (proof x 4 x 3; nullptr: zeros).  cols[proof] = bits | ip | ax | ay (4 x N evaluations).
-template <class F>
-__global__ void __launch_bounds__(256)
-k_ring_witness_cols(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ kidx,
-                    const uint32_t *__restrict__ vals, const uint32_t *__restrict__ zk, uint32_t N, uint32_t cap, uint32_t *__restrict__ cols) {
-  __shared__ uint32_t sp[256];
-  const uint32_t p = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-  sp[threadIdx.x] = pos[(size_t)p * 256 + threadIdx.x];
-  __syncthreads();
-  if (i >= N) return;
-  const uint32_t m = cnt[p], ki = kidx[p];
-  uint32_t lo = 0, hi = m;                               // r = number of pos < i
-  while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (sp[mid] < i) lo = mid + 1; else hi = mid; }
-  const bool bit = lo < m && sp[lo] == i;
-  const fp one = fp_one<F>(), zero = fp_zero();
-  uint32_t *c = cols + (size_t)p * 4 * N * 8;
-  if (i >= cap) {                                          // the 3 zero-knowledge rows: random when hiding, else zero
-    for (int col = 0; col < 4; col++)
-      fp_store(c + ((size_t)col * N + i) * 8, zk ? fp_load(zk + (((size_t)p * 4 + col) * 3 + (i - cap)) * 8) : zero);
-    return;
-  }
-  fp_store(c + (size_t)i * 8, bit ? one : zero);
-  fp_store(c + ((size_t)N + i) * 8, i > ki ? one : zero);
-  const uint32_t *v = vals + ((size_t)p * 257 + lo) * 16;
-  fp_store(c + ((size_t)2 * N + i) * 8, fp_load(v));
-  fp_store(c + ((size_t)3 * N + i) * 8, fp_load(v + 8));
-}
-// RingProver round 0 on the device (A.7 step 1; w3f-ring-proof `PiopProver::build`): the witness in sparse form.  One lane per
-// proof.  Rows with bit 1: the signer's key, then the set bits of the blinding (row keyset + i).  The accumulator column only
-// changes there: acc_0 = seed, acc_{j+1} = acc_j + point[pos_j] on the suite's twisted-Edwards curve (mixed additions, the ring's
-// points tabulated as te_pre at index time), all m + 1 <= 255 partial sums normalised with ONE inversion (Montgomery's trick over
-// the lane's own chain; the extended points and prefix products live in `scratch`, 257 x 160 bytes per proof).  Written: the row
-// list and count, the affine partial sums (k_ring_witness_cols expands them into the columns), the four sparse vectors of the
-// Lagrange-basis commitments (bits | index polynomial | acc_x | acc_y: base index + PLAIN scalar), and per proof the result
-// and the instance (= result - seed) for the transcript.  Until round 3 this ran on host threads (<= 254 additions + 2
-// inversions per proof): 4 ms of two cores per 128-proof chunk, the largest host item of a rank of an 8-GPU node.
-template <class S>
-__global__ void __launch_bounds__(64)
-k_ring_witness_acc(const te_pre *__restrict__ points, const uint32_t *__restrict__ kidx, const uint8_t *__restrict__ blind, uint32_t n, uint32_t keyset,
-                   uint32_t L, uint32_t N, uint32_t cap, fp seedx, fp seedy, const uint32_t *__restrict__ zk, uint32_t *__restrict__ scratch,
-                   uint32_t *__restrict__ pos, uint32_t *__restrict__ cnt, uint32_t *__restrict__ vals, uint32_t *__restrict__ sc, uint32_t *__restrict__ bi,
-                   uint32_t *__restrict__ out) {
-  // FOUR lanes per proof (te_quad.h: lane jc of the quad holds coordinate jc of the accumulator): a mixed addition is two rounds
-  // of multiplications instead of eight sequential ones, the backward pass two rounds per row instead of four multiplications.
-  using F = typename S::Fq;
-  constexpr uint32_t MP = 264;
-  const uint32_t lane = threadIdx.x & 63, jc = lane & 3;
-  uint32_t p = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-  const bool live = p < n;
-  if (!live) p = n - 1;                                                        // (whole quads stay in step for the cross-lane moves; they write nothing)
-  uint32_t *ppos = pos + (size_t)p * 256;
-  const uint32_t ki = kidx[p];
-  // the row list (every lane of the quad derives it; lane 0 writes it)
-  uint32_t m = 1;
-  for (uint32_t i = 0; i < L; i++) if ((blind[32 * (size_t)p + (i >> 3)] >> (i & 7)) & 1) m++;
-  if (live && jc == 0) {
-    uint32_t w = 0; ppos[w++] = ki;
-    for (uint32_t i = 0; i < L; i++) if ((blind[32 * (size_t)p + (i >> 3)] >> (i & 7)) & 1) ppos[w++] = keyset + i;
-    for (uint32_t j = w; j < 256; j++) ppos[j] = 0xffffffffu;
-    cnt[p] = m;
-  }
-  // pass 1: the chain.  Scratch entry i of the proof: x | y | z of acc_i | prefix product z_0 .. z_{i-1}; lane jc stores word block jc
-  // (lane 2 carries T, which is not kept: it stores the prefix product instead)
-  uint32_t *sp = scratch + (size_t)p * 257 * 32;
-  fp acc = jc == 0 ? seedx : jc == 1 ? seedy : jc == 2 ? fp_mul<F>(seedx, seedy) : fp_one<F>();
-  fp run = fp_one<F>();                                                        // (meaningful on lane 3, mirrored to lane 2 for the store)
-  uint32_t next_row = ki, bit = 0;
-#pragma unroll 1
-  for (uint32_t j = 0; j <= m; j++) {
-    const fp z = qperm<3, 3, 3, 3>(acc);
-    if (live) fp_store(sp + (size_t)j * 32 + 8 * (jc == 2 ? 3 : jc == 3 ? 2 : jc), jc == 2 ? run : acc);   // x, y, [z at block 2 from lane 3], run at block 3 from lane 2
-    run = fp_mul<F>(run, z);
-    if (j < m) {
-      const te_pre q = points[next_row];
-      acc = q_madd<S>(acc, q.x, q.y, q.k, jc);
-      while (bit < L && !((blind[32 * (size_t)p + (bit >> 3)] >> (bit & 7)) & 1)) bit++;     // the next set bit of the blinding
-      next_row = keyset + bit; bit++;
-    }
-  }
-  fp inv = fp_inv_nf<F>(run);                                                   // (binary GCD, fp256.h: the fixed power was ~30 % of this kernel)
-  // pass 2 (backwards): affine coordinates (Montgomery form) and, one row behind, the sparse scalars of the two accumulator columns
-  uint32_t *v = vals + (size_t)p * 257 * 16;
-  uint32_t *b = bi + (size_t)p * 4 * MP; uint32_t *qv = sc + (size_t)p * 4 * MP * 8;
-  fp prev = fp_zero(), res = fp_zero();                                        // lane 0 / 1: x / y of row i + 1; of the last row (the result)
-#pragma unroll 1
-  for (uint32_t i = m + 1; i-- > 0;) {
-    const uint32_t *e = sp + (size_t)i * 32;
-    // round 1: lane 3: zi = inv * pre_i; lane 2: inv * z_i (the next inv); lanes 0, 1: from_mont of the previous row's difference
-    const fp z = fp_load(e + 16), pre = fp_load(e + 24), xy = fp_load(e + 8 * (jc & 1));
-    fp one_plain = fp_zero(); one_plain.v[0] = 1;
-    const fp a1 = jc >= 2 ? inv : fp_zero(), b1 = jc == 3 ? pre : z;
-    const fp r1 = fp_mul<F>(a1, b1);
-    const fp zi = qperm<3, 3, 3, 3>(r1);
-    inv = qperm<2, 2, 2, 2>(r1);
-    // round 2: lanes 0, 1: x_i zi, y_i zi
-    const fp aff = fp_mul<F>(xy, zi);
-    if (live && jc < 2) fp_store(v + (size_t)i * 16 + 8 * jc, aff);
-    if (i < m) {                                                               // scalar of row i: from_mont(v_i - v_{i+1}), base N + pos_i + 1
-      const fp d = fp_from_mont<F>(fp_sub<F>(aff, prev));
-      if (live && jc < 2) fp_store(qv + (size_t)((2 + jc) * MP + i) * 8, d);
-    }
-    if (i == m) res = aff;
-    prev = aff;
-  }
-  // the rest is cheap and done by lane 0 of the quad (result coordinates from the registers of lanes 0 and 1, not through memory)
-  const fp resx = qperm<0, 0, 0, 0>(res), resy = qperm<1, 1, 1, 1>(res);
-  if (!live || jc != 0) return;
-  // instance = result - seed  (-(x, y) = (-x, y))
-  te_ext r; r.x = resx; r.y = resy; r.t = fp_mul<F>(resx, resy); r.z = fp_one<F>();
-  const te_aff inst = te_to_aff<S>(te_madd<S>(r, te_make_pre<S>(fp_neg<F>(seedx), seedy)));
-  uint32_t *o = out + (size_t)p * 32;
-  fp_store(o, resx); fp_store(o + 8, resy); fp_store(o + 16, inst.x); fp_store(o + 24, inst.y);
-  // sparse vectors: bits | ip | ax | ay   (the host zeroed both arrays: unused entries are scalar 0 at base 0)
-  fp one_plain = fp_zero(); one_plain.v[0] = 1;
-  const fp minus1 = fp_from_mont<F>(fp_neg<F>(fp_one<F>()));
-  for (uint32_t j = 0; j < m; j++) { b[j] = ppos[j]; fp_store(qv + (size_t)j * 8, one_plain); }
-  b[MP] = N + cap; fp_store(qv + (size_t)MP * 8, one_plain);
-  b[MP + 1] = N + ki + 1; fp_store(qv + (size_t)(MP + 1) * 8, minus1);
-  for (uint32_t j = 0; j < m; j++) b[2 * MP + j] = b[3 * MP + j] = N + ppos[j] + 1;
-  b[2 * MP + m] = b[3 * MP + m] = N + cap;
-  fp_store(qv + (size_t)(2 * MP + m) * 8, fp_from_mont<F>(resx)); fp_store(qv + (size_t)(3 * MP + m) * 8, fp_from_mont<F>(resy));
-  if (zk) for (uint32_t col = 0; col < 4; col++) for (uint32_t j = 0; j < 3; j++) {     // + zk_j * L_{cap+j}(tau) G
-    b[col * MP + m + 1 + j] = cap + j;
-    fp_store(qv + (size_t)(col * MP + m + 1 + j) * 8, fp_from_mont<F>(fp_load(zk + (((size_t)p * 4 + col) * 3 + j) * 8)));
-  }
-}
-template <class S>
-__global__ void k_ring_points_pre(const uint32_t *__restrict__ xy_mont, uint32_t n, te_pre *__restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = te_make_pre<S>(fp_load(xy_mont + (size_t)i * 16), fp_load(xy_mont + (size_t)i * 16 + 8));
-}
-template <class F>
-__global__ void k_set_diag(uint32_t *__restrict__ mat, uint32_t n, uint32_t rows, uint32_t col0) {   // row i of the tile = unit vector e_(col0 + i)
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < rows) fp_store(mat + ((size_t)i * n + col0 + i) * 8, fp_one<F>());
-}
-
-// ------------------------------------------------------------------------------------------------
-// SHAKE128 + ark-transcript
-
-struct ArkTranscript {
-  HostShake128 h; bool has_len = false; uint32_t len = 0;
-  void write(const void *d, size_t n) { h.update(d, n); len = (has_len ? len : 0) + (uint32_t)n; has_len = true; }
-  void separate() { if (has_len) { uint8_t b[4] = {(uint8_t)(len >> 24), (uint8_t)(len >> 16), (uint8_t)(len >> 8), (uint8_t)len}; h.update(b, 4); has_len = false; } }
-  void label(const char *l) { separate(); write(l, strlen(l)); separate(); }
-  void label(const uint8_t *l, size_t n) { separate(); write(l, n); separate(); }
-  void append(const std::vector<uint8_t> &d) { separate(); write(d.data(), d.size()); separate(); }
-  void challenge48(const char *l, uint8_t out[48]) { label(l); write("challenge", 9); h.squeeze_copy(out, 48); separate(); }
 };
-
-// ------------------------------------------------------------------------------------------------
-// suite-generic host helpers
-
-template <class S, class G> struct RingTypes {
-  using Fr = HostField<typename S::Fq>;              // Fr(pairing curve) = Fq(TE curve)
-  using Te = HostTe<S>;
-  using HG = HostG1<G>;
-  using FqN = HostField<typename G::Fq>;
-  static constexpr int FQB = G::Fq::N * 4;            // bytes of a G1 coordinate
-};
-
-// host-side data parallelism over the proofs of a chunk: parallel_for of host_pool.h (one bounded persistent pool per process)
-
-// int_BE(48 bytes) mod r, Montgomery form
-// (hi 2^256 + lo) R = (hi R) R^2 / R + lo R: three Montgomery products -- sixteen challenges per proof on the prover AND the verifier;
-// the byte-by-byte Horner form this replaces cost 96 products, 3.8 us, i.e. 60 us of a core per proof of the ~80 a proof took)
-template <class F> static H256 fr_from_be48(const uint8_t b[48]) {
-  using Fr = HostField<F>;
-  H256 hi = {{0, 0, 0, 0}}, lo;
-  for (int i = 0; i < 2; i++) { uint64_t v; memcpy(&v, b + 8 * i, 8); hi.l[1 - i] = __builtin_bswap64(v); }
-  for (int i = 0; i < 4; i++) { uint64_t v; memcpy(&v, b + 16 + 8 * i, 8); lo.l[3 - i] = __builtin_bswap64(v); }
-  static const H256 r2 = Fr::r2();
-  return Fr::add(Fr::mul(Fr::mul(hi, r2), r2), Fr::mul(lo, r2));    // (mul reduces any 256-bit left operand: its result is below 2 p before the final subtraction)
-}
-template <class F> static H256 fr_pow(H256 a, uint64_t e) {
-  using Fr = HostField<F>; H256 r = Fr::one();
-  while (e) { if (e & 1) r = Fr::mul(r, a); a = Fr::sqr(a); e >>= 1; }
-  return r;
-}
-template <class F> static H256 fr_small(uint64_t v) { return HostField<F>::to_mont(H256{{v, 0, 0, 0}}); }
-
-struct G1Aff { uint8_t xy[96]; bool inf; };           // canonical LE x || y (FQB bytes each)
-// a result of the MSM engine or of HostG1::to_affine_bytes (x || y, fqb bytes each): the point at infinity iff all zero
-static G1Aff g1_from_xy(const uint8_t *xy, int fqb) {
-  G1Aff r; memset(&r, 0, sizeof r); memcpy(r.xy, xy, 2 * fqb);
-  r.inf = true; for (int i = 0; i < 2 * fqb; i++) if (r.xy[i]) r.inf = false;
-  return r;
-}
-// PIOP domain size of a ring (src/ring.rs:810-821): the keys, 4 more rows and the bits of the blinding, up to a power of two
-static size_t ring_domain_size(size_t ring_size, size_t scalar_bits) {
-  size_t need = ring_size + 4 + scalar_bits, N = 1; while (N < need) N <<= 1;
-  return N;
-}
-
-// ark-serialize G1 encodings: BLS12-381 zcash big-endian; BN254 arkworks little-endian
-template <class G> static void g1_encode(const G1Aff &p, bool compressed, std::vector<uint8_t> &out) {
-  constexpr int B = G::Fq::N * 4;
-  using FqN = HostField<typename G::Fq>;
-  typename FqN::El y, half = FqN::from32(G::Fq::HALF), t;
-  memcpy(y.l, p.xy + B, B);
-  bool big = !p.inf && FqN::subb(t, half, y) != 0;    // y > (p-1)/2
-  size_t o = out.size();
-  if (B == 48) {                                      // zcash
-    out.resize(o + (compressed ? B : 2 * B), 0);
-    if (p.inf) { out[o] = compressed ? 0xC0 : 0x40; return; }
-    for (int i = 0; i < B; i++) out[o + i] = p.xy[B - 1 - i];
-    if (compressed) { out[o] |= 0x80; if (big) out[o] |= 0x20; }
-    else for (int i = 0; i < B; i++) out[o + B + i] = p.xy[2 * B - 1 - i];
-  } else {
-    out.resize(o + (compressed ? B : 2 * B), 0);
-    if (p.inf) { out[out.size() - 1] |= 0x40; return; }
-    memcpy(&out[o], p.xy, compressed ? B : 2 * B);
-    if (big) out[out.size() - 1] |= 0x80;
-  }
-}
 
 }  // namespace avrf
 
@@ -565,6 +91,19 @@ struct RingLane {
   DevMem scr[6];
   MsmWorkspace ws;
   uint32_t *scratch(int which, size_t bytes) { scr[which].ensure(bytes); return scr[which].as(); }
+  // A scratch slot cut into typed fields: carve().take(p, count) ... .into(which).  Every field's size and its pointer come from the
+  // ONE request that names it; each field starts on a 256-byte boundary, in the order taken; into() is the slot's one scratch() call.
+  struct Carve {
+    static constexpr int MAX_FIELDS = 12;
+    RingLane &ln; size_t total = 0; int nf = 0; struct { void *ptr; size_t off; void (*set)(void *, uint8_t *); } f[MAX_FIELDS];
+    template <class T> Carve &take(T *&p, size_t count) {
+      if (nf == MAX_FIELDS) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};
+      f[nf++] = {&p, total, [](void *ptr, uint8_t *at) { *(T **)ptr = (T *)at; }}; total += (count * sizeof(T) + 255) / 256 * 256;
+      return *this;
+    }
+    void into(int which) { uint8_t *base = (uint8_t *)ln.scratch(which, total); for (int i = 0; i < nf; i++) f[i].set(f[i].ptr, base + f[i].off); }
+  };
+  Carve carve() { return Carve{*this}; }
   RingLane() = default;
   RingLane(const RingLane &) = delete;
   RingLane &operator=(const RingLane &) = delete;
@@ -633,6 +172,8 @@ template <class S, class G> struct Ring {
   using T = RingTypes<S, G>;
   using Fr = typename T::Fr; using Te = typename T::Te;
   using F = typename S::Fq;
+  using HR = HostRing<S, G>;                          // the host arithmetic (host_ring.h)
+  using PL = RingProofLayout<G>;
   static constexpr int FQB = T::FQB;
 
   static DevMem make_twiddles(H256 w, size_t n) {
@@ -641,13 +182,6 @@ template <class S, class G> struct Ring {
     for (size_t i = 0; i < n / 2; i++) { tw[i] = x; x = Fr::mul(x, w); }
     DevMem d((n / 2) * 32); HIP_CHECK(hipMemcpy(d.p, tw.data(), (n / 2) * 32, hipMemcpyHostToDevice));
     return d;
-  }
-  // host coordinates of an affine point (HostG1's XYZZ form)
-  static typename T::HG::Pt g1_lift(const G1Aff &p) {
-    using HG = typename T::HG; using FqN = typename T::FqN;
-    typename HG::Pt q = HG::identity();
-    if (!p.inf) { typename FqN::El x, y; memcpy(x.l, p.xy, FQB); memcpy(y.l, p.xy + FQB, FQB); q.x = FqN::to_mont(x); q.y = FqN::to_mont(y); q.zz = FqN::one(); q.zzz = FqN::one(); }
-    return q;
   }
   static void g1_from_xy_batch(const std::vector<uint8_t> &xy, size_t batch, G1Aff *out) {
     for (size_t b = 0; b < batch; b++) out[b] = g1_from_xy(&xy[b * 2 * FQB], FQB);
@@ -672,18 +206,13 @@ template <class S, class G> struct Ring {
     msm_g1_device(su->curve, su->d_srs.as(), ln.buf.as(), n, ln.ws, ln.stream, xy.data(), batch);
     g1_from_xy_batch(xy, batch, out);
   }
-  static H256 challenge(ArkTranscript &t, const char *l) { uint8_t b[48]; t.challenge48(l, b); return fr_from_be48<F>(b); }
-  static void push_le32(std::vector<uint8_t> &o, const H256 &mont) { H256 p = Fr::from_mont(mont); size_t k = o.size(); o.resize(k + 32); memcpy(&o[k], p.l, 32); }
 
   // a handle with what both loaders fill alike: identity, lane 0 on the context's stream, sizes and the domain constants
   static std::unique_ptr<avrf_ring_setup> new_setup(avrf_ctx *ctx, size_t N, size_t n_srs) {
     auto su = std::make_unique<avrf_ring_setup>();
     su->ctx = ctx; su->suite = S::ID; su->curve = pairing_curve_of(S::ID); su->lane[0].stream = avrf_ctx_stream_(ctx); su->device = avrf_ctx_device_(ctx);
     su->N = N; su->cap = N - 3; su->L = S::Fr::BITS; su->keyset = su->cap - su->L - 1; su->n_srs = n_srs;
-    H256 root = Fr::from32(G::ROOT_OF_UNITY);
-    int lg = 0; while (((size_t)1 << lg) < N) lg++;
-    H256 w4 = root; for (int i = 0; i < G::TWO_ADICITY - (lg + 2); i++) w4 = Fr::sqr(w4);
-    su->w4 = w4; su->w = Fr::sqr(Fr::sqr(w4));
+    su->w4 = HR::domain_root(4 * N); su->w = Fr::sqr(Fr::sqr(su->w4));
     su->ninv = Fr::inv_fermat(fr_small<F>(N)); su->n4inv = Fr::inv_fermat(fr_small<F>(4 * N));
     return su;
   }
@@ -704,7 +233,7 @@ template <class S, class G> struct Ring {
         using HP = HostPairing<G>;
         std::vector<G1Aff> pts(pcs);
         std::atomic<int> bad{0};
-        parallel_for(pcs, [&](size_t i) { if (!g1_decompress(srs + 8 + i * FQB, &pts[i])) bad = 1; });
+        parallel_for(pcs, [&](size_t i) { if (!g1_decompress<G>(srs + 8 + i * FQB, &pts[i])) bad = 1; });
         if (bad) return AVRF_INVALID_DATA;
         unc.resize(8);
         { uint64_t v = pcs; memcpy(unc.data(), &v, 8); }
@@ -725,11 +254,7 @@ template <class S, class G> struct Ring {
     std::unique_ptr<avrf_ring_setup> owner = new_setup(ctx, N, pcs);
     avrf_ring_setup *su = owner.get(); RingLane &ln = su->lane[0];
     std::vector<uint8_t> le(pcs * e1);
-    for (size_t i = 0; i < pcs; i++) {
-      const uint8_t *p = srs + 8 + i * e1; uint8_t *q = &le[i * e1];
-      if (FQB == 48) { bool inf = p[0] & 0x40; for (int k = 0; k < FQB; k++) { q[k] = inf ? 0 : p[FQB - 1 - k]; q[FQB + k] = inf ? 0 : p[2 * FQB - 1 - k]; } }
-      else { bool inf = p[2 * FQB - 1] & 0x40; memcpy(q, p, e1); q[e1 - 1] &= 0x3f; if (inf) memset(q, 0, e1); }
-    }
+    for (size_t i = 0; i < pcs; i++) { const G1Aff a = g1_from_raw<G>(srs + 8 + i * e1); memcpy(&le[i * e1], a.xy, e1); }   // (infinity: all zero)
     memcpy(su->g1_0.xy, le.data(), e1); su->g1_0.inf = false;
     su->g2_raw.assign(srs + 8 + cnt * e1 + 8, srs + 8 + cnt * e1 + 8 + 2 * e2);
     su->g1_raw.assign(srs + 8, srs + 8 + pcs * e1);
@@ -792,12 +317,12 @@ template <class S, class G> struct Ring {
     const size_t e1 = 2 * FQB, e2 = 4 * FQB;
     G1Aff g1; std::vector<uint8_t> g2(2 * e2);
     if (len == e1 + 2 * e2) {
-      g1 = g1_from_raw(vp);
+      g1 = g1_from_raw<G>(vp);
       memcpy(g2.data(), vp + e1, 2 * e2);
       typename HP::G2 q;
       for (int i = 0; i < 2; i++) if (!HP::g2_decode(g2.data() + (size_t)i * e2, &q) || q.inf || !HP::g2_on_twist(q)) return AVRF_INVALID_DATA;
     } else if (len == FQB + 2 * 2 * FQB) {
-      if (!g1_decompress(vp, &g1)) return AVRF_INVALID_DATA;
+      if (!g1_decompress<G>(vp, &g1)) return AVRF_INVALID_DATA;
       for (int i = 0; i < 2; i++) {
         typename HP::G2 q;
         if (!HP::g2_decode_compressed(vp + FQB + (size_t)i * 2 * FQB, &q)) return AVRF_INVALID_DATA;
@@ -808,7 +333,7 @@ template <class S, class G> struct Ring {
     // coordinates, so the curve equation is checked here; BN254 G1 has cofactor 1).  The two G2 points are decoded and checked to
     // lie on the twist; like the reference's RingSetup deserialisation they get no G2 subgroup test -- PcsVerifierParams are
     // trusted-setup material published with the ring parameters, not per-proof input (src/ring.rs:466-474).
-    if (g1.inf || !g1_on_curve_host(g1) || !g1_in_subgroup_host(g1)) return AVRF_INVALID_DATA;
+    if (g1.inf || !g1_on_curve_host<G>(g1) || !g1_in_subgroup_host<G>(g1)) return AVRF_INVALID_DATA;
     std::unique_ptr<avrf_ring_setup> su = new_setup(ctx, ring_domain_size(ring_size, S::Fr::BITS), 0);
     su->g1_0 = g1; su->g2_raw = g2;
     *out = su.release();
@@ -1000,21 +525,11 @@ template <class S, class G> struct Ring {
     return AVRF_OK;
   }
 
-  static void transcript_prelude(avrf_ring_key *k, ArkTranscript &t) {
-    avrf_ring_setup *su = k->setup;
-    t.label(S::SUITE_ID, S::SUITE_ID_LEN);
-    t.label("vk");
-    std::vector<uint8_t> vk; g1_encode<G>(su->g1_0, false, vk);
-    vk.insert(vk.end(), su->g2_raw.begin(), su->g2_raw.end());
-    for (int i = 0; i < 3; i++) g1_encode<G>(k->C[i], false, vk);
-    t.append(vk);
-  }
-
   // ---- VerifierKeyBuilder (src/ring.rs:539-637): start from the all-padding ring, then every appended key replaces a
   // padding point: C_x += (x - x_pad) L_i(tau) G, C_y likewise -- two sparse MSMs over the Lagrange-basis table per append
   static G1Aff g1_add_aff(const G1Aff &a, const G1Aff &b) {
     using HG = typename T::HG;
-    uint8_t xy[2 * FQB]; HG::to_affine_bytes(HG::add(g1_lift(a), g1_lift(b)), xy);
+    uint8_t xy[2 * FQB]; HG::to_affine_bytes(HG::add(g1_lift<G>(a), g1_lift<G>(b)), xy);
     return g1_from_xy(xy, FQB);
   }
   static int builder_new(avrf_ring_setup *su, avrf_ring_vk_builder **out) {
@@ -1038,8 +553,8 @@ template <class S, class G> struct Ring {
       sc[i] = Fr::from_mont(Fr::sub(Fr::to_mont(x), padx)); sc[n + i] = Fr::from_mont(Fr::sub(Fr::to_mont(y), pady));
       bi[i] = bi[n + i] = (uint32_t)(b->curr + i);
     }
-    uint32_t *d = ln.scratch(1, 2 * n * 36);
-    uint32_t *d_sc = d, *d_bi = d + 2 * n * 8;
+    uint32_t *d_sc, *d_bi;
+    ln.carve().take(d_sc, 2 * n * 8).take(d_bi, 2 * n).into(1);
     HIP_CHECK(hipMemcpyAsync(d_sc, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, ln.stream));
     HIP_CHECK(hipMemcpyAsync(d_bi, bi.data(), 2 * n * 4, hipMemcpyHostToDevice, ln.stream));
     std::vector<G1Aff> D; commit_sparse(su, ln, d_sc, d_bi, n, 2, D);
@@ -1065,14 +580,13 @@ template <class S, class G> struct Ring {
     constexpr int mont_id = std::is_same<F, FqBandersnatch>::value ? 1 : 2;
     static_assert(std::is_same<F, FqBandersnatch>::value || std::is_same<F, FqBabyJubJub>::value, "scalar field of the KZG commitments");
     std::vector<uint8_t> xy(batch * 2 * FQB);
-    static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
-    struct timespec t0; if (trace) { HIP_CHECK(hipStreamSynchronize(ln.stream)); clock_gettime(CLOCK_MONOTONIC, &t0); }
+    RingTrace trace("commit", batch, false);
+    if (trace.on()) { HIP_CHECK(hipStreamSynchronize(ln.stream)); trace.restart(); }
     // many vectors at once and the table of all multiples is there: one gathered point per (coefficient, row), no buckets (msm.hip)
     if (su->direct && batch >= 32) { msm_g1_direct_device(su->direct->t, d_coeffs_mont, n, stride, ln.ws, ln.stream, xy.data(), batch, mont_id); ++su->table_batches; }
     else msm_g1_fixed_device(su->curve, su->d_srs_table.as(), su->table_c, su->n_srs, d_coeffs_mont, n, stride, ln.ws, ln.stream, xy.data(), batch, nullptr, mont_id);
-    if (trace) { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-      fprintf(stderr, "    commit n=%zu batch=%zu: %.3f ms wall, accumulate %.3f ms (c=%d seg=%d)\n", n, batch,
-              (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6, ln.ws.accum_ms_last, ln.ws.last_plan.c, ln.ws.last_plan.lpb); }
+    if (trace.on()) fprintf(stderr, "    commit n=%zu batch=%zu: %.3f ms wall, accumulate %.3f ms (c=%d seg=%d)\n", n, batch,
+                            trace.wall_ms(), ln.ws.accum_ms_last, ln.ws.last_plan.c, ln.ws.last_plan.lpb);
     out.resize(batch); g1_from_xy_batch(xy, batch, out.data());
   }
   // Lagrange-basis SRS for the witness columns, built on first use: L_i(tau) G = commit(iNTT(e_i)) (N commits in one
@@ -1098,7 +612,7 @@ template <class S, class G> struct Ring {
     using HG = typename T::HG;
     std::vector<typename HG::Pt> ps(N + 1);
     ps[0] = HG::identity();
-    for (size_t i = 0; i < N; i++) ps[i + 1] = HG::add(ps[i], g1_lift(lag[i]));
+    for (size_t i = 0; i < N; i++) ps[i + 1] = HG::add(ps[i], g1_lift<G>(lag[i]));
     std::vector<uint8_t> le(nb * 2 * FQB);
     for (size_t i = 0; i < N; i++) memcpy(&le[i * 2 * FQB], lag[i].xy, 2 * FQB);
     HG::to_affine_bytes_batch(ps.data(), N + 1, &le[N * 2 * FQB]);
@@ -1124,13 +638,9 @@ template <class S, class G> struct Ring {
   // (the witness table is there: avrf_ring_prove builds it before the first chunk -- two chunks run this at once)
   static int prove_chunk(avrf_ring_key *k, RingLane &ln, size_t n, const uint32_t *key_index, const uint8_t *blindings, bool hiding, uint8_t *out) {
     avrf_ring_setup *su = k->setup;
-    const size_t N = su->N, cap = su->cap, M = 4 * N, plen = 4 * FQB + 7 * 32 + FQB + 32 + 2 * FQB;
+    const size_t N = su->N, cap = su->cap, M = 4 * N;
     const H256 one = Fr::one();
-    static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
-    auto now = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    auto cpu_now = [] { struct timespec ts; clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    double t_prev = now(), c_prev = cpu_now();                         // (trace: wall time and the PROCESS's CPU time of every phase, workers included)
-    auto lap = [&](const char *what) { if (trace) { double t = now(), c = cpu_now(); fprintf(stderr, "  ring_prove[%zu] %-32s %8.3f ms wall %8.3f ms cpu\n", n, what, t - t_prev, c - c_prev); t_prev = t; c_prev = c; } };
+    RingTrace lap("ring_prove", n, true);                              // (wall time and the PROCESS's CPU time of every phase, workers included)
     std::vector<ProofState> st(n);
     const H256 w_last = fr_pow<F>(su->w, cap - 1);
     // ---- round 0: the witness in sparse form (A.7 step 1).  Rows with bit 1: the signer's key and the set bits
@@ -1151,10 +661,10 @@ template <class S, class G> struct Ring {
     uint32_t *d_coef = ln.scratch(2, n * 4 * N * 32), *d_e4 = ln.scratch(0, std::max(n * 4 * M * 32, n * 257 * 128));
     std::vector<H256> wout(n * 4);
     {
-      const size_t b_pos = n * 256 * 4, b_cnt = n * 4, b_val = n * 257 * 64, b_sc = n * 4 * MP * 32, b_bi = n * 4 * MP * 4, b_zk = n * 12 * 32, b_bl = n * 32, b_out = n * 128;
-      uint32_t *d_w = ln.scratch(1, b_sc + b_val + b_zk + b_pos + b_bi + 2 * b_cnt + b_bl + b_out);
-      uint32_t *d_sc = d_w, *d_val = d_sc + b_sc / 4, *d_zk = d_val + b_val / 4, *d_pos = d_zk + b_zk / 4, *d_bi = d_pos + b_pos / 4, *d_cnt = d_bi + b_bi / 4,
-               *d_ki = d_cnt + n, *d_bl = d_ki + n, *d_out = d_bl + b_bl / 4;
+      const size_t b_cnt = n * 4, b_sc = n * 4 * MP * 32, b_bi = n * 4 * MP * 4, b_zk = n * 12 * 32, b_bl = n * 32, b_out = n * 128;
+      uint32_t *d_sc, *d_val, *d_zk, *d_pos, *d_bi, *d_cnt, *d_ki, *d_bl, *d_out;
+      ln.carve().take(d_sc, b_sc / 4).take(d_val, n * 257 * 16).take(d_zk, b_zk / 4).take(d_pos, n * 256).take(d_bi, b_bi / 4).take(d_cnt, n).take(d_ki, n)
+          .take(d_bl, b_bl / 4).take(d_out, b_out / 4).into(1);
       if (hiding) HIP_CHECK(hipMemcpyAsync(d_zk, zk.data(), b_zk, hipMemcpyHostToDevice, ln.stream));
       HIP_CHECK(hipMemcpyAsync(d_ki, key_index, b_cnt, hipMemcpyHostToDevice, ln.stream));
       HIP_CHECK(hipMemcpyAsync(d_bl, blindings, b_bl, hipMemcpyHostToDevice, ln.stream));
@@ -1177,21 +687,19 @@ template <class S, class G> struct Ring {
       }
     }
     lap("intt + ntt4n + 4n commits");
-    ArkTranscript t0; transcript_prelude(k, t0);                       // shared by every proof over this ring
+    const ArkTranscript t0 = HR::prelude(su->g1_0, su->g2_raw, k->C);   // shared by every proof over this ring
     parallel_for(n, [&](size_t p) {
       ProofState &ps = st[p];
       ps.t = t0;
-      { std::vector<uint8_t> b; push_le32(b, ps.instx); push_le32(b, ps.insty); ps.t.label("instance"); ps.t.append(b); }
-      { std::vector<uint8_t> b; for (int i = 0; i < 4; i++) g1_encode<G>(ps.C[i], false, b); ps.t.label("committed_cols"); ps.t.append(b); }
-      for (int i = 0; i < 7; i++) ps.al[i] = challenge(ps.t, "constraints_aggregation");
+      uint8_t inst[64]; fr_store_le32<F>(inst, ps.instx); fr_store_le32<F>(inst + 32, ps.insty);
+      HR::alphas(ps.t, inst, ps.C, ps.al);
     }, 64);                                                            // (3 us per proof on one thread: a worker is worth waking for ~200 us)
     lap("transcript: alphas");
     // per-chunk parameter block on the device: RingConsts[n] | zeta[n] | nu[8n] | ev[7n] | lin_zw[n]
     const size_t qlen = 3 * N + 1, olen = 3 * N;
-    const size_t rc_bytes = (n * sizeof(RingConsts) + 31) / 32 * 32;
-    uint32_t *d_par = ln.scratch(3, rc_bytes + n * (1 + 8 + 7 + 1) * 32);
-    RingConsts *d_rc = (RingConsts *)d_par;
-    uint32_t *d_zeta = d_par + rc_bytes / 4, *d_nu = d_zeta + n * 8, *d_ev = d_nu + n * 64, *d_linzw = d_ev + n * 56;
+    RingConsts *d_rc; uint32_t *d_zeta, *d_nu, *d_ev;
+    ln.carve().take(d_rc, n).take(d_zeta, n * 8).take(d_nu, n * 64).take(d_ev, n * 64).into(3);   // (ev and lin_zw one field: they come back in one copy)
+    uint32_t *d_linzw = d_ev + n * 56;
     // ---- round 2 (device): constraint aggregation on the 4N domain, iNTT(4N), * Z_zk / (X^N - 1), n quotient commits
     uint32_t *d_agg = ln.scratch(1, n * M * 32), *d_q = ln.scratch(4, n * qlen * 32);
     {
@@ -1222,8 +730,7 @@ template <class S, class G> struct Ring {
     {
       parallel_for(n, [&](size_t p) {
         ProofState &ps = st[p];
-        std::vector<uint8_t> b; g1_encode<G>(ps.Cq, false, b); ps.t.label("quotient"); ps.t.append(b);
-        ps.zeta = challenge(ps.t, "evaluation_point"); zs[p] = ps.zeta;
+        ps.zeta = HR::zeta(ps.t, ps.Cq); zs[p] = ps.zeta;
       }, 256);
       HIP_CHECK(hipMemcpyAsync(d_zeta, zs.data(), n * 32, hipMemcpyHostToDevice, ln.stream));
     }
@@ -1242,9 +749,10 @@ template <class S, class G> struct Ring {
         ProofState &ps = st[p];
         for (int i = 0; i < 7; i++) ps.ev[i] = evh[p * 7 + i];
         ps.lin_zw = evh[n * 7 + p];
-        { std::vector<uint8_t> b; for (int i = 0; i < 7; i++) push_le32(b, ps.ev[i]); ps.t.label("register_evaluations"); ps.t.append(b); }
-        { std::vector<uint8_t> bb; push_le32(bb, ps.lin_zw); ps.t.label("shifted_linearization_evaluation"); ps.t.append(bb); }
-        for (int i = 0; i < 8; i++) { ps.nu[i] = challenge(ps.t, "kzg_aggregation"); nus[p * 8 + i] = ps.nu[i]; }
+        uint8_t evb[8 * 32]; for (int i = 0; i < 7; i++) fr_store_le32<F>(evb + 32 * i, ps.ev[i]);
+        fr_store_le32<F>(evb + 7 * 32, ps.lin_zw);
+        HR::nus(ps.t, evb, evb + 7 * 32, ps.nu);
+        for (int i = 0; i < 8; i++) nus[p * 8 + i] = ps.nu[i];
       }, 64);
       HIP_CHECK(hipMemcpyAsync(d_nu, nus.data(), n * 8 * 32, hipMemcpyHostToDevice, ln.stream));
       HIP_CHECK(hipStreamSynchronize(ln.stream));                     // nus goes out of scope
@@ -1281,73 +789,14 @@ template <class S, class G> struct Ring {
     lap("2n opening commits");
     for (size_t p = 0; p < n; p++) {
       const ProofState &ps = st[p];
-      std::vector<uint8_t> pr;
-      for (int i = 0; i < 4; i++) g1_encode<G>(ps.C[i], true, pr);
-      for (int i = 0; i < 7; i++) push_le32(pr, ps.ev[i]);
-      g1_encode<G>(ps.Cq, true, pr); push_le32(pr, ps.lin_zw); g1_encode<G>(ps.pi[0], true, pr); g1_encode<G>(ps.pi[1], true, pr);
-      if (pr.size() != plen) return AVRF_ERR_BAD_ARG;
-      memcpy(out + plen * p, pr.data(), plen);
+      const G1Aff *const pts[7] = {&ps.C[0], &ps.C[1], &ps.C[2], &ps.C[3], &ps.Cq, &ps.pi[0], &ps.pi[1]};
+      HR::proof_serialize(pts, ps.ev, ps.lin_zw, out + PL::LEN * p);
     }
     lap("proof bytes");
     return AVRF_OK;
   }
 
-  // ---- G1 decompression (ark-serialize compressed forms); p = 3 mod 4 for both curves
   using FqN = typename T::FqN; using QEl = typename FqN::El;
-  static bool g1_decompress(const uint8_t *b, G1Aff *out) {
-    memset(out, 0, sizeof *out);
-    uint8_t le[48]; bool big, inf;
-    if (FQB == 48) { inf = b[0] & 0x40; big = b[0] & 0x20; if (!(b[0] & 0x80)) return false; for (int i = 0; i < FQB; i++) le[i] = b[FQB - 1 - i]; le[FQB - 1] &= 0x1f; }
-    else { inf = b[FQB - 1] & 0x40; big = b[FQB - 1] & 0x80; memcpy(le, b, FQB); le[FQB - 1] &= 0x3f; }
-    if (inf) {                                                          // canonical encoding only: no sort flag, every other bit zero
-      if (big) return false;
-      for (int i = 0; i < FQB; i++) if (le[i]) return false;
-      out->inf = true; return true;
-    }
-    QEl x; memcpy(x.l, le, FQB);
-    QEl t; if (FqN::subb(t, x, FqN::P()) == 0) return false;           // x >= p
-    QEl xm = FqN::to_mont(x);
-    QEl rhs = FqN::add(FqN::mul(FqN::sqr(xm), xm), FqN::from32(G::B));
-    static const QEl e = [] { QEl v = FqN::P(), one = FqN::zero(); one.l[0] = 1; FqN::addc(v, v, one);   // (p + 1) / 4
-                              for (int k = 0; k < 2; k++) for (int i = 0; i < FqN::L; i++) v.l[i] = (v.l[i] >> 1) | (i + 1 < FqN::L ? v.l[i + 1] << 63 : 0);
-                              return v; }();
-    QEl y = FqN::one();
-    for (int i = 64 * FqN::L - 1; i >= 0; i--) { y = FqN::sqr(y); if ((e.l[i / 64] >> (i % 64)) & 1) y = FqN::mul(y, rhs); }
-    if (!FqN::eq(FqN::sqr(y), rhs)) return false;                       // not on the curve
-    QEl yp = FqN::from_mont(y), half = FqN::from32(G::Fq::HALF);
-    bool is_big = FqN::subb(t, half, yp) != 0;
-    if (is_big != big) { y = FqN::neg(y); yp = FqN::from_mont(y); }
-    memcpy(out->xy, x.l, FQB); memcpy(out->xy + FQB, yp.l, FQB);
-    return true;
-  }
-  // The same subgroup test as k_g1_subgroup_bls (phi(P) = [-z^2] P) on the host, for small batches: one lane of the device
-  // needs 2.8 ms for the two 64-bit ladders however few points there are; a host core does them in ~0.1 ms per point.
-  static bool g1_in_subgroup_host(const G1Aff &a) {
-    if (FQB != 48 || a.inf) return true;                              // BN254 G1 has cofactor 1
-    using HG = typename T::HG;
-    static const uint32_t BETA[12] = {0x798a64e8, 0x30f1361b, 0x7ece5a2a, 0xf3b8ddab, 0xc61577f7, 0x16a8ca3a,
-                                      0x74fd029b, 0xc26a2ff8, 0x60701c6e, 0x3636b766, 0x241b6160, 0x051ba4ab};
-    QEl beta; memcpy(beta.l, BETA, sizeof BETA > sizeof beta.l ? sizeof beta.l : sizeof BETA);
-    QEl x, y; memset(&x, 0, sizeof x); memset(&y, 0, sizeof y); memcpy(x.l, a.xy, FQB); memcpy(y.l, a.xy + FQB, FQB);
-    typename HG::Pt p; p.x = FqN::to_mont(x); p.y = FqN::to_mont(y); p.zz = FqN::one(); p.zzz = FqN::one();
-    const uint64_t z = 0xd201000000010000ull;
-    typename HG::Pt q = p;
-    for (int b = 62; b >= 0; b--) { q = HG::dbl(q); if ((z >> b) & 1) q = HG::add(q, p); }
-    const typename HG::Pt q1 = q;
-    for (int b = 62; b >= 0; b--) { q = HG::dbl(q); if ((z >> b) & 1) q = HG::add(q, q1); }
-    if (HG::is_identity(q)) return false;
-    return FqN::eq(q.x, FqN::mul(FqN::mul(beta, p.x), q.zz)) && FqN::eq(q.y, FqN::neg(FqN::mul(p.y, q.zzz)));
-  }
-
-  // coordinates < p and y^2 = x^3 + b (the point at infinity passes): the check of an UNCOMPRESSED G1 entry that ark-serialize's
-  // Validate::Yes makes before the subgroup test (a decompressed point is on the curve by construction)
-  static bool g1_on_curve_host(const G1Aff &a) {
-    if (a.inf) return true;
-    QEl x, y; memset(&x, 0, sizeof x); memset(&y, 0, sizeof y); memcpy(x.l, a.xy, FQB); memcpy(y.l, a.xy + FQB, FQB);
-    if (FqN::geq(x, FqN::P()) || FqN::geq(y, FqN::P())) return false;
-    const QEl xm = FqN::to_mont(x), ym = FqN::to_mont(y);
-    return FqN::eq(FqN::sqr(ym), FqN::add(FqN::mul(FqN::sqr(xm), xm), FqN::from32(G::B)));
-  }
 
   // the verifier's two sums over one launch chain: vector 0 = scalars_a over bases_a, vector 1 = scalars_b over bases_b, as two
   // scalar vectors over the concatenated bases (a zero scalar has no digits and costs nothing downstream).  One chain instead
@@ -1356,9 +805,8 @@ template <class S, class G> struct Ring {
                       const std::vector<uint8_t> &bases_b, const std::vector<H256> &scalars_b, bool check_subgroup_a, bool *bad_points,
                       G1Aff *out_a, G1Aff *out_b) {
     const size_t na = scalars_a.size(), nbv = scalars_b.size(), n = na + nbv;
-    const size_t pb = (n * 2 * FQB + 255) / 256 * 256, sb = (2 * n * 32 + 255) / 256 * 256;
-    uint8_t *base = (uint8_t *)ln.scratch(1, 2 * pb + sb + 256);
-    uint8_t *d_xy = base; uint32_t *d_b = (uint32_t *)(base + pb), *d_s = (uint32_t *)(base + 2 * pb), *d_flag = (uint32_t *)(base + 2 * pb + sb);
+    uint8_t *d_xy; uint32_t *d_b, *d_s, *d_flag;
+    ln.carve().take(d_xy, n * 2 * FQB).take(d_b, n * 2 * FQB / 4).take(d_s, 2 * n * 8).take(d_flag, 1).into(1);
     HIP_CHECK(hipMemcpyAsync(d_xy, bases_a.data(), na * 2 * FQB, hipMemcpyHostToDevice, ln.stream));
     HIP_CHECK(hipMemcpyAsync(d_xy + na * 2 * FQB, bases_b.data(), nbv * 2 * FQB, hipMemcpyHostToDevice, ln.stream));
     HIP_CHECK(hipMemsetAsync(d_s, 0, 2 * n * 32, ln.stream));
@@ -1375,16 +823,10 @@ template <class S, class G> struct Ring {
 
   // ---- CanonicalSerialize of the setup objects (src/ring.rs:484-542): RingSetup = its PcsParams (URS { powers_in_g1,
   // powers_in_g2 }), RingBuilderPcsParams = Vec<G1Affine> (the SRS in Lagrangian form); both in either ark-serialize mode
-  static G1Aff g1_from_raw(const uint8_t *p) {                         // one serialize_uncompressed G1 entry
-    G1Aff a; memset(&a, 0, sizeof a);
-    if (FQB == 48) { a.inf = p[0] & 0x40; if (!a.inf) for (int k = 0; k < FQB; k++) { a.xy[k] = p[FQB - 1 - k]; a.xy[FQB + k] = p[2 * FQB - 1 - k]; } }
-    else { a.inf = p[2 * FQB - 1] & 0x40; if (!a.inf) { memcpy(a.xy, p, 2 * FQB); a.xy[2 * FQB - 1] &= 0x3f; } }
-    return a;
-  }
   static void put_points(const std::vector<uint8_t> &raw, size_t n, bool compress, std::vector<uint8_t> &o) {
     { uint64_t v = n; size_t at = o.size(); o.resize(at + 8); memcpy(&o[at], &v, 8); }
     if (!compress) { o.insert(o.end(), raw.begin(), raw.begin() + n * 2 * FQB); return; }
-    for (size_t i = 0; i < n; i++) g1_encode<G>(g1_from_raw(&raw[i * 2 * FQB]), true, o);
+    for (size_t i = 0; i < n; i++) g1_encode<G>(g1_from_raw<G>(&raw[i * 2 * FQB]), true, o);
   }
   static int setup_serialize(avrf_ring_setup *su, bool compress, std::vector<uint8_t> &o) {
     using HP = HostPairing<G>;
@@ -1436,8 +878,7 @@ template <class S, class G> struct Ring {
       QEl px[2], py[2]; bool pinf[2];
       for (int i = 0; i < 2; i++) {
         const uint32_t *w = pts + (2 * it + i) * 2 * FW;
-        memset(&px[i], 0, sizeof(QEl)); memset(&py[i], 0, sizeof(QEl));
-        memcpy(px[i].l, w, FQB); memcpy(py[i].l, w + FW, FQB);
+        g1_coords<G>((const uint8_t *)w, &px[i], &py[i]);
         bool z = true; for (size_t k = 0; k < 2 * FW; k++) z = z && w[k] == 0;
         pinf[i] = z;
       }
@@ -1449,9 +890,8 @@ template <class S, class G> struct Ring {
     const size_t e1 = 2 * FQB; RingLane &ln = su->lane[0];
     std::vector<uint8_t> le(2 * n * e1);
     for (size_t i = 0; i < n; i++) { memcpy(&le[(2 * i) * e1], a_xy + i * e1, e1); memcpy(&le[(2 * i + 1) * e1], b_xy + i * e1, e1); }
-    const size_t pb = (2 * n * e1 + 255) / 256 * 256, ob = (n * 4 + 255) / 256 * 256;
-    uint8_t *base = (uint8_t *)ln.scratch(1, 2 * pb + ob + 256);
-    uint8_t *d_le = base; uint32_t *d_pts = (uint32_t *)(base + pb); int32_t *d_ok = (int32_t *)(base + 2 * pb); uint32_t *d_flag = (uint32_t *)(base + 2 * pb + ob);
+    uint8_t *d_le; uint32_t *d_pts, *d_flag; int32_t *d_ok;
+    ln.carve().take(d_le, 2 * n * e1).take(d_pts, 2 * n * e1 / 4).take(d_ok, n).take(d_flag, 1).into(1);
     HIP_CHECK(hipMemcpyAsync(d_le, le.data(), 2 * n * e1, hipMemcpyHostToDevice, ln.stream));
     HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream));
     launch_g1_bases(su->curve, d_le, 2 * n, d_pts, d_flag, ln.stream);
@@ -1479,231 +919,174 @@ template <class S, class G> struct Ring {
   // two G1 MSMs on the GPU (10 n + 1 and 2 n terms) and one 2-pairing check on the host.
   // each_status != nullptr: the n items are verified INDEPENDENTLY (n x RingVerifier::verify): per-item status, one 2-pairing
   // check per item on the device (k_g1_lincomb + pairing.hip) instead of one randomised check for the whole batch.
+  // The call is a sequence of stages over one record (verify_batch, below, is the sequence); the arithmetic of an item is HR::reduce.
   static constexpr size_t DEVICE_DECOMPRESS_MIN = 128;   // items; below, the pool's cores finish sooner than a device round trip
-  static int verify_batch(avrf_ring_setup *su, size_t n, const uint8_t *commitments, const uint32_t *ring_of_item, size_t n_rings,
-                          const uint8_t *instances_xy, const uint8_t *proofs, int32_t *each_status = nullptr) {
-    if (n == 0) return AVRF_OK;
-    RingLane &ln = su->lane[0];
-    static const bool trace = getenv("AVRF_RING_TRACE") != nullptr;
-    auto now = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    double t_prev = now();
-    auto lap = [&](const char *what) { if (trace) { double t = now(); fprintf(stderr, "  ring_verify[%zu] %-28s %8.3f ms\n", n, what, t - t_prev); t_prev = t; } };
-    const size_t N = su->N, cap = su->cap, plen = 4 * FQB + 7 * 32 + FQB + 32 + 2 * FQB, clen = 3 * FQB;
-    const H256 one = Fr::one();
-    std::vector<G1Aff> fixed(3 * n_rings);
-    for (size_t i = 0; i < 3 * n_rings; i++) if (!g1_decompress(commitments + FQB * i, &fixed[i])) return AVRF_INVALID_DATA;
-    // Validate::Yes (subgroup) of the deserialised G1 points: on the host pool for small batches, on the device otherwise
-    const bool host_subgroup = FQB == 48 && 10 * n + 3 * n_rings <= 512;
-    if (host_subgroup) {
+  struct VerifyRun {
+    avrf_ring_setup *su; RingLane &ln; size_t n, n_rings;
+    const uint8_t *commitments; const uint32_t *ring_of_item; const uint8_t *instances_xy, *proofs; int32_t *each_status;
+    RingTrace lap;
+    bool host_subgroup;                                // Validate::Yes (subgroup) of the deserialised G1 points: on the host pool for small batches, on the device otherwise
+    std::vector<G1Aff> fixed;                          // verify_commitments: the three commitments of every ring
+    std::vector<uint8_t> rnd;                          // HR::batch_randomisers: 32 bytes per item
+    std::vector<G1Aff> dec; std::vector<uint8_t> dec_ok;   // verify_points: the 7 G1 points of every proof (RingProofLayout order) | 0: did not decode
+    std::vector<ArkTranscript> t_ring;                 // verify_transcripts: per ring
+    // verify_reduce.  per item: 10 terms of the first MSM (3 fixed + 4 witness + C_q + pi1 + pi2) and 2 of the second
+    std::vector<uint8_t> b1, b2; std::vector<H256> s1, s2, gsc;
+    std::vector<int32_t> item_st;                      // (each_status only) what the host part found wrong with an item
+  };
+  static int verify_commitments(VerifyRun &r) {
+    r.fixed.resize(3 * r.n_rings);
+    for (size_t i = 0; i < 3 * r.n_rings; i++) if (!g1_decompress<G>(r.commitments + FQB * i, &r.fixed[i])) return AVRF_INVALID_DATA;
+    if (r.host_subgroup) {
       std::atomic<int> badc{0};
-      parallel_for(3 * n_rings, [&](size_t i) { if (!g1_in_subgroup_host(fixed[i])) badc = 1; });
+      parallel_for(3 * r.n_rings, [&](size_t i) { if (!g1_in_subgroup_host<G>(r.fixed[i])) badc = 1; });
       if (badc) return AVRF_INVALID_DATA;
     }
-    (void)clen;
-    // randomisers: SHAKE128 over everything the batch contains
-    // (the statement is bound in full: sizes, the verifier key, which ring every proof is checked against)
-    HostShake128 rh; rh.update("avrf-ring-batch", 15);
-    { uint64_t hdr[3] = {(uint64_t)n, (uint64_t)n_rings, (uint64_t)N}; rh.update(hdr, sizeof hdr); }
-    rh.update(su->g1_0.xy, 2 * FQB); rh.update(su->g2_raw.data(), su->g2_raw.size());
-    for (size_t i = 0; i < n; i++) { uint32_t ri = ring_of_item ? ring_of_item[i] : 0; rh.update(&ri, 4); }
-    rh.update(commitments, 3 * FQB * n_rings); rh.update(instances_xy, 64 * n); rh.update(proofs, plen * n);
-    std::vector<uint8_t> rnd(32 * n); rh.squeeze_copy(rnd.data(), rnd.size());
-    // per item: 10 terms of the first MSM (3 fixed + 4 witness + C_q + pi1 + pi2) and 2 of the second; the
-    // items are independent until the MSMs, so the host part runs on the thread pool
-    std::vector<uint8_t> b1((10 * n + 1) * 2 * FQB), b2(2 * n * 2 * FQB); std::vector<H256> s1(10 * n + 1), s2(2 * n);
-    auto put = [&](std::vector<uint8_t> &b, std::vector<H256> &sv, size_t slot, const G1Aff &p, const H256 &k_mont) {
-      memcpy(&b[slot * 2 * FQB], p.xy, 2 * FQB); sv[slot] = Fr::from_mont(k_mont); };
-    std::vector<H256> gsc(n);
-    std::atomic<int> status{AVRF_OK};
-    const H256 w_last = fr_pow<F>(su->w, cap - 1), ninv = su->ninv;
-    H256 wz[3]; for (int j = 0; j < 3; j++) wz[j] = fr_pow<F>(su->w, N - 3 + j);
-    H256 seedx = Fr::from32(S::ACC_X), seedy = Fr::from32(S::ACC_Y);
-    std::vector<int32_t> item_st(each_status ? n : 0, 0);
-    auto fail = [&](size_t it, int st) { if (each_status) item_st[it] = st; else status = st; };
-    // the 7 G1 points of every proof: decompression (a 381-bit square root each) and, for small batches, the subgroup test,
-    // one host task per POINT so that a single verification spreads over the pool
-    const size_t g1_off[7] = {0, (size_t)FQB, 2 * (size_t)FQB, 3 * (size_t)FQB, 4 * (size_t)FQB + 7 * 32, 5 * (size_t)FQB + 8 * 32, 6 * (size_t)FQB + 8 * 32};
-    std::vector<G1Aff> dec(7 * n); std::vector<uint8_t> dec_ok(7 * n, 0);
+    return AVRF_OK;
+  }
+  // the 7 G1 points of every proof: decompression (a 381-bit square root each) and, for small batches, the subgroup test,
+  // one host task per POINT so that a single verification spreads over the pool
+  static void verify_points(VerifyRun &r) {
+    const size_t n = r.n, np = 7 * n; RingLane &ln = r.ln;
+    r.dec.resize(np); r.dec_ok.assign(np, 0);
     if (n >= DEVICE_DECOMPRESS_MIN) {
       // large batches: the square roots on the device (k_g1_decompress), one lane per point; the y coordinates come back
       // because the transcript replay below absorbs the uncompressed points
-      const size_t np = 7 * n, cb = (np * FQB + 255) / 256 * 256, xb = (np * 2 * FQB + 255) / 256 * 256;
       std::vector<uint8_t> comp(np * FQB), xy(np * 2 * FQB);
-      for (size_t k = 0; k < np; k++) memcpy(&comp[k * FQB], proofs + plen * (k / 7) + g1_off[k % 7], FQB);
-      uint8_t *base = (uint8_t *)ln.scratch(1, cb + xb + np + 256);
-      HIP_CHECK(hipMemcpyAsync(base, comp.data(), np * FQB, hipMemcpyHostToDevice, ln.stream));
-      launch_g1_decompress(su->curve, base, np, base + cb, base + cb + xb, ln.stream);
-      HIP_CHECK(hipMemcpyAsync(xy.data(), base + cb, np * 2 * FQB, hipMemcpyDeviceToHost, ln.stream));
-      HIP_CHECK(hipMemcpyAsync(dec_ok.data(), base + cb + xb, np, hipMemcpyDeviceToHost, ln.stream));
+      for (size_t k = 0; k < np; k++) memcpy(&comp[k * FQB], r.proofs + PL::LEN * (k / 7) + PL::G1_OFF[k % 7], FQB);
+      uint8_t *d_comp, *d_xy, *d_ok;
+      ln.carve().take(d_comp, np * FQB).take(d_xy, np * 2 * FQB).take(d_ok, np).into(1);
+      HIP_CHECK(hipMemcpyAsync(d_comp, comp.data(), np * FQB, hipMemcpyHostToDevice, ln.stream));
+      launch_g1_decompress(r.su->curve, d_comp, np, d_xy, d_ok, ln.stream);
+      HIP_CHECK(hipMemcpyAsync(xy.data(), d_xy, np * 2 * FQB, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(r.dec_ok.data(), d_ok, np, hipMemcpyDeviceToHost, ln.stream));
       HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
       for (size_t k = 0; k < np; k++) {
-        memset(&dec[k], 0, sizeof dec[k]);
-        if (dec_ok[k] == 2) dec[k].inf = true; else memcpy(dec[k].xy, &xy[k * 2 * FQB], 2 * FQB);
+        memset(&r.dec[k], 0, sizeof r.dec[k]);
+        if (r.dec_ok[k] == 2) r.dec[k].inf = true; else memcpy(r.dec[k].xy, &xy[k * 2 * FQB], 2 * FQB);
       }
-      lap("G1 decompression (device)");
+      r.lap("G1 decompression (device)");
     } else
-    parallel_for(7 * n, [&](size_t k) {
-      const size_t it = k / 7, j = k % 7;
-      bool ok = g1_decompress(proofs + plen * it + g1_off[j], &dec[k]);
-      if (ok && host_subgroup) ok = g1_in_subgroup_host(dec[k]);
-      dec_ok[k] = ok;
+    parallel_for(np, [&](size_t k) {
+      bool ok = g1_decompress<G>(r.proofs + PL::LEN * (k / 7) + PL::G1_OFF[k % 7], &r.dec[k]);
+      if (ok && r.host_subgroup) ok = g1_in_subgroup_host<G>(r.dec[k]);
+      r.dec_ok[k] = ok;
     });
-    // the transcript up to the verifier key is the same for every proof checked against one ring: absorbed once per ring
-    std::vector<ArkTranscript> t_ring(n_rings);
-    for (size_t r = 0; r < n_rings; r++) {
-      ArkTranscript &t = t_ring[r];
-      t.label(S::SUITE_ID, S::SUITE_ID_LEN); t.label("vk");
-      std::vector<uint8_t> vk; g1_encode<G>(su->g1_0, false, vk); vk.insert(vk.end(), su->g2_raw.begin(), su->g2_raw.end());
-      for (int i = 0; i < 3; i++) g1_encode<G>(fixed[3 * r + i], false, vk);
-      t.append(vk);
-    }
+  }
+  // the transcript up to the verifier key is the same for every proof checked against one ring: absorbed once per ring
+  static void verify_transcripts(VerifyRun &r) {
+    r.t_ring.resize(r.n_rings);
+    for (size_t k = 0; k < r.n_rings; k++) r.t_ring[k] = HR::prelude(r.su->g1_0, r.su->g2_raw, &r.fixed[3 * k]);
+  }
+  // every item to its bases and scalars; the items are independent until the MSMs, so the host part runs on the thread pool
+  static int verify_reduce(VerifyRun &r) {
+    const size_t n = r.n, e1 = 2 * FQB;
+    r.b1.resize((10 * n + 1) * e1); r.b2.resize(2 * n * e1); r.s1.resize(10 * n + 1); r.s2.resize(2 * n); r.gsc.resize(n);
+    r.item_st.assign(r.each_status ? n : 0, 0);
+    std::atomic<int> status{AVRF_OK};
+    auto fail = [&](size_t it, int st) { if (r.each_status) r.item_st[it] = st; else status = st; };
+    const typename HR::VerifierConsts vc(r.su->N, r.su->w, r.su->ninv);
     parallel_for(n, [&](size_t it) {
-      const uint8_t *pr = proofs + plen * it;
-      const uint32_t ring = ring_of_item ? ring_of_item[it] : 0;
-      if (ring >= n_rings) { status = AVRF_ERR_BAD_ARG; return; }
-      const G1Aff *fx = &fixed[3 * ring];
-      G1Aff C[4], Cq, pi1, pi2; H256 ev[7], lin_zw;
-      for (int j = 0; j < 7; j++) if (!dec_ok[7 * it + j]) { fail(it, AVRF_INVALID_DATA); return; }
-      size_t off = 0;
-      for (int i = 0; i < 4; i++) { C[i] = dec[7 * it + i]; off += FQB; }
-      for (int i = 0; i < 7; i++) { H256 v = Fr::load_le(pr + off); if (Fr::geq_p(v)) { fail(it, AVRF_INVALID_DATA); return; } ev[i] = Fr::to_mont(v); off += 32; }
-      Cq = dec[7 * it + 4]; off += FQB;
-      { H256 v = Fr::load_le(pr + off); if (Fr::geq_p(v)) { fail(it, AVRF_INVALID_DATA); return; } lin_zw = Fr::to_mont(v); off += 32; }
-      pi1 = dec[7 * it + 5]; off += FQB;
-      pi2 = dec[7 * it + 6]; off += FQB;
-      H256 ix = Fr::load_le(instances_xy + 64 * it), iy = Fr::load_le(instances_xy + 64 * it + 32);
-      if (Fr::geq_p(ix) || Fr::geq_p(iy)) { fail(it, AVRF_INVALID_DATA); return; }
-      H256 ixm = Fr::to_mont(ix), iym = Fr::to_mont(iy);
-      // transcript replay
-      ArkTranscript t = t_ring[ring];
-      { std::vector<uint8_t> b(instances_xy + 64 * it, instances_xy + 64 * it + 64); t.label("instance"); t.append(b); }
-      { std::vector<uint8_t> b; for (int i = 0; i < 4; i++) g1_encode<G>(C[i], false, b); t.label("committed_cols"); t.append(b); }
-      H256 al[7]; for (int i = 0; i < 7; i++) al[i] = challenge(t, "constraints_aggregation");
-      { std::vector<uint8_t> b; g1_encode<G>(Cq, false, b); t.label("quotient"); t.append(b); }
-      H256 zeta = challenge(t, "evaluation_point");
-      { std::vector<uint8_t> b(pr + 4 * FQB, pr + 4 * FQB + 7 * 32); t.label("register_evaluations"); t.append(b); }
-      { std::vector<uint8_t> b(pr + 5 * FQB + 7 * 32, pr + 5 * FQB + 8 * 32); t.label("shifted_linearization_evaluation"); t.append(b); }
-      H256 nu[8]; for (int i = 0; i < 8; i++) nu[i] = challenge(t, "kzg_aggregation");
-      // q(zeta) from the evaluations (A.8)
-      const H256 x2 = ev[0], y2 = ev[1], sel = ev[2], b = ev[3], ip = ev[4], x1 = ev[5], y1 = ev[6];
-      const H256 nl = Fr::sub(zeta, w_last), omb = Fr::sub(one, b);
-      H256 zn = zeta; for (size_t k = 1; k < N; k <<= 1) zn = Fr::sqr(zn);
-      const H256 zn1 = Fr::sub(zn, one);
-      if (Fr::is_zero(zn1)) { fail(it, AVRF_VERIFICATION_FAILURE); return; }
-      HostExt sd; sd.x = seedx; sd.y = seedy; sd.t = Fr::mul(seedx, seedy); sd.z = one;
-      HostExt in; in.x = ixm; in.y = iym; in.t = Fr::mul(ixm, iym); in.z = one;
-      HostExt rs = Te::add(sd, in);
-      // the item's four inversions -- 1 / (zeta - 1), 1 / (zeta - w^(cap-1)) of the two Lagrange values, 1 / z of seed + instance,
-      // 1 / (zeta^N - 1) -- as ONE (Montgomery's trick; a fixed-exponent inversion is 380 products, 13 us).  zeta^N != 1 was checked, so
-      // the first, second and fourth are non-zero; z = 0 (an instance off the curve) keeps the old meaning: 1 / 0 = 0
-      const bool z_zero = Fr::is_zero(rs.z);
-      const H256 v0 = Fr::sub(zeta, one), v1 = nl, v2 = z_zero ? one : rs.z, v3 = zn1;
-      const H256 p01 = Fr::mul(v0, v1), p012 = Fr::mul(p01, v2);
-      H256 tinv = Fr::inv_fermat(Fr::mul(p012, v3));
-      const H256 i3 = Fr::mul(tinv, p012); tinv = Fr::mul(tinv, v3);
-      const H256 i2 = Fr::mul(tinv, p01); tinv = Fr::mul(tinv, v2);
-      const H256 i1 = Fr::mul(tinv, v0), i0 = Fr::mul(tinv, v1);
-      const H256 zn1n = Fr::mul(zn1, ninv);
-      const H256 lf = Fr::mul(zn1n, i0), ll = Fr::mul(Fr::mul(w_last, zn1n), i1);      // L_i(zeta) = w^i (zeta^N - 1) / (N (zeta - w^i))
-      const H256 rzi = z_zero ? H256{{0, 0, 0, 0}} : i2; const H256 resx = Fr::mul(rs.x, rzi), resy = Fr::mul(rs.y, rzi);
-      const H256 x1y1 = Fr::mul(x1, y1), x2y2 = Fr::mul(x2, y2);
-      H256 rest[7];
-      rest[0] = Fr::mul(Fr::neg(Fr::add(ip, Fr::mul(sel, b))), nl);
-      rest[1] = Fr::mul(Fr::sub(Fr::mul(b, Fr::neg(Fr::add(x1y1, x2y2))), Fr::mul(omb, x1)), nl);
-      rest[2] = Fr::mul(Fr::sub(Fr::mul(b, Fr::sub(x2y2, x1y1)), Fr::mul(omb, y1)), nl);
-      rest[3] = Fr::mul(b, omb);
-      rest[4] = Fr::add(Fr::mul(lf, Fr::sub(x1, seedx)), Fr::mul(ll, Fr::sub(x1, resx)));
-      rest[5] = Fr::add(Fr::mul(lf, Fr::sub(y1, seedy)), Fr::mul(ll, Fr::sub(y1, resy)));
-      rest[6] = Fr::add(Fr::mul(lf, ip), Fr::mul(ll, Fr::sub(ip, one)));
-      H256 aggz = lin_zw; for (int i = 0; i < 7; i++) aggz = Fr::add(aggz, Fr::mul(al[i], rest[i]));
-      H256 zk = one; for (int j = 0; j < 3; j++) zk = Fr::mul(zk, Fr::sub(zeta, wz[j]));
-      const H256 qz = Fr::mul(Fr::mul(aggz, zk), i3);
-      H256 vagg = Fr::mul(nu[7], qz); for (int i = 0; i < 7; i++) vagg = Fr::add(vagg, Fr::mul(nu[i], ev[i]));
-      const H256 a_coef = S::A_KIND == 1 ? Fr::neg(fr_small<F>(5)) : S::A_KIND == 2 ? Fr::neg(one) : one;
-      const H256 k1 = Fr::add(Fr::mul(b, Fr::add(Fr::mul(y1, y2), Fr::mul(a_coef, Fr::mul(x1, x2)))), omb);
-      const H256 k2 = Fr::add(Fr::mul(b, Fr::sub(Fr::mul(x1, y2), Fr::mul(x2, y1))), omb);
-      const H256 zw = Fr::mul(zeta, su->w);
+      const uint32_t ring = r.ring_of_item ? r.ring_of_item[it] : 0;
+      if (ring >= r.n_rings) { status = AVRF_ERR_BAD_ARG; return; }
+      const G1Aff *fx = &r.fixed[3 * ring], *pts = &r.dec[7 * it];
+      for (int j = 0; j < 7; j++) if (!r.dec_ok[7 * it + j]) { fail(it, AVRF_INVALID_DATA); return; }
       // randomisers r1, r2 (128 bits each)
-      H256 r1 = Fr::to_mont(H256{{0, 0, 0, 0}}), r2 = r1;
-      { H256 a = {{0, 0, 0, 0}}, c = {{0, 0, 0, 0}}; memcpy(a.l, &rnd[32 * it], 16); memcpy(c.l, &rnd[32 * it + 16], 16); r1 = Fr::to_mont(a); r2 = Fr::to_mont(c); }
-      if (n == 1) r1 = one;
-      const size_t o = 10 * it;
-      for (int j = 0; j < 3; j++) put(b1, s1, o + j, fx[j], Fr::mul(r1, nu[j]));
-      put(b1, s1, o + 3, C[0], Fr::mul(r1, nu[3]));
-      put(b1, s1, o + 4, C[1], Fr::add(Fr::mul(r1, nu[4]), Fr::mul(r2, Fr::mul(nl, al[0]))));
-      put(b1, s1, o + 5, C[2], Fr::add(Fr::mul(r1, nu[5]), Fr::mul(r2, Fr::mul(nl, Fr::mul(al[1], k1)))));
-      put(b1, s1, o + 6, C[3], Fr::add(Fr::mul(r1, nu[6]), Fr::mul(r2, Fr::mul(nl, Fr::mul(al[2], k2)))));
-      put(b1, s1, o + 7, Cq, Fr::mul(r1, nu[7]));
-      put(b1, s1, o + 8, pi1, Fr::mul(r1, zeta)); put(b1, s1, o + 9, pi2, Fr::mul(r2, zw));
-      gsc[it] = Fr::add(Fr::mul(r1, vagg), Fr::mul(r2, lin_zw));
-      put(b2, s2, 2 * it, pi1, Fr::neg(r1)); put(b2, s2, 2 * it + 1, pi2, Fr::neg(r2));
+      H256 r1, r2; HR::randomiser_pair(&r.rnd[32 * it], &r1, &r2);
+      if (n == 1) r1 = Fr::one();
+      typename HR::Item o;
+      if (int st = HR::reduce(vc, r.t_ring[ring], pts, r.proofs + PL::LEN * it, r.instances_xy + 64 * it, r1, r2, o)) { fail(it, st); return; }
+      uint8_t *b = &r.b1[10 * it * e1];
+      for (int j = 0; j < 3; j++) memcpy(b + j * e1, fx[j].xy, e1);
+      for (int j = 0; j < 7; j++) memcpy(b + (3 + j) * e1, pts[j].xy, e1);
+      memcpy(&r.s1[10 * it], o.s1, sizeof o.s1);
+      r.gsc[it] = o.gsc;
+      memcpy(&r.b2[2 * it * e1], pts[5].xy, e1); memcpy(&r.b2[(2 * it + 1) * e1], pts[6].xy, e1);
+      r.s2[2 * it] = o.s2[0]; r.s2[2 * it + 1] = o.s2[1];
     }, 4);
-    if (status != AVRF_OK) return status;
-    lap("decode + transcripts (host)");
-    // ONE independent verification is a batch of one: its two 11- / 2-term sums go through the MSM engine and the pairing
-    // check runs on the host (2.4 ms; the per-item device form below is paced by lone 381-bit double-and-add chains: 5 ms)
-    if (each_status && n == 1 && item_st[0]) { each_status[0] = item_st[0]; return AVRF_OK; }
-    if (each_status && n > 1) {
-      // 13 (base, scalar) pairs per item: its 10 terms of the first argument, the g1 term, its 2 terms of the second
-      const size_t e1 = 2 * FQB, TPI = 13;
-      std::vector<uint8_t> bb(n * TPI * e1); std::vector<H256> ss(n * TPI);
-      for (size_t it = 0; it < n; it++) {
-        memcpy(&bb[(it * TPI) * e1], &b1[(10 * it) * e1], 10 * e1);
-        for (int j = 0; j < 10; j++) ss[it * TPI + j] = s1[10 * it + j];
-        memcpy(&bb[(it * TPI + 10) * e1], su->g1_0.xy, e1); ss[it * TPI + 10] = Fr::from_mont(Fr::neg(gsc[it]));
-        memcpy(&bb[(it * TPI + 11) * e1], &b2[(2 * it) * e1], 2 * e1);
-        ss[it * TPI + 11] = s2[2 * it]; ss[it * TPI + 12] = s2[2 * it + 1];
-      }
-      const bool host_pair = few_checks(n);
-      if (!host_pair) ensure_pairing(su);
-      const size_t nb = n * TPI;
-      const size_t pb = (nb * e1 + 255) / 256 * 256, sb = (nb * 32 + 255) / 256 * 256, ob = (n * 2 * e1 + 255) / 256 * 256, kb = (n * 4 + 255) / 256 * 256;
-      uint8_t *base = (uint8_t *)ln.scratch(1, 2 * pb + sb + ob + 2 * kb + 256);
-      uint8_t *d_xy = base; uint32_t *d_b = (uint32_t *)(base + pb), *d_s = (uint32_t *)(base + 2 * pb), *d_pts = (uint32_t *)(base + 2 * pb + sb);
-      int32_t *d_ok = (int32_t *)(base + 2 * pb + sb + ob), *d_rec = (int32_t *)(base + 2 * pb + sb + ob + kb);
-      uint32_t *d_flag = (uint32_t *)(base + 2 * pb + sb + ob + 2 * kb);
-      HIP_CHECK(hipMemcpyAsync(d_xy, bb.data(), nb * e1, hipMemcpyHostToDevice, ln.stream));
-      if (su->curve == 0) parallel_for(n, [&](size_t it) { for (size_t j = 0; j < TPI; j++) g1_glv_split_bls(ss[it * TPI + j].l); });   // k -> (k mod z^2, k div z^2)
-      HIP_CHECK(hipMemcpyAsync(d_s, ss.data(), nb * 32, hipMemcpyHostToDevice, ln.stream));
-      HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream)); HIP_CHECK(hipMemsetAsync(d_rec, 0, n * 4, ln.stream));
-      launch_g1_bases(su->curve, d_xy, nb, d_b, d_flag, ln.stream);
-      if (!host_subgroup) launch_g1_subgroup_check(su->curve, d_b, nb, d_flag, ln.stream, d_rec, (uint32_t)TPI);
-      launch_g1_lincomb(su->curve, d_b, d_s, n, (uint32_t)TPI, 11, d_pts, ln.stream, su->curve == 0);
-      std::vector<int32_t> okv(n), rec(n); uint32_t range_flag = 0;
-      std::vector<uint32_t> pts(host_pair ? n * 2 * e1 / 4 : 0);
-      if (host_pair) HIP_CHECK(hipMemcpyAsync(pts.data(), d_pts, n * 2 * e1, hipMemcpyDeviceToHost, ln.stream));
-      else {
-        launch_pairing_check(su->ptab, d_pts, n, d_ok, ln.stream);
-        HIP_CHECK(hipMemcpyAsync(okv.data(), d_ok, n * 4, hipMemcpyDeviceToHost, ln.stream));
-      }
-      HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec, n * 4, hipMemcpyDeviceToHost, ln.stream));
-      HIP_CHECK(hipMemcpyAsync(&range_flag, d_flag, 4, hipMemcpyDeviceToHost, ln.stream));
-      HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
-      lap(host_pair ? "per-item G1 sums (device)" : "per-item G1 sums + pairing checks (device)");
-      if (range_flag & 1) return AVRF_INVALID_DATA;      // a base with a coordinate >= p (launch_g1_bases): no item to pin it on
-      if (host_pair) { host_pair_checks(su, pts.data(), n, okv.data()); lap("pairing checks (host pool)"); }
-      for (size_t it = 0; it < n; it++)
-        each_status[it] = item_st[it] ? item_st[it] : rec[it] ? AVRF_INVALID_DATA : okv[it] ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
-      return AVRF_OK;
+    return status;
+  }
+  // n > 1 independent verifications: per-item sums on the device, then the pairing checks on the device or, when few, on the host pool
+  static int verify_tail_each(VerifyRun &r) {
+    avrf_ring_setup *su = r.su; RingLane &ln = r.ln; const size_t n = r.n;
+    // 13 (base, scalar) pairs per item: its 10 terms of the first argument, the g1 term, its 2 terms of the second
+    const size_t e1 = 2 * FQB, TPI = 13;
+    std::vector<uint8_t> bb(n * TPI * e1); std::vector<H256> ss(n * TPI);
+    for (size_t it = 0; it < n; it++) {
+      memcpy(&bb[(it * TPI) * e1], &r.b1[(10 * it) * e1], 10 * e1);
+      for (int j = 0; j < 10; j++) ss[it * TPI + j] = r.s1[10 * it + j];
+      memcpy(&bb[(it * TPI + 10) * e1], su->g1_0.xy, e1); ss[it * TPI + 10] = Fr::from_mont(Fr::neg(r.gsc[it]));
+      memcpy(&bb[(it * TPI + 11) * e1], &r.b2[(2 * it) * e1], 2 * e1);
+      ss[it * TPI + 11] = r.s2[2 * it]; ss[it * TPI + 12] = r.s2[2 * it + 1];
     }
+    const bool host_pair = few_checks(n);
+    if (!host_pair) ensure_pairing(su);
+    const size_t nb = n * TPI;
+    uint8_t *d_xy; uint32_t *d_b, *d_s, *d_pts, *d_flag; int32_t *d_ok, *d_rec;
+    ln.carve().take(d_xy, nb * e1).take(d_b, nb * e1 / 4).take(d_s, nb * 8).take(d_pts, n * 2 * e1 / 4).take(d_ok, n).take(d_rec, n).take(d_flag, 1).into(1);
+    HIP_CHECK(hipMemcpyAsync(d_xy, bb.data(), nb * e1, hipMemcpyHostToDevice, ln.stream));
+    if (su->curve == 0) parallel_for(n, [&](size_t it) { for (size_t j = 0; j < TPI; j++) g1_glv_split_bls(ss[it * TPI + j].l); });   // k -> (k mod z^2, k div z^2)
+    HIP_CHECK(hipMemcpyAsync(d_s, ss.data(), nb * 32, hipMemcpyHostToDevice, ln.stream));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream)); HIP_CHECK(hipMemsetAsync(d_rec, 0, n * 4, ln.stream));
+    launch_g1_bases(su->curve, d_xy, nb, d_b, d_flag, ln.stream);
+    if (!r.host_subgroup) launch_g1_subgroup_check(su->curve, d_b, nb, d_flag, ln.stream, d_rec, (uint32_t)TPI);
+    launch_g1_lincomb(su->curve, d_b, d_s, n, (uint32_t)TPI, 11, d_pts, ln.stream, su->curve == 0);
+    std::vector<int32_t> okv(n), rec(n); uint32_t range_flag = 0;
+    std::vector<uint32_t> pts(host_pair ? n * 2 * e1 / 4 : 0);
+    if (host_pair) HIP_CHECK(hipMemcpyAsync(pts.data(), d_pts, n * 2 * e1, hipMemcpyDeviceToHost, ln.stream));
+    else {
+      launch_pairing_check(su->ptab, d_pts, n, d_ok, ln.stream);
+      HIP_CHECK(hipMemcpyAsync(okv.data(), d_ok, n * 4, hipMemcpyDeviceToHost, ln.stream));
+    }
+    HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec, n * 4, hipMemcpyDeviceToHost, ln.stream));
+    HIP_CHECK(hipMemcpyAsync(&range_flag, d_flag, 4, hipMemcpyDeviceToHost, ln.stream));
+    HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
+    r.lap(host_pair ? "per-item G1 sums (device)" : "per-item G1 sums + pairing checks (device)");
+    if (range_flag & 1) return AVRF_INVALID_DATA;      // a base with a coordinate >= p (launch_g1_bases): no item to pin it on
+    if (host_pair) { host_pair_checks(su, pts.data(), n, okv.data()); r.lap("pairing checks (host pool)"); }
+    for (size_t it = 0; it < n; it++)
+      r.each_status[it] = r.item_st[it] ? r.item_st[it] : rec[it] ? AVRF_INVALID_DATA : okv[it] ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
+    return AVRF_OK;
+  }
+  // the batch folded into two sums: one MSM chain on the device, one 2-pairing check on the host.  The verdict of the batch.
+  static int verify_tail_folded(VerifyRun &r) {
+    avrf_ring_setup *su = r.su; const size_t n = r.n;
     H256 g1_scalar = {{0, 0, 0, 0}};
-    for (size_t it = 0; it < n; it++) g1_scalar = Fr::sub(g1_scalar, gsc[it]);
-    put(b1, s1, 10 * n, su->g1_0, g1_scalar);
+    for (size_t it = 0; it < n; it++) g1_scalar = Fr::sub(g1_scalar, r.gsc[it]);
+    memcpy(&r.b1[10 * n * 2 * FQB], su->g1_0.xy, 2 * FQB); r.s1[10 * n] = Fr::from_mont(g1_scalar);
     // b1 holds every deserialised G1 point of the batch (ring commitments, proof commitments, opening proofs): its bases are
     // subgroup-checked on the device before they are used (ark-serialize Validate::Yes; BLS12-381 G1 has a large cofactor)
     bool bad = false;
     G1Aff acc1, acc2;
-    g1_msm2(su, ln, b1, s1, b2, s2, !host_subgroup, &bad, &acc1, &acc2);
-    if (bad) { if (each_status) { each_status[0] = AVRF_INVALID_DATA; return AVRF_OK; } return AVRF_INVALID_DATA; }
-    lap("two G1 MSMs (device, one chain)");
+    g1_msm2(su, r.ln, r.b1, r.s1, r.b2, r.s2, !r.host_subgroup, &bad, &acc1, &acc2);
+    if (bad) return AVRF_INVALID_DATA;
+    r.lap("two G1 MSMs (device, one chain)");
     const typename HP::G2Lines *lines = host_lines(su);
     QEl px[2], py[2]; bool pinf[2] = {acc1.inf, acc2.inf};
     const G1Aff *accs[2] = {&acc1, &acc2};
-    for (int i = 0; i < 2; i++) { QEl x, y; memset(&x, 0, sizeof x); memset(&y, 0, sizeof y); memcpy(x.l, accs[i]->xy, FQB); memcpy(y.l, accs[i]->xy + FQB, FQB); px[i] = FqN::to_mont(x); py[i] = FqN::to_mont(y); }
+    for (int i = 0; i < 2; i++) { QEl x, y; g1_coords<G>(accs[i]->xy, &x, &y); px[i] = FqN::to_mont(x); py[i] = FqN::to_mont(y); }
     const bool ok = HP::product_is_one_lines_par(px, py, pinf, lines, 2, [](size_t k, auto fn) { parallel_for(k, fn); });   // the two Miller loops side by side
-    lap("2-pairing check (host)");
-    if (each_status) { each_status[0] = ok ? AVRF_OK : AVRF_VERIFICATION_FAILURE; return AVRF_OK; }
+    r.lap("2-pairing check (host)");
     return ok ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
+  }
+  static int verify_batch(avrf_ring_setup *su, size_t n, const uint8_t *commitments, const uint32_t *ring_of_item, size_t n_rings,
+                          const uint8_t *instances_xy, const uint8_t *proofs, int32_t *each_status = nullptr) {
+    if (n == 0) return AVRF_OK;
+    VerifyRun r{su, su->lane[0], n, n_rings, commitments, ring_of_item, instances_xy, proofs, each_status, RingTrace("ring_verify", n, false),
+                FQB == 48 && 10 * n + 3 * n_rings <= 512};
+    if (int st = verify_commitments(r)) return st;
+    r.rnd = HR::batch_randomisers(n, n_rings, su->N, su->g1_0, su->g2_raw, ring_of_item, commitments, instances_xy, proofs);
+    verify_points(r);
+    verify_transcripts(r);
+    if (int st = verify_reduce(r)) return st;
+    r.lap("decode + transcripts (host)");
+    // ONE independent verification is a batch of one: its two 11- / 2-term sums go through the MSM engine and the pairing
+    // check runs on the host (2.4 ms; the per-item device form is paced by lone 381-bit double-and-add chains: 5 ms)
+    if (each_status && n == 1 && r.item_st[0]) { each_status[0] = r.item_st[0]; return AVRF_OK; }
+    if (each_status && n > 1) return verify_tail_each(r);
+    const int verdict = verify_tail_folded(r);
+    if (each_status) { each_status[0] = verdict; return AVRF_OK; }
+    return verdict;
   }
 };
 
@@ -1857,8 +1240,8 @@ void avrf_ring_setup_free(avrf_ring_setup *su) {
 }
 size_t avrf_ring_max_ring_size(const avrf_ring_setup *su) { return su ? su->keyset : 0; }
 size_t avrf_ring_domain_size(const avrf_ring_setup *su) { return su ? su->N : 0; }
-size_t avrf_ring_proof_len(const avrf_ring_setup *su) { return su ? (su->curve == 0 ? 592 : 480) : 0; }
-size_t avrf_ring_commitment_len(const avrf_ring_setup *su) { return su ? (su->curve == 0 ? 144 : 96) : 0; }
+size_t avrf_ring_proof_len(const avrf_ring_setup *su) { return su ? ring_proof_len(su->curve) : 0; }
+size_t avrf_ring_commitment_len(const avrf_ring_setup *su) { return su ? ring_commitment_len(su->curve) : 0; }
 int avrf_ring_setup_suite(const avrf_ring_setup *su) { return su ? su->suite : -1; }
 avrf_ring_setup *avrf_ring_key_setup(const avrf_ring_key *key) { return key ? key->setup : nullptr; }
 int avrf_ring_setup_plan(const avrf_ring_setup *su, int32_t out[4]) {
@@ -1961,7 +1344,7 @@ int avrf_ring_prove(avrf_ring_key *k, size_t n, const uint32_t *key_index, const
   if (avrf_ctx_busy_(k->setup->ctx)) return AVRF_ERR_BAD_ARG;
   if (blinding_mode != 0 && blinding_mode != 1) return AVRF_ERR_BAD_ARG;
   if (hipSetDevice(k->setup->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
-  const size_t plen = k->setup->curve == 0 ? 592 : 480;
+  const size_t plen = ring_proof_len(k->setup->curve);
   // proofs proved in lockstep per device round: at most 512, and a call of up to 1024 proofs is cut in TWO so that both lanes
   // work (the host rounds of one chunk hide behind the device rounds of the other) -- a rank of an 8-GPU node proves 128 proofs
   // per context (BASELINE configs[3]: 4096 proofs / 8 ranks / 4 contexts), which as ONE chunk on one lane left the device

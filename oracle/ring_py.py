@@ -571,13 +571,10 @@ def _g1_lincomb(s, terms):
     return acc
 
 
-def verify(prm, srs, fixed_commitments, proof, instance, pairing=None):
-    """Returns True iff the ring proof verifies for `instance` (the Pedersen key commitment Yb as a TE
-    point) under the verifier key (srs.g1[0], srs.g2[0..2], fixed_commitments)."""
-    from . import pairing_py as PP
+def verifier_values(prm, srs, fixed_commitments, proof, instance):
+    """What RingVerifier::verify derives from a proof before any group arithmetic: the decoded proof, the Fiat-Shamir challenges and
+    the scalars of its two KZG opening checks.  None when an evaluation or lin_zw is not below r.  `verify` below runs on exactly these."""
     s = prm.s
-    PP.use_curve("bls12_381" if s.zcash else "bn254")
-    g2_decode = PP.g2_decode_zcash_uncompressed if s.zcash else PP.g2_decode_arkworks_uncompressed
     r, N, cap, w = s.r, prm.N, prm.capacity, prm.w
     n = s.fp_bytes
     off = 0
@@ -591,7 +588,7 @@ def verify(prm, srs, fixed_commitments, proof, instance, pairing=None):
     pi2 = g1_decode_compressed(s, proof[off: off + n]); off += n
     assert off == len(proof)
     if any(v >= r for v in evals) or lin_zw >= r:
-        return False
+        return None
     cols = {"C": fixed_commitments}
     t = _transcript_prelude(prm, srs, cols)
     t.label(b"instance"); t.append(_le32(instance[0]) + _le32(instance[1]))
@@ -626,11 +623,28 @@ def verify(prm, srs, fixed_commitments, proof, instance, pairing=None):
     for i in (N - 3, N - 2, N - 1):
         zk = zk * (zeta - pow(w, i, r)) % r
     q_z = agg_z * zk % r * pow(zn1, -1, r) % r
-    col_commits = list(fixed_commitments) + C                      # px, py, sel, bits, ip, ax, ay
-    C_agg = _g1_lincomb(s, [(nu, c) for nu, c in zip(nus, col_commits)] + [(nus[7], Cq)])
     v_agg = (sum(nu * e for nu, e in zip(nus, evals)) + nus[7] * q_z) % r
     k1 = (b * ((y1 * y2 + a * x1 % r * x2) % r) + 1 - b) % r
     k2 = (b * ((x1 * y2 - x2 * y1) % r) + 1 - b) % r
+    return dict(C=C, Cq=Cq, pi1=pi1, pi2=pi2, evals=evals, lin_zw=lin_zw, alphas=alphas, zeta=zeta, nus=nus, nl=nl, k1=k1, k2=k2, q_z=q_z,
+                v_agg=v_agg)
+
+
+def verify(prm, srs, fixed_commitments, proof, instance, pairing=None):
+    """Returns True iff the ring proof verifies for `instance` (the Pedersen key commitment Yb as a TE
+    point) under the verifier key (srs.g1[0], srs.g2[0..2], fixed_commitments)."""
+    from . import pairing_py as PP
+    s = prm.s
+    PP.use_curve("bls12_381" if s.zcash else "bn254")
+    g2_decode = PP.g2_decode_zcash_uncompressed if s.zcash else PP.g2_decode_arkworks_uncompressed
+    r, w = s.r, prm.w
+    v = verifier_values(prm, srs, fixed_commitments, proof, instance)
+    if v is None:
+        return False
+    C, Cq, pi1, pi2, lin_zw = v["C"], v["Cq"], v["pi1"], v["pi2"], v["lin_zw"]
+    alphas, zeta, nus, nl, k1, k2, v_agg = v["alphas"], v["zeta"], v["nus"], v["nl"], v["k1"], v["k2"], v["v_agg"]
+    col_commits = list(fixed_commitments) + C                      # px, py, sel, bits, ip, ax, ay
+    C_agg = _g1_lincomb(s, [(nu, c) for nu, c in zip(nus, col_commits)] + [(nus[7], Cq)])
     C_lin = _g1_lincomb(s, [(nl * alphas[0] % r, C[1]), (nl * alphas[1] % r * k1 % r, C[2]), (nl * alphas[2] % r * k2 % r, C[3])])
     g1 = srs.g1[0]
     g2 = g2_decode(srs.g2_raw[0]); tg2 = g2_decode(srs.g2_raw[1])

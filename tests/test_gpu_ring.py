@@ -233,6 +233,25 @@ def test_ring_verify_large_batch_device_decompression(env, suite):
     assert ring_batch_verify(setup, coms, rings, insts, only_dec) == 2
 
 
+@pytest.mark.parametrize("suite", [0, 1])
+def test_ring_verify_each_host_decode_device_pairing(env, suite):
+    """17 to 127 independent verifications decompress their G1 points on the host pool and run their pairing checks on the device:
+    the seven vectors three times (21 items), with a perturbed evaluation, a scalar >= r and an item checked against the wrong ring."""
+    from ark_vrf_amd.ring import ring_batch_verify, ring_verify_each
+    ctx, setup, vs, srs = env[suite]
+    fq = 48 if suite == 0 else 32
+    coms = [bytes.fromhex(v["ring_pks_com"]) for v in vs]
+    insts = [xy(suite, bytes.fromhex(v["proof_pk_com"])) for v in vs] * 3
+    proofs = [bytes.fromhex(v["ring_proof"]) for v in vs] * 3
+    rings = list(range(7)) * 3
+    assert ring_batch_verify(setup, coms, rings, insts, proofs) == 0
+    bad, exp = list(proofs), [0] * 21
+    b = bytearray(bad[9]); b[4 * fq + 5] ^= 1; bad[9] = bytes(b); exp[9] = 1                          # an evaluation
+    b = bytearray(bad[12]); b[4 * fq + 7 * 32 + fq + 31] = 0xff; bad[12] = bytes(b); exp[12] = 2      # lin_zw >= r: InvalidData
+    wrong = list(rings); wrong[17] = (rings[17] + 1) % 7; exp[17] = 1                                 # against the wrong ring
+    assert ring_verify_each(setup, coms, wrong, insts, bad) == exp
+
+
 def test_ring_verify_validates_g1_points(env):
     """Validate::Yes of the deserialised RingProof / RingCommitment points (ADVICE r1): a BLS12-381 G1 point ON the curve but
     OUTSIDE the prime-order subgroup (cofactor ~2^126) and a non-canonical encoding of infinity are InvalidData, not merely
