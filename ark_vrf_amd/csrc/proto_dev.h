@@ -144,6 +144,34 @@ template <class S, class T> AVRF_DI void tr_base(T &h, uint8_t scheme, bool schn
   if (schnorr) { x = fp_load_le(pk_xy); y = fp_load_le(pk_xy + 32); }        // pk_xy: global memory (staged batch)
   tr_base<S>(h, scheme, schnorr, x, y, ios_xy, m, ad, adl, flags);
 }
+// The thin transcript of an item with ONE I/O pair, on a suite whose points serialise to 32 bytes and whose transcript is
+// HashTranscript<Sha512> (the flagship shape), up to the additional data:
+//   SUITE_ID || DS_THIN || LE64(2) || G || pk || I || O || LE64(adl)                        (tr_base with the Schnorr pair first)
+// Every offset is a constant of the suite (sha512_dev.h, static-layout absorb); the first PK bytes are a literal.
+template <class S> struct ThinLayout1 {
+  static constexpr bool OK = !S::SW_CODEC && !S::XOF_SHAKE && !S::TR_SHA256 && S::POINT_LEN == 32;
+  static constexpr int TAG = S::SUITE_ID_LEN, COUNT = TAG + 1, G = COUNT + 8, PK = G + S::POINT_LEN, IN = PK + S::POINT_LEN,
+                       OUT = IN + S::POINT_LEN, ADL = OUT + S::POINT_LEN, END = ADL + 8;
+  static_assert(!OK || PK <= 128, "the literal prefix (suite id, tag, count, generator) lies within the first block");
+  static constexpr ShaLit prefix() {
+    ShaLit l{};
+    for (int i = 0; i < S::SUITE_ID_LEN; i++) sha512_lit_byte(l, i, S::SUITE_ID[i]);
+    sha512_lit_byte(l, TAG, DS_THIN);
+    sha512_lit_byte(l, COUNT, 2);                                              // LE64(m + 1), m = 1
+    for (int i = 0; i < S::POINT_LEN; i++) sha512_lit_byte(l, G + i, S::G_ENC[i]);
+    return l;
+  }
+};
+static_assert(ThinLayout1<SuiteBandersnatch>::OK && ThinLayout1<SuiteBandersnatch>::PK == 68 && ThinLayout1<SuiteBandersnatch>::IN == 100 &&
+              ThinLayout1<SuiteBandersnatch>::OUT == 132 && ThinLayout1<SuiteBandersnatch>::ADL == 164 && ThinLayout1<SuiteBandersnatch>::END == 172,
+              "Bandersnatch: 27 + 1 + 8 + 4 x 32 + 8 = 172 bytes before the additional data");
+// the compressed form of an affine point (absorb_point_xy, twisted-Edwards branch) as eight little-endian words
+template <class S> AVRF_DI void point_words(const fp &x, const fp &y, uint32_t (&v)[8]) {
+  const uint32_t sign = fp_is_negative_plain<typename S::Fq>(x) ? 0x80000000u : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; i++) v[i] = y.v[i] | (i == 7 ? sign : 0u);
+}
+
 // reader of the delinearisation stream: fork + [0x30] + finalize (DelinearizeScalars, common.rs:335-369)
 template <class T> AVRF_DI auto delin_seed(const T &h) {
   T hd = h; tr_byte(hd, DS_DELINEARIZE); return tr_reader(hd);

@@ -179,13 +179,107 @@ AVRF_DI void sha512_xof_block(const uint64_t (&seed)[8], uint64_t counter, uint6
 #pragma unroll
   for (int i = 0; i < 8; i++) out[i] = s.h[i];
 }
+// sixteen digest bytes, given as the two big-endian digest words that hold them, as four little-endian u32 words
+AVRF_DI void be128_le(uint64_t hi, uint64_t lo, uint32_t (&w)[4]) {
+  uint64_t b0 = __builtin_bswap64(hi), b1 = __builtin_bswap64(lo);   // little-endian integers of bytes 0..7, 8..15
+  w[0] = (uint32_t)b0; w[1] = (uint32_t)(b0 >> 32); w[2] = (uint32_t)b1; w[3] = (uint32_t)(b1 >> 32);
+}
 // bytes [off, off+16) of a digest (off multiple of 16) as four little-endian u32 words
 AVRF_DI void digest_le128(const uint64_t (&dg)[8], int off16, uint32_t (&w)[4]) {
   uint64_t hi = 0, lo = 0;   // dg words are big-endian: byte k of the digest is the (k&7)-th MSB of dg[k>>3]
 #pragma unroll
   for (int i = 0; i < 4; i++) { if (off16 == i) { hi = dg[2 * i]; lo = dg[2 * i + 1]; } }
-  uint64_t b0 = __builtin_bswap64(hi), b1 = __builtin_bswap64(lo);   // little-endian integers of bytes 0..7, 8..15
-  w[0] = (uint32_t)b0; w[1] = (uint32_t)(b0 >> 32); w[2] = (uint32_t)b1; w[3] = (uint32_t)(b1 >> 32);
+  be128_le(hi, lo, w);
+}
+
+// ---- static-layout absorb.  Where the byte offset of a datum in the MESSAGE is a compile-time constant (everything a transcript
+// absorbs before its first variable-length string), the datum goes into the block by shifts the compiler knows: at most two block
+// words are touched, no select chain over the sixteen, and the block is compressed at the point where the layout says it is full.
+// The caller states every offset (sha512_lit / sha512_u32le_at<POS>) in ascending order and closes with sha512_static_end<END>,
+// which sets the run-time position for whatever follows.
+struct ShaLit { uint64_t w[16]; };                       // block words of a literal prefix, built in a constant expression
+constexpr void sha512_lit_byte(ShaLit &l, int pos, uint8_t b) { l.w[pos >> 3] |= (uint64_t)b << (56 - 8 * (pos & 7)); }
+// the literal prefix of a fresh transcript: bytes [0, LEN), LEN <= 128, as whole block words (OR-ed in: the rest of the block is zero)
+template <int LEN> AVRF_DI void sha512_lit(Sha512 &s, const ShaLit &l) {
+  static_assert(LEN > 0 && LEN <= 128, "a literal prefix lies within the first block");
+#pragma unroll
+  for (int i = 0; i < (LEN + 7) / 8; i++) s.w[i] |= l.w[i];
+  if constexpr (LEN == 128) sha512_flush(s);
+}
+// a 32-bit little-endian word at message offset POS (any alignment; a word that straddles the block edge is split around the flush)
+template <int POS> AVRF_DI void sha512_u32le_at(Sha512 &s, uint32_t v) {
+  constexpr int p = POS & 127, wi = p >> 3, k = p & 7;
+  const uint64_t be = __builtin_bswap32(v);
+  if constexpr (k <= 4) s.w[wi] |= be << (8 * (4 - k));
+  else {
+    s.w[wi] |= be >> (8 * (k - 4));
+    if constexpr (wi == 15) sha512_flush(s);
+    s.w[(wi + 1) & 15] |= be << (64 - 8 * (k - 4));
+  }
+  if constexpr (p + 4 == 128) sha512_flush(s);
+}
+// eight such words (a field element, a compressed point) from message offset POS on
+template <int POS, int I = 0> AVRF_DI void sha512_words_at(Sha512 &s, const uint32_t (&v)[8]) {
+  sha512_u32le_at<POS + 4 * I>(s, v[I]);
+  if constexpr (I < 7) sha512_words_at<POS, I + 1>(s, v);
+}
+template <int END> AVRF_DI void sha512_static_end(Sha512 &s) { s.fill = END & 127; s.total = END; }
+
+// ---- word-granular absorb at a RUN-TIME position (after a variable-length string; the position may differ in every lane of a
+// wave).  The block word that is being filled lives in `acc` (big-endian, its first fill & 7 bytes valid, the rest zero) and is
+// absent from the block; up to eight bytes arrive as one big-endian word, are funnel-shifted by 8 (fill & 7) onto acc, and every
+// COMPLETED word is deposited with one select per block word -- against one sixteen-way OR chain per byte in sha512_byte.
+struct Sha512Tail { Sha512 s; uint64_t acc; };
+AVRF_DI void sha512_deposit(Sha512 &s, uint32_t wi, uint64_t v) {
+#pragma unroll
+  for (int i = 0; i < 16; i++) s.w[i] = (wi == (uint32_t)i) ? v : s.w[i];
+}
+// take over a transcript whose position is s.fill: lift the word being filled out of the block
+AVRF_DI Sha512Tail sha512_tail_begin(const Sha512 &s) {
+  Sha512Tail t; t.s = s; t.acc = 0;
+  const uint32_t wi = s.fill >> 3;
+#pragma unroll
+  for (int i = 0; i < 16; i++) { if (wi == (uint32_t)i) { t.acc = s.w[i]; t.s.w[i] = 0; } }
+  return t;
+}
+// absorb the first nb bytes (1..8) of x, a big-endian word whose other bytes are zero
+AVRF_DI void sha512_tail_absorb(Sha512Tail &t, uint64_t x, uint32_t nb) {
+  const uint32_t k = t.s.fill & 7;
+  const uint64_t full = t.acc | (x >> (8 * k));
+  if (k + nb >= 8) {
+    sha512_deposit(t.s, t.s.fill >> 3, full);
+    t.acc = k ? x << (64 - 8 * k) : 0ULL;
+    t.s.fill += nb; t.s.total += nb;
+    if (t.s.fill >= 128) { const uint32_t rest = t.s.fill - 128; sha512_flush(t.s); t.s.fill = rest; }
+  } else {
+    t.acc = full; t.s.fill += nb; t.s.total += nb;
+  }
+}
+// n bytes from memory (any alignment), eight to a step
+AVRF_DI void sha512_tail_bytes(Sha512Tail &t, const uint8_t *p, uint32_t n) {
+  for (uint32_t off = 0; off < n; off += 8) {
+    const uint32_t nb = n - off < 8 ? n - off : 8;
+    uint64_t x = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i++) if (i < nb) x |= (uint64_t)p[off + i] << (56 - 8 * i);
+    sha512_tail_absorb(t, x, nb);
+  }
+}
+// eight 32-bit little-endian words (a field element, a compressed point)
+AVRF_DI void sha512_tail_words(Sha512Tail &t, const uint32_t (&v)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) sha512_tail_absorb(t, ((uint64_t)__builtin_bswap32(v[2 * i]) << 32) | __builtin_bswap32(v[2 * i + 1]), 8);
+}
+// digest of what was absorbed, as eight big-endian words; the tail is passed by value and the caller's copy continues
+AVRF_DI void sha512_tail_final(Sha512Tail t, uint64_t (&out)[8]) {
+  const uint64_t bits = (uint64_t)t.s.total * 8;
+  const uint32_t k = t.s.fill & 7;
+  sha512_deposit(t.s, t.s.fill >> 3, t.acc | (0x8000000000000000ULL >> (8 * k)));
+  if (t.s.fill >= 112) sha512_flush(t.s);
+  t.s.w[15] = bits;
+  sha512_compress(t.s.h, t.s.w);
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[i] = t.s.h[i];
 }
 
 // ---- the transcript interface shared with shake_dev.h (XofTranscript<H>, src/utils/transcript.rs:103-195): kernels are

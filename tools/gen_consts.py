@@ -25,6 +25,7 @@ def field(name, p):
     s.append(f"  static constexpr uint32_t P[8] = {{{limbs(p)}}};")
     s.append(f"  static constexpr uint32_t ONE[8] = {{{limbs(R % p)}}};   /* R mod p */")
     s.append(f"  static constexpr uint32_t R2[8] = {{{limbs(R * R % p)}}};    /* R^2 mod p */")
+    s.append(f"  static constexpr uint32_t R3[8] = {{{limbs(R * R * R % p)}}};    /* R^3 mod p: a product of three plain values, two Montgomery steps deep, back to plain */")
     s.append(f"  static constexpr uint32_t HALF[8] = {{{limbs((p - 1) // 2)}}};  /* (p-1)/2, plain */")
     s.append(f"  static constexpr uint32_t NINV = 0x{ninv:08x}u;  /* -p^-1 mod 2^32 */")
     s.append(f"  static constexpr int BITS = {p.bit_length()};")
