@@ -365,6 +365,17 @@ class Context:
             raise AvrfError(f"avrf_msm_te_segments -> {st}")
         return [bytes(out)[64 * v: 64 * v + 64] for v in range(n_seg)]
 
+    def msm_segments_chain(self, n_seg, bases_xy, scalars, own_record=True):
+        """msm_segments through the chain's two halves (avrf_msm_te_segments_chain, a test probe): one chain whatever n_seg is;
+        own_record False: reported to a record of the call's own, as a pool slot's chain is."""
+        L = len(scalars) // 32 // n_seg if n_seg else 0
+        assert len(scalars) == 32 * n_seg * L and len(bases_xy) == 64 * n_seg * L
+        out = (C.c_uint8 * max(1, 64 * n_seg))()
+        st = lib().avrf_msm_te_segments_chain(self._h, C.c_size_t(n_seg), C.c_size_t(L), _u8(bases_xy), _u8(scalars), 1 if own_record else 0, out)
+        if st != OK:
+            raise AvrfError(f"avrf_msm_te_segments_chain -> {st}")
+        return [bytes(out)[64 * v: 64 * v + 64] for v in range(n_seg)]
+
     def pedersen_batch_verify(self, items_ios_xy, ads, proofs):
         b = Batch.from_items(items_ios_xy, ads, proofs=proofs)
         return lib().avrf_pedersen_batch_verify(self._h, C.c_size_t(b.n), b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
@@ -601,6 +612,7 @@ class Pool:
             raise AvrfError(f"avrf_pool_create -> {st}")
         self.kind = kind
         self._keep = {}                                         # ticket -> batch object (its buffers must outlive the run)
+        self._segs = {}                                         # segmented tickets -> number of segments
 
     def close(self):
         if self._h:
@@ -650,6 +662,33 @@ class Pool:
         """b: a Batch / PinnedBatch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes (compressed points)"""
         return self._submit("avrf_pool_submit_wire", b, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, int(validate))
 
+    def submit_segments(self, b, seg_items):
+        """A segmented job (avrf_pool_submit_segments): b as for submit, one verdict per run of seg_items[v] items.  Returns the ticket."""
+        t = self._submit("avrf_pool_submit_segments", b, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs,
+                         C.c_size_t(len(seg_items)), _u32(seg_items))
+        self._segs[t] = len(seg_items)
+        return t
+
+    def submit_segments_wire(self, b, seg_items, validate=1):
+        """The same from wire bytes (b as for submit_wire)."""
+        t = self._submit("avrf_pool_submit_segments_wire", b, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs,
+                         int(validate), C.c_size_t(len(seg_items)), _u32(seg_items))
+        self._segs[t] = len(seg_items)
+        return t
+
+    def wait_segments(self, ticket, cap=None):
+        """-> (status, statuses) of a segmented ticket: the job's status (the largest of its segments') and one status per segment, or
+        None in their place when the job ended before any verdict (a staging error).  cap: room for that many statuses (default: the
+        ticket's segments)."""
+        unwritten = -(1 << 31)
+        n_seg = self._segs.get(ticket, 0) if cap is None else int(cap)
+        s, out = C.c_int(0), (C.c_int32 * max(1, n_seg))(*([unwritten] * max(1, n_seg)))
+        st = lib().avrf_pool_wait_segments(self._h, C.c_uint64(ticket), C.byref(s), out, C.c_size_t(n_seg))
+        if st != OK:
+            raise AvrfError(f"avrf_pool_wait_segments -> {st}")
+        got = list(out)[:n_seg]
+        return s.value, (None if unwritten in got else got)
+
     def wait(self, ticket):
         s = C.c_int(0)
         st = lib().avrf_pool_wait(self._h, C.c_uint64(ticket), C.byref(s))
@@ -663,6 +702,8 @@ class Pool:
         if st != OK:
             raise AvrfError(f"avrf_pool_resubmit -> {st}")
         self._keep[t.value] = self._keep.pop(ticket, None)
+        if ticket in self._segs:
+            self._segs[t.value] = self._segs.pop(ticket)
         return t.value
 
     def cycle(self, steps_block, min_seconds=0.0, from_host=False, max_steps=0, expect=0):

@@ -847,94 +847,187 @@ int avrf_pedersen_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_it
 
 // The segmented run of either batch verifier (include/avrf.h avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments).  What the
 // kind decides: the record and weight sizes (kind_facts), the scratch per item, the terms and flags launches, n_terms in seg_layout.
+// Where a segmented run's padded term arrays live.  A context keeps arrays of its own for them, so that the plain run's terms on its lane
+// stay what they were (avrf_batch_last_terms, avrf_*_segment_terms).  A pool slot uses the term arrays of the lane it borrows, as a plain
+// pool job does: a slot that held them itself would grow by padded x 128 bytes (134 MB at the limit, times every slot).  Several chains
+// queue on one lane, and reusing the lane's arrays is safe for the reason it is safe for plain jobs: everything that writes and reads
+// them -- the copies up, the zeroing, the terms kernel, the chain -- is enqueued on the lane's one stream, so the next job's writes run
+// behind this job's last read; and an array that has to grow is freed by hipFree, which waits for the device first.
+struct SegArrays { DevBuf &scalars, &pre; };
+static SegArrays seg_arrays(avrf_ctx *c) { return c->lane_owner ? SegArrays{c->d_seg_scalars, c->d_seg_pre} : SegArrays{c->L->d_scalars, c->L->d_pre}; }
+static int seg_ensure(avrf_ctx *c, int kind) {
+  const avrf_ctx::SegRun &r = c->seg; const SegArrays a = seg_arrays(c);
+  // (scratch per item: Thin's w s z0, Pedersen's u s and u sb)
+  HIP_TRY(a.scalars.ensure(r.padded * 32)); HIP_TRY(a.pre.ensure(r.padded * sizeof(te_pre_raw))); HIP_TRY(c->L->d_seg_wsz.ensure(c->n * (kind == Thin ? 32 : 64)));
+  HIP_TRY(c->L->d_seg_off.ensure((r.n_seg + 1) * 4)); HIP_TRY(c->L->d_seg_seeds.ensure(r.n_seg * sizeof(Seed64)));
+  return AVRF_OK;
+}
 static void launch_seg_terms(avrf_ctx *c, int kind, const BatchDev &b, size_t n_seg, size_t L) {
-  const uint32_t *off = c->d_seg_off.as<uint32_t>(); const Seed64 *seeds = c->d_seg_seeds.as<Seed64>();
-  if (kind == Thin) AVRF_SEG(c->suite, thin_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_seg_wsz.as<uint32_t>(),
-                                                  c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
-  else AVRF_SEG(c->suite, ped_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_seg_wsz.as<uint32_t>(),
-                                    c->d_seg_scalars.as<uint32_t>(), c->d_seg_pre.as<te_pre_raw>(), c->stream));
+  const uint32_t *off = c->L->d_seg_off.as<uint32_t>(); const Seed64 *seeds = c->L->d_seg_seeds.as<Seed64>(); const SegArrays a = seg_arrays(c);
+  if (kind == Thin) AVRF_SEG(c->suite, thin_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_seg_wsz.as<uint32_t>(),
+                                                  a.scalars.as<uint32_t>(), a.pre.as<te_pre_raw>(), c->stream));
+  else AVRF_SEG(c->suite, ped_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_seg_wsz.as<uint32_t>(),
+                                    a.scalars.as<uint32_t>(), a.pre.as<te_pre_raw>(), c->stream));
 }
 static void launch_seg_item_flags(avrf_ctx *c, int kind, const BatchDev &b) {
   if (kind == Thin) AVRF_SEG(c->suite, item_flags(b, c->d_status.as<int32_t>(), c->stream));
   else AVRF_SEG(c->suite, ped_item_flags(b, c->d_status.as<int32_t>(), c->stream));
 }
 
-static int run_segments(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
-  if (!c || ctx_busy(c) || c->staged_kind != kind || c->n_shared || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
-  std::vector<uint32_t> seg_off; uint64_t lay[4];
-  if (int e = seg_layout(kind, c->n, n_seg, seg_items, c->h_io.as<uint32_t>(), &seg_off, lay)) return e;
-  for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;          // what an empty segment keeps (src/thin.rs:262-264, src/pedersen.rs:343-345)
-  if (!n_seg || !c->n) return AVRF_OK;
+namespace avrf {
+// h_seg_up: the item offsets, then (64-byte aligned) the seeds
+static size_t seg_up_seeds_at(size_t n_seg) { return ((n_seg + 1) * 4 + 63) / 64 * 64; }
+static bool seg_nothing(const avrf_ctx *c) { return !c->seg.n_seg || !c->n; }   // every (empty) segment is Ok: no device work at all
+
+int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items) {
+  if (!c || c->run_phase != 0 || c->staged_kind != kind || c->n_shared) return AVRF_ERR_BAD_ARG;
+  avrf_ctx::SegRun &r = c->seg; uint64_t lay[4];
+  if (int e = seg_layout(kind, c->n, n_seg, seg_items, c->h_io.as<uint32_t>(), &r.off, lay)) return e;
+  r.n_seg = n_seg; r.L = (size_t)lay[0]; r.padded = (size_t)lay[1]; r.item_status.clear();
+  if (seg_nothing(c)) { c->run_phase = 3; return AVRF_OK; }
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->n, L = (size_t)lay[0], padded = (size_t)lay[1];
-  const KindFacts &k = kind_facts(kind);
-  // (scratch per item: Thin's w s z0, Pedersen's u s and u sb)
-  HIP_TRY(c->d_seg_scalars.ensure(padded * 32)); HIP_TRY(c->d_seg_pre.ensure(padded * sizeof(te_pre_raw))); HIP_TRY(c->d_seg_wsz.ensure(n * (kind == Thin ? 32 : 64)));
-  HIP_TRY(c->d_seg_off.ensure((n_seg + 1) * 4)); HIP_TRY(c->d_seg_seeds.ensure(n_seg * sizeof(Seed64)));
+  HIP_TRY(c->h_seg_up.ensure(seg_up_seeds_at(n_seg) + n_seg * sizeof(Seed64)));
+  memcpy(c->h_seg_up.p, r.off.data(), (n_seg + 1) * 4);
+  if (c->lane_owner) if (int e = seg_ensure(c, kind)) return e;        // (a pool slot has no lane yet: seg_launch sizes the lane's arrays)
   // prepare once, for all segments: the prepare kernels know nothing about batches, and their records are contiguous per item
-  const double t0 = now_us();
   if (int e = batch_begin(c, kind)) return e;
-  c->run_phase = 0;                                                    // (the phases below are this call's own; an error leaves the context idle)
-  HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
+  c->run_phase = 3;
+  return AVRF_OK;
+}
+
+// the prepare kernel and the copies back have completed (the caller waited for c->stream or for an event behind them)
+int seg_collect(avrf_ctx *c, int kind) {
+  if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
+  if (seg_nothing(c)) return AVRF_OK;
+  c->run_phase = 0;                                                    // an error below leaves the context idle
+  if (c->wire_pending) {                                               // as batch_collect: a wire point that failed to decode / validate is the whole job's status
+    c->wire_pending = false;
+    if (c->h_flags.as<uint32_t>()[2]) { c->staged_kind = 0; return AVRF_INVALID_DATA; }
+  }
   // The flag word is the batch's.  Only when it is set: which items raised it -- the prepare kernel's checks again, per item, and
-  // the validation with a status per item (the clean case pays nothing).
-  std::vector<int32_t> item_status;
+  // the validation with a status per item (the clean case pays nothing).  This rare path WAITS for the stream it runs on, c->stream:
+  // a pool worker sits here for one prepare-sized kernel on its ingest stream, where only its own stagings queue.
   if (*c->h_flags.as<uint32_t>()) {
-    item_status.resize(n);
+    const size_t n = c->n;
+    HIP_TRY(hipSetDevice(c->device));
+    c->seg.item_status.resize(n);
     HIP_TRY(c->d_status.ensure(n * 4));
     HIP_TRY(hipMemsetAsync(c->d_status.p, 0, n * 4, c->stream));
     launch_seg_item_flags(c, kind, batch_of(c));
     validate_staged(c, kind, c->d_status.as<int32_t>());
-    HIP_TRY(hipMemcpyAsync(item_status.data(), c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->seg.item_status.data(), c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
   }
-  // the n_seg weight transcripts, each SUITE_ID || 0x50 || its own records (src/thin.rs:274-279, src/pedersen.rs:361-367), on the process's host pool
-  const double t1 = now_us();
-  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
-  BatchDev b = batch_of(c);
-  std::vector<Seed64> seeds(n_seg);
   if (!suite_host_weights(c->suite)) {
+    uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+    c->h_seg_msg.resize(c->seg.n_seg * pl + c->n * kind_facts(kind).record());
+  } else c->h_weights.resize(c->n * kind_facts(kind).weight);
+  c->run_phase = 3;
+  return AVRF_OK;
+}
+
+// The weight transcript of segment v, SUITE_ID || 0x50 || its own records (src/thin.rs:274-279, src/pedersen.rs:361-367), built in
+// h_seg_msg at a place of its own (distinct v may be built from different threads) and described for sha512_many; seg_seed takes its digest.
+void seg_job(avrf_ctx *c, int kind, size_t v, WeightJob *job) {
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix), recsz = kind_facts(kind).record();
+  const size_t first = c->seg.off[v], items = c->seg.off[v + 1] - first;
+  uint8_t *m = c->h_seg_msg.data() + v * pl + first * recsz;
+  memcpy(m, prefix, pl); memcpy(m + pl, c->h_msg.as<uint8_t>() + pl + first * recsz, items * recsz);
+  *job = WeightJob::whole(m, pl + items * recsz);
+}
+void seg_seed(avrf_ctx *c, size_t v, const uint8_t digest[64]) {
+  ((Seed64 *)(c->h_seg_up.as<uint8_t>() + seg_up_seeds_at(c->seg.n_seg)))[v] = seed_of(digest);
+}
+int seg_hash(avrf_ctx *c, int kind, bool spread) {
+  if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
+  if (seg_nothing(c)) return AVRF_OK;
+  const size_t n_seg = c->seg.n_seg; const std::vector<uint32_t> &off = c->seg.off;
+  auto each = [&](size_t count, auto fn) { if (spread) parallel_for(count, fn); else for (size_t i = 0; i < count; i++) fn(i); };
+  if (!suite_host_weights(c->suite))
     // counter-mode transcripts: sixteen messages at a time through the multi-buffer hash; a group builds its messages itself
-    const size_t recsz = k.record();
-    const uint8_t *rec = c->h_msg.as<uint8_t>() + pl;
-    c->h_seg_msg.resize(n_seg * pl + n * recsz);
-    parallel_for((n_seg + 15) / 16, [&](size_t g) {
+    each((n_seg + 15) / 16, [&](size_t g) {
       WeightJob jobs[16]; WeightJob *pj[16]; int cnt = 0;
-      for (size_t v = 16 * g; v < n_seg && v < 16 * g + 16; v++, cnt++) {
-        const size_t first = seg_off[v], items = seg_off[v + 1] - first;
-        uint8_t *m = c->h_seg_msg.data() + v * pl + first * recsz;
-        memcpy(m, prefix, pl); memcpy(m + pl, rec + first * recsz, items * recsz);
-        jobs[cnt] = WeightJob::whole(m, pl + items * recsz); pj[cnt] = &jobs[cnt];
-      }
+      for (size_t v = 16 * g; v < n_seg && v < 16 * g + 16; v++, cnt++) { seg_job(c, kind, v, &jobs[cnt]); pj[cnt] = &jobs[cnt]; }
       sha512_many(pj, cnt);
-      for (int i = 0; i < cnt; i++) seeds[16 * g + i] = seed_of(jobs[i].digest);
+      for (int i = 0; i < cnt; i++) seg_seed(c, 16 * g + i, jobs[i].digest);
     });
-    HIP_TRY(hipMemcpyAsync(c->d_seg_seeds.p, seeds.data(), n_seg * sizeof(Seed64), hipMemcpyHostToDevice, c->stream));
-  } else {
+  else
     // sponge / SHA-256 transcripts: every segment's weight stream squeezed on the host, item j's 16 (Pedersen: 32) bytes at 16 (32) j
-    c->h_weights.resize(n * k.weight);
-    parallel_for(n_seg, [&](size_t v) { if (seg_off[v + 1] != seg_off[v]) squeeze_weights(c, kind, seg_off[v], seg_off[v + 1] - seg_off[v]); });
-    HIP_TRY(c->d_weights.ensure(n * k.weight));
-    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), n * k.weight, hipMemcpyHostToDevice, c->stream));
+    each(n_seg, [&](size_t v) { if (off[v + 1] != off[v]) squeeze_weights(c, kind, off[v], off[v + 1] - off[v]); });
+  return AVRF_OK;
+}
+
+int seg_launch(avrf_ctx *c, int kind) {
+  if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
+  if (seg_nothing(c)) { c->run_phase = 4; return AVRF_OK; }
+  c->run_phase = 0;                                                    // an error below leaves the context idle
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n_seg = c->seg.n_seg, L = c->seg.L, padded = c->seg.padded;
+  if (int e = seg_ensure(c, kind)) return e;
+  BatchDev b = batch_of(c);
+  if (!suite_host_weights(c->suite))
+    HIP_TRY(hipMemcpyAsync(c->L->d_seg_seeds.p, c->h_seg_up.as<uint8_t>() + seg_up_seeds_at(n_seg), n_seg * sizeof(Seed64), hipMemcpyHostToDevice, c->stream));
+  else {
+    const size_t wbytes = c->n * kind_facts(kind).weight;
+    HIP_TRY(c->d_weights.ensure(wbytes));
+    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), wbytes, hipMemcpyHostToDevice, c->stream));
     b.weights = c->d_weights.as<uint8_t>();
   }
-  // terms into the padded layout (the padding scalars are zeroed on every run), then all segments' MSMs in one chain
+  // terms into the padded layout (the padding scalars are zeroed on every run), then all segments' MSMs in ONE chain
+  const SegArrays a = seg_arrays(c);
   const double t2 = now_us();
-  HIP_TRY(hipMemcpyAsync(c->d_seg_off.p, seg_off.data(), (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_seg_scalars.p, 0, padded * 32, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->L->d_seg_off.p, c->h_seg_up.p, (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(a.scalars.p, 0, padded * 32, c->stream));
   launch_seg_terms(c, kind, b, n_seg, L);
   const double t3 = now_us();
-  std::vector<HostExt> sums(n_seg);
-  if (int e = lane_msm_segments(c, c->d_seg_pre, c->d_seg_scalars, L, n_seg, sums.data())) return e;
-  for (size_t v = 0; v < n_seg; v++) {
-    if (seg_off[v] == seg_off[v + 1]) continue;
+  c->timing[3] = t3 - t2;
+  // a context's own call keeps msm_te_segments' choice (fewer than eight segments: one MSM each, waited for) in seg_end; a chain
+  // that others queue behind -- a pool slot's -- is enqueued here, one chain whatever n_seg is
+  if (!c->lane_owner)
+    if (int e = msm_guarded([&] { return msm_te_segments_enqueue(c->suite, a.pre.as<te_pre_raw>(), a.scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->chain(), c->stream); })) return e;
+  c->run_msm_us = now_us() - t3;
+  c->run_phase = 4;
+  return AVRF_OK;
+}
+
+int seg_end(avrf_ctx *c, int kind, int32_t *status_out) {
+  if (!c || c->staged_kind != kind || c->run_phase != 4 || (c->seg.n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
+  c->run_phase = 0;
+  avrf_ctx::SegRun &r = c->seg;
+  for (size_t v = 0; v < r.n_seg; v++) status_out[v] = AVRF_OK;        // what an empty segment keeps (src/thin.rs:262-264, src/pedersen.rs:343-345)
+  if (seg_nothing(c)) return AVRF_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<HostExt> sums(r.n_seg);
+  const SegArrays a = seg_arrays(c);
+  if (c->lane_owner) { if (int e = lane_msm_segments(c, a.pre, a.scalars, r.L, r.n_seg, sums.data())) return e; }
+  else if (int e = msm_guarded([&] { return msm_te_segments_finish(c->suite, c->L->ws, c->chain(), c->stream, sums.data()); })) return e;
+  for (size_t v = 0; v < r.n_seg; v++) {
+    if (r.off[v] == r.off[v + 1]) continue;
     status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
-    for (size_t j = seg_off[v]; !item_status.empty() && j < seg_off[v + 1]; j++) if (item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // src/thin.rs:266-271, src/pedersen.rs:348-353
+    for (size_t j = r.off[v]; !r.item_status.empty() && j < r.off[v + 1]; j++) if (r.item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // src/thin.rs:266-271, src/pedersen.rs:348-353
   }
-  c->seg_gen = c->stage_gen; c->seg_L = L; c->seg_off = std::move(seg_off);
+  if (c->lane_owner) { c->seg_gen = c->stage_gen; c->seg_L = r.L; c->seg_off = r.off; }   // what avrf_*_segment_terms describes
+  return AVRF_OK;
+}
+}  // namespace avrf
+
+// the context's call: the phases one after the other, waiting for the stream between them
+static int run_segments(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  if (!c || ctx_busy(c) || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
+  const double t0 = now_us();
+  if (int e = seg_begin(c, kind, n_seg, seg_items)) return e;
+  for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;
+  if (!n_seg || !c->n) { c->run_phase = 0; return AVRF_OK; }
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) { c->run_phase = 0; (void)hipGetLastError(); return AVRF_ERR_NO_DEVICE; }
+  if (int e = seg_collect(c, kind)) return e;
+  const double t1 = now_us();
+  if (int e = seg_hash(c, kind, /*spread=*/true)) { c->run_phase = 0; return e; }
+  const double t2 = now_us();
+  if (int e = seg_launch(c, kind)) return e;
+  if (int e = seg_end(c, kind, status_out)) return e;
   // avrf_last_timing: prepare + its wait (and the attribution pass), the transcripts, the terms launches, the MSM chain with its wait
   const double t4 = now_us();
-  c->timing[1] = t1 - t0; c->timing[2] = t2 - t1; c->timing[3] = t3 - t2; c->timing[4] = t4 - t3; c->timing[5] = 0; c->timing[0] = t4 - t0;
+  c->timing[1] = t1 - t0; c->timing[2] = t2 - t1; c->timing[4] = t4 - t2 - c->timing[3]; c->timing[5] = 0; c->timing[0] = t4 - t0;
   return AVRF_OK;
 }
 // the terms of one segment of the last segmented run, as avrf_batch_last_terms gives the plain run's
@@ -995,6 +1088,33 @@ int avrf_msm_te_segments(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bas
   }
   c->staged_kind = 0;
   if (int e = lane_msm_segments(c, c->L->d_pre, c->L->d_scalars, L, n_seg, sums.data())) return e;
+  if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
+  for (size_t v = 0; v < n_seg; v++) finish_point(c, sums[v], out_xy + 64 * v);
+  return AVRF_OK;
+}
+// Test probe: the same MSMs through the two halves of the chain (msm.h msm_te_segments_enqueue / _finish) -- ONE chain whatever n_seg is,
+// no per-segment loop below eight.  own_record != 0: the lane's own record, finish waits for the stream.  0: a record of the call's own,
+// as a pool slot hands in; the call waits for the stream itself before it finishes, which then does not.
+int avrf_msm_te_segments_chain(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, int own_record, uint8_t *out_xy) {
+  if (!c || ctx_busy(c) || (n_seg && !out_xy) || (n_seg && L && (!bases_xy || !scalars)) || n_seg > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  uint64_t lay[4];
+  if (int e = seg_limits(n_seg < 8 ? 8 : n_seg, L, lay)) return e;     // (the windows limit holds for every n_seg here: there is no looped route)
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = n_seg * L;
+  for (size_t i = 0; i < n; i++) if (!scalar_in_range(c->suite, scalars + 32 * i)) return AVRF_INVALID_DATA;
+  std::vector<HostExt> sums(n_seg);
+  if (n) {
+    if (int e = upload_bases_and_scalars(c, n, bases_xy, scalars, n * 32)) return e;
+    launch_pre_from_affine(c->suite, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<te_pre_raw>(), c->d_flags.as<uint32_t>(), 0, c->stream);
+    HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  c->staged_kind = 0;
+  MsmChain mine;
+  MsmChain &rec = own_record ? c->L->ws.own : mine;
+  int st = msm_guarded([&] { return msm_te_segments_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), L, n_seg, c->L->ws, rec, c->stream); });
+  if (st == AVRF_OK && !own_record && hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); st = AVRF_ERR_NO_DEVICE; }
+  if (st == AVRF_OK) st = msm_guarded([&] { return msm_te_segments_finish(c->suite, c->L->ws, rec, c->stream, sums.data()); });
+  if (st != AVRF_OK) { (void)hipStreamSynchronize(c->stream); rec.disarm(); return st; }   // (`mine` must not go while a copy into it is in flight)
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   for (size_t v = 0; v < n_seg; v++) finish_point(c, sums[v], out_xy + 64 * v);
   return AVRF_OK;

@@ -48,6 +48,9 @@ struct Lane : LaneStream {
   MsmWorkspace ws;
   DevBuf d_scalars, d_pre, d_gpart;
   DevBuf d_shared;                // a shared-table batch: the row scalars' contributions and partial sums of the chain being built (thin_shared.h)
+  // a segmented run (seg_launch below): the terms kernel's per-item scratch (Thin w s z0, n x 32 bytes; Pedersen u s and u sb, n x 64),
+  // the n_seg + 1 item offsets and the n_seg weight seeds of the chain being built
+  DevBuf d_seg_wsz, d_seg_off, d_seg_seeds;
 };
 
 }  // namespace avrf
@@ -81,12 +84,17 @@ struct avrf_ctx {
   avrf::PinBuf h_c, h_flags, h_io;
   // the last segmented run of the staged batch (avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments; thin_seg.h): terms of its
   // own, n_seg * seg_L of them, so that the plain run's terms stay what they were; seg_off (n_seg + 1 item offsets) describes them while
-  // seg_gen == stage_gen.  d_seg_wsz: per-item scratch of the terms kernel (Thin w s z0, n x 32 bytes; Pedersen u s and u sb, n x 64)
+  // seg_gen == stage_gen.  (A pool slot has neither: its segmented terms go to the arrays of the lane it borrows, seg_launch.)
   uint64_t seg_gen = 0; size_t seg_L = 0; std::vector<uint32_t> seg_off;
-  avrf::DevBuf d_seg_scalars, d_seg_pre, d_seg_wsz, d_seg_off, d_seg_seeds;
+  avrf::DevBuf d_seg_scalars, d_seg_pre;
   std::vector<uint8_t> h_seg_msg;   // the segments' weight-transcript messages, prefix || records each
+  // the segmented run in flight (seg_begin .. seg_end, run_phase 3 and 4): its layout, the per-item statuses of the attribution pass
+  // (empty unless the batch's flag word was set) and, page-locked so that the copies up never wait for the lane, the item offsets
+  // (n_seg + 1 words, padded to 64 bytes) followed by the n_seg weight seeds
+  struct SegRun { size_t n_seg = 0, L = 0, padded = 0; std::vector<uint32_t> off; std::vector<int32_t> item_status; } seg;
+  avrf::PinBuf h_seg_up;
   double timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int run_phase = 0;              // batch_begin / batch_hash / batch_end
+  int run_phase = 0;              // batch_begin / batch_hash / batch_end: 1, 2; a segmented run (seg_begin .. seg_end): 3, 4
   bool unit_weights = false;      // batch_launch: every item's weight is 1 (avrf_thin_verify runs ONE item as its own equation through the MSM path)
   double run_t0 = 0, run_begin_us = 0, run_msm_us = 0;
   // The order a context goes in: its device made current and its own stream drained; then the members, last first -- the staging
@@ -137,5 +145,26 @@ int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]);            // the wei
 void sha512_many(WeightJob *const *jobs, int k);                      // k <= 16 transcripts hashed together: scalar, eight or sixteen lanes, as the host CPU allows
 int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]);    // terms kernel + MSM chain enqueued on c->stream / c->L
 int batch_end(avrf_ctx *c, int kind);                                 // waits for the chain, folds, verdict
+// The segmented run of a staged Thin or Pedersen batch (include/avrf.h avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments) in
+// phases of the same discipline: each refuses out of order, an error leaves the context idle.  run_phase 3 from seg_begin, 4 from seg_launch.
+//   seg_begin    layout check (counts, limits), buffer sizing, batch_begin: validation + prepare kernel + copies back on c->stream
+//   seg_collect  (c->stream's work has completed) a wire batch's decode flag; only when the batch's flag word is set, the per-item
+//                attribution pass, which waits for c->stream
+//   seg_hash     the n_seg weight transcripts on the calling thread (spread: and the process's host pool): counter-mode suites hash
+//                prefix || the segment's records, sponge / SHA-256 suites squeeze every segment's weight stream.  A caller that hashes
+//                several contexts' transcripts together (pool.hip) takes the counter-mode messages one by one instead: seg_job builds
+//                message v and describes it, seg_seed stores its digest
+//   seg_launch   seeds and offsets up, padding scalars zeroed, terms kernel; a pool slot: ONE chain enqueued on c->stream / c->L with
+//                c->chain(), whatever n_seg is
+//   seg_end      a pool slot: collects the chain (waits for the stream only with the lane's own record).  A context of its own lane
+//                runs msm_te_segments here instead, which keeps that call's loop of single MSMs below eight segments.  Then
+//                status_out[0 .. n_seg), the per-item statuses folded in
+int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items);
+int seg_collect(avrf_ctx *c, int kind);
+int seg_hash(avrf_ctx *c, int kind, bool spread);
+void seg_job(avrf_ctx *c, int kind, size_t v, WeightJob *job);
+void seg_seed(avrf_ctx *c, size_t v, const uint8_t digest[64]);
+int seg_launch(avrf_ctx *c, int kind);
+int seg_end(avrf_ctx *c, int kind, int32_t *status_out);
 double now_us();
 }  // namespace avrf

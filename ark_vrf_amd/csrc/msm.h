@@ -138,8 +138,16 @@ int msm_te_small_vectors(int suite, const te_pre_raw *d_pre, const uint32_t *d_s
 constexpr size_t MSM_SEG_TERMS_MAX = 8191;          // L: keeps nb <= 256, so one reduction kernel (k_bits_direct)
 constexpr size_t MSM_SEG_WINDOWS_MAX = 65535;       // n_seg * nwin: the sort kernels carry the virtual window in blockIdx.y
 int msm_te_segments(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out);
+// the chain in two halves, under the contract of msm_te_enqueue / msm_te_finish: msm_te_segments_enqueue launches the whole chain and
+// the copy back of the n_seg finished points on `stream` and returns without waiting -- always ONE chain, whatever n_seg >= 1 is (no
+// per-segment loop below eight) -- and msm_te_segments_finish collects it and folds out[0 .. n_seg).  ws.own: finish waits for the
+// stream.  A caller's record (every suite: the device Horner's points fit any record): finish does NOT wait, the caller has seen an
+// event recorded behind the chain complete.  Beyond the limits above enqueue returns -1 with nothing launched and the record not armed;
+// finish on a record that no enqueue armed returns -1.
+int msm_te_segments_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream);
+int msm_te_segments_finish(int suite, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out);
 int msm_segments_window_bits(size_t L);             // the window width msm_plan gives an L-term MSM (host arithmetic)
-bool msm_te_pending_supported(int suite);   // a caller's record is taken by the window-sum form of the chain only
+bool msm_te_pending_supported(int suite);   // msm_te_enqueue: a caller's record is taken by the window-sum form of the chain only
 
 // G1 MSM over a short-Weierstrass curve (curve: 0 BLS12-381, 1 BN254): d_bases = n Montgomery affine
 // points (2 * Fq words each, (0,0) = infinity), d_scalars = n plain 256-bit scalars (< r).

@@ -932,10 +932,11 @@ template <class CV> static void tail_device_horner(const MsmRun &r) {
   else rowcol_bits<CV>(r);
   if constexpr (CV::QUAD) hipLaunchKernelGGL(k_horner_quads<typename CV::suite>, dim3(batch), dim3(64), 0, r.stream, r.ws.bits.as(), vbits, r.ws.rc.as());   // a wave per MSM (te_quad.h)
   else hipLaunchKernelGGL(k_horner<CV>, dim3((batch + 63) / 64), dim3(64), 0, r.stream, r.ws.bits.as(), vbits, batch, r.ws.rc.as());                      // a lane per MSM
+  r.rec.ensure((size_t)batch * r.acc_bytes);   // the `batch` finished points, whoever's record it is (chain_accumulate sized it for the window triples already: no growth here)
   copy_back(r.rec, r.ws.rc, MsmResult{MsmResult::POINTS, batch, 1, (size_t)CV::ACC_WORDS}, r.stream);
 }
 // Enqueues the device pipeline of o.batch MSMs: the single launch, or sort, accumulation and the tail msm_tail picks; collects it unless
-// o.defer.  `rec`: the workspace's own record or a caller's (single-launch and window-sum forms only).  Throws HipFailure when a HIP call fails.
+// o.defer.  `rec`: the workspace's own record or a caller's (window-sum form and the segmented chain's device Horner only).  Throws HipFailure when a HIP call fails.
 template <class CV>
 static void msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_t n_in, int scalar_bits, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream,
                        const MsmLaunch &o = MsmLaunch()) {
@@ -959,7 +960,8 @@ static void msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_
     r.tile_len = tile_len_for(r.n, r.vwin); r.ntiles = (uint32_t)((r.n + r.tile_len - 1) / r.tile_len);
     chain_sort(d_scalars, n_in, dig_nwin, lanes_target, r);
     chain_accumulate<CV>(d_bases, lanes_max, red, r);
-    if (tail != MsmTail::WINDOW_TRIPLES && !ws.owns(rec)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // a caller's record is taken by the window-sum form only
+    // a caller's record is taken by the tails that size it: the window triples and the finished points of the segmented chain
+    if (tail != MsmTail::WINDOW_TRIPLES && tail != MsmTail::DEVICE_HORNER && !ws.owns(rec)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};
     if constexpr (CV::WINDOW_SUMS) if (tail == MsmTail::WINDOW_TRIPLES) tail_window_triples<CV>(r);
     if constexpr (CV::FIXED_TABLE) if (tail == MsmTail::TABLE_WSUM) tail_table_wsum<CV>(r);
     if constexpr (!CV::FIXED_TABLE) if (tail == MsmTail::DEVICE_HORNER) tail_device_horner<CV>(r);
@@ -1019,8 +1021,39 @@ int msm_te_small_vectors(int suite, const te_pre_raw *d_pre, const uint32_t *d_s
   return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_small_vectors_impl<S>(d_pre, d_scalars, n, n_vectors, ws, stream, out); });
 }
 // n_seg independent MSMs of L terms each in ONE chain: vector v over bases of its own (MsmLaunch::base_stride), bucket sums by
-// k_bits_direct (L <= 8191 keeps nb <= 256), the Horner on the device, n_seg finished points back.  Fewer than MSM_SEG_CHAIN_MIN
-// vectors loop the single-MSM path instead; the threshold has not been measured, and this is the one place it is written.
+// k_bits_direct (L <= 8191 keeps nb <= 256), the Horner on the device, n_seg finished points back.  The chain comes in two halves, as
+// msm_te_enqueue / msm_te_finish do: everything launched and `defer`red, then collected and folded.  The enqueue form runs ONE chain
+// whatever n_seg >= 1 is; every limit is checked before anything is launched.
+template <class S>
+static int msm_te_segments_enqueue_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
+  if (L > MSM_SEG_TERMS_MAX || n_seg * L > 0x7fffffffull) return -1;
+  const size_t vwin = n_seg * (size_t)msm_plan(L ? L : 1, S::Fr::BITS).nwin;
+  // k_hist / k_scan_tiles take the virtual window as blockIdx.y; the sorted array is addressed by 32-bit entry offsets
+  if (L && (vwin > MSM_SEG_WINDOWS_MAX || vwin * L >= 0xffff0000ull)) return -1;
+  rec.n = n_seg * L; rec.armed = true;
+  rec.res = MsmResult{MsmResult::POINTS, n_seg, 1, (size_t)TeCurve<S>::ACC_WORDS};   // what the tail's copy back will say again; all there is to say when no term exists
+  MsmLaunch o; o.batch = n_seg; o.scalar_stride = L; o.base_stride = L; o.defer = true;
+  if (rec.n) msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, L, S::Fr::BITS, ws, rec, stream, o);
+  return 0;
+}
+template <class S>
+static int msm_te_segments_finish_impl(MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out) {
+  if (!rec.armed) return -1;                              // nothing was enqueued (or another call consumed the chain): an error, never identities
+  rec.disarm();
+  const size_t n_seg = rec.res.vectors;
+  if (rec.n == 0) { for (size_t v = 0; v < n_seg; v++) out[v] = HostTe<S>::identity(); return 0; }
+  msm_collect(ws, rec, stream);
+  for (size_t v = 0; v < n_seg; v++) out[v] = msm_fold<HostTe<S>>(rec, v);
+  return 0;
+}
+int msm_te_segments_enqueue(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream) {
+  return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_segments_enqueue_impl<S>(d_pre, d_scalars, L, n_seg, ws, rec, stream); });
+}
+int msm_te_segments_finish(int suite, MsmWorkspace &ws, MsmChain &rec, hipStream_t stream, HostExt *out) {
+  return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_segments_finish_impl<S>(ws, rec, stream, out); });
+}
+// The synchronous call.  Fewer than MSM_SEG_CHAIN_MIN vectors loop the single-MSM path instead of the chain; the threshold has not
+// been measured, and this is the one place it is written.
 constexpr size_t MSM_SEG_CHAIN_MIN = 8;
 template <class S>
 static int msm_te_segments_impl(const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
@@ -1035,15 +1068,8 @@ static int msm_te_segments_impl(const te_pre_raw *d_pre, const uint32_t *d_scala
     }
     return 0;
   }
-  const MsmPlan p = msm_plan(L, S::Fr::BITS);
-  const size_t vwin = n_seg * (size_t)p.nwin;
-  // k_hist / k_scan_tiles take the virtual window as blockIdx.y; the sorted array is addressed by 32-bit entry offsets
-  if (vwin > MSM_SEG_WINDOWS_MAX || vwin * L >= 0xffff0000ull) return -1;
-  MsmLaunch o; o.batch = n_seg; o.scalar_stride = L; o.base_stride = L;
-  msm_device<TeCurve<S>>((const uint32_t *)d_pre, d_scalars, L, S::Fr::BITS, ws, ws.own, stream, o);
-  ws.own.disarm();
-  for (size_t v = 0; v < n_seg; v++) out[v] = msm_fold<HT>(ws.own, v);
-  return 0;
+  if (int e = msm_te_segments_enqueue_impl<S>(d_pre, d_scalars, L, n_seg, ws, ws.own, stream)) return e;
+  return msm_te_segments_finish_impl<S>(ws, ws.own, stream, out);
 }
 int msm_te_segments(int suite, const te_pre_raw *d_pre, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, HostExt *out) {
   return te_call(suite, [&](auto tag) { using S = typename decltype(tag)::type; return msm_te_segments_impl<S>(d_pre, d_scalars, L, n_seg, ws, stream, out); });

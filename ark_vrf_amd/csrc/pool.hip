@@ -17,6 +17,10 @@
 // workers call the same stager and phases (capi_internal.h: ctx_stage over that source, whatever its flavour; batch_begin / _collect /
 // _seed / _launch / _end; grouped hashing through sha512_many), each under `guarded` -- a failed HIP call or allocation inside a
 // worker becomes the batch's status, never an exception off the thread.
+// A SEGMENTED job (avrf_pool_submit_segments: one verdict per run of consecutive items, include/avrf.h) walks the same states through the
+// segmented phases (seg_begin / _collect / seg_job + seg_seed or seg_hash / seg_launch / seg_end): its n_seg transcripts go through the
+// same grouped hash, so a slot with many segments fills groups by itself and segments of different slots share a group, and its MSMs are
+// ONE chain on the lane.  Plain and segmented jobs share slots, lanes and workers.
 #include "capi_internal.h"
 #include "suite_dispatch.h"
 #include "host_sha512_mb.h"
@@ -49,6 +53,10 @@ struct Slot {
   uint64_t seq = 0;               // order in which the worker enqueued the slot's current phase (oldest is waited for first)
   BatchSource src;                // the host sources, as submitted (the caller keeps them alive while the slot may stage from them)
   uint8_t digest[64];
+  // a segmented job: the items per segment (copied at submission, kept for resubmission and the cycle), the statuses of the last run
+  // (seg_have: that run reached its verdicts) and how many of the run's transcripts have been hashed
+  bool segmented = false, seg_have = false;
+  std::vector<uint32_t> seg_items; std::vector<int32_t> seg_status; size_t seg_hashed = 0;
   // the event, the record, then the context: it has no stream or workspace of its own and is detached from the pool's lane before it dies
   ~Slot() {
     ev.destroy(); pend.release();
@@ -130,29 +138,46 @@ struct Run {
       st = guarded([&] { return ctx_stage(c, S.src, /*wait=*/false); });
       S.has_batch = st == AVRF_OK;
     }
-    if (st == AVRF_OK) st = guarded([&] { return batch_begin(c, P->kind); });
+    S.seg_have = false; S.seg_hashed = 0;
+    if (st == AVRF_OK) st = guarded([&] { return S.segmented ? seg_begin(c, P->kind, S.seg_items.size(), S.seg_items.data()) : batch_begin(c, P->kind); });
     if (st == AVRF_OK && hipEventRecord(S.ev, c->stream) != hipSuccess) { (void)hipGetLastError(); st = AVRF_ERR_NO_DEVICE; }
     W.cpu_us[0] += thread_cpu_us() - t0;
     if (st != AVRF_OK) { done(S, st); return; }
     S.seq = ++seq; S.state = S_BEGUN;
   }
 
+  // transcripts waiting in `ready`: one per plain slot, the segments not hashed yet of a segmented one
+  static bool own_stream(avrf_pool *P, const Slot &S) { return suite_host_weights(P->suite) || S.c->n == 0 || (S.segmented && S.seg_items.empty()); }
+  size_t waiting(const std::vector<int> &ready) const {
+    size_t k = 0;
+    for (int si : ready) { const Slot &S = P->slots[si]; k += S.segmented && !own_stream(P, S) ? S.seg_items.size() - S.seg_hashed : 1; }
+    return k;
+  }
+  // up to `count` <= 16 transcripts from the front of `ready`, hashed together; a slot leaves `ready` with its last transcript
   void hash(std::vector<int> &ready, size_t count) {
     const double t0 = thread_cpu_us();
-    WeightJob jobs[16]; WeightJob *pj[16]; Slot *ss[16]; int k = 0;
-    for (size_t i = 0; i < count; i++) {
-      Slot &S = P->slots[ready[i]];
-      if (suite_host_weights(P->suite) || S.c->n == 0) {               // sponge transcripts squeeze their own stream; empty batches have no transcript
-        int st = guarded([&] { return batch_seed(S.c, P->kind, S.digest); });
+    WeightJob jobs[16]; WeightJob *pj[16]; Slot *ss[16]; size_t seg[16]; int k = 0;
+    size_t taken = 0, used = 0;
+    for (; taken < ready.size() && used < count; taken++) {
+      Slot &S = P->slots[ready[taken]];
+      if (own_stream(P, S)) {                                          // sponge transcripts squeeze their own stream; empty batches have no transcript
+        used++;
+        int st = guarded([&] { return S.segmented ? seg_hash(S.c, P->kind, /*spread=*/false) : batch_seed(S.c, P->kind, S.digest); });
         if (st != AVRF_OK) { done(S, st); continue; }
         S.state = S_HASHED;
         continue;
       }
-      jobs[k] = WeightJob::whole(S.c->h_msg.as<uint8_t>(), S.c->h_msg_len); pj[k] = &jobs[k]; ss[k] = &S; k++;
+      if (!S.segmented) { jobs[k] = WeightJob::whole(S.c->h_msg.as<uint8_t>(), S.c->h_msg_len); pj[k] = &jobs[k]; ss[k] = &S; seg[k] = 0; k++; used++; continue; }
+      for (; S.seg_hashed < S.seg_items.size() && used < count; S.seg_hashed++, k++, used++) { seg_job(S.c, P->kind, S.seg_hashed, &jobs[k]); pj[k] = &jobs[k]; ss[k] = &S; seg[k] = S.seg_hashed; }
+      if (S.seg_hashed < S.seg_items.size()) break;                    // the group is full: the slot stays at the front of `ready`
     }
     if (k) sha512_many(pj, k);
-    for (int i = 0; i < k; i++) { memcpy(ss[i]->digest, jobs[i].digest, 64); ss[i]->state = S_HASHED; }
-    ready.erase(ready.begin(), ready.begin() + count);
+    for (int i = 0; i < k; i++) {
+      if (!ss[i]->segmented) { memcpy(ss[i]->digest, jobs[i].digest, 64); ss[i]->state = S_HASHED; continue; }
+      seg_seed(ss[i]->c, seg[i], jobs[i].digest);
+      if (seg[i] + 1 == ss[i]->seg_items.size()) ss[i]->state = S_HASHED;
+    }
+    ready.erase(ready.begin(), ready.begin() + taken);
     if (k) { W.hash_groups++; W.hash_msgs += k; }
     W.cpu_us[2] += thread_cpu_us() - t0;
   }
@@ -167,16 +192,23 @@ struct Run {
     const double t0 = thread_cpu_us();
     S.lane = pick_lane(); S.lane->queued++;
     S.c->L = S.lane; S.c->stream = S.lane->stream;
-    int st = guarded([&] { return batch_launch(S.c, P->kind, S.digest); });
+    int st = guarded([&] { return S.segmented ? seg_launch(S.c, P->kind) : batch_launch(S.c, P->kind, S.digest); });
     if (st == AVRF_OK && hipEventRecord(S.ev, S.lane->stream) != hipSuccess) { (void)hipGetLastError(); st = AVRF_ERR_NO_DEVICE; }
     W.cpu_us[3] += thread_cpu_us() - t0;
-    if (st != AVRF_OK) { if (S.c->run_phase == 2) { (void)hipStreamSynchronize(S.lane->stream); S.c->chain().disarm(); } done(S, st); return; }
+    // (run_phase 2, a segmented run's 4: the chain was enqueued and only the event failed -- it is waited for and given up)
+    if (st != AVRF_OK) { if (S.c->run_phase == 2 || S.c->run_phase == 4) { (void)hipStreamSynchronize(S.lane->stream); S.c->chain().disarm(); } done(S, st); return; }
     S.seq = ++seq; S.state = S_MSM;
   }
 
   void finish(Slot &S) {
     const double t0 = thread_cpu_us();
-    const int st = guarded([&] { return batch_end(S.c, P->kind); });
+    int st;
+    if (!S.segmented) st = guarded([&] { return batch_end(S.c, P->kind); });
+    else {
+      S.seg_status.assign(S.seg_items.size(), AVRF_OK);
+      st = guarded([&] { return seg_end(S.c, P->kind, S.seg_status.data()); });
+      if (st == AVRF_OK) { S.seg_have = true; for (int32_t v : S.seg_status) if (v > st) st = v; }   // the job's status: the largest of its segments'
+    }
     W.cpu_us[4] += thread_cpu_us() - t0;
     done(S, st);
   }
@@ -212,7 +244,7 @@ struct Run {
         if (S.state != S_BEGUN) continue;
         if (hipEventQuery(S.ev) == hipSuccess) {
           const double t0 = thread_cpu_us();
-          const int st = guarded([&] { return batch_collect(S.c, P->kind); });
+          const int st = guarded([&] { return S.segmented ? seg_collect(S.c, P->kind) : batch_collect(S.c, P->kind); });
           W.cpu_us[1] += thread_cpu_us() - t0;
           if (st != AVRF_OK) { latch(S, st); done(S, st); } else { S.state = S_READY; ready.push_back(si); }
           progress = true;
@@ -221,7 +253,7 @@ struct Run {
       // hash a full group at once; a partial one only when nothing else is on its way and the lanes are running dry
       if (!ready.empty()) {
         const size_t g = (size_t)P->group;
-        if (ready.size() >= g || (n_begun == 0 && 2 * n_msm <= W.capacity)) { hash(ready, ready.size() < g ? ready.size() : g); progress = true; }
+        if (waiting(ready) >= g || (n_begun == 0 && 2 * n_msm <= W.capacity)) { hash(ready, g); progress = true; }
       }
       if (progress) continue;
       if (oldest) { W.waits++; (void)hipEventSynchronize(oldest->ev); continue; }        // sleeps in the driver (blocking-sync events)
@@ -312,7 +344,7 @@ int avrf_pool_set_validation(avrf_pool *P, int level) {
 
 // A free slot of the least loaded worker takes the source (waiting for one while batches are running).  What every flavour needs is
 // checked here, on the calling thread, before a ticket exists; the shared ones check their indices there as well.
-static int pool_submit(avrf_pool *P, const BatchSource &src, uint64_t *ticket) {
+static int pool_submit(avrf_pool *P, const BatchSource &src, uint64_t *ticket, bool segmented = false, size_t n_seg = 0, const uint32_t *seg_items = nullptr) {
   const uint8_t *keys = src.n_shared ? src.table : src.pks;
   if (!P || !ticket || (src.n && (!src.proofs || !src.io_counts || !src.ad_lens)) || (src.n && kind_facts(P->kind).pk && !keys)) return AVRF_ERR_BAD_ARG;
   std::unique_lock<std::mutex> lk(P->m);
@@ -328,6 +360,8 @@ static int pool_submit(avrf_pool *P, const BatchSource &src, uint64_t *ticket) {
     if (best >= 0) {
       Slot &S = P->slots[best];
       S.src = src;
+      S.segmented = segmented; S.seg_have = false;
+      if (segmented) S.seg_items.assign(seg_items, seg_items + n_seg); else S.seg_items.clear();
       S.from_host = true; S.resident_invalid = false; S.ticket = P->next_ticket++; S.status = 0;
       S.state = S_SUBMITTED;
       *ticket = S.ticket;
@@ -386,18 +420,43 @@ int avrf_pool_submit_pedersen_shared_wire(avrf_pool *P, size_t n, size_t n_share
   return pool_submit_ped_shared(P, wire_source(shared_source(Pedersen, n, n_shared, shared, nullptr, input_index, outputs, io_counts, ads, ad_lens, proofs), validate), ticket);
 }
 
-int avrf_pool_wait(avrf_pool *P, uint64_t ticket, int *status) {
+// Segmented jobs (include/avrf.h): the layout is checked here, on the calling thread, before a ticket exists, by the seg_layout the
+// context's call uses (through the public layout functions); seg_items is copied into the slot.  No shared-table flavour.
+static int pool_submit_segments(avrf_pool *P, const BatchSource &src, size_t n_seg, const uint32_t *seg_items, uint64_t *ticket) {
+  uint64_t lay[4];
+  if (!P || (src.n && !src.io_counts)) return AVRF_ERR_BAD_ARG;
+  if (int e = P->kind == Thin ? avrf_thin_segments_layout(src.n, n_seg, seg_items, src.io_counts, lay) : avrf_pedersen_segments_layout(src.n, n_seg, seg_items, lay)) return e;
+  return pool_submit(P, src, ticket, true, n_seg, seg_items);
+}
+int avrf_pool_submit_segments(avrf_pool *P, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
+                              const uint32_t *ad_lens, const uint8_t *proofs, size_t n_seg, const uint32_t *seg_items, uint64_t *ticket) {
+  if (!P) return AVRF_ERR_BAD_ARG;
+  return pool_submit_segments(P, plain_source(P->kind, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs), n_seg, seg_items, ticket);
+}
+int avrf_pool_submit_segments_wire(avrf_pool *P, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                                   const uint32_t *ad_lens, const uint8_t *proofs, int validate, size_t n_seg, const uint32_t *seg_items, uint64_t *ticket) {
+  if (!P) return AVRF_ERR_BAD_ARG;
+  return pool_submit_segments(P, wire_source(plain_source(P->kind, n, pks, ios, io_counts, ads, ad_lens, proofs), validate), n_seg, seg_items, ticket);
+}
+
+// the verdict of `ticket`; status_out != NULL: a segmented job's statuses as well (avrf_pool_wait_segments)
+static int pool_wait(avrf_pool *P, uint64_t ticket, int *status, int32_t *status_out, size_t cap, bool want_segments) {
   if (!P || !status) return AVRF_ERR_BAD_ARG;
   std::unique_lock<std::mutex> lk(P->m);
   Slot *S = nullptr;
   for (auto &s : P->slots) if (s.ticket == ticket && s.state != S_FREE) { S = &s; break; }
   if (!S) return AVRF_ERR_BAD_ARG;
+  // (what a ticket is and how many segments it has is fixed at submission: refused before waiting, and the ticket is not consumed)
+  if (want_segments && (!S->segmented || cap < S->seg_items.size() || (S->seg_items.size() && !status_out))) return AVRF_ERR_BAD_ARG;
   P->cv_done.wait(lk, [&] { return S->state == S_DONE; });
   *status = S->status;
+  if (want_segments && S->seg_have) for (size_t v = 0; v < S->seg_status.size(); v++) status_out[v] = S->seg_status[v];
   S->state = S_FREE;
   P->cv_done.notify_all();
   return AVRF_OK;
 }
+int avrf_pool_wait(avrf_pool *P, uint64_t ticket, int *status) { return pool_wait(P, ticket, status, nullptr, 0, false); }
+int avrf_pool_wait_segments(avrf_pool *P, uint64_t ticket, int *status, int32_t *status_out, size_t cap) { return pool_wait(P, ticket, status, status_out, cap, true); }
 
 int avrf_pool_resubmit(avrf_pool *P, uint64_t ticket, int from_host, uint64_t *new_ticket) {
   if (!P || !new_ticket) return AVRF_ERR_BAD_ARG;

@@ -266,6 +266,11 @@ size_t avrf_thin_segment_terms(avrf_ctx *ctx, size_t seg, uint8_t *bases_xy, uin
  * bases_xy[v L ..], scalars[v L ..]; out_xy: n_seg x 64.  n_seg >= 8 runs as one chain, fewer as n_seg single MSMs.
  * L <= AVRF_SEGMENT_TERMS_MAX and the other limits above, else AVRF_ERR_BAD_ARG. */
 int avrf_msm_te_segments(avrf_ctx *ctx, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy);
+/* Test probe: the same MSMs through the two halves the pool's segmented jobs use (enqueue the chain, collect it later): ONE chain
+ * whatever n_seg >= 1 is, the windows limit holding for every n_seg.  own_record != 0: the context's own result record; 0: a record
+ * of the call's own, as a pool slot hands in.  Results and refusals as avrf_msm_te_segments. */
+int avrf_msm_te_segments_chain(avrf_ctx *ctx, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, int own_record,
+                               uint8_t *out_xy);
 
 /* ---- pedersen::BatchVerifier over SEGMENTS of one staged batch (src/pedersen.rs:303-426): the five calls above for the Pedersen
  * verifier, with the same meaning, limits and refusals.  n_seg independent BatchVerifiers over consecutive runs of the staged
@@ -467,6 +472,49 @@ int avrf_pool_submit_pedersen_shared_wire(avrf_pool *pool, size_t n, size_t n_sh
                                           const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
                                           const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
                                           uint64_t *ticket);
+/* avrf_pool_submit_segments / _segments_wire: a SEGMENTED job -- n_seg independent BatchVerifiers over consecutive runs of the batch's
+ * items, one verdict each (thin::BatchVerifier src/thin.rs:188-326 on a kind 1 pool, pedersen::BatchVerifier src/pedersen.rs:303-426 on
+ * a kind 2 pool with pks NULL; every suite the pool accepts).  What avrf_thin_batch_run_segments / avrf_pedersen_batch_run_segments do
+ * on one context, with other jobs in flight beside it: one prepare pass, the n_seg weight transcripts (src/thin.rs:274-279,
+ * src/pedersen.rs:361-367, each over ITS items only) hashed through the pool's grouped hash -- a job with many segments fills groups
+ * by itself, segments of different jobs share a group -- one terms pass and ONE MSM chain on a lane, whatever n_seg is.  Plain and
+ * segmented jobs may be in flight in one pool at once.
+ *   contract   arguments as avrf_pool_submit / avrf_pool_submit_wire, then the segments as avrf_thin_batch_run_segments takes them:
+ *              segment v covers the next seg_items[v] items, the counts sum to n.
+ *   ownership  seg_items is copied before the call returns; the other buffers follow avrf_pool_submit's rule (untouched until the
+ *              verdict is out, read again by avrf_pool_resubmit with from_host = 1).
+ *   refusals   AVRF_ERR_BAD_ARG on the submitting thread, before a ticket exists, by the layout check of the context's call
+ *              (avrf_thin_segments_layout / avrf_pedersen_segments_layout): counts that do not sum to n, a segment over
+ *              AVRF_SEGMENT_TERMS_MAX, a layout over AVRF_SEGMENTS_PADDED_TERMS_MAX or AVRF_SEGMENTS_WINDOWS_MAX (the windows limit
+ *              holds for every n_seg here: the job is one chain, there is no looped route below eight segments).  There is no
+ *              shared-table flavour, as the context's call refuses a shared staging.
+ *   statuses   avrf_pool_wait_segments: status_out[v] (cap >= n_seg entries) is exactly what avrf_thin_batch_run_segments /
+ *              avrf_pedersen_batch_run_segments answers for segment v -- an empty segment AVRF_OK, a bad item marks its own segment
+ *              only -- and *status the largest of them (AVRF_OK when all are).  avrf_pool_wait on a segmented ticket returns that
+ *              same fold, and avrf_pool_cycle compares expect_status with it.  A staging error -- a wire point that does not decode
+ *              or, under validate, fails -- is the job's *status with status_out left unwritten, as
+ *              avrf_thin_batch_verify_segments_wire returns it; runs from the resident state repeat it.  avrf_pool_wait_segments on
+ *              a plain ticket, or with cap < n_seg, is AVRF_ERR_BAD_ARG and the ticket is not consumed.
+ *   reruns     avrf_pool_resubmit (both from_host values) and the cycle mode run the same segmentation again.
+ *   memory     the padded term arrays (n_seg * L terms of 128 bytes), the per-item scratch, the seeds and the offsets are the
+ *              LANE's, as a plain job's terms are: a slot does not grow with the segmentation.
+ * avrf_pool_stats: out[7] counts every segment's transcript.
+ * Runtime (tools/segments_bench.py legs e and f; 65 536 one-pair Thin items as 256 segments of 256 per job, 24 jobs
+ * in flight on 144 slots / 12 lanes / 6 threads): 38.6-43.6 M items/s from the resident state, 39.5-41.0 M staged from page-locked
+ * buffers on every run (Pedersen 37.8-41.7 / 32.6-35.8).  That beats one context's segmented call (26.8-28.2) and the per-item
+ * avrf_thin_verify (27.3-28.1), ranges apart.  IT DOES NOT BEAT what a caller could already do with k contexts on k host threads,
+ * each calling avrf_thin_batch_verify_segments: 45.2-46.2 M items/s with four, 48.6-48.9 with eight (resident: 42.5-43.7 / 42.6-44.8,
+ * overlapping the pool's range).  The pool form is a convenience -- one object, tickets, plain and segmented jobs side by side, no host
+ * thread per context -- and a memory saving (lanes, not contexts, hold the workspaces), not a speed-up.  Jobs want MANY segments: sixteen
+ * segments of 256 items per job run at 8.3-9.3 M items/s with 144 jobs in flight (0.45 ms per job: the chain's lone-wave kernels, a
+ * few chains at a time). */
+int avrf_pool_submit_segments(avrf_pool *pool, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
+                              const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, size_t n_seg,
+                              const uint32_t *seg_items, uint64_t *ticket);
+int avrf_pool_submit_segments_wire(avrf_pool *pool, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts,
+                                   const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate, size_t n_seg,
+                                   const uint32_t *seg_items, uint64_t *ticket);
+int avrf_pool_wait_segments(avrf_pool *pool, uint64_t ticket, int *status, int32_t *status_out, size_t cap);
 int avrf_pool_wait(avrf_pool *pool, uint64_t ticket, int *status);
 int avrf_pool_resubmit(avrf_pool *pool, uint64_t ticket, int from_host, uint64_t *new_ticket);
 int avrf_pool_cycle(avrf_pool *pool, int from_host, uint64_t steps_block, double min_seconds, uint64_t max_steps, int expect_status,

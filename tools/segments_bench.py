@@ -8,15 +8,22 @@ call the Pedersen twin of every entry point named below) gives against the calls
     c  the same 256 batches of 256 items as separate submissions through an avrf_pool with the headline's slots / lanes / threads
        (from page-locked host buffers; and the pool's resident cycle over 144 such batches)
     d  the plain thin_batch_run: one verdict for everything
+    e  SEGMENTED JOBS through an avrf_pool of the same slots / lanes / threads (avrf_pool_submit_segments): the 65 536 items as one job
+       of 256 x 256, 24 such jobs in flight, and as sixteen jobs of 16 x 256, 144 in flight; each from the slots' resident state and
+       staged again from page-locked host buffers on every run (the pool's cycle mode, no foreign-function call per step)
+    f  what a caller could do before: k contexts on k host threads, k = 2, 4, 8, each calling thin_batch_verify_segments (stage from
+       the host + 256 x 256) on the whole batch, and the same with the batch resident (thin_batch_run_segments)
 Per leg: items/s, and for the context's legs the k_accumulate milliseconds per call (avrf_kernel_stats) and the host-side stage times
 of the segmented call (avrf_last_timing: prepare + wait, transcripts, terms launches, MSM chain + wait).
-python tools/segments_bench.py [n] [--quick] [--legs=abcd] [--shape=ITEMS] [--kind=thin|pedersen]
-    --legs: only these legs; --shape=256: of leg a only the segments of that many items (a kernel trace of one leg keeps its kernels apart)
+python tools/segments_bench.py [n] [--quick] [--legs=abcdef] [--shape=ITEMS] [--kind=thin|pedersen]
+    --legs: only these legs; --shape=256: of leg a only the segments of that many items, of leg e only the whole-batch jobs (a kernel
+            trace of one leg keeps its kernels apart)
     --kind=pedersen: the same legs over the Pedersen verifier (avrf_pedersen_batch_run_segments, avrf_pedersen_verify, a kind 2 pool)"""
 import ctypes as C
 import json
 import os
 import sys
+import threading
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +36,7 @@ n = int(args[0]) if args else 65536
 QUICK = "--quick" in sys.argv
 SLOTS, LANES, THREADS, GROUP, DEPTH = 144, 12, 6, 8, 3
 REPS, CALLS, WARM = (1, 3, 1) if QUICK else (3, 10, 2)
-LEGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--legs=")), "abcd")
+LEGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--legs=")), "abcdef")
 SHAPE = next((int(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--shape=")), None)
 SHAPES = [(n // k, k) for k in (256, 64, 1024) if SHAPE in (None, k)]             # (segments, items per segment)
 KIND = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--kind=")), "thin")
@@ -93,6 +100,50 @@ def main():
         for t in tk[max(0, len(tk) - SLOTS):]:
             assert pool.wait(t) == 0
 
+    # leg e: two pools of the headline's shape; every job of a pool reads the same page-locked buffers
+    seg_pools = []
+    if "e" in LEGS:
+        whole = nat.PinnedBatch(n, b["ios_xy"], b["io_counts"], b["ads"], b["ad_lens"], pks_xy=pks(0, n), proofs=b["proofs"])
+        part_n = 16 * per
+        part = nat.PinnedBatch(part_n, b["ios_xy"][:128 * part_n], [1] * part_n, b["ads"][:off[part_n]], b["ad_lens"][:part_n], pks_xy=pks(0, part_n),
+                               proofs=b["proofs"][:PROOF * part_n])
+        shapes_e = (("%d x %d per job, 24 jobs" % (n // per, per), whole, n, 24), ("16 x %d per job, %d jobs" % (per, SLOTS), part, part_n, SLOTS))
+        for name, pb, items, jobs in shapes_e[:1] if SHAPE else shapes_e:          # (--shape: the whole-batch jobs only)
+            sp = nat.Pool(0, kind=POOL_KIND, slots=SLOTS, lanes=LANES, threads=THREADS, hash_group=GROUP, depth=DEPTH)
+            tk = [sp.submit_segments(pb, [per] * (items // per)) for _ in range(jobs)]
+            assert all(sp.wait_segments(t) == (0, [0] * (items // per)) for t in tk)
+            seg_pools.append((name, sp, pb, items, jobs))
+    # leg f: eight contexts, each with the whole batch
+    many = [nat.Context(0) for _ in range(8)] if "f" in LEGS else []
+
+    def contexts_leg(k, from_host):
+        """k host threads, a context each: CALLS calls after WARM warm-ups, started together -> seconds per call of ONE context"""
+        segs = [per] * (n // per)
+        gate = threading.Barrier(k + 1)
+        bad = []
+
+        def work(c):
+            vs, rs = getattr(c, KIND + "_batch_verify_segments"), getattr(c, KIND + "_batch_run_segments")
+            call = (lambda: vs(batch, segs)) if from_host else (lambda: rs(segs))
+            if not from_host:
+                getattr(c, KIND + "_batch_stage")(batch)
+            for _ in range(WARM):
+                call()
+            gate.wait()
+            for _ in range(CALLS):
+                if call() != [0] * len(segs):
+                    bad.append(1)
+            gate.wait()
+        th = [threading.Thread(target=work, args=(c,)) for c in many[:k]]
+        [t.start() for t in th]
+        gate.wait()
+        t0 = time.perf_counter()
+        gate.wait()
+        sec = time.perf_counter() - t0
+        [t.join() for t in th]
+        assert not bad
+        return sec / CALLS
+
     try:
         for rep in range(REPS):
             assert stage(batch) == 0
@@ -114,6 +165,20 @@ def main():
                 sec, _, _ = timed(ctx, lambda: verify_into(batch, status))
                 assert not any(status)
                 record("b %s_verify" % KIND, sec, rep=rep)
+            for name, sp, pb, items, jobs in seg_pools:                           # e
+                for from_host in (False, True):
+                    sp.cycle(steps_block=jobs, min_seconds=0.1, from_host=from_host, expect=0)
+                    sp.stats(reset=True)
+                    done, mism, sec = sp.cycle(steps_block=jobs, min_seconds=0.3 if QUICK else 1.0, from_host=from_host, expect=0)
+                    assert mism == 0
+                    st = sp.stats()
+                    record("e pool segments, %s, %s" % (name, "from pinned host" if from_host else "resident"), sec / done, items=items, rep=rep,
+                           accumulate_ms=round(st["accumulate_ms_total"] / done, 4), sleeps_per_job=round(st["sleeps"] / done, 2),
+                           host_cpu_us_per_job={k[7:]: round(st[k] / done) for k in ("cpu_us_begin", "cpu_us_collect", "cpu_us_hash", "cpu_us_launch", "cpu_us_end")})
+            for k in (2, 4, 8) if "f" in LEGS else []:                              # f
+                for from_host in (True, False):
+                    sec = contexts_leg(k, from_host)
+                    record("f %d contexts, 256 x 256 %s" % (k, "from host" if from_host else "resident"), sec, items=k * n, rep=rep)
             if "c" not in LEGS:
                 continue
             for _ in range(WARM):                                                  # c
@@ -135,6 +200,12 @@ def main():
     finally:
         if pool:
             pool.close()
+        for _, sp, pb, _, _ in seg_pools:
+            sp.close()
+        for pb in {id(x[2]): x[2] for x in seg_pools}.values():
+            pb.close()
+        for c in many:
+            c.close()
         for sb in small:
             sb.close()
         ctx.close()
