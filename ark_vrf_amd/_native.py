@@ -272,6 +272,18 @@ class Context:
             raise AvrfError(f"avrf_g1_msm -> {st}")
         return bytes(out)
 
+    def g1_msm_segments(self, n_seg, L, bases_xy, scalars):
+        """n_seg independent G1 MSMs of L terms each as ONE chain (avrf_g1_msm_segments) -> list of n_seg points (LE x || y), or the
+        refusal's status (ERR_BAD_ARG, INVALID_DATA)."""
+        fq = 32 if int(self.suite) == 1 else 48          # BN254 for Baby-JubJub, BLS12-381 for every other suite with a pairing curve
+        assert len(scalars) == 32 * n_seg * L and len(bases_xy) == 2 * fq * n_seg * L
+        out = (C.c_uint8 * max(1, 2 * fq * n_seg))()
+        st = lib().avrf_g1_msm_segments(self._h, C.c_size_t(n_seg), C.c_size_t(L), _u8(bases_xy), _u8(scalars), out)
+        if st != OK:
+            return st
+        b = bytes(out)
+        return [b[2 * fq * v: 2 * fq * (v + 1)] for v in range(n_seg)]
+
     # -- batch verifiers
     def thin_batch_verify(self, pks_xy, items_ios_xy, ads, proofs):
         b = Batch.from_items(items_ios_xy, ads, pks_xy=pks_xy, proofs=proofs)

@@ -254,6 +254,33 @@ int avrf_g1_msm(avrf_ctx *c, size_t n, const uint8_t *bases_xy, const uint8_t *s
   if (n && *c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   return AVRF_OK;
 }
+// n_seg independent <E::G1 as VariableBaseMSM>::msm calls of L terms each (segment v: bases and scalars [v L, v L + L)) as ONE launch
+// chain with the Horner and the affine conversion on the device (msm.h msm_g1_segments), for every n_seg >= 1: the probe of that chain.
+int avrf_g1_msm_segments(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy) {
+  if (!c || (n_seg && !out_xy) || (n_seg && L && (!bases_xy || !scalars))) return AVRF_ERR_BAD_ARG;
+  if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
+  if (L > (size_t)AVRF_SEGMENT_TERMS_MAX || n_seg > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  const int curve = pairing_curve_of(c->suite);
+  const size_t fqb = curve == 0 ? 48 : 32, n = n_seg * L;
+  if (!n) { if (n_seg) memset(out_xy, 0, n_seg * 2 * fqb); return AVRF_OK; }
+  if (n > (size_t)AVRF_SEGMENTS_PADDED_TERMS_MAX || n_seg * (size_t)msm_g1_segments_windows(curve, L) > (size_t)AVRF_SEGMENTS_WINDOWS_MAX) return AVRF_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  for (size_t i = 0; i < n; i++) {
+    H256 v; memcpy(v.l, scalars + 32 * i, 32);
+    bool ok = curve == 0 ? !HostField<FqBandersnatch>::geq_p(v) : !HostField<FqBabyJubJub>::geq_p(v);   // Fr of the pairing curve
+    if (!ok) return AVRF_INVALID_DATA;
+  }
+  c->staged_kind = 0;
+  HIP_TRY(c->d_misc.ensure(n * 2 * fqb)); HIP_TRY(c->L->d_scalars.ensure(n * 32)); HIP_TRY(c->L->d_pre.ensure(n * 2 * fqb));
+  HIP_TRY(hipMemcpyAsync(c->d_misc.p, bases_xy, n * 2 * fqb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->L->d_scalars.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 4, c->stream));
+  launch_g1_bases(curve, c->d_misc.as<uint8_t>(), n, c->L->d_pre.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream);
+  HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+  if (int e = msm_guarded([&] { return msm_g1_segments(curve, c->L->d_pre.as<uint32_t>(), c->L->d_scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->stream, out_xy); })) return e;
+  if (*c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
+  return AVRF_OK;
+}
 
 // ---------------------------------------------------------------- staging
 

@@ -205,4 +205,38 @@ int avrf_ring_vrf_verify(avrf_ctx *ctx, avrf_ring_setup *setup, size_t n, const 
   return AVRF_OK;
 }
 
+// n_seg ring::BatchVerifiers (src/ring.rs:682-735) over consecutive runs of the items, both halves segmented: the Pedersen half is the
+// segmented Pedersen path on ctx (wire_prepare, staging, avrf_pedersen_batch_run_segments), the ring half avrf_ring_batch_verify_segments
+// on the setup with the Yb of the Pedersen proofs as instances; side by side, as the halves of avrf_ring_vrf_verify run.
+int avrf_ring_vrf_verify_segments(avrf_ctx *ctx, avrf_ring_setup *setup, size_t n, const uint8_t *ring_commitments, size_t n_rings, const uint32_t *ring_of_item,
+                                  const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                                  int validate, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  if (!ctx || !setup || (n && (!ring_commitments || !n_rings || !io_counts || !ad_lens || !proofs)) || (n_seg && (!seg_items || !status_out))) return AVRF_ERR_BAD_ARG;
+  if (avrf_ring_setup_suite(setup) != avrf_ctx_suite_(ctx)) return AVRF_ERR_BAD_ARG;
+  { uint64_t lay[4]; if (int rc = avrf_ring_segments_layout(n, n_seg, seg_items, lay)) return rc; }   // the ring half's limits are the narrower ones
+  if (!n) { for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK; return AVRF_OK; }
+  const size_t L = avrf_point_len(avrf_ctx_suite_(ctx)), pedlen = kind_facts(Pedersen).wire_proof(L);
+  const size_t rlen = avrf_ring_proof_len(setup), plen = pedlen + rlen, tot = sum_counts(io_counts, n);
+  if (tot && !ios) return AVRF_ERR_BAD_ARG;
+  std::vector<uint8_t> ped(n * pedlen), rp(n * rlen);
+  for (size_t j = 0; j < n; j++) { memcpy(&ped[j * pedlen], proofs + j * plen, pedlen); memcpy(&rp[j * rlen], proofs + j * plen + pedlen, rlen); }
+  std::vector<uint8_t> yb; std::vector<int32_t> yst;
+  std::vector<int32_t> s1(n_seg), s2(n_seg);
+  WirePrep w;
+  int rc = wire_prepare(ctx, Pedersen, true, n, nullptr, ios, io_counts, ads, ad_lens, ped.data(), validate, false, w, &yb, &yst);
+  if (rc != AVRF_OK) return rc;
+  rc = avrf_pedersen_batch_stage(ctx, n, w.x_ios, io_counts, ads, ad_lens, w.px.data());
+  if (rc != AVRF_OK) return rc;
+  int rc_ped = AVRF_OK;
+  std::thread ped_half; bool threaded = true;
+  try { ped_half = std::thread([&] { rc_ped = avrf_pedersen_batch_run_segments(ctx, n_seg, seg_items, s1.data()); }); } catch (...) { threaded = false; }
+  rc = avrf_ring_batch_verify_segments(setup, n, ring_commitments, n_rings, ring_of_item, yb.data(), rp.data(), n_seg, seg_items, s2.data());
+  if (threaded) ped_half.join(); else rc_ped = avrf_pedersen_batch_run_segments(ctx, n_seg, seg_items, s1.data());
+  if (rc_ped != AVRF_OK) return rc_ped;
+  if (rc != AVRF_OK) return rc;
+  for (size_t v = 0; v < n_seg; v++)
+    status_out[v] = (s1[v] == AVRF_INVALID_DATA || s2[v] == AVRF_INVALID_DATA) ? AVRF_INVALID_DATA : (s1[v] || s2[v]) ? AVRF_VERIFICATION_FAILURE : AVRF_OK;
+  return AVRF_OK;
+}
+
 }  // extern "C"

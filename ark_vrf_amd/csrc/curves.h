@@ -153,7 +153,7 @@ template <class S> struct TeCurve {
 // XYZZ: x = X/ZZ, y = Y/ZZZ, ZZ^3 = ZZZ^2; identity <=> ZZ = 0.  Affine bases: (0, 0) = infinity.
 template <class C> struct G1RedCurve;
 template <class C> struct G1Curve {
-  using Fq = typename C::Fq;
+  using Fq = typename C::Fq; using curve = C;
   static constexpr int N = Fq::N;
   using el = fpn<N>;
   struct base_t { el x, y; };

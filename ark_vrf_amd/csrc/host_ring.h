@@ -259,6 +259,16 @@ template <class S, class G> struct HostRing {
     std::vector<uint8_t> rnd(32 * n); rh.squeeze_copy(rnd.data(), rnd.size());
     return rnd;
   }
+  // the randomisers of ONE segment of a segmented call (avrf_ring_batch_verify_segments): the items [first, first + count) of the
+  // call's arrays, derived exactly as a batch call on those items alone derives them -- its own item count, its slice of
+  // ring_of_item, ALL the call's commitments, its instances and proofs.  32 bytes per item of the segment into out.
+  static void segment_randomisers(size_t first, size_t count, size_t n_rings, size_t N, const G1Aff &g1_0, const std::vector<uint8_t> &g2_raw,
+                                  const uint32_t *ring_of_item, const uint8_t *commitments, const uint8_t *instances_xy, const uint8_t *proofs, uint8_t *out) {
+    if (!count) return;
+    const std::vector<uint8_t> rnd = batch_randomisers(count, n_rings, N, g1_0, g2_raw, ring_of_item ? ring_of_item + first : nullptr, commitments,
+                                                       instances_xy + 64 * first, proofs + PL::LEN * first);
+    memcpy(out, rnd.data(), rnd.size());
+  }
   // an item's r1, r2 (Montgomery) from its 32 bytes
   static void randomiser_pair(const uint8_t rnd[32], H256 *r1, H256 *r2) {
     H256 a = {{0, 0, 0, 0}}, c = {{0, 0, 0, 0}}; memcpy(a.l, rnd, 16); memcpy(c.l, rnd + 16, 16); *r1 = Fr::to_mont(a); *r2 = Fr::to_mont(c);

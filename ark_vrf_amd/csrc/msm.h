@@ -67,8 +67,9 @@ MsmPlan msm_plan(size_t n, int scalar_bits);
 
 // What the tail of a chain left in MsmChain::bits_host, vector after vector: `per` bit sums T_p (sum_p 2^p T_p), `per` window triples
 // (W_w = P1 + 2^4 P2 + 2^lg P3, sum_w 2^(c w) W_w) or one finished point.  Set with the tail's copy back only; read by msm.hip msm_fold.
+// (AFFINE: one finished Montgomery affine point x | y, (0, 0) = infinity -- the segmented G1 chain, read by msm_g1_segments itself.)
 struct MsmResult {
-  enum Form { NONE, BIT_SUMS, WINDOW_TRIPLES, POINTS } form = NONE;
+  enum Form { NONE, BIT_SUMS, WINDOW_TRIPLES, POINTS, AFFINE } form = NONE;
   size_t vectors = 0;            // scalar vectors (independent MSMs) of the chain
   size_t per = 0;                // entries per vector: bit sums or windows (POINTS: 1)
   size_t words = 0;              // u32 words per point (accumulator layout of the curve policy)
@@ -153,9 +154,19 @@ bool msm_te_pending_supported(int suite);   // msm_te_enqueue: a caller's record
 // points (2 * Fq words each, (0,0) = infinity), d_scalars = n plain 256-bit scalars (< r).
 // out_xy: canonical affine x || y little-endian (2 * FQ_BYTES), all-zero for the point at infinity.
 // batch > 1: `batch` scalar vectors over the same bases (vector b starts at element b * scalar_stride; 0 = n),
-// `batch` results in out_xy.  Eight or more vectors without a window table stay correct through the host fold (no device Horner for G1); nothing calls it so.
+// `batch` results in out_xy.  Eight or more vectors over SHARED bases without a window table stay correct through the host fold (the
+// device Horner for G1, k_g1_horner_wave, belongs to the segmented chain below); nothing calls it so.
 int msm_g1_device(int curve, const uint32_t *d_bases, const uint32_t *d_scalars, size_t n, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
                   size_t batch = 1, size_t scalar_stride = 0);
+// n_seg independent G1 MSMs in ONE Pippenger chain of n_seg * nwin virtual windows, beside msm_te_segments and under its limits
+// (MSM_SEG_TERMS_MAX, MSM_SEG_WINDOWS_MAX, 32-bit entry offsets: -1 with nothing launched beyond them): vector v is the L bases at
+// d_bases + v * L * 2 Fq words with the L scalars at d_scalars + 8 v L.  A zero scalar is never gathered, so shorter segments are padded
+// with zero scalars.  The Horner and the affine conversion run on the device (k_g1_horner_wave, a wave per vector): the n_seg results are
+// left as Montgomery affine points ((0, 0) = infinity, the layout launch_pairing_check reads) at d_out when it is given, and come back
+// as canonical x || y in out_xy when that is given.  The chain for every n_seg >= 1 (no per-segment loop).  Synchronises the stream.
+int msm_g1_segments(int curve, const uint32_t *d_bases, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
+                    uint32_t *d_out = nullptr);
+int msm_g1_segments_windows(int curve, size_t L);   // windows per vector of that chain (host arithmetic)
 // Fixed-base form for MSMs over one shared base set (the KZG SRS): build_g1_table fills
 // table[w * n + i] = 2^(c w) * P_i (nwin = ceil((Fr bits + 1) / c) rows); msm_g1_fixed_device then treats all
 // windows of a scalar vector as ONE bucket set (n may be smaller than the table's row length `table_stride`).
@@ -190,6 +201,10 @@ void launch_g1_bases(int curve, const uint8_t *d_xy, size_t n, uint32_t *d_out, 
 // (d_rec_status != nullptr: record i / ppr of a failing point gets status 2)
 void launch_g1_subgroup_check(int curve, const uint32_t *d_bases, size_t n, uint32_t *d_flag, hipStream_t stream, int32_t *d_rec_status = nullptr,
                               uint32_t ppr = 1);
+// the same test over records of UNEQUAL length: entry i < n tests base d_point[i] (an index into d_bases, which the caller keeps inside
+// the array) and gives record d_rec_of[i] (inside d_rec_status) status 2 when it fails; bit 1 of *d_flag as above
+void launch_g1_subgroup_check_list(int curve, const uint32_t *d_bases, const uint32_t *d_point, const uint32_t *d_rec_of, size_t n, uint32_t *d_flag,
+                                   int32_t *d_rec_status, hipStream_t stream);
 // per item (16-lane group): point 0 = sum_{t < split} s_t P_t, point 1 = sum_{split <= t < tpi} s_t P_t over the item's tpi <= 16
 // (base, scalar) pairs; out: n_items x 2 Montgomery affine points.  glv_split_scalars (BLS12-381 only): every 32-byte scalar slot
 // holds k mod z^2 | (k div z^2) << 128 (g1_glv_split_bls) and the kernel takes the 128-doubling GLV chain.

@@ -538,6 +538,45 @@ k_horner_quads(const uint32_t *__restrict__ bits, uint32_t nbits, uint32_t *__re
   if (q == 0) fp_store(out + (size_t)v * 32 + j * 8, acc);
 }
 
+// The Horner of the segmented G1 chain (msm_g1_segments), a WAVE per MSM, and the affine conversion behind it.  An XYZZ point of the
+// 12-limb curve fills 48 registers, so a point stays in its lane (no quad form as te_quad.h has for the 8-limb Edwards points); the
+// split is the one of k_horner_quads with lanes for quads.  Lane q folds the m = ceil(nbits / 64) bit sums from q m on (m doublings and
+// m additions, all lanes side by side); a tree over the lanes then shifts the upper half by s m doublings and adds it, s = 1, 2, .., 32
+// (points move between lanes as in k_g1_lincomb, one shuffle per limb).  In a row: 64 m >= nbits doublings -- the 2^(nbits - m) of the top
+// lane, which no arrangement avoids -- but m + 6 additions instead of nbits.  Bit sums at or beyond nbits count as the identity; what the
+// lanes without a partner compute is dropped.  The result leaves as a Montgomery AFFINE point ((0, 0) = infinity, fp_inv_gcd as at the
+// end of k_g1_lincomb) at out[v]: the layout launch_pairing_check reads, two consecutive vectors being one check's (A, B).
+template <class C>
+__global__ void __launch_bounds__(64)
+k_g1_horner_wave(const uint32_t *__restrict__ bits, uint32_t nbits, uint32_t *__restrict__ out) {
+  using CV = G1Curve<C>; using Fq = typename C::Fq; constexpr int N = Fq::N;
+  const uint32_t v = blockIdx.x, q = threadIdx.x, m = (nbits + 63) / 64;
+  const uint32_t *T = bits + (size_t)v * nbits * CV::ACC_WORDS;
+  typename CV::acc_t acc = CV::identity();
+#pragma unroll 1
+  for (int i = (int)m - 1; i >= 0; i--) {
+    const uint32_t p = q * m + (uint32_t)i;
+    acc = CV::dbl(acc);
+    if (p < nbits) acc = CV::add(acc, CV::load_acc(T + (size_t)p * CV::ACC_WORDS));
+  }
+#pragma unroll 1
+  for (uint32_t s = 1; s < 64; s <<= 1) {
+    typename CV::acc_t o = CV::shfl_down(acc, (int)s);                 // lane q + s
+#pragma unroll 1
+    for (uint32_t d = 0; d < s * m; d++) o = CV::dbl(o);
+    acc = CV::add(acc, o);
+  }
+  if (q == 0) {
+    uint32_t *o = out + (size_t)v * 2 * N;
+    if (CV::is_identity(acc)) { fp_store<N>(o, fp_zero<N>()); fp_store<N>(o + N, fp_zero<N>()); }
+    else {
+      const fpn<N> inv = fp_inv_gcd<Fq>(fp_mul<Fq>(acc.zz, acc.zzz));
+      fp_store<N>(o, fp_mul<Fq>(acc.x, fp_mul<Fq>(inv, acc.zzz)));       // X / ZZ
+      fp_store<N>(o + N, fp_mul<Fq>(acc.y, fp_mul<Fq>(inv, acc.zz)));    // Y / ZZZ
+    }
+  }
+}
+
 // Fixed-base (table) batched MSMs have ONE bucket set per MSM: out[set] = sum_b b * B_b.  A group of 2^lps_log lanes
 // (inside one wave) shares a set; lane g owns the m = nb >> lps_log consecutive buckets above g*m (running sums: 2 adds
 // per bucket); then sum_g W_g + m * sum_g g * S_g by a group suffix scan and a group reduction.
@@ -813,16 +852,18 @@ struct MsmLaunch {
   bool defer = false;                    // everything up to the copies back is enqueued, nothing is waited for: the caller collects later (msm_collect)
   int scalars_mont = 0;                  // the scalars are Montgomery limbs (msm.h msm_g1_fixed_device)
   size_t base_stride = 0;                // segmented form (msm.h msm_te_segments): vector v multiplies bases [v * base_stride, v * base_stride + n); 0: shared bases
+  uint32_t *d_affine_out = nullptr;      // segmented G1 form (msm.h msm_g1_segments): where the device leaves the finished affine points (nullptr: ws.rc)
 };
 
-// The five chains of msm_device, named by what ends them; msm_tail is the one place that decides between them.
-enum class MsmTail { SINGLE_LAUNCH, WINDOW_TRIPLES, TABLE_WSUM, DEVICE_HORNER, HOST_BITS };
+// The six chains of msm_device, named by what ends them; msm_tail is the one place that decides between them.
+enum class MsmTail { SINGLE_LAUNCH, WINDOW_TRIPLES, TABLE_WSUM, DEVICE_HORNER, G1_HORNER_AFFINE, HOST_BITS };
 template <class CV> static MsmTail msm_tail(size_t n, const MsmLaunch &o) {
   const bool plain = !o.table_c && !o.d_base_idx && !o.scalars_mont && !o.base_stride;
   if (plain && n <= MSM_TINY_TERMS && o.batch <= MSM_TINY_VECTORS && msm_env().tiny) return MsmTail::SINGLE_LAUNCH;   // k_msm_tiny_bits alone: bit sums
   if (CV::WINDOW_SUMS && o.batch == 1 && msm_env().window_sums) return MsmTail::WINDOW_TRIPLES;                        // three points per window
   if (CV::FIXED_TABLE && o.table_c) return MsmTail::TABLE_WSUM;                       // one weighted sum per bucket set: a finished point per vector
   if (!CV::FIXED_TABLE && o.base_stride) return MsmTail::DEVICE_HORNER;   // segmented (msm_te_segments only: G1 does not build this tail's kernels): device bit sums and Horner
+  if (CV::FIXED_TABLE && o.base_stride) return MsmTail::G1_HORNER_AFFINE;  // segmented G1 (msm_g1_segments only): device bit sums, a wave's Horner and affine point per vector
   return MsmTail::HOST_BITS;                                                          // k_rowcol / k_bits: the bit sums of every vector
 }
 // what the stages of one chain share: the lane, the record, the launch and, for the general chain, the plan with the sizes derived from it
@@ -935,6 +976,17 @@ template <class CV> static void tail_device_horner(const MsmRun &r) {
   r.rec.ensure((size_t)batch * r.acc_bytes);   // the `batch` finished points, whoever's record it is (chain_accumulate sized it for the window triples already: no growth here)
   copy_back(r.rec, r.ws.rc, MsmResult{MsmResult::POINTS, batch, 1, (size_t)CV::ACC_WORDS}, r.stream);
 }
+// segmented G1 launch (msm_g1_segments keeps nb <= 256): the bit sums in one kernel, Horner and affine conversion by a wave per vector;
+// the `batch` Montgomery affine points stay on the device (o.d_affine_out, or ws.rc) for a kernel behind this chain and come back as well
+template <class CV> static void tail_g1_horner_affine(const MsmRun &r) {
+  const uint32_t nbits = r.vwin * (uint32_t)r.p.c, vbits = (uint32_t)(r.p.nwin * r.p.c), batch = (uint32_t)r.o.batch;
+  uint32_t *d_out = r.o.d_affine_out ? r.o.d_affine_out : r.ws.rc.as();
+  hipLaunchKernelGGL(k_bits_direct<CV>, dim3((nbits + 127) / 128), dim3(128), 0, r.stream, r.ws.buckets.as(), r.p.c, nbits, r.ws.bits.as());
+  hipLaunchKernelGGL(k_g1_horner_wave<typename CV::curve>, dim3(batch), dim3(64), 0, r.stream, r.ws.bits.as(), vbits, d_out);
+  r.rec.res = MsmResult{MsmResult::AFFINE, batch, 1, (size_t)CV::BASE_WORDS};
+  r.rec.ensure((size_t)batch * CV::BASE_WORDS * 4);
+  HIP_CHECK(hipMemcpyAsync(r.rec.bits_host.p, d_out, (size_t)batch * CV::BASE_WORDS * 4, hipMemcpyDeviceToHost, r.stream));
+}
 // Enqueues the device pipeline of o.batch MSMs: the single launch, or sort, accumulation and the tail msm_tail picks; collects it unless
 // o.defer.  `rec`: the workspace's own record or a caller's (window-sum form and the segmented chain's device Horner only).  Throws HipFailure when a HIP call fails.
 template <class CV>
@@ -965,6 +1017,7 @@ static void msm_device(const uint32_t *d_bases, const uint32_t *d_scalars, size_
     if constexpr (CV::WINDOW_SUMS) if (tail == MsmTail::WINDOW_TRIPLES) tail_window_triples<CV>(r);
     if constexpr (CV::FIXED_TABLE) if (tail == MsmTail::TABLE_WSUM) tail_table_wsum<CV>(r);
     if constexpr (!CV::FIXED_TABLE) if (tail == MsmTail::DEVICE_HORNER) tail_device_horner<CV>(r);
+    if constexpr (CV::FIXED_TABLE) if (tail == MsmTail::G1_HORNER_AFFINE) tail_g1_horner_affine<CV>(r);
     if (tail == MsmTail::HOST_BITS) { rowcol_bits<CV>(r); copy_back(r.rec, ws.bits, MsmResult{MsmResult::BIT_SUMS, o.batch, (size_t)(p.nwin * p.c), (size_t)CV::ACC_WORDS}, r.stream); }
   }
   if (!o.defer) msm_collect(ws, rec, stream);
@@ -1229,13 +1282,10 @@ static int msm_g1_impl(const uint32_t *d_bases, const uint32_t *d_scalars, size_
 // 255-bit one.  One lane per point; (0, 0) = infinity passes.  BN254 G1 has cofactor 1: nothing to test.
 __device__ static const uint32_t BLS12_381_BETA_MONT[12] = {0x798a64e8, 0x30f1361b, 0x7ece5a2a, 0xf3b8ddab, 0xc61577f7, 0x16a8ca3a,
                                                             0x74fd029b, 0xc26a2ff8, 0x60701c6e, 0x3636b766, 0x241b6160, 0x051ba4ab};
-__global__ void __launch_bounds__(64)
-k_g1_subgroup_bls(const uint32_t *__restrict__ bases, uint32_t n, uint32_t *__restrict__ flag, int32_t *__restrict__ rec_status, uint32_t ppr) {
+// (0, 0) = infinity passes
+AVRF_DI bool g1_bls_in_subgroup(const G1Curve<G1Bls12381>::base_t &P) {
   using CV = G1Curve<G1Bls12381>; using Fq = G1Bls12381::Fq; constexpr int N = Fq::N;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const CV::base_t P = CV::load_base(bases + (size_t)i * 2 * N);
-  if (fp_is_zero(P.x) && fp_is_zero(P.y)) return;
+  if (fp_is_zero(P.x) && fp_is_zero(P.y)) return true;
   const uint64_t z = 0xd201000000010000ull;
   CV::acc_t a = CV::from_affine(P);
 #pragma unroll 1
@@ -1248,11 +1298,32 @@ k_g1_subgroup_bls(const uint32_t *__restrict__ bases, uint32_t n, uint32_t *__re
   bool ok = !fp_is_zero(a.zz);
   ok = ok && fp_eq(a.x, fp_mul<Fq>(fp_mul<Fq>(beta, P.x), a.zz));
   ok = ok && fp_eq(a.y, fp_neg<Fq>(fp_mul<Fq>(P.y, a.zzz)));
-  if (!ok) { atomicOr(flag, 2u); if (rec_status) rec_status[i / ppr] = 2; }
+  return ok;
+}
+__global__ void __launch_bounds__(64)
+k_g1_subgroup_bls(const uint32_t *__restrict__ bases, uint32_t n, uint32_t *__restrict__ flag, int32_t *__restrict__ rec_status, uint32_t ppr) {
+  using CV = G1Curve<G1Bls12381>; constexpr int N = G1Bls12381::Fq::N;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!g1_bls_in_subgroup(CV::load_base(bases + (size_t)i * 2 * N))) { atomicOr(flag, 2u); if (rec_status) rec_status[i / ppr] = 2; }
+}
+// the same test for a LIST of points of records of unequal length: entry i tests base point[i] and pins a failure on record rec_of[i]
+__global__ void __launch_bounds__(64)
+k_g1_subgroup_bls_list(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ point, const uint32_t *__restrict__ rec_of, uint32_t n,
+                       uint32_t *__restrict__ flag, int32_t *__restrict__ rec_status) {
+  using CV = G1Curve<G1Bls12381>; constexpr int N = G1Bls12381::Fq::N;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!g1_bls_in_subgroup(CV::load_base(bases + (size_t)point[i] * 2 * N))) { atomicOr(flag, 2u); rec_status[rec_of[i]] = 2; }
 }
 void launch_g1_subgroup_check(int curve, const uint32_t *d_bases, size_t n, uint32_t *d_flag, hipStream_t stream, int32_t *d_rec_status, uint32_t ppr) {
   if (!n || curve != 0) return;
   hipLaunchKernelGGL(k_g1_subgroup_bls, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_bases, (uint32_t)n, d_flag, d_rec_status, ppr ? ppr : 1u);
+}
+void launch_g1_subgroup_check_list(int curve, const uint32_t *d_bases, const uint32_t *d_point, const uint32_t *d_rec_of, size_t n, uint32_t *d_flag,
+                                   int32_t *d_rec_status, hipStream_t stream) {
+  if (!n || curve != 0) return;
+  hipLaunchKernelGGL(k_g1_subgroup_bls_list, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_bases, d_point, d_rec_of, (uint32_t)n, d_flag, d_rec_status);
 }
 
 // Small linear combinations, one 16-lane group per item: lane t < tpi computes scalar_t * P_t, lanes [0, split) are summed into
@@ -1375,6 +1446,38 @@ int msm_g1_device(int curve, const uint32_t *d_bases, const uint32_t *d_scalars,
   if (curve == 1) return msm_g1_impl<G1Bn254>(d_bases, d_scalars, n, ws, stream, out_xy, o);
   return -1;
 }
+// n_seg independent G1 MSMs of L terms each in ONE chain, beside msm_te_segments and under its limits (all checked before anything is
+// launched): vector v over bases of its own (MsmLaunch::base_stride), the sort, k_accumulate<G1Curve<C>> and the bucket sums of every G1
+// chain, bit sums by k_bits_direct, then k_g1_horner_wave.  Always the chain, whatever n_seg >= 1 is.  Collects (synchronises the stream).
+template <class C>
+static int msm_g1_segments_impl(const uint32_t *d_bases, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
+                                uint32_t *d_out) {
+  using Fq = HostField<typename C::Fq>; constexpr size_t B = 4 * C::Fq::N;
+  if (L > MSM_SEG_TERMS_MAX || n_seg * L > 0x7fffffffull) return -1;
+  const size_t vwin = n_seg * (size_t)msm_plan(L ? L : 1, C::Fr::BITS).nwin;
+  if (L && (vwin > MSM_SEG_WINDOWS_MAX || vwin * L >= 0xffff0000ull)) return -1;
+  if (!L || !n_seg) {                                    // no terms: the point at infinity for every vector
+    if (out_xy) memset(out_xy, 0, n_seg * 2 * B);
+    if (d_out && n_seg) HIP_CHECK(hipMemsetAsync(d_out, 0, n_seg * 2 * B, stream));
+    return 0;
+  }
+  MsmLaunch o; o.batch = n_seg; o.scalar_stride = L; o.base_stride = L; o.d_affine_out = d_out;
+  msm_device<G1Curve<C>>(d_bases, d_scalars, L, C::Fr::BITS, ws, ws.own, stream, o);
+  ws.own.disarm();
+  for (size_t v = 0; out_xy && v < n_seg; v++) {         // Montgomery affine -> canonical bytes; (0, 0) stays all-zero
+    typename Fq::El x, y; memcpy(x.l, ws.own.bits_host.as<uint8_t>() + v * 2 * B, B); memcpy(y.l, ws.own.bits_host.as<uint8_t>() + v * 2 * B + B, B);
+    x = Fq::from_mont(x); y = Fq::from_mont(y);
+    memcpy(out_xy + v * 2 * B, x.l, B); memcpy(out_xy + v * 2 * B + B, y.l, B);
+  }
+  return 0;
+}
+int msm_g1_segments(int curve, const uint32_t *d_bases, const uint32_t *d_scalars, size_t L, size_t n_seg, MsmWorkspace &ws, hipStream_t stream, uint8_t *out_xy,
+                    uint32_t *d_out) {
+  if (curve == 0) return msm_g1_segments_impl<G1Bls12381>(d_bases, d_scalars, L, n_seg, ws, stream, out_xy, d_out);
+  if (curve == 1) return msm_g1_segments_impl<G1Bn254>(d_bases, d_scalars, L, n_seg, ws, stream, out_xy, d_out);
+  return -1;
+}
+int msm_g1_segments_windows(int curve, size_t L) { return msm_plan(L ? L : 1, curve == 0 ? G1Bls12381::Fr::BITS : G1Bn254::Fr::BITS).nwin; }
 // ---------------------------------------------------------------- fixed-base MSM over a table of ALL multiples (no buckets, no sort)
 //
 // A KZG commitment is an MSM over ONE fixed base set (the SRS), and an MI355X has 288 GB of HBM.  G1DirectTable holds, for every

@@ -137,6 +137,7 @@ struct avrf_ring_setup {
   std::vector<std::pair<H256, H256>> h_pows;          // 2^i * BLINDING_BASE, affine Montgomery
   DevMem d_l4;                                        // L_first | L_last evaluated on the 4N domain (2 x 4N)
   PairingTables ptab; bool ptab_ready = false;        // line tables of (g2, tau g2) for the device pairing checks (built on first use)
+  std::vector<uint8_t> seg_sums; size_t seg_sums_n = 0;   // the last segmented verification's two G1 sums per segment (avrf_ring_segment_sums); n = 0: none
   RingLane lane[2];
 };
 static_assert(!std::is_copy_constructible<avrf_ring_setup>::value && !std::is_copy_assignable<avrf_ring_setup>::value,
@@ -167,6 +168,37 @@ extern "C" int avrf_ctx_suite_(avrf_ctx *c);
 extern "C" int avrf_ctx_device_(avrf_ctx *c);
 
 namespace {
+
+// The layout of a segmented verification (include/avrf.h avrf_ring_segments_layout; host arithmetic only): every segment is two
+// vectors of L = 10 (longest segment) + 1 terms, and a round is as many consecutive segments as ONE segmented chain takes: its virtual
+// windows (2 per_round windows(L) <= AVRF_SEGMENTS_WINDOWS_MAX, with the windows of a 256-bit scalar: no curve's are more), its
+// padded terms (2 per_round L <= AVRF_SEGMENTS_PADDED_TERMS_MAX) and its 32-bit entry offsets.
+constexpr size_t RING_SEGMENT_ITEMS_MAX = ((size_t)AVRF_SEGMENT_TERMS_MAX - 1) / 10;   // 10 items + 1 terms in the longer vector: 819
+struct RingSegLayout {
+  uint64_t L = 1, rounds = 0, padded = 0, c = 0; size_t per_round = 1;
+  std::vector<uint32_t> off;                          // n_seg + 1 item offsets
+};
+static int ring_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, RingSegLayout &o) {
+  if ((n_seg && !seg_items) || n_seg > 0x0fffffffULL || n > 0xffffffffULL) return AVRF_ERR_BAD_ARG;
+  o.off.assign(n_seg + 1, (uint32_t)n);
+  uint64_t at = 0, longest = 0;
+  for (size_t v = 0; v < n_seg; v++) {
+    const uint64_t items = seg_items[v];
+    if (items > RING_SEGMENT_ITEMS_MAX || at + items > n) return AVRF_ERR_BAD_ARG;
+    o.off[v] = (uint32_t)at; at += items;
+    if (items > longest) longest = items;
+  }
+  if (at != n) return AVRF_ERR_BAD_ARG;
+  o.L = 10 * longest + 1; o.c = (uint64_t)msm_segments_window_bits((size_t)o.L);
+  const uint64_t nwin = (257 + o.c - 1) / o.c;
+  uint64_t per = (uint64_t)AVRF_SEGMENTS_WINDOWS_MAX / (2 * nwin);
+  if (per > (uint64_t)AVRF_SEGMENTS_PADDED_TERMS_MAX / (2 * o.L)) per = (uint64_t)AVRF_SEGMENTS_PADDED_TERMS_MAX / (2 * o.L);
+  if (per > 0xfffeffffull / (2 * nwin * o.L)) per = 0xfffeffffull / (2 * nwin * o.L);
+  o.per_round = (size_t)per;                          // >= 64: L <= AVRF_SEGMENT_TERMS_MAX
+  o.rounds = (n_seg + per - 1) / per;
+  o.padded = 2 * (n_seg < per ? n_seg : per) * o.L;
+  return AVRF_OK;
+}
 
 template <class S, class G> struct Ring {
   using T = RingTypes<S, G>;
@@ -932,7 +964,11 @@ template <class S, class G> struct Ring {
     std::vector<ArkTranscript> t_ring;                 // verify_transcripts: per ring
     // verify_reduce.  per item: 10 terms of the first MSM (3 fixed + 4 witness + C_q + pi1 + pi2) and 2 of the second
     std::vector<uint8_t> b1, b2; std::vector<H256> s1, s2, gsc;
-    std::vector<int32_t> item_st;                      // (each_status only) what the host part found wrong with an item
+    std::vector<int32_t> item_st;                      // (each_status, segments) what the host part found wrong with an item
+    // verify_segments: segment v is the items [seg_off[v], seg_off[v + 1]); empty for the two unsegmented sequences
+    std::vector<uint32_t> seg_off;
+    std::vector<uint8_t> lone;                         // (segments) the item is the only one of its segment: r1 = 1, the rule of a batch of one
+    bool per_item() const { return each_status || !seg_off.empty(); }   // a failing item is booked on the item, not on the call
   };
   static int verify_commitments(VerifyRun &r) {
     r.fixed.resize(3 * r.n_rings);
@@ -982,9 +1018,9 @@ template <class S, class G> struct Ring {
   static int verify_reduce(VerifyRun &r) {
     const size_t n = r.n, e1 = 2 * FQB;
     r.b1.resize((10 * n + 1) * e1); r.b2.resize(2 * n * e1); r.s1.resize(10 * n + 1); r.s2.resize(2 * n); r.gsc.resize(n);
-    r.item_st.assign(r.each_status ? n : 0, 0);
+    r.item_st.assign(r.per_item() ? n : 0, 0);
     std::atomic<int> status{AVRF_OK};
-    auto fail = [&](size_t it, int st) { if (r.each_status) r.item_st[it] = st; else status = st; };
+    auto fail = [&](size_t it, int st) { if (r.per_item()) r.item_st[it] = st; else status = st; };
     const typename HR::VerifierConsts vc(r.su->N, r.su->w, r.su->ninv);
     parallel_for(n, [&](size_t it) {
       const uint32_t ring = r.ring_of_item ? r.ring_of_item[it] : 0;
@@ -993,7 +1029,7 @@ template <class S, class G> struct Ring {
       for (int j = 0; j < 7; j++) if (!r.dec_ok[7 * it + j]) { fail(it, AVRF_INVALID_DATA); return; }
       // randomisers r1, r2 (128 bits each)
       H256 r1, r2; HR::randomiser_pair(&r.rnd[32 * it], &r1, &r2);
-      if (n == 1) r1 = Fr::one();
+      if (r.lone.empty() ? n == 1 : r.lone[it] != 0) r1 = Fr::one();
       typename HR::Item o;
       if (int st = HR::reduce(vc, r.t_ring[ring], pts, r.proofs + PL::LEN * it, r.instances_xy + 64 * it, r1, r2, o)) { fail(it, st); return; }
       uint8_t *b = &r.b1[10 * it * e1];
@@ -1049,7 +1085,8 @@ template <class S, class G> struct Ring {
     return AVRF_OK;
   }
   // the batch folded into two sums: one MSM chain on the device, one 2-pairing check on the host.  The verdict of the batch.
-  static int verify_tail_folded(VerifyRun &r) {
+  // (sums_out: the two sums, for the probe of the segmented call)
+  static int verify_tail_folded(VerifyRun &r, G1Aff *sums_out = nullptr) {
     avrf_ring_setup *su = r.su; const size_t n = r.n;
     H256 g1_scalar = {{0, 0, 0, 0}};
     for (size_t it = 0; it < n; it++) g1_scalar = Fr::sub(g1_scalar, r.gsc[it]);
@@ -1060,6 +1097,7 @@ template <class S, class G> struct Ring {
     G1Aff acc1, acc2;
     g1_msm2(su, r.ln, r.b1, r.s1, r.b2, r.s2, !r.host_subgroup, &bad, &acc1, &acc2);
     if (bad) return AVRF_INVALID_DATA;
+    if (sums_out) { sums_out[0] = acc1; sums_out[1] = acc2; }
     r.lap("two G1 MSMs (device, one chain)");
     const typename HP::G2Lines *lines = host_lines(su);
     QEl px[2], py[2]; bool pinf[2] = {acc1.inf, acc2.inf};
@@ -1087,6 +1125,134 @@ template <class S, class G> struct Ring {
     const int verdict = verify_tail_folded(r);
     if (each_status) { each_status[0] = verdict; return AVRF_OK; }
     return verdict;
+  }
+
+  // ---- n_seg independent BatchVerifiers (src/ring.rs:682-735, one per segment) over consecutive runs of the items: DESIGN.md 4.17.
+  // The stages of verify_batch with the segment boundaries in the record, then a third tail.  Segment v's randomisers are those of a
+  // batch call on its items alone (HR::segment_randomisers), so its two sums are the sums avrf_ring_batch_verify forms for them.
+  //
+  // verify_tail_segments: every segment is two vectors of ONE segmented G1 chain (msm.h msm_g1_segments), A_v = its items' 10 terms each
+  // and the g1 term with -sum gsc, B_v = its items' 2 terms each, both padded with zero scalars to L = 10 (longest segment) + 1; the
+  // finishing kernel leaves (A_v, B_v) side by side as one pairing check's two points, which the device pairing kernel reads where they
+  // lie -- or, for few segments (few_checks), the host pool from the copy back.  A segment the host part condemned contributes zero
+  // scalars and keeps the host's status; so does an empty one (AVRF_OK).  More segments than one chain's limits hold run as several
+  // chains over consecutive runs of segments (RingSegLayout::per_round).
+  // st: n_seg statuses, the host's verdicts on entry; sums: 2 n_seg canonical points for avrf_ring_segment_sums.
+  static int verify_tail_segments(VerifyRun &r, const RingSegLayout &lay, std::vector<int32_t> &st, std::vector<uint8_t> &sums) {
+    avrf_ring_setup *su = r.su; RingLane &ln = r.ln;
+    const size_t n_seg = r.seg_off.size() - 1, e1 = 2 * FQB, L = (size_t)lay.L;
+    const bool host_pair = few_checks(n_seg), dev_subgroup = !r.host_subgroup && su->curve == 0;
+    if (!host_pair) ensure_pairing(su);
+    for (size_t s0 = 0; s0 < n_seg; s0 += lay.per_round) {
+      const size_t ns = n_seg - s0 < lay.per_round ? n_seg - s0 : lay.per_round, nv = 2 * ns, np = nv * L;
+      std::vector<uint8_t> bb(np * e1, 0); std::vector<H256> ss(np, H256{{0, 0, 0, 0}});
+      std::vector<uint32_t> pt, rec_of;                // the proofs' G1 points still to be subgroup-tested | the segment (of this round) each belongs to
+      for (size_t j = 0; j < ns; j++) {
+        const size_t v = s0 + j, first = r.seg_off[v], cnt = r.seg_off[v + 1] - first;
+        if (!cnt || st[v]) continue;
+        const size_t a0 = 2 * j * L, b0 = (2 * j + 1) * L;
+        memcpy(&bb[a0 * e1], &r.b1[10 * first * e1], 10 * cnt * e1);
+        for (size_t k = 0; k < 10 * cnt; k++) ss[a0 + k] = r.s1[10 * first + k];
+        H256 g = {{0, 0, 0, 0}};
+        for (size_t it = first; it < first + cnt; it++) g = Fr::sub(g, r.gsc[it]);
+        memcpy(&bb[(a0 + 10 * cnt) * e1], su->g1_0.xy, e1); ss[a0 + 10 * cnt] = Fr::from_mont(g);
+        memcpy(&bb[b0 * e1], &r.b2[2 * first * e1], 2 * cnt * e1);
+        for (size_t k = 0; k < 2 * cnt; k++) ss[b0 + k] = r.s2[2 * first + k];
+        // (the ring commitments, terms 0 .. 2 of an item, were tested once per call; pi_1 and pi_2 of B_v are terms 8 and 9 of A_v)
+        if (dev_subgroup) for (size_t it = 0; it < cnt; it++) for (size_t p = 3; p < 10; p++) { pt.push_back((uint32_t)(a0 + 10 * it + p)); rec_of.push_back((uint32_t)j); }
+      }
+      uint8_t *d_xy; uint32_t *d_b, *d_s, *d_pts, *d_flag, *d_pt, *d_rec_of; int32_t *d_ok, *d_rec;
+      ln.carve().take(d_xy, np * e1).take(d_b, np * e1 / 4).take(d_s, np * 8).take(d_pts, nv * e1 / 4).take(d_ok, ns).take(d_rec, ns).take(d_flag, 1)
+          .take(d_pt, pt.size()).take(d_rec_of, pt.size()).into(1);
+      HIP_CHECK(hipMemcpyAsync(d_xy, bb.data(), np * e1, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(d_s, ss.data(), np * 32, hipMemcpyHostToDevice, ln.stream));
+      HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, ln.stream)); HIP_CHECK(hipMemsetAsync(d_rec, 0, ns * 4, ln.stream));
+      launch_g1_bases(su->curve, d_xy, np, d_b, d_flag, ln.stream);
+      if (!pt.empty()) {
+        HIP_CHECK(hipMemcpyAsync(d_pt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice, ln.stream));
+        HIP_CHECK(hipMemcpyAsync(d_rec_of, rec_of.data(), pt.size() * 4, hipMemcpyHostToDevice, ln.stream));
+        launch_g1_subgroup_check_list(su->curve, d_b, d_pt, d_rec_of, pt.size(), d_flag, d_rec, ln.stream);
+      }
+      std::vector<uint8_t> xy(nv * e1);
+      // (the layout keeps every round inside the engine's limits: a refusal here is a defect, not an input)
+      if (msm_g1_segments(su->curve, d_b, d_s, L, nv, ln.ws, ln.stream, xy.data(), d_pts)) throw HipFailure{hipErrorInvalidValue, __FILE__, __LINE__};   // (synchronises the stream)
+      r.lap("segment sums (device, one chain)");
+      std::vector<int32_t> okv(ns), rec(ns); uint32_t range_flag = 0;
+      if (!host_pair) {
+        launch_pairing_check(su->ptab, d_pts, ns, d_ok, ln.stream);
+        HIP_CHECK(hipMemcpyAsync(okv.data(), d_ok, ns * 4, hipMemcpyDeviceToHost, ln.stream));
+      }
+      HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec, ns * 4, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipMemcpyAsync(&range_flag, d_flag, 4, hipMemcpyDeviceToHost, ln.stream));
+      HIP_CHECK(hipStreamSynchronize(ln.stream)); HIP_CHECK(hipGetLastError());
+      if (range_flag & 1) return AVRF_INVALID_DATA;      // a base with a coordinate >= p (launch_g1_bases): no segment to pin it on
+      // the chain's record holds the Montgomery affine points the finishing kernel wrote: what the host pairing reads
+      if (host_pair) { host_pair_checks(su, ln.ws.own.bits_host.template as<uint32_t>(), ns, okv.data()); r.lap("pairing checks (host pool)"); }
+      else r.lap("pairing checks (device)");
+      for (size_t j = 0; j < ns; j++) {
+        const size_t v = s0 + j;
+        if (r.seg_off[v + 1] == r.seg_off[v] || st[v]) continue;
+        st[v] = rec[j] ? AVRF_INVALID_DATA : okv[j] ? AVRF_OK : AVRF_VERIFICATION_FAILURE;
+        memcpy(&sums[2 * v * e1], &xy[2 * j * e1], 2 * e1);
+      }
+    }
+    return AVRF_OK;
+  }
+  // one segment through the folded tail: the batch of its items alone
+  static int verify_segment_folded(VerifyRun &r, size_t v, uint8_t *sums_xy) {
+    const size_t first = r.seg_off[v], cnt = r.seg_off[v + 1] - first, e1 = 2 * FQB;
+    VerifyRun q{r.su, r.ln, cnt, r.n_rings, r.commitments, r.ring_of_item, r.instances_xy, r.proofs, nullptr, RingTrace("ring_verify_segment", cnt, false), r.host_subgroup};
+    q.b1.assign(r.b1.begin() + 10 * first * e1, r.b1.begin() + 10 * (first + cnt) * e1); q.b1.resize((10 * cnt + 1) * e1);
+    q.s1.assign(r.s1.begin() + 10 * first, r.s1.begin() + 10 * (first + cnt)); q.s1.resize(10 * cnt + 1);
+    q.b2.assign(r.b2.begin() + 2 * first * e1, r.b2.begin() + 2 * (first + cnt) * e1);
+    q.s2.assign(r.s2.begin() + 2 * first, r.s2.begin() + 2 * (first + cnt));
+    q.gsc.assign(r.gsc.begin() + first, r.gsc.begin() + first + cnt);
+    G1Aff acc[2];
+    const int verdict = verify_tail_folded(q, acc);
+    if (verdict != AVRF_INVALID_DATA) { memcpy(sums_xy, acc[0].xy, e1); memcpy(sums_xy + e1, acc[1].xy, e1); }
+    return verdict;
+  }
+  // Fewer segments than this run the folded tail once per segment instead of the chain: one segment IS the folded batch, and two
+  // folded tails are two launch chains, two host Horners and two host pairings against one chain.  The threshold has not been
+  // measured (tools/ring_segments_bench.py times 16 segments and more); this is the one place it is written.
+  static constexpr size_t RING_SEG_CHAIN_MIN = 2;
+  static int verify_segments(avrf_ring_setup *su, size_t n, const uint8_t *commitments, const uint32_t *ring_of_item, size_t n_rings,
+                             const uint8_t *instances_xy, const uint8_t *proofs, const RingSegLayout &lay, int32_t *status_out) {
+    const size_t n_seg = lay.off.size() - 1, e1 = 2 * FQB;
+    std::vector<int32_t> st(n_seg, AVRF_OK);
+    std::vector<uint8_t> sums(2 * n_seg * e1, 0);
+    su->seg_sums_n = 0;
+    if (n) {
+      VerifyRun r{su, su->lane[0], n, n_rings, commitments, ring_of_item, instances_xy, proofs, nullptr, RingTrace("ring_verify_segments", n, false),
+                  FQB == 48 && 10 * n + 3 * n_rings <= 512};
+      r.seg_off = lay.off; r.lone.assign(n, 0);
+      for (size_t v = 0; v < n_seg; v++) if (lay.off[v + 1] - lay.off[v] == 1) r.lone[lay.off[v]] = 1;
+      // all 3 n_rings commitments before any segment: decoded, and in the subgroup whichever side tests the proofs' points
+      if (int s = verify_commitments(r)) return s;
+      if (!r.host_subgroup) {
+        std::atomic<int> badc{0};
+        parallel_for(3 * n_rings, [&](size_t i) { if (!g1_in_subgroup_host<G>(r.fixed[i])) badc = 1; });
+        if (badc) return AVRF_INVALID_DATA;
+      }
+      r.rnd.resize(32 * n);
+      parallel_for(n_seg, [&](size_t v) {
+        HR::segment_randomisers(lay.off[v], lay.off[v + 1] - lay.off[v], n_rings, su->N, su->g1_0, su->g2_raw, ring_of_item, commitments, instances_xy, proofs, &r.rnd[32 * lay.off[v]]);
+      });
+      verify_points(r);
+      verify_transcripts(r);
+      if (int s = verify_reduce(r)) return s;
+      r.lap("decode + transcripts (host)");
+      // the host's verdict on a segment: AVRF_INVALID_DATA wins over AVRF_VERIFICATION_FAILURE, whatever the order of its items
+      for (size_t v = 0; v < n_seg; v++)
+        for (size_t it = lay.off[v]; it < lay.off[v + 1]; it++)
+          if (r.item_st[it] == AVRF_INVALID_DATA || (r.item_st[it] && !st[v])) st[v] = r.item_st[it];
+      if (n_seg < RING_SEG_CHAIN_MIN) {
+        for (size_t v = 0; v < n_seg; v++) if (lay.off[v + 1] != lay.off[v] && !st[v]) st[v] = verify_segment_folded(r, v, &sums[2 * v * e1]);
+      } else if (int s = verify_tail_segments(r, lay, st, sums)) return s;
+    }
+    for (size_t v = 0; v < n_seg; v++) status_out[v] = st[v];
+    su->seg_sums = std::move(sums); su->seg_sums_n = n_seg;
+    return AVRF_OK;
   }
 };
 
@@ -1443,6 +1609,35 @@ int avrf_ring_batch_verify(avrf_ring_setup *su, size_t n, const uint8_t *ring_co
   if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
   return guarded([&] {
     return with_ring(su->suite, [&](auto r) { return r.verify_batch(su, n, ring_commitments, ring_of_item, n_rings, instances_xy, ring_proofs); }); });
+}
+
+// n_seg independent ring BatchVerifiers (src/ring.rs:682-735) over consecutive runs of the n items: include/avrf.h.  Every refusal for
+// the arguments is decided before anything is decoded or launched.
+int avrf_ring_batch_verify_segments(avrf_ring_setup *su, size_t n, const uint8_t *ring_commitments, size_t n_rings, const uint32_t *ring_of_item,
+                                    const uint8_t *instances_xy, const uint8_t *ring_proofs, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  if (!su || su->g2_raw.empty() || (n && (!ring_commitments || !n_rings || !instances_xy || !ring_proofs)) || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
+  if (avrf_ctx_busy_(su->ctx)) return AVRF_ERR_BAD_ARG;
+  RingSegLayout lay;
+  if (int st = ring_segments_layout(n, n_seg, seg_items, lay)) return st;
+  for (size_t i = 0; ring_of_item && i < n; i++) if (ring_of_item[i] >= n_rings) return AVRF_ERR_BAD_ARG;
+  if (hipSetDevice(su->device) != hipSuccess) return AVRF_ERR_NO_DEVICE;
+  return guarded([&] {
+    return with_ring(su->suite, [&](auto r) { return r.verify_segments(su, n, ring_commitments, ring_of_item, n_rings, instances_xy, ring_proofs, lay, status_out); }); });
+}
+int avrf_ring_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, uint64_t out[4]) {
+  if (!out) return AVRF_ERR_BAD_ARG;
+  RingSegLayout lay;
+  if (int st = ring_segments_layout(n, n_seg, seg_items, lay)) return st;
+  out[0] = lay.L; out[1] = lay.rounds; out[2] = lay.padded; out[3] = lay.c;
+  return AVRF_OK;
+}
+// test probe: the two G1 sums the last segmented call on this setup formed for segment `seg` (all-zero: infinity, an empty segment or
+// one the host part had condemned before any sum was formed)
+int avrf_ring_segment_sums(avrf_ring_setup *su, size_t seg, uint8_t *a_xy, uint8_t *b_xy) {
+  if (!su || !a_xy || !b_xy || seg >= su->seg_sums_n) return AVRF_ERR_BAD_ARG;
+  const size_t e1 = su->seg_sums.size() / (2 * su->seg_sums_n);
+  memcpy(a_xy, &su->seg_sums[2 * seg * e1], e1); memcpy(b_xy, &su->seg_sums[(2 * seg + 1) * e1], e1);
+  return AVRF_OK;
 }
 
 }  // extern "C"

@@ -204,6 +204,52 @@ def ring_batch_verify(setup, ring_commitments, ring_of_item, instances_xy, ring_
                                             roi, nat._u8(b"".join(instances_xy)), nat._u8(b"".join(ring_proofs)))
 
 
+def ring_batch_verify_segments(setup, ring_commitments, ring_of_item, instances_xy, ring_proofs, seg_items, status_buf=None):
+    """n_seg independent ring BatchVerifiers over consecutive runs of the items (avrf_ring_batch_verify_segments): seg_items[v] items
+    in segment v.  Returns the list of n_seg statuses, or the call's own status when it wrote none (ERR_BAD_ARG, INVALID_DATA).
+    status_buf: a ctypes int32 array to receive the statuses instead of a fresh one (tests: a refusal leaves it untouched)."""
+    n, seg_items = len(ring_proofs), list(seg_items)
+    roi = nat._u32(ring_of_item) if ring_of_item is not None else None
+    out = status_buf if status_buf is not None else (C.c_int32 * max(1, len(seg_items)))()
+    st = nat.lib().avrf_ring_batch_verify_segments(setup._h, C.c_size_t(n), nat._u8(b"".join(ring_commitments)), C.c_size_t(len(ring_commitments)),
+                                                   roi, nat._u8(b"".join(instances_xy)), nat._u8(b"".join(ring_proofs)),
+                                                   C.c_size_t(len(seg_items)), nat._u32(seg_items), out)
+    return list(out)[: len(seg_items)] if st == nat.OK else st
+
+
+def ring_segments_layout(n, seg_items):
+    """Layout of a segmented ring verification over n items (host arithmetic, no device): (L, rounds, padded terms of the largest
+    round, window bits), or ERR_BAD_ARG when the counts do not sum to n or a segment has more than 819 items."""
+    seg_items = list(seg_items)
+    out = (C.c_uint64 * 4)()
+    st = nat.lib().avrf_ring_segments_layout(C.c_size_t(n), C.c_size_t(len(seg_items)), nat._u32(seg_items), out)
+    return tuple(out) if st == nat.OK else st
+
+
+def ring_segment_sums(setup, seg):
+    """(A, B): the two G1 sums (canonical LE x || y, all-zero = infinity) the last ring_batch_verify_segments on this setup formed for
+    segment `seg`; raises AvrfError without such a call or for seg out of range."""
+    fq = (setup.commitment_len // 3)
+    a, b = (C.c_uint8 * (2 * fq))(), (C.c_uint8 * (2 * fq))()
+    st = nat.lib().avrf_ring_segment_sums(setup._h, C.c_size_t(seg), a, b)
+    if st != nat.OK:
+        raise nat.AvrfError(f"avrf_ring_segment_sums -> {st}")
+    return bytes(a), bytes(b)
+
+
+def ring_vrf_verify_segments(ctx, setup, ring_commitments, ring_of_item, ios, io_counts, ads, proofs, seg_items, validate=1):
+    """Complete ring-VRF verification, one verdict per segment (avrf_ring_vrf_verify_segments): ios / proofs in wire format as for
+    avrf_ring_vrf_verify (lists of per-item bytes), io_counts pairs per item, ads per item.  Returns the list of statuses, or the
+    call's own status when it wrote none."""
+    n, seg_items = len(proofs), list(seg_items)
+    roi = nat._u32(ring_of_item) if ring_of_item is not None else None
+    out = (C.c_int32 * max(1, len(seg_items)))()
+    st = nat.lib().avrf_ring_vrf_verify_segments(ctx._h, setup._h, C.c_size_t(n), nat._u8(b"".join(ring_commitments)), C.c_size_t(len(ring_commitments)), roi,
+                                                 nat._u8(b"".join(ios)), nat._u32(list(io_counts)), nat._u8(b"".join(ads)), nat._u32([len(a) for a in ads]),
+                                                 nat._u8(b"".join(proofs)), int(validate), C.c_size_t(len(seg_items)), nat._u32(seg_items), out)
+    return list(out)[: len(seg_items)] if st == nat.OK else st
+
+
 def srs_generate(ctx, suite, tau, g1, g2, ring_size):
     """Kzg::setup with an explicit trapdoor (RingSetup::from_seed / from_rand, src/ring.rs:359-374): URS bytes for a ring
     of `ring_size` keys.  tau: int < r; g1, g2: generator entries in URS encoding (e.g. sliced from an SRS file)."""

@@ -114,6 +114,13 @@ int avrf_msm_te_mont(avrf_ctx *ctx, size_t n, const uint8_t *bases_mont_xy, cons
  * bases_xy: n x (2*FQ) bytes, canonical little-endian x || y (FQ = 48 / 32), all-zero = point at infinity;
  * scalars: n x 32 (< r of the pairing curve); out_xy: same point format. */
 int avrf_g1_msm(avrf_ctx *ctx, size_t n, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy);
+/* n_seg independent <E::G1 as VariableBaseMSM>::msm calls (the same call sites, src/ring.rs:220,404,416,731) of L terms each in one
+ * call, beside avrf_g1_msm: segment v is bases_xy[v L ..], scalars[v L ..]; out_xy: n_seg points in the format above.  ONE launch
+ * chain for every n_seg >= 1 (no per-segment loop), with the Horner and the affine conversion on the device: it is the probe of the
+ * chain avrf_ring_batch_verify_segments runs.  A coordinate >= p or a scalar >= r gives AVRF_INVALID_DATA; L > AVRF_SEGMENT_TERMS_MAX,
+ * n_seg * L > AVRF_SEGMENTS_PADDED_TERMS_MAX or n_seg * windows(L) > AVRF_SEGMENTS_WINDOWS_MAX gives AVRF_ERR_BAD_ARG; L == 0 writes
+ * n_seg points at infinity, n_seg == 0 nothing, both AVRF_OK. */
+int avrf_g1_msm_segments(avrf_ctx *ctx, size_t n_seg, size_t L, const uint8_t *bases_xy, const uint8_t *scalars, uint8_t *out_xy);
 
 /* thin::BatchVerifier::{new, push*, verify}  (src/thin.rs:188-326).
  * n items; item j has io_counts[j] VRF I/O pairs; ios_xy holds sum(io_counts) pairs as
@@ -750,6 +757,48 @@ int avrf_ring_batch_verify(avrf_ring_setup *setup, size_t n, const uint8_t *ring
 int avrf_ring_verify_each(avrf_ring_setup *setup, size_t n, const uint8_t *ring_commitments, size_t n_rings, const uint32_t *ring_of_item,
                           const uint8_t *instances_xy, const uint8_t *ring_proofs, int32_t *status_out);
 
+/* ---- ring BatchVerifier over SEGMENTS: one verdict per group of proofs (src/ring.rs:682-735, one BatchVerifier per segment).
+ * n_seg independent ring BatchVerifiers over consecutive runs of the n items -- segment v covers the next seg_items[v] items, the
+ * counts sum to n -- with the other arguments of avrf_ring_batch_verify.  Every segment derives its own randomisers, exactly as
+ * avrf_ring_batch_verify on its items alone does (a one-item segment: r1 = 1), and gets its own 2-pairing check; the G1 sums of all
+ * segments are ONE segmented MSM chain on the device (two vectors per segment, 10 items + 1 and 2 items terms, padded to
+ * L = 10 (longest segment) + 1), whose finishing kernel leaves every segment's two points where the pairing kernel reads them.
+ * For a caller with many small groups of proofs (a block importer: a handful of tickets per block).
+ *   statuses  status_out[v] is what avrf_ring_batch_verify answers for segment v's items alone with the same commitments table;
+ *             an empty segment is AVRF_OK.  Where avrf_ring_batch_verify may answer 1 or 2 for a batch that holds both kinds of
+ *             defect, this call is deterministic: AVRF_INVALID_DATA wins (a proof point that does not decode or lies outside the
+ *             subgroup, an evaluation or lin_zw >= r, an instance coordinate >= r), otherwise AVRF_VERIFICATION_FAILURE.  A defect
+ *             marks ITS segment and no other.  The call returns AVRF_OK whenever the statuses were written.
+ *   failures  of the call, no status written: a ring commitment that does not decode or lies outside the subgroup gives
+ *             AVRF_INVALID_DATA (all 3 n_rings commitments are checked before any segment).  AVRF_ERR_BAD_ARG: counts that do not
+ *             sum to n, a ring_of_item entry >= n_rings, a segment of more than 819 items (10 items + 1 <= AVRF_SEGMENT_TERMS_MAX),
+ *             a busy handle.  These refusals are decided before anything is decoded or launched; the setup stays usable and
+ *             avrf_ring_batch_verify / avrf_ring_verify_each behave as before.
+ *   rounds    the NUMBER of segments is never refused: when 2 n_seg windows(L), the padded term count 2 n_seg L
+ *             (AVRF_SEGMENTS_PADDED_TERMS_MAX) or the 32-bit entry offsets would be exceeded, the call runs several chains over
+ *             consecutive runs of segments.  avrf_ring_segments_layout states them.
+ *   pairings  up to 16 segments: on the host pool from the copied-back sums (as avrf_ring_verify_each); more: the device pairing
+ *             kernel on the finishing kernel's output.  One segment is exactly avrf_ring_batch_verify.
+ * Runtime (tools/ring_segments_bench.py, profiles/ring_segments_bench.txt; one setup, 4 096 valid proofs over one ring
+ * of 1 024, Bandersnatch / BLS12-381): 256 segments of 16 proofs 20.8-21.6 ms, 64 x 64 21.8-22.1 ms, 16 x 256 12.6-13.3 ms.  The same
+ * groups as separate avrf_ring_batch_verify calls: 513-518 / 256-261 / 82-83 ms (24 x, 12 x, 6 x slower).  avrf_ring_verify_each on the
+ * same proofs, one verdict per PROOF: 25.3-25.8 ms -- behind the segmented call, ranges apart; avrf_ring_batch_verify on all of them,
+ * ONE verdict: 11.4-11.5 ms.  The host reduction is not what bounds the segmented call (2.1 ms of it): the device pairing kernel
+ * takes 9.6 ms whatever it carries and the chain's finishing kernel 3.3-4.0 ms.  Use segments for many small groups and to locate a
+ * bad group; use avrf_ring_verify_each when a verdict per proof is what is wanted. */
+int avrf_ring_batch_verify_segments(avrf_ring_setup *setup, size_t n, const uint8_t *ring_commitments, size_t n_rings,
+                                    const uint32_t *ring_of_item, const uint8_t *instances_xy, const uint8_t *ring_proofs,
+                                    size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+/* The layout of such a call (src/ring.rs:682-735: term counts of n_seg BatchVerifiers), host arithmetic only, no device:
+ * out = { L, rounds, padded terms of the largest round (2 segments-per-round L), window bits of the L-term MSMs }.
+ * AVRF_ERR_BAD_ARG when the counts do not sum to n or a segment has more than 819 items. */
+int avrf_ring_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, uint64_t out[4]);
+/* Test probe, like avrf_thin_segment_terms (src/ring.rs:693-735, the two sums of BatchVerifier::verify): the two G1 sums (canonical
+ * little-endian x || y, all-zero = infinity) the last avrf_ring_batch_verify_segments on this setup formed for segment `seg` --
+ * all-zero too for an empty segment and for one the host part had condemned before any sum was formed.  AVRF_ERR_BAD_ARG without
+ * such a call (or after one that failed) and for seg out of range. */
+int avrf_ring_segment_sums(avrf_ring_setup *setup, size_t seg, uint8_t *a_xy, uint8_t *b_xy);
+
 /* The pairing half of the KZG verifier on the device (arkworks `Pairing::multi_pairing` + final exponentiation as reached
  * from RingVerifier::verify, src/ring.rs:242): for i < n,  ok_out[i] = 1 iff  e(A_i, g2) * e(B_i, tau g2) == 1  with (g2, tau g2)
  * the two `powers_in_g2` of the setup's SRS.  a_xy / b_xy: n G1 points each, canonical little-endian x || y (48+48 bytes
@@ -828,6 +877,16 @@ int avrf_ring_vrf_prove(avrf_ctx *ctx, avrf_ring_key *key, size_t ring_proof_len
 int avrf_ring_vrf_verify(avrf_ctx *ctx, avrf_ring_setup *setup, size_t n, const uint8_t *ring_commitments, size_t n_rings, const uint32_t *ring_of_item,
                          const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
                          int validate, int each, int32_t *status_out);
+/* n_seg ring::BatchVerifiers (src/ring.rs:682-735) over consecutive runs of the n items, with the arguments of avrf_ring_vrf_verify:
+ * the Pedersen half is the segmented Pedersen path on the context (avrf_pedersen_batch_run_segments over the decompressed proofs; a
+ * staging or validation failure is returned as avrf_pedersen_batch_verify_segments_wire returns it, no status written), the ring
+ * half avrf_ring_batch_verify_segments on the setup with the Yb of the Pedersen proofs as instances; the halves run side by side.
+ * status_out[v] is AVRF_INVALID_DATA if either half says so, else AVRF_VERIFICATION_FAILURE if either half is not AVRF_OK, else
+ * AVRF_OK.  Mismatched suites, counts that do not sum to n or a segment of more than 819 items give AVRF_ERR_BAD_ARG. */
+int avrf_ring_vrf_verify_segments(avrf_ctx *ctx, avrf_ring_setup *setup, size_t n, const uint8_t *ring_commitments, size_t n_rings,
+                                  const uint32_t *ring_of_item, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                                  const uint32_t *ad_lens, const uint8_t *proofs, int validate, size_t n_seg, const uint32_t *seg_items,
+                                  int32_t *status_out);
 
 #ifdef __cplusplus
 }

@@ -508,6 +508,21 @@ class BatchVerifier {
     std::vector<uint8_t> coms; for (const RingCommitment &c : rings_) coms.insert(coms.end(), c.begin(), c.end());
     return avrf_ring_batch_verify(setup_->handle(), ring_of_.size(), coms.data(), rings_.size(), ring_of_.data(), inst_.data(), proofs_.data());
   }
+  // One verdict per segment: seg_items[v] consecutive pushed items each, summing to the number pushed; what n_seg BatchVerifiers over
+  // those runs of items would answer (:682-735), both halves in one pass each (avrf_pedersen_batch_verify_segments, then
+  // avrf_ring_batch_verify_segments).  InvalidData if either half says so, else VerificationFailure if either half fails.  At most 819
+  // items per segment.  Throws when a call is refused or a ring commitment does not decode.
+  std::vector<Status> verify_segments(const std::vector<uint32_t> &seg_items) const {
+    const std::vector<Status> ped = ped_.verify_segments(seg_items);
+    std::vector<uint8_t> coms; for (const RingCommitment &c : rings_) coms.insert(coms.end(), c.begin(), c.end());
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_ring_batch_verify_segments(setup_->handle(), ring_of_.size(), coms.data(), rings_.size(), ring_of_.data(), inst_.data(), proofs_.data(),
+                                        seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: ring verify segments");
+    std::vector<Status> out(seg_items.size());
+    for (size_t v = 0; v < out.size(); v++)
+      out[v] = (ped[v] == AVRF_INVALID_DATA || st[v] == AVRF_INVALID_DATA) ? AVRF_INVALID_DATA : (ped[v] || st[v]) ? AVRF_VERIFICATION_FAILURE : AVRF_OK;
+    return out;
+  }
 
  private:
   const Suite &su_; const RingSetup *setup_;
