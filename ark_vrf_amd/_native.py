@@ -216,11 +216,31 @@ def pedersen_segments_layout(n, seg_items):
     return tuple(out) if st == OK else st
 
 
+def thin_shared_segments_layout(seg_items, io_counts, n_shared):
+    """Layout avrf_thin_batch_run_shared_segments takes over a table of n_shared rows (host arithmetic; no device needed) ->
+    (L, padded terms, total terms, window bits, mode) with mode 1 = merged, 0 = expanded, or ERR_BAD_ARG as thin_segments_layout."""
+    seg_items, io_counts = list(seg_items), list(io_counts)
+    out = (C.c_uint64 * 5)()
+    st = lib().avrf_thin_shared_segments_layout(C.c_size_t(len(io_counts)), C.c_size_t(n_shared), C.c_size_t(len(seg_items)), _u32(seg_items),
+                                                _u32(io_counts), out)
+    return tuple(out) if st == OK else st
+
+
+def pedersen_shared_segments_layout(n, seg_items, n_shared):
+    """The same for avrf_pedersen_batch_run_shared_segments over n items and a table of n_shared inputs."""
+    seg_items = list(seg_items)
+    out = (C.c_uint64 * 5)()
+    st = lib().avrf_pedersen_shared_segments_layout(C.c_size_t(n), C.c_size_t(n_shared), C.c_size_t(len(seg_items)), _u32(seg_items), out)
+    return tuple(out) if st == OK else st
+
+
 class Context:
     """One engine instance = suite + HIP stream + device workspace (avrf_ctx)."""
 
     thin_segments_layout = staticmethod(thin_segments_layout)
     pedersen_segments_layout = staticmethod(pedersen_segments_layout)
+    thin_shared_segments_layout = staticmethod(thin_shared_segments_layout)
+    pedersen_shared_segments_layout = staticmethod(pedersen_shared_segments_layout)
 
     def __init__(self, suite=BANDERSNATCH_SHA512_ELL2, device=0):
         self._h = C.c_void_p()
@@ -330,6 +350,22 @@ class Context:
         """The same for a Batch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes (compressed points)."""
         return self._segments(seg_items, lib().avrf_thin_batch_verify_segments_wire, C.c_size_t(b.n), b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens,
                               b.proofs, int(validate))
+
+    # -- one verdict per segment of whatever Thin / Pedersen batch is staged, a shared-table one included (include/avrf.h
+    # avrf_thin_batch_run_shared_segments): segment_terms afterwards are in the layout the run chose
+    def thin_batch_run_shared_segments(self, seg_items):
+        return self._segments(seg_items, lib().avrf_thin_batch_run_shared_segments)
+
+    def pedersen_batch_run_shared_segments(self, seg_items):
+        return self._segments(seg_items, lib().avrf_pedersen_batch_run_shared_segments)
+
+    def thin_batch_verify_shared_segments_wire(self, b, seg_items, validate=1):
+        """stage_shared_wire + thin_batch_run_shared_segments for a SharedWireBatch."""
+        return self._segments(seg_items, lib().avrf_thin_batch_verify_shared_segments_wire, *b.args(), int(validate))
+
+    def pedersen_batch_verify_shared_segments_wire(self, b, seg_items, validate=1):
+        """stage_shared_wire + pedersen_batch_run_shared_segments for a PedersenSharedWireBatch."""
+        return self._segments(seg_items, lib().avrf_pedersen_batch_verify_shared_segments_wire, *b.args(), int(validate))
 
     def _segments(self, seg_items, call, *args):
         """call(ctx, *args, n_seg, seg_items, status_out) -> the list of n_seg statuses, or the refusal."""

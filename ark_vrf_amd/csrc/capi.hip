@@ -21,7 +21,6 @@
 #include "suite_dispatch.h"
 #include <chrono>
 #include <optional>
-#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -82,9 +81,9 @@ static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status) {
   uint32_t *fl = c->d_flags.as<uint32_t>();
   const uint32_t n = (uint32_t)c->n;
   const KindFacts &k = kind_facts(kind);
-  if (c->n_shared) {                                                   // a shared table: every row once, not once per reference; the outputs where they were gathered
-    // (batch verifiers only: the per-item calls, which want d_rec_status, restage through ctx_stage and so never see a shared staging)
-    assert(!d_rec_status);
+  if (c->n_shared && !d_rec_status) {                                  // a shared table: every row once, not once per reference; the outputs where they were gathered
+    // (a status per item is wanted by the per-item calls, which restage through ctx_stage and so never see a shared staging, and by the
+    // attribution pass of a segmented run, which takes the plain route below over the rows as shared_plan gathered them)
     AVRF_SINGLE(c->suite, validate_xy(c->d_table.as<uint8_t>(), 64, 1, (uint32_t)c->n_shared, c->validate, fl, nullptr, c->stream));
     AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>() + 64, 128, 1, (uint32_t)c->tot_io, c->validate, fl, nullptr, c->stream));
     AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, nullptr, c->stream));
@@ -619,13 +618,16 @@ static Seed64 seed_of(const uint8_t digest[64]) {
 }
 // the kind's prepare kernel (challenges into d_c, the terms kernel's other inputs into d_z, the checks into d_flags) and terms kernel
 // The run's check flags start clear -- or, over a shared table, from what staging found in it (a non-canonical coordinate in any row)
-static hipError_t reset_flags(avrf_ctx *c) {
-  if (!c->n_shared) return hipMemsetAsync(c->d_flags.p, 0, 4, c->stream);
+// (items_only: a segmented run, whose verdicts depend on the rows a segment REFERENCES -- the prepare kernel checks those where they were gathered)
+static hipError_t reset_flags(avrf_ctx *c, bool items_only = false) {
+  if (!c->n_shared || items_only) return hipMemsetAsync(c->d_flags.p, 0, 4, c->stream);
   return hipMemcpyAsync(c->d_flags.p, shared_plan_flag(c->d_table_plan.as<uint32_t>(), c->n_shared, c->n_contrib), 4, hipMemcpyDeviceToDevice, c->stream);
 }
-static void launch_prepare(avrf_ctx *c, int kind, const BatchDev &b) {
+// rows_stay: the inputs of a Pedersen batch stay rows of the table (k_ped_prepare<S, true>: no merged input) -- every run of a shared
+// staging but a segmented one in the expanded layout
+static void launch_prepare(avrf_ctx *c, int kind, const BatchDev &b, bool rows_stay) {
   if (kind == Thin) AVRF_BATCH(c->suite, thin_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->d_flags.as<uint32_t>(), c->stream));
-  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), c->n_shared != 0, c->stream));
+  else AVRF_BATCH(c->suite, ped_prepare(b, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->d_flags.as<uint32_t>(), rows_stay, c->stream));
 }
 static void launch_terms(avrf_ctx *c, int kind, const BatchDev &b, const Seed64 &seed, uint64_t first, uint32_t *d_scalars) {
   if (kind == Thin && c->n_shared)
@@ -642,7 +644,7 @@ static void launch_terms(avrf_ctx *c, int kind, const BatchDev &b, const Seed64 
                                       c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
 }
 
-int batch_begin(avrf_ctx *c, int kind) {
+int batch_begin(avrf_ctx *c, int kind, bool segmented) {
   if (!c || c->staged_kind != kind || c->run_phase != 0) return AVRF_ERR_BAD_ARG;
   if (c->n == 0) { c->run_phase = 1; return AVRF_OK; }                 // src/thin.rs:262-264, src/pedersen.rs:343-345
   if (!c->n_terms) return AVRF_ERR_BAD_ARG;
@@ -650,7 +652,7 @@ int batch_begin(avrf_ctx *c, int kind) {
   c->run_t0 = now_us();
   const size_t n = c->n;
   BatchDev b = batch_of(c);
-  HIP_TRY(reset_flags(c));
+  HIP_TRY(reset_flags(c, segmented));
   validate_staged(c, kind, nullptr);
   const bool host_weights = suite_host_weights(c->suite);
   // the weight transcript's message, prefix || records: the prepare kernel writes the records, one copy brings them back
@@ -660,7 +662,7 @@ int batch_begin(avrf_ctx *c, int kind) {
     HIP_TRY(c->d_rec.ensure(n * recsz)); HIP_TRY(c->h_msg.ensure(pl + n * recsz));
     b.records = c->d_rec.as<uint8_t>();
   }
-  launch_prepare(c, kind, b);
+  launch_prepare(c, kind, b, c->n_shared && !(segmented && !c->seg.merged));
   if (!host_weights) {
     memcpy(c->h_msg.p, prefix, pl);
     HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl, c->d_rec.p, n * recsz, hipMemcpyDeviceToHost, c->stream));
@@ -795,7 +797,7 @@ static int run_call(avrf_ctx *c, int (*phase)(avrf_ctx *, int)) {
   }
   return phase(c, c->staged_kind);
 }
-int avrf_batch_run_begin(avrf_ctx *c) { return run_call(c, batch_begin); }
+int avrf_batch_run_begin(avrf_ctx *c) { return run_call(c, [](avrf_ctx *ctx, int kind) { return batch_begin(ctx, kind); }); }
 int avrf_batch_run_hash(avrf_ctx *c) { return run_call(c, batch_hash); }
 int avrf_batch_run_end(avrf_ctx *c) { return run_call(c, batch_end); }
 
@@ -841,21 +843,46 @@ static int seg_limits(size_t n_seg, uint64_t L, uint64_t out[4]) {
   out[0] = L; out[1] = n_seg * L; out[3] = c;
   return AVRF_OK;
 }
-static int seg_layout(int kind, size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_off, std::vector<uint32_t> *seg_off, uint64_t out[4]) {
-  if ((n_seg && !seg_items) || n_seg > 0x0fffffffULL || (kind == Thin && n && !io_off)) return AVRF_ERR_BAD_ARG;
+// Over a table of T = n_shared rows (avrf_thin_shared_segments_layout, avrf_pedersen_shared_segments_layout; 0: a plain staging) a segment
+// has a second, MERGED layout -- its item terms (Thin items + pairs, Pedersen 4 items), then T row terms, then its base term(s) -- and the
+// run takes it exactly when its padded length is the smaller one (a tie goes to the expanded layout, which needs no plan): out[4] = 1,
+// and *row0 (when wanted) the term of each segment's row 0, SHARED_NO_ROW for an empty segment.  The limits apply to the chosen L.
+static int seg_layout(int kind, size_t n, size_t n_shared, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_off, std::vector<uint32_t> *seg_off,
+                      std::vector<uint32_t> *row0, uint64_t out[5]) {
+  if ((n_seg && !seg_items) || n_seg > 0x0fffffffULL || n_shared > 0x0fffffffULL || (kind == Thin && n && !io_off)) return AVRF_ERR_BAD_ARG;
   if (seg_off) seg_off->assign(n_seg + 1, (uint32_t)n);
-  uint64_t at = 0, L = 0, total = 0;
+  const uint64_t T = n_shared, nbase = kind == Thin ? 1 : 2;
+  uint64_t at = 0, L = 0, total = 0, body = 0, total_m = 0;
   for (size_t v = 0; v < n_seg; v++) {
     const uint64_t items = seg_items[v];
     if (at + items > n) return AVRF_ERR_BAD_ARG;
     if (seg_off) (*seg_off)[v] = (uint32_t)at;
-    const uint64_t n_v = items ? n_terms(kind, items, kind == Thin ? io_off[at + items] - io_off[at] : 0) : 0;   // none for an empty segment
+    const uint64_t pairs = kind == Thin && items ? io_off[at + items] - io_off[at] : 0;
+    const uint64_t n_v = items ? n_terms(kind, items, pairs) : 0;    // none for an empty segment
+    const uint64_t b_v = kind == Thin ? items + pairs : 4 * items;   // the item terms of the merged layout
     if (n_v > L) L = n_v;
-    total += n_v; at += items;
+    if (b_v > body) body = b_v;
+    total += n_v; total_m += items ? b_v + T + nbase : 0; at += items;
   }
   if (at != n) return AVRF_ERR_BAD_ARG;
-  out[2] = total;
-  return seg_limits(n_seg, L, out);
+  const uint64_t L_m = body ? body + T + nbase : 0;
+  const bool merged = T && L_m < L;
+  out[2] = merged ? total_m : total; out[4] = merged;
+  if (int e = seg_limits(n_seg, merged ? L_m : L, out)) return e;
+  if (row0) {
+    row0->clear();
+    for (size_t v = 0; merged && v < n_seg; v++) {
+      const uint64_t first = (*seg_off)[v], items = seg_items[v];
+      row0->push_back(items ? (uint32_t)(v * L_m + (kind == Thin ? items + (io_off[first + items] - io_off[first]) : 4 * items)) : (uint32_t)SHARED_NO_ROW);
+    }
+  }
+  return AVRF_OK;
+}
+static int seg_layout4(int kind, size_t n, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_off, uint64_t out[4]) {
+  uint64_t lay[5];
+  const int st = seg_layout(kind, n, 0, n_seg, seg_items, io_off, nullptr, nullptr, lay);
+  if (st == AVRF_OK) memcpy(out, lay, 4 * sizeof(uint64_t));
+  return st;
 }
 
 extern "C" {
@@ -864,11 +891,21 @@ int avrf_thin_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items,
   if (!out || (n && !io_counts) || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   std::vector<uint32_t> io_off(n + 1); uint64_t a;
   if (!prefix_sums(io_counts, n, io_off.data(), 0x1fffffffULL, &a)) return AVRF_ERR_BAD_ARG;
-  return seg_layout(Thin, n, n_seg, seg_items, io_off.data(), nullptr, out);
+  return seg_layout4(Thin, n, n_seg, seg_items, io_off.data(), out);
 }
 int avrf_pedersen_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_items, uint64_t out[4]) {
   if (!out || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
-  return seg_layout(Pedersen, n, n_seg, seg_items, nullptr, nullptr, out);
+  return seg_layout4(Pedersen, n, n_seg, seg_items, nullptr, out);
+}
+int avrf_thin_shared_segments_layout(size_t n, size_t n_shared, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_counts, uint64_t out[5]) {
+  if (!out || (n && !io_counts) || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  std::vector<uint32_t> io_off(n + 1); uint64_t a;
+  if (!prefix_sums(io_counts, n, io_off.data(), 0x1fffffffULL, &a)) return AVRF_ERR_BAD_ARG;
+  return seg_layout(Thin, n, n_shared, n_seg, seg_items, io_off.data(), nullptr, nullptr, out);
+}
+int avrf_pedersen_shared_segments_layout(size_t n, size_t n_shared, size_t n_seg, const uint32_t *seg_items, uint64_t out[5]) {
+  if (!out || n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  return seg_layout(Pedersen, n, n_shared, n_seg, seg_items, nullptr, nullptr, nullptr, out);
 }
 }  // extern "C"
 
@@ -887,10 +924,22 @@ static int seg_ensure(avrf_ctx *c, int kind) {
   // (scratch per item: Thin's w s z0, Pedersen's u s and u sb)
   HIP_TRY(a.scalars.ensure(r.padded * 32)); HIP_TRY(a.pre.ensure(r.padded * sizeof(te_pre_raw))); HIP_TRY(c->L->d_seg_wsz.ensure(c->n * (kind == Thin ? 32 : 64)));
   HIP_TRY(c->L->d_seg_off.ensure((r.n_seg + 1) * 4)); HIP_TRY(c->L->d_seg_seeds.ensure(r.n_seg * sizeof(Seed64)));
+  if (r.merged) {                                                      // the run's plan, and the scratch of the row sums (the plain shared run's, ensure_terms)
+    HIP_TRY(c->d_seg_plan.ensure(shared_seg_plan_words(r.n_seg, c->n_shared, c->n_contrib) * 4));
+    HIP_TRY(c->L->d_shared.ensure(shared_scratch_words(c->n_contrib) * 4));
+  }
   return AVRF_OK;
 }
 static void launch_seg_terms(avrf_ctx *c, int kind, const BatchDev &b, size_t n_seg, size_t L) {
   const uint32_t *off = c->L->d_seg_off.as<uint32_t>(); const Seed64 *seeds = c->L->d_seg_seeds.as<Seed64>(); const SegArrays a = seg_arrays(c);
+  if (c->seg.merged) {
+    const SharedPlan p = shared_seg_plan_view(c->d_seg_plan.as<uint32_t>(), c->d_table_rows.as<te_pre_raw>(), n_seg, c->n_shared, c->n_contrib);
+    if (kind == Thin) AVRF_SHARED(c->suite, thin_seg_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), p, c->L->d_shared.as<uint32_t>(),
+                                                           c->L->d_seg_wsz.as<uint32_t>(), a.scalars.as<uint32_t>(), a.pre.as<te_pre_raw>(), c->stream));
+    else AVRF_SHARED(c->suite, ped_seg_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), p, c->L->d_shared.as<uint32_t>(),
+                                             c->L->d_seg_wsz.as<uint32_t>(), a.scalars.as<uint32_t>(), a.pre.as<te_pre_raw>(), c->stream));
+    return;
+  }
   if (kind == Thin) AVRF_SEG(c->suite, thin_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), c->L->d_seg_wsz.as<uint32_t>(),
                                                   a.scalars.as<uint32_t>(), a.pre.as<te_pre_raw>(), c->stream));
   else AVRF_SEG(c->suite, ped_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint8_t>(), c->L->d_seg_wsz.as<uint32_t>(),
@@ -902,22 +951,28 @@ static void launch_seg_item_flags(avrf_ctx *c, int kind, const BatchDev &b) {
 }
 
 namespace avrf {
-// h_seg_up: the item offsets, then (64-byte aligned) the seeds
+// h_seg_up: the item offsets, then (64-byte aligned) the seeds, then (the merged layout) each segment's row0
 static size_t seg_up_seeds_at(size_t n_seg) { return ((n_seg + 1) * 4 + 63) / 64 * 64; }
+static size_t seg_up_row0_at(size_t n_seg) { return seg_up_seeds_at(n_seg) + n_seg * sizeof(Seed64); }
 static bool seg_nothing(const avrf_ctx *c) { return !c->seg.n_seg || !c->n; }   // every (empty) segment is Ok: no device work at all
 
-int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items) {
-  if (!c || c->run_phase != 0 || c->staged_kind != kind || c->n_shared) return AVRF_ERR_BAD_ARG;
-  avrf_ctx::SegRun &r = c->seg; uint64_t lay[4];
-  if (int e = seg_layout(kind, c->n, n_seg, seg_items, c->h_io.as<uint32_t>(), &r.off, lay)) return e;
-  r.n_seg = n_seg; r.L = (size_t)lay[0]; r.padded = (size_t)lay[1]; r.item_status.clear();
+int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, bool shared_ok) {
+  if (!c || c->run_phase != 0 || c->staged_kind != kind || (c->n_shared && !(shared_ok && c->lane_owner))) return AVRF_ERR_BAD_ARG;
+  // (the layout goes to locals first: a refusal leaves the last run's description, and the context, as they were)
+  std::vector<uint32_t> off, row0; uint64_t lay[5];
+  if (int e = seg_layout(kind, c->n, c->n_shared, n_seg, seg_items, c->h_io.as<uint32_t>(), &off, &row0, lay)) return e;
+  avrf_ctx::SegRun &r = c->seg;
+  r.off.swap(off); r.row0.swap(row0);
+  r.n_seg = n_seg; r.L = (size_t)lay[0]; r.padded = (size_t)lay[1]; r.merged = lay[4] != 0; r.item_status.clear();
   if (seg_nothing(c)) { c->run_phase = 3; return AVRF_OK; }
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(c->h_seg_up.ensure(seg_up_seeds_at(n_seg) + n_seg * sizeof(Seed64)));
+  HIP_TRY(c->h_seg_up.ensure(seg_up_row0_at(n_seg) + n_seg * 4));
   memcpy(c->h_seg_up.p, r.off.data(), (n_seg + 1) * 4);
+  if (r.merged) memcpy(c->h_seg_up.as<uint8_t>() + seg_up_row0_at(n_seg), r.row0.data(), n_seg * 4);
   if (c->lane_owner) if (int e = seg_ensure(c, kind)) return e;        // (a pool slot has no lane yet: seg_launch sizes the lane's arrays)
+  if (c->n_shared) c->chal_gen = 0;                                    // (what avrf_*_batch_challenges left in d_c / d_z is overwritten, for Pedersen in another form)
   // prepare once, for all segments: the prepare kernels know nothing about batches, and their records are contiguous per item
-  if (int e = batch_begin(c, kind)) return e;
+  if (int e = batch_begin(c, kind, /*segmented=*/true)) return e;
   c->run_phase = 3;
   return AVRF_OK;
 }
@@ -1005,6 +1060,13 @@ int seg_launch(avrf_ctx *c, int kind) {
   const double t2 = now_us();
   HIP_TRY(hipMemcpyAsync(c->L->d_seg_off.p, c->h_seg_up.p, (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(a.scalars.p, 0, padded * 32, c->stream));
+  if (c->seg.merged) {                                                 // this run's plan: the references sorted by (segment, row)
+    uint32_t *plan = c->d_seg_plan.as<uint32_t>();
+    HIP_TRY(hipMemcpyAsync(shared_seg_plan_row0(plan, n_seg, c->n_shared, c->n_contrib), c->h_seg_up.as<uint8_t>() + seg_up_row0_at(n_seg), n_seg * 4,
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(shared_seg_plan(c->d_table_idx.as<uint32_t>(), c->d_io_off.as<uint32_t>(), c->L->d_seg_off.as<uint32_t>(), (uint32_t)n_seg, (uint32_t)c->n_shared,
+                            (uint32_t)c->n, (uint32_t)(c->n_contrib - c->tot_io), (uint32_t)c->tot_io, plan, c->stream));
+  }
   launch_seg_terms(c, kind, b, n_seg, L);
   const double t3 = now_us();
   c->timing[3] = t3 - t2;
@@ -1033,16 +1095,16 @@ int seg_end(avrf_ctx *c, int kind, int32_t *status_out) {
     status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
     for (size_t j = r.off[v]; !r.item_status.empty() && j < r.off[v + 1]; j++) if (r.item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // src/thin.rs:266-271, src/pedersen.rs:348-353
   }
-  if (c->lane_owner) { c->seg_gen = c->stage_gen; c->seg_L = r.L; c->seg_off = r.off; }   // what avrf_*_segment_terms describes
+  if (c->lane_owner) { c->seg_gen = c->stage_gen; c->seg_L = r.L; c->seg_off = r.off; c->seg_row0 = r.row0; }   // what avrf_*_segment_terms describes
   return AVRF_OK;
 }
 }  // namespace avrf
 
 // the context's call: the phases one after the other, waiting for the stream between them
-static int run_segments(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+static int run_segments(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, int32_t *status_out, bool shared_ok = false) {
   if (!c || ctx_busy(c) || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
   const double t0 = now_us();
-  if (int e = seg_begin(c, kind, n_seg, seg_items)) return e;
+  if (int e = seg_begin(c, kind, n_seg, seg_items, shared_ok)) return e;
   for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;
   if (!n_seg || !c->n) { c->run_phase = 0; return AVRF_OK; }
   if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) { c->run_phase = 0; (void)hipGetLastError(); return AVRF_ERR_NO_DEVICE; }
@@ -1065,14 +1127,32 @@ static size_t segment_terms(avrf_ctx *c, int kind, size_t seg, uint8_t *bases_xy
   const size_t first = c->seg_off[seg], items = c->seg_off[seg + 1] - first;
   if (!items) return 0;
   const size_t t0 = seg * c->seg_L;
-  return terms_to_host(c, c->d_seg_pre.as<te_pre_raw>() + t0, c->d_seg_scalars.as<uint8_t>() + 32 * t0,
-                       n_terms(kind, items, kind == Thin ? io_off[first + items] - io_off[first] : 0), bases_xy, scalars);
+  // the merged layout of a shared-table staging: item terms up to the segment's row 0, the rows, the base term(s)
+  const size_t count = !c->seg_row0.empty() ? (c->seg_row0[seg] - t0) + c->n_shared + (kind == Thin ? 1 : 2)
+                                            : n_terms(kind, items, kind == Thin ? io_off[first + items] - io_off[first] : 0);
+  return terms_to_host(c, c->d_seg_pre.as<te_pre_raw>() + t0, c->d_seg_scalars.as<uint8_t>() + 32 * t0, count, bases_xy, scalars);
 }
 
 extern "C" {
 
 int avrf_thin_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) { return run_segments(c, Thin, n_seg, seg_items, status_out); }
 int avrf_pedersen_batch_run_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) { return run_segments(c, Pedersen, n_seg, seg_items, status_out); }
+// the same on WHATEVER staging of the kind the context holds: over a shared table in the shorter of the merged and the expanded layout
+// (seg_layout), on a plain staging exactly the calls above
+int avrf_thin_batch_run_shared_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) { return run_segments(c, Thin, n_seg, seg_items, status_out, true); }
+int avrf_pedersen_batch_run_shared_segments(avrf_ctx *c, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) { return run_segments(c, Pedersen, n_seg, seg_items, status_out, true); }
+int avrf_thin_batch_verify_shared_segments_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *pk_index, const uint32_t *input_index,
+                                                const uint8_t *outputs, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs,
+                                                int validate, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  int st = avrf_thin_batch_stage_shared_wire(c, n, n_shared, shared, pk_index, input_index, outputs, io_counts, ads, ad_lens, proofs, validate);
+  return st ? st : avrf_thin_batch_run_shared_segments(c, n_seg, seg_items, status_out);
+}
+int avrf_pedersen_batch_verify_shared_segments_wire(avrf_ctx *c, size_t n, size_t n_shared, const uint8_t *shared, const uint32_t *input_index, const uint8_t *outputs,
+                                                    const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
+                                                    size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
+  int st = avrf_pedersen_batch_stage_shared_wire(c, n, n_shared, shared, input_index, outputs, io_counts, ads, ad_lens, proofs, validate);
+  return st ? st : avrf_pedersen_batch_run_shared_segments(c, n_seg, seg_items, status_out);
+}
 
 int avrf_thin_batch_verify_segments(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
                                     const uint32_t *ad_lens, const uint8_t *proofs, size_t n_seg, const uint32_t *seg_items, int32_t *status_out) {
@@ -1210,7 +1290,7 @@ static int batch_challenges(avrf_ctx *c, int kind, uint8_t *c_out) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(reset_flags(c));
   validate_staged(c, kind, nullptr);
-  launch_prepare(c, kind, batch_of(c));
+  launch_prepare(c, kind, batch_of(c), c->n_shared != 0);
   HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -85,13 +85,15 @@ struct avrf_ctx {
   // the last segmented run of the staged batch (avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments; thin_seg.h): terms of its
   // own, n_seg * seg_L of them, so that the plain run's terms stay what they were; seg_off (n_seg + 1 item offsets) describes them while
   // seg_gen == stage_gen.  (A pool slot has neither: its segmented terms go to the arrays of the lane it borrows, seg_launch.)
-  uint64_t seg_gen = 0; size_t seg_L = 0; std::vector<uint32_t> seg_off;
-  avrf::DevBuf d_seg_scalars, d_seg_pre;
+  // seg_row0: non-empty exactly when that run took the merged layout of a shared-table staging (thin_shared.h "Segments"): the term of each
+  // segment's row 0.  d_seg_plan: the per-run plan of such a run (shared_seg_plan).
+  uint64_t seg_gen = 0; size_t seg_L = 0; std::vector<uint32_t> seg_off, seg_row0;
+  avrf::DevBuf d_seg_scalars, d_seg_pre, d_seg_plan;
   std::vector<uint8_t> h_seg_msg;   // the segments' weight-transcript messages, prefix || records each
   // the segmented run in flight (seg_begin .. seg_end, run_phase 3 and 4): its layout, the per-item statuses of the attribution pass
   // (empty unless the batch's flag word was set) and, page-locked so that the copies up never wait for the lane, the item offsets
-  // (n_seg + 1 words, padded to 64 bytes) followed by the n_seg weight seeds
-  struct SegRun { size_t n_seg = 0, L = 0, padded = 0; std::vector<uint32_t> off; std::vector<int32_t> item_status; } seg;
+  // (n_seg + 1 words, padded to 64 bytes) followed by the n_seg weight seeds and, for the merged layout, the n_seg terms row0
+  struct SegRun { size_t n_seg = 0, L = 0, padded = 0; bool merged = false; std::vector<uint32_t> off, row0; std::vector<int32_t> item_status; } seg;
   avrf::PinBuf h_seg_up;
   double timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int run_phase = 0;              // batch_begin / batch_hash / batch_end: 1, 2; a segmented run (seg_begin .. seg_end): 3, 4
@@ -138,7 +140,9 @@ int ctx_stage(avrf_ctx *c, const BatchSource &src, bool wait);
 // the host's check of a shared-table source (every index < n_shared; outputs present), which ctx_stage makes itself and the pool makes on
 // the submitting thread as well
 bool shared_indices_ok(const BatchSource &src);
-int batch_begin(avrf_ctx *c, int kind);                               // validation + prepare kernel + copies back enqueued on c->stream
+// validation + prepare kernel + copies back enqueued on c->stream.  segmented (seg_begin): over a shared table the checks are those of the
+// items alone -- the table's range flag is not taken over -- and Pedersen's prepare merges the pairs as the run's layout (c->seg) wants them
+int batch_begin(avrf_ctx *c, int kind, bool segmented = false);
 int batch_collect(avrf_ctx *c, int kind);                             // (c->stream's work has completed) AVRF_INVALID_DATA for a refused item
 bool suite_host_weights(int suite);                                   // sponge / SHA-256 transcript: batch_seed squeezes the weight stream itself (no seed)
 int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]);            // the weight transcript on the calling thread
@@ -147,7 +151,9 @@ int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]);    // terms k
 int batch_end(avrf_ctx *c, int kind);                                 // waits for the chain, folds, verdict
 // The segmented run of a staged Thin or Pedersen batch (include/avrf.h avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments) in
 // phases of the same discipline: each refuses out of order, an error leaves the context idle.  run_phase 3 from seg_begin, 4 from seg_launch.
-//   seg_begin    layout check (counts, limits), buffer sizing, batch_begin: validation + prepare kernel + copies back on c->stream
+//   seg_begin    layout check (counts, limits), buffer sizing, batch_begin: validation + prepare kernel + copies back on c->stream.
+//                A shared-table staging is refused unless shared_ok (avrf_*_batch_run_shared_segments, a context of its own lane): the
+//                layout is then the shorter of merged and expanded (include/avrf.h)
 //   seg_collect  (c->stream's work has completed) a wire batch's decode flag; only when the batch's flag word is set, the per-item
 //                attribution pass, which waits for c->stream
 //   seg_hash     the n_seg weight transcripts on the calling thread (spread: and the process's host pool): counter-mode suites hash
@@ -159,7 +165,7 @@ int batch_end(avrf_ctx *c, int kind);                                 // waits f
 //   seg_end      a pool slot: collects the chain (waits for the stream only with the lane's own record).  A context of its own lane
 //                runs msm_te_segments here instead, which keeps that call's loop of single MSMs below eight segments.  Then
 //                status_out[0 .. n_seg), the per-item statuses folded in
-int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items);
+int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, bool shared_ok = false);
 int seg_collect(avrf_ctx *c, int kind);
 int seg_hash(avrf_ctx *c, int kind, bool spread);
 void seg_job(avrf_ctx *c, int kind, size_t v, WeightJob *job);

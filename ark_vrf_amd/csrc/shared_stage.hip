@@ -1,7 +1,9 @@
 // shared_stage.hip -- the suite-independent staging of a Thin or Pedersen batch over a table of shared points (thin_shared.h): the plain staged
 // layout gathered from the table, and the counting sort of the references by row (32-bit integer atomics on counters only).  Thin: n keys
 // and tot_io inputs; Pedersen: the tot_io inputs alone (n = 0 here, and a batch whose items have no pairs leaves every row unreferenced).
+// A segmented run over such a staging sorts the same references once more, by (segment, row): shared_seg_plan.
 #include "thin_shared.h"
+#include "thin_seg.h"
 #include "fpn.h"
 
 namespace avrf {
@@ -96,6 +98,38 @@ hipError_t shared_plan(const uint8_t *d_table, uint32_t n_shared, const uint32_t
   hipLaunchKernelGGL(k_shared_scan, dim3(1), dim3(1024), 0, st, cursor, row_off, n_shared);
   if (nc) hipLaunchKernelGGL(k_shared_place, dim3((nc + 255) / 256), dim3(256), 0, st, d_idx, n_shared, nc, cursor, pos, slot_row);
   return hipGetLastError();                                             // (a launch that was refused)
+}
+
+// ---------------------------------------------------------------- the plan of one segmented run (thin_shared.h shared_seg_plan)
+
+// reference t (as above) -> its virtual row v T + row: v the segment of its item -- item t for a key, the item of I/O pair t - nk for an
+// input (both by the search of thin_seg.h) -- and the histogram of the virtual rows
+__global__ void __launch_bounds__(256)
+k_shared_seg_rows(const uint32_t *__restrict__ idx, const uint32_t *__restrict__ io_off, const uint32_t *__restrict__ seg_off, uint32_t n_seg,
+                  uint32_t n_shared, uint32_t n, uint32_t nk, uint32_t tot_io, uint32_t *__restrict__ vrow, uint32_t *__restrict__ cnt) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < nk + tot_io;
+  uint32_t row = 0;
+  if (active) {
+    uint32_t r = idx[t];
+    if (r >= n_shared) r = n_shared - 1;                                // (refused on the host; never a row outside the histogram)
+    const uint32_t j = t < nk ? t : segment_of(io_off, n, t - nk);
+    row = segment_of(seg_off, n_seg, j) * n_shared + r;
+    vrow[t] = row;
+  }
+  wave_count(cnt, row, active);
+}
+
+hipError_t shared_seg_plan(const uint32_t *d_idx, const uint32_t *d_io_off, const uint32_t *d_seg_off, uint32_t n_seg, uint32_t n_shared, uint32_t n,
+                           uint32_t nk, uint32_t tot_io, uint32_t *d_plan, hipStream_t st) {
+  const uint32_t nc = nk + tot_io, rows = n_seg * n_shared;
+  if (!rows) return hipSuccess;
+  uint32_t *cursor = d_plan, *row_off = d_plan + (rows + 1), *pos = row_off + (rows + 1), *slot_row = pos + nc, *vrow = slot_row + nc;
+  if (hipError_t e = hipMemsetAsync(cursor, 0, (size_t)(rows + 1) * 4, st)) return e;
+  if (nc) hipLaunchKernelGGL(k_shared_seg_rows, dim3((nc + 255) / 256), dim3(256), 0, st, d_idx, d_io_off, d_seg_off, n_seg, n_shared, n, nk, tot_io, vrow, cursor);
+  hipLaunchKernelGGL(k_shared_scan, dim3(1), dim3(1024), 0, st, cursor, row_off, rows);
+  if (nc) hipLaunchKernelGGL(k_shared_place, dim3((nc + 255) / 256), dim3(256), 0, st, vrow, rows, nc, cursor, pos, slot_row);
+  return hipGetLastError();
 }
 
 }  // namespace avrf

@@ -20,6 +20,14 @@ namespace avrf {
 struct BatchDev;
 struct Seed64;
 
+// the segment of item j: the largest v < n_seg with seg_off[v] <= j (an empty segment shares its offset with the next one, which wins).
+// The same search finds the item of I/O pair k in the items' pair offsets (an item without pairs shares its offset likewise).
+__device__ __forceinline__ uint32_t segment_of(const uint32_t *__restrict__ seg_off, uint32_t n_seg, uint32_t j) {
+  uint32_t lo = 0, hi = n_seg;
+  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (seg_off[mid] <= j) lo = mid; else hi = mid; }
+  return lo;
+}
+
 // Per-suite launch table (thin_seg.hip, built once per suite like vrf_batch.hip).
 template <class S> struct SegOps {
   // d_seg_off: n_seg + 1 item offsets; d_seeds: n_seg weight-transcript digests (counter-mode transcripts; a sponge suite's streams are

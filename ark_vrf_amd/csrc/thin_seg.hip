@@ -18,13 +18,6 @@
 #endif
 namespace avrf {
 
-// the segment of item j: the largest v < n_seg with seg_off[v] <= j (an empty segment shares its offset with the next one, which wins)
-AVRF_DI uint32_t segment_of(const uint32_t *__restrict__ seg_off, uint32_t n_seg, uint32_t j) {
-  uint32_t lo = 0, hi = n_seg;
-  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (seg_off[mid] <= j) lo = mid; else hi = mid; }
-  return lo;
-}
-
 // k_thin_terms_seg's sink of thin_item's terms: the plain batch's positions (k_thin_terms: item j's four kinds at 2 j + 2 io0 ..) moved by
 // t0 = v L - (2 first + 2 io_off[first]), first = the segment's first item -- so the segment's slice starts with its first item's R
 template <class S> struct SegTerms {

@@ -233,8 +233,8 @@ int avrf_thin_batch_verify_shared_wire(avrf_ctx *ctx, size_t n, size_t n_shared,
  *             AVRF_SEGMENTS_PADDED_TERMS_MAX terms (n_seg * L, L = the longest segment's term count: about 1.7 KB of device
  *             workspace per padded term at the narrowest window); n_seg * windows(L) at most AVRF_SEGMENTS_WINDOWS_MAX.
  *   refusals  AVRF_ERR_BAD_ARG, with the context and its staged batch untouched and usable: counts that do not sum to n, a
- *             limit exceeded, nothing staged, a Pedersen batch staged, a shared-table batch staged (its merged rows have no
- *             per-segment meaning), a call between avrf_batch_run_begin and _end.
+ *             limit exceeded, nothing staged, a Pedersen batch staged, a shared-table batch staged (its rows are merged over the
+ *             whole batch: avrf_thin_batch_run_shared_segments sums them per segment), a call between avrf_batch_run_begin and _end.
  *   after     avrf_thin_batch_run on the same staging gives its usual verdict and avrf_batch_last_terms its usual terms: the
  *             segmented terms live in buffers of their own.
  *   terms     (avrf_thin_segment_terms; this layout is ABI) segment v's terms are those of avrf_batch_last_terms for a batch
@@ -346,8 +346,8 @@ int avrf_pedersen_batch_verify_segments_wire(avrf_ctx *ctx, size_t n, const uint
  *             avrf_pedersen_shared_n_terms = 4 n + n_shared + 2 (host arithmetic only, no device needed).
  *   pairs     the merged input of an item with several pairs is sum z_i I_i, so its term -t s I_merged IS the contributions
  *             -t s z_i to the pairs' rows (the reference's own linearity); the merged OUTPUT stays one term per item.
- *   segments  avrf_pedersen_batch_run_segments refuses a shared-table staging (AVRF_ERR_BAD_ARG: the merged rows have no
- *             per-segment meaning); avrf_pedersen_batch_run afterwards still answers.
+ *   segments  avrf_pedersen_batch_run_segments refuses a shared-table staging (AVRF_ERR_BAD_ARG: the rows are merged over the whole
+ *             batch); avrf_pedersen_batch_run afterwards still answers.  avrf_pedersen_batch_run_shared_segments takes it.
  *   restaging a later avrf_pedersen_batch_stage on the same context gives the plain 5 n + 2 terms again; a failed shared staging
  *             leaves nothing staged.
  * Measured (tools/shared_bench.py --kind=pedersen; kind 2 pool, 65 536 one-pair items over 3 inputs): resident
@@ -394,6 +394,80 @@ int avrf_pedersen_segments_layout(size_t n, size_t n_seg, const uint32_t *seg_it
 /* The MSM terms the last avrf_pedersen_batch_run_segments built for segment `seg` (src/pedersen.rs:303-426; tests), as
  * avrf_thin_segment_terms. */
 size_t avrf_pedersen_segment_terms(avrf_ctx *ctx, size_t seg, uint8_t *bases_xy, uint8_t *scalars);
+
+/* ---- SEGMENTS of a batch staged over a table of shared points: one verdict per group of items, rows still merged.
+ * The two segmented calls above refuse a shared-table staging, because a row's merged scalar mixes the items of every segment.  Summed
+ * per (segment, row) pair instead of per row, the merged rows do have a per-segment meaning: segment v gets exactly the treatment the
+ * reference gives G and BLINDING_BASE (src/thin.rs:303,316-317, src/pedersen.rs:387-418), restricted to its own items.  For the ticket
+ * workload that arrives per block (one verdict per block over two or three shared inputs) and for locating the bad items of a failed
+ * shared-table batch without staging it again in expanded form.
+ *   stagings  avrf_thin_batch_run_shared_segments / avrf_pedersen_batch_run_shared_segments work on WHATEVER batch of their kind the
+ *             context holds.  On a shared-table staging (x || y or wire) they do what is described here; on a plain staging --
+ *             including a Pedersen "shared" staging with n_shared == 0, which is staged plain -- they ARE avrf_thin_batch_run_segments /
+ *             avrf_pedersen_batch_run_segments.  A caller that always stages through the shared calls never switches entry points.
+ *             The two calls above keep refusing a shared staging.  *_verify_shared_segments_wire are avrf_*_batch_stage_shared_wire +
+ *             the run (a staging error, e.g. AVRF_INVALID_DATA for a row that does not decode, is returned as it is and no status is
+ *             written).
+ *   statuses  status_out[v] is what avrf_thin_batch_verify / avrf_pedersen_batch_verify answers for segment v's items alone, every
+ *             index replaced by its row: AVRF_OK, AVRF_VERIFICATION_FAILURE or AVRF_INVALID_DATA; an empty segment is AVRF_OK.  A row
+ *             that nothing in segment v refers to has NO influence on status_out[v], whatever bytes it holds.  THIS DIFFERS FROM
+ *             avrf_thin_batch_run / avrf_pedersen_batch_run ON THE SAME x || y STAGING, which refuse a non-canonical coordinate in ANY
+ *             row.  A segment is AVRF_INVALID_DATA, and no other segment is, when a row it references is the identity, has a
+ *             non-canonical coordinate or fails avrf_ctx_set_validation 1 / 2, or when one of its items has a defect the plain
+ *             segmented call attributes to it (an output or proof point, a scalar >= r).  The call returns AVRF_OK whenever the
+ *             statuses were written.
+ *   layouts   two, chosen by host arithmetic alone (avrf_*_shared_segments_layout says which).  items_v / p_v: segment v's items and
+ *             I/O pairs, T = n_shared, maxima over the non-empty segments.
+ *             MERGED, Thin (this layout is ABI): n_v = items_v + p_v + T + 1 terms at [v L, v L + n_v).  With `first` the segment's first
+ *             item and io_off the prefix sums of io_counts: (R_j, w_j) at v L + (j - first) + (io_off[j] - io_off[first]), its
+ *             (O_ji, w c z_i) directly behind it; row r at v L + items_v + p_v + r with the scalar  sum of w c z0 over the SEGMENT's
+ *             items whose key is r  -  sum of w s z_i over the SEGMENT's pairs whose input is r  (mod r_order), 0 -- and the base still
+ *             written -- for a row the segment does not reference; (G, g_v) last.  The weights are those of the segment's own
+ *             transcript, the item index taken inside the segment, as in avrf_thin_batch_run_segments.
+ *             MERGED, Pedersen (ABI): n_v = 4 items_v + T + 2.  Item j's (O_merged, t c), (Ok, t), (Yb, u c), (R, u) at
+ *             v L + 4 (j - first) + k; row r at v L + 4 items_v + r with the scalar  - sum of t s z_i over the segment's pairs whose
+ *             input is r; then (G, -sum u s), then (BLINDING_BASE, -sum u sb).
+ *             EXPANDED: the plain segmented layout of avrf_thin_batch_run_segments / avrf_pedersen_batch_run_segments over the rows
+ *             as staging gathered them.
+ *             L_m = max(items_v + p_v) + T + 1 (Thin), 4 max(items_v) + T + 2 (Pedersen); L_p as for the plain segmented call.  The
+ *             run takes the merged layout exactly when L_m < L_p (a tie goes to expanded), so it is never a worse MSM than the
+ *             expanded batch and never refused where the expanded batch would be accepted.  The three limits above apply to the
+ *             chosen L: the merged layout admits segments the plain one cannot (2 048 one-pair Thin items over 1 027 rows are
+ *             5 124 terms; the plain layout's 8 193 is over the limit).
+ *   refusals  as for the plain segmented calls, AVRF_ERR_BAD_ARG with the staging untouched and usable: counts that do not sum to n,
+ *             nothing staged, a staging of the other kind, a busy context or a call between avrf_batch_run_begin and _end, a limit
+ *             exceeded.
+ *   after     avrf_*_batch_run on the same staging gives its usual verdict and avrf_batch_last_terms its usual shared-layout terms
+ *             (avrf_*_batch_challenges must be repeated before avrf_*_batch_partial).  avrf_thin_segment_terms /
+ *             avrf_pedersen_segment_terms describe the last segmented run of either entry point, in the layout that run chose.
+ *             avrf_last_timing keeps the slots of the segmented calls; the per-run plan is part of [3].
+ * avrf_*_shared_segments_layout: host arithmetic only, no device, the same refusals: out = { L, n_seg * L, sum of the n_v of the
+ * non-empty segments, window bits, mode } with mode 1 = merged, 0 = expanded; n_shared == 0 describes a plain staging (mode 0).
+ * Term counts (derived): Pedersen 256 x 256 one-pair items over T = 3: L 1 029 against 1 282 (0.80 of the padded MSM); 4 096 x 16: 69
+ * against 82 (0.84); Thin 64 x 1 024 over 1 024 keys + 3 inputs: 3 076 against 4 097 (0.75); Thin 256 x 256 on the same table: expanded
+ * is chosen (1.00).  (Pedersen 4 096 x 16 is over AVRF_SEGMENTS_WINDOWS_MAX in either layout.)
+ * Measured (tools/segments_bench.py --legs=g; 65 536 one-pair items over 1 024 keys + 3 inputs, against
+ * avrf_*_batch_run_segments on the expanded staging of the same items in the same process, M items/s): resident, Thin 64 x 1 024
+ * 24.2-29.0 against 22.3-23.3, Pedersen 256 x 256 25.9-26.3 against 25.0-25.3, Pedersen 1 024 x 64 19.3-19.6 against 18.3-18.5; from
+ * page-locked x || y buffers 22.7-24.3 / 19.7-20.0, 20.7-20.8 / 20.2-20.3, 16.1-16.2 / 15.5-15.6; from wire bytes with validate = 1
+ * 20.6-21.7 / 15.2-16.3, 17.6-17.7 / 15.4-15.6, 14.4-14.5 / 12.6-12.7: ahead with the ranges apart wherever the merged layout is chosen.
+ * THE TERM RATIOS DO NOT REACH THE WALL CLOCK (1.03-1.07 x for Pedersen resident where 1.19-1.25 x is derived: the chain's tail does not
+ * shrink with L).  THIN 256 x 256, WHERE EXPANDED IS CHOSEN, IS LEVEL (26.2-27.5 against 26.6-27.7 resident, 22.2-22.8 against 21.9-22.6
+ * from x || y); only its wire run gains (19.8-20.3 against 16.4-18.0: each row decoded once). */
+int avrf_thin_batch_run_shared_segments(avrf_ctx *ctx, size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+int avrf_pedersen_batch_run_shared_segments(avrf_ctx *ctx, size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+int avrf_thin_batch_verify_shared_segments_wire(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared,
+                                                const uint32_t *pk_index, const uint32_t *input_index, const uint8_t *outputs,
+                                                const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                                const uint8_t *proofs, int validate, size_t n_seg, const uint32_t *seg_items,
+                                                int32_t *status_out);
+int avrf_pedersen_batch_verify_shared_segments_wire(avrf_ctx *ctx, size_t n, size_t n_shared, const uint8_t *shared,
+                                                    const uint32_t *input_index, const uint8_t *outputs, const uint32_t *io_counts,
+                                                    const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs, int validate,
+                                                    size_t n_seg, const uint32_t *seg_items, int32_t *status_out);
+int avrf_thin_shared_segments_layout(size_t n, size_t n_shared, size_t n_seg, const uint32_t *seg_items, const uint32_t *io_counts,
+                                     uint64_t out[5]);
+int avrf_pedersen_shared_segments_layout(size_t n, size_t n_shared, size_t n_seg, const uint32_t *seg_items, uint64_t out[5]);
 
 /* ---- Ownership of host buffers; page-locked memory (SURVEY.md 8b "Ownership").
  * Every entry point copies what it needs out of the caller's buffers before it returns, EXCEPT avrf_pool_submit (below), whose

@@ -181,6 +181,12 @@ class BatchVerifier {
     if (avrf_thin_batch_run_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: thin run segments");
     return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
   }
+  // the same on whatever Thin batch the context holds, one staged over a table of shared points included (avrf_thin_batch_run_shared_segments)
+  std::vector<Status> run_shared_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_thin_batch_run_shared_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: thin run shared segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
   // the MSM terms of segment `seg` of the last segmented run (avrf_thin_segment_terms): bases x || y and scalars
   std::pair<std::vector<uint8_t>, std::vector<uint8_t>> segment_terms(size_t seg) const {
     const size_t k = avrf_thin_segment_terms(su_.ctx(), seg, nullptr, nullptr);
@@ -199,6 +205,28 @@ inline std::array<uint64_t, 4> segments_layout(const std::vector<uint32_t> &seg_
   std::array<uint64_t, 4> out{};
   if (avrf_thin_segments_layout(io_counts.size(), seg_items.size(), seg_items.data(), io_counts.data(), out.data()) != AVRF_OK) throw std::invalid_argument("avrf: segments layout");
   return out;
+}
+// { L, padded terms, total terms, window bits, mode (1 merged, 0 expanded) } of a segmented run over a table of n_shared points
+// (avrf_thin_shared_segments_layout; host arithmetic): throws beyond the limits
+inline std::array<uint64_t, 5> shared_segments_layout(const std::vector<uint32_t> &seg_items, const std::vector<uint32_t> &io_counts, size_t n_shared) {
+  std::array<uint64_t, 5> out{};
+  if (avrf_thin_shared_segments_layout(io_counts.size(), n_shared, seg_items.size(), seg_items.data(), io_counts.data(), out.data()) != AVRF_OK)
+    throw std::invalid_argument("avrf: shared segments layout");
+  return out;
+}
+// One verdict per segment over a table of shared points, from the reference's byte strings (avrf_thin_batch_verify_shared_segments_wire):
+// shared holds n_shared compressed points, outputs one per I/O pair, proofs n serialised proofs.  Throws when a point does not decode
+// (AVRF_INVALID_DATA from staging) or the call is refused.
+inline std::vector<Status> verify_shared_segments_wire(const Suite &su, size_t n_shared, const std::vector<uint8_t> &shared, const std::vector<uint32_t> &pk_index,
+                                                       const std::vector<uint32_t> &input_index, const std::vector<uint8_t> &outputs, const std::vector<uint32_t> &io_counts,
+                                                       const std::vector<uint8_t> &ads, const std::vector<uint32_t> &ad_lens, const std::vector<uint8_t> &proofs, int validate,
+                                                       const std::vector<uint32_t> &seg_items) {
+  std::vector<int32_t> st(seg_items.size() + 1);
+  if (io_counts.size() != ad_lens.size() || pk_index.size() != io_counts.size() ||
+      avrf_thin_batch_verify_shared_segments_wire(su.ctx(), io_counts.size(), n_shared, shared.data(), pk_index.data(), input_index.data(), outputs.data(), io_counts.data(),
+                                                  ads.data(), ad_lens.data(), proofs.data(), validate, seg_items.size(), seg_items.data(), st.data()) != AVRF_OK)
+    throw std::invalid_argument("avrf: thin verify shared segments (wire)");
+  return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
 }
 // n_seg independent msm_unchecked calls of L terms each (avrf_msm_te_segments): bases n_seg * L x 64, scalars n_seg * L x 32 -> n_seg points
 inline std::vector<Point> msm_segments(const Suite &su, size_t n_seg, size_t L, const std::vector<uint8_t> &bases_xy, const std::vector<uint8_t> &scalars) {
@@ -293,6 +321,12 @@ class BatchVerifier {
     if (avrf_pedersen_batch_run_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen run segments");
     return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
   }
+  // the same on whatever Pedersen batch the context holds, one staged over a table of shared inputs included (avrf_pedersen_batch_run_shared_segments)
+  std::vector<Status> run_shared_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_pedersen_batch_run_shared_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen run shared segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
   // the MSM terms of segment `seg` of the last segmented run (avrf_pedersen_segment_terms): bases x || y and scalars
   std::pair<std::vector<uint8_t>, std::vector<uint8_t>> segment_terms(size_t seg) const {
     const size_t k = avrf_pedersen_segment_terms(su_.ctx(), seg, nullptr, nullptr);
@@ -327,6 +361,22 @@ class SharedBatchVerifier {
     if (int e = avrf_pedersen_batch_stage_shared(su_.ctx(), n_, n_shared(), rows_.data(), input_index_.data(), outputs_.data(), io_counts_.data(),
                                                  ads_.data(), ad_lens_.data(), proofs_.data())) return e;
     return avrf_pedersen_batch_run(su_.ctx());
+  }
+  // One verdict per segment (avrf_pedersen_batch_run_shared_segments): seg_items[v] consecutive pushed items each, summing to len(); what
+  // n_seg BatchVerifiers over those runs of items would answer, the inputs still merged per (segment, row).  Throws when refused.
+  std::vector<Status> verify_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_pedersen_batch_stage_shared(su_.ctx(), n_, n_shared(), rows_.data(), input_index_.data(), outputs_.data(), io_counts_.data(),
+                                         ads_.data(), ad_lens_.data(), proofs_.data()) != AVRF_OK ||
+        avrf_pedersen_batch_run_shared_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK)
+      throw std::invalid_argument("avrf: pedersen verify shared segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+  // { L, padded terms, total terms, window bits, mode (1 merged, 0 expanded) } of that run (avrf_pedersen_shared_segments_layout; host arithmetic)
+  std::array<uint64_t, 5> segments_layout(const std::vector<uint32_t> &seg_items) const {
+    std::array<uint64_t, 5> out{};
+    if (avrf_pedersen_shared_segments_layout(n_, n_shared(), seg_items.size(), seg_items.data(), out.data()) != AVRF_OK) throw std::invalid_argument("avrf: shared segments layout");
+    return out;
   }
   size_t len() const { return n_; }
   size_t n_shared() const { return rows_.size() / 64; }
@@ -372,6 +422,18 @@ inline std::vector<Status> verify_segments_wire(const Suite &su, const std::vect
   if (io_counts.size() != ad_lens.size() ||
       avrf_pedersen_batch_verify_segments_wire(su.ctx(), io_counts.size(), ios.data(), io_counts.data(), ads.data(), ad_lens.data(), proofs.data(), validate,
                                                seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen verify segments (wire)");
+  return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+}
+// The same over a table of shared inputs (avrf_pedersen_batch_verify_shared_segments_wire): the arguments of verify_shared_wire, then the segments.
+inline std::vector<Status> verify_shared_segments_wire(const Suite &su, size_t n_shared, const std::vector<uint8_t> &shared, const std::vector<uint32_t> &input_index,
+                                                       const std::vector<uint8_t> &outputs, const std::vector<uint32_t> &io_counts, const std::vector<uint8_t> &ads,
+                                                       const std::vector<uint32_t> &ad_lens, const std::vector<uint8_t> &proofs, int validate,
+                                                       const std::vector<uint32_t> &seg_items) {
+  std::vector<int32_t> st(seg_items.size() + 1);
+  if (io_counts.size() != ad_lens.size() ||
+      avrf_pedersen_batch_verify_shared_segments_wire(su.ctx(), io_counts.size(), n_shared, shared.data(), input_index.data(), outputs.data(), io_counts.data(),
+                                                      ads.data(), ad_lens.data(), proofs.data(), validate, seg_items.size(), seg_items.data(), st.data()) != AVRF_OK)
+    throw std::invalid_argument("avrf: pedersen verify shared segments (wire)");
   return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
 }
 

@@ -13,9 +13,13 @@ call the Pedersen twin of every entry point named below) gives against the calls
        staged again from page-locked host buffers on every run (the pool's cycle mode, no foreign-function call per step)
     f  what a caller could do before: k contexts on k host threads, k = 2, 4, 8, each calling thin_batch_verify_segments (stage from
        the host + 256 x 256) on the whole batch, and the same with the batch resident (thin_batch_run_segments)
+    g  SHARED TABLES (avrf_thin_batch_run_shared_segments / avrf_pedersen_batch_run_shared_segments): the n items over 1 024 keys + 3
+       inputs staged over the table on one context, against avrf_*_batch_run_segments on the expanded staging of the same items on
+       another, alternately: resident, staged from page-locked x || y buffers on every call, and from wire bytes with validate = 1;
+       Thin 64 x 1 024 (merged layout) and 256 x 256 (expanded is chosen), Pedersen 256 x 256 and 1 024 x 64 (both merged)
 Per leg: items/s, and for the context's legs the k_accumulate milliseconds per call (avrf_kernel_stats) and the host-side stage times
 of the segmented call (avrf_last_timing: prepare + wait, transcripts, terms launches, MSM chain + wait).
-python tools/segments_bench.py [n] [--quick] [--legs=abcdef] [--shape=ITEMS] [--kind=thin|pedersen]
+python tools/segments_bench.py [n] [--quick] [--legs=abcdefg] [--shape=ITEMS] [--kind=thin|pedersen]
     --legs: only these legs; --shape=256: of leg a only the segments of that many items, of leg e only the whole-batch jobs (a kernel
             trace of one leg keeps its kernels apart)
     --kind=pedersen: the same legs over the Pedersen verifier (avrf_pedersen_batch_run_segments, avrf_pedersen_verify, a kind 2 pool)"""
@@ -36,7 +40,7 @@ n = int(args[0]) if args else 65536
 QUICK = "--quick" in sys.argv
 SLOTS, LANES, THREADS, GROUP, DEPTH = 144, 12, 6, 8, 3
 REPS, CALLS, WARM = (1, 3, 1) if QUICK else (3, 10, 2)
-LEGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--legs=")), "abcdef")
+LEGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--legs=")), "abcdefg")
 SHAPE = next((int(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--shape=")), None)
 SHAPES = [(n // k, k) for k in (256, 64, 1024) if SHAPE in (None, k)]             # (segments, items per segment)
 KIND = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--kind=")), "thin")
@@ -61,6 +65,68 @@ def timed(ctx, call):
     sec = (time.perf_counter() - t0) / CALLS
     ms, cnt = accum(ctx, True)
     return sec, ms / CALLS, cnt / CALLS
+
+
+def shared_leg(ctx, record):
+    """leg g: the n items over 1 024 keys + 3 inputs (shared_bench.py's table; Pedersen: the 3 inputs) staged over the table on one
+    context and in expanded form on another; per shape the new call against the existing one, alternately: resident, staged from
+    page-locked x || y buffers on every call, and from page-locked wire bytes with validate = 1"""
+    from shared_bench import shared_items                                         # (reads the same n and --kind from the command line)
+    b = shared_items(ctx, 1024, 3)
+    ped = KIND == "pedersen"
+    plen = ctx.point_len
+    comp = ctx.points_compress
+    w_ios = comp(b["ios_xy"])
+    w_proofs = comp(b"".join(b["proofs"][PROOF * j: PROOF * j + PROOF - (64 if ped else 32)] for j in range(n)))
+    npts = 3 if ped else 1
+    tail = lambda j: b["proofs"][PROOF * j + 64 * npts: PROOF * (j + 1)]
+    w_proofs = b"".join(w_proofs[plen * npts * j: plen * npts * (j + 1)] + tail(j) for j in range(n))
+    common = (b["io_counts"], b["ads"], b["ad_lens"])
+    if ped:
+        rows, input_index, outs = nat.dedup_inputs(b["ios_xy"])
+        sh_xy = nat.PinnedPedersenSharedBatch(n, rows, input_index, outs, *common, b["proofs"])
+        sh_w = nat.PinnedPedersenSharedWireBatch(n, comp(rows), input_index, comp(outs), *common, w_proofs, plen)
+        ex_xy = nat.PinnedBatch(n, b["ios_xy"], *common, proofs=b["proofs"])
+        ex_w = nat.PinnedBatch(n, w_ios, *common, proofs=w_proofs)
+        layout = lambda segs: nat.pedersen_shared_segments_layout(n, segs, sh_xy.n_shared)
+        shapes = [(n // 256, 256), (n // 64, 64)]
+    else:
+        rows, pk_index, input_index, outs = nat.dedup_points(b["pks_xy"], b["ios_xy"])
+        sh_xy = nat.PinnedSharedBatch(n, rows, pk_index, input_index, outs, *common, b["proofs"])
+        sh_w = nat.PinnedSharedWireBatch(n, comp(rows), pk_index, input_index, comp(outs), *common, w_proofs, plen)
+        ex_xy = nat.PinnedBatch(n, b["ios_xy"], *common, pks_xy=b["pks_xy"], proofs=b["proofs"])
+        ex_w = nat.PinnedBatch(n, w_ios, *common, pks_xy=comp(b["pks_xy"]), proofs=w_proofs)
+        layout = lambda segs: nat.thin_shared_segments_layout(segs, b["io_counts"], sh_xy.n_shared)
+        shapes = [(n // 1024, 1024), (n // 256, 256)]
+    m = lambda c, name: getattr(c, KIND + "_" + name)
+    cs, ce = nat.Context(0), nat.Context(0)                                       # the shared staging and the expanded one, side by side
+    try:
+        for c in (cs, ce):
+            c.set_validation(1)
+        for rep in range(REPS):
+            for n_seg, k in shapes if SHAPE is None else [(n // SHAPE, SHAPE)]:
+                segs = [k] * n_seg
+                lay = layout(segs)
+                arms = {
+                    "resident": (lambda: m(cs, "batch_run_shared_segments")(segs), lambda: m(ce, "batch_run_segments")(segs)),
+                    "from pinned x||y": (lambda: (m(cs, "batch_stage_shared")(sh_xy), m(cs, "batch_run_shared_segments")(segs))[1],
+                                         lambda: m(ce, "batch_verify_segments")(ex_xy, segs)),
+                    "from pinned wire": (lambda: m(cs, "batch_verify_shared_segments_wire")(sh_w, segs, 1),
+                                         lambda: m(ce, "batch_verify_segments_wire")(ex_w, segs, 1)),
+                }
+                assert m(cs, "batch_stage_shared")(sh_xy) == 0 and m(ce, "batch_stage")(ex_xy) == 0
+                for mode, (new, old) in arms.items():
+                    for arm, c, call in (("shared", cs, new), ("expanded", ce, old)):   # alternately, in this one process
+                        assert call() == [0] * n_seg, (mode, arm)
+                        sec, ms, cnt = timed(c, call)
+                        tm = c.last_timing()
+                        record("g %d x %d %s, %s" % (n_seg, k, mode, arm), sec, rep=rep, accumulate_ms=round(ms, 4), L=lay[0] if arm == "shared" else None,
+                               merged=lay[4] if arm == "shared" else None,
+                               stage_us=dict(prepare=round(tm[1]), transcripts=round(tm[2]), terms=round(tm[3]), msm=round(tm[4])))
+    finally:
+        cs.close(); ce.close()
+        for pb in (sh_xy, sh_w, ex_xy, ex_w):
+            pb.close()
 
 
 def main():
@@ -145,7 +211,9 @@ def main():
         return sec / CALLS
 
     try:
-        for rep in range(REPS):
+        if "g" in LEGS:
+            shared_leg(ctx, record)
+        for rep in range(REPS if LEGS != "g" else 0):
             assert stage(batch) == 0
             for n_seg, k in SHAPES if "a" in LEGS else []:                         # a: resident
                 segs = [k] * n_seg
