@@ -444,6 +444,39 @@ class Context:
     def batch_run_end(self):
         return lib().avrf_batch_run_end(self._h)
 
+    # -- open batches (include/avrf.h avrf_*_batch_open): BatchVerifier::new, push as items arrive, then the run calls above
+    def batch_open(self, kind, items_hint=0, pairs_hint=0, ad_bytes_hint=0):
+        """kind: 1 Thin, 2 Pedersen.  An empty open batch on the context; the hints size its buffers (0: grow on demand)."""
+        f = lib().avrf_thin_batch_open if kind == 1 else lib().avrf_pedersen_batch_open
+        return f(self._h, C.c_size_t(items_hint), C.c_size_t(pairs_hint), C.c_size_t(ad_bytes_hint))
+
+    def batch_push(self, kind, b):
+        """b: a Batch, the chunk's items as x || y (a Thin chunk with pks_xy).  Returns at once: the chunk is copied, nothing is waited for."""
+        n = C.c_size_t(b.n)
+        if kind == 1:
+            return lib().avrf_thin_batch_push(self._h, n, b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
+        return lib().avrf_pedersen_batch_push(self._h, n, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs)
+
+    def batch_push_wire(self, kind, b, validate=1):
+        """The same for a Batch whose pks_xy / ios_xy / proofs fields hold the WIRE bytes.  A point that fails shows at the next push, flush or run."""
+        n = C.c_size_t(b.n)
+        if kind == 1:
+            return lib().avrf_thin_batch_push_wire(self._h, n, b.pks_xy, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, int(validate))
+        return lib().avrf_pedersen_batch_push_wire(self._h, n, b.ios_xy, b.io_counts, b.ads, b.ad_lens, b.proofs, int(validate))
+
+    def batch_flush(self):
+        """Waits for everything pushed and absorbs it; INVALID_DATA (and no batch) when a wire chunk did not decode."""
+        return lib().avrf_batch_flush(self._h)
+
+    def batch_pushed(self):
+        """(items, pairs, bytes of additional data) pushed to the open batch so far; zeros when nothing is open."""
+        out = (C.c_size_t * 3)()
+        f = lib().avrf_batch_pushed
+        f.restype = C.c_size_t
+        n = f(self._h, out)
+        assert n == out[0]
+        return tuple(out)
+
     def last_terms(self):
         k = lib().avrf_batch_last_terms(self._h, None, None)
         bases, sc = (C.c_uint8 * max(1, 64 * k))(), (C.c_uint8 * max(1, 32 * k))()

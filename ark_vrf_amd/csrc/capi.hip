@@ -76,10 +76,11 @@ template <class F> static int per_item_chunks(avrf_ctx *c, bool with_pks, F laun
 
 // Validate::Yes over every point of the staged batch (pk, I/O pairs, proof points) when the context asks for it;
 // rec_status (device, n x int32) receives 2 for items with a bad point (per-item verifiers), else NULL.
-static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status) {
-  if (c->validate <= 0 || !c->n) return;
+// n0, a0 (a chunk pushed to an open batch, without rec_status): only the items from n0 and the pairs from a0 on.
+static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status, size_t n0 = 0, size_t a0 = 0) {
+  if (c->validate <= 0 || c->n <= n0) return;
   uint32_t *fl = c->d_flags.as<uint32_t>();
-  const uint32_t n = (uint32_t)c->n;
+  const uint32_t n = (uint32_t)(c->n - n0);
   const KindFacts &k = kind_facts(kind);
   if (c->n_shared && !d_rec_status) {                                  // a shared table: every row once, not once per reference; the outputs where they were gathered
     // (a status per item is wanted by the per-item calls, which restage through ctx_stage and so never see a shared staging, and by the
@@ -89,10 +90,10 @@ static void validate_staged(avrf_ctx *c, int kind, int32_t *d_rec_status) {
     AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, nullptr, c->stream));
     return;
   }
-  if (k.pk && c->d_pks.p) AVRF_SINGLE(c->suite, validate_xy(c->d_pks.as<uint8_t>(), 64, 1, n, c->validate, fl, d_rec_status, c->stream));
-  if (k.points) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>(), (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, d_rec_status, c->stream));
-  if (c->tot_io) {
-    if (!d_rec_status) AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>(), 128, 2, (uint32_t)c->tot_io, c->validate, fl, nullptr, c->stream));
+  if (k.pk && c->d_pks.p) AVRF_SINGLE(c->suite, validate_xy(c->d_pks.as<uint8_t>() + 64 * n0, 64, 1, n, c->validate, fl, d_rec_status, c->stream));
+  if (k.points) AVRF_SINGLE(c->suite, validate_xy(c->d_proofs.as<uint8_t>() + k.xy_proof() * n0, (uint32_t)k.xy_proof(), (uint32_t)k.points, n, c->validate, fl, d_rec_status, c->stream));
+  if (c->tot_io > a0) {
+    if (!d_rec_status) AVRF_SINGLE(c->suite, validate_xy(c->d_ios.as<uint8_t>() + 128 * a0, 128, 2, (uint32_t)(c->tot_io - a0), c->validate, fl, nullptr, c->stream));
     else {   // per-item status: the I/O pairs of item j are records io_off[j] .. io_off[j+1]; uniform M = 1 is the common case
       const uint32_t *io_off = c->h_io.as<uint32_t>();
       bool uniform = c->tot_io == c->n;
@@ -338,6 +339,10 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
   if (n && (!io_counts || !ad_lens)) return AVRF_ERR_BAD_ARG;
   if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
+  // An open batch ends here (include/avrf.h "Implicit close").  Its chunks may still be queued on the stream: copies up that read the
+  // page-locked offsets in h_io, prepare kernels that take their loop bounds from them, copies back into h_msg / h_c / h_flags.  All of
+  // that is rewritten below and by the run, so it is waited for first -- the one place a staging call waits before it has enqueued anything.
+  if (!c->open.chunks.empty()) { HIP_TRY(hipStreamSynchronize(c->stream)); c->open.chunks.clear(); }
   c->staged_kind = 0; c->n = n; c->tot_io = 0; c->n_terms = 0; c->n_shared = 0; c->n_contrib = 0; c->stage_gen++; c->wire_pending = false;
   if (n == 0) { c->staged_kind = kind; return AVRF_OK; }
   HIP_TRY(c->h_io.ensure((n + 1) * 8));
@@ -356,16 +361,18 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
 }
 // The close every flavour shares for a batch VERIFIER: the host copy of the responses (item 0's at `resp`, `stride` apart) for a sponge
 // transcript, which absorbs them on the host (counter-mode ones hash the device's records); the term count; the buffers the run writes.
-static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t stride) {
+// n0 (a chunk appended to an open batch): `resp` is item n0's; the buffers are the open batch's, grown before (open_grow), and the
+// lane's term arrays are left to the run (batch_launch), which knows the final count.
+static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t stride, bool append = false, size_t n0 = 0) {
   const size_t n = c->n, rsz = kind_facts(kind).resp;
   if (suite_host_weights(c->suite)) {
     c->h_resp.resize(n * rsz);
-    for (size_t j = 0; j < n; j++) memcpy(&c->h_resp[rsz * j], resp + stride * j, rsz);
+    for (size_t j = n0; j < n; j++) memcpy(&c->h_resp[rsz * j], resp + stride * (j - n0), rsz);
   }
   c->n_terms = c->n_shared ? shared_n_terms(kind, n, c->tot_io, c->n_shared) : n_terms(kind, n, c->tot_io);
   HIP_TRY(c->d_c.ensure(n * 16)); HIP_TRY(c->h_c.ensure(n * 16));
   HIP_TRY(c->d_z.ensure(z_bytes(kind, n, c->tot_io, c->n_shared != 0)));
-  return c->lane_owner ? ensure_terms(c) : (int)AVRF_OK;
+  return c->lane_owner && !append ? ensure_terms(c) : (int)AVRF_OK;
 }
 
 bool shared_indices_ok(const BatchSource &s) {
@@ -398,7 +405,7 @@ bool shared_indices_ok(const BatchSource &s) {
 static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
   const KindFacts &k = kind_facts(s.kind);
   const bool shared = s.n_shared != 0;
-  const size_t n = s.n, a = c->tot_io, nk = shared && k.pk ? n : 0, nc = nk + a, ns = s.n_shared, psz = k.xy_proof();   // nk: references to key rows
+  const size_t n = s.n, n0 = s.n0, a0 = s.a0, a = c->tot_io - a0, nk = shared && k.pk ? n : 0, nc = nk + a, ns = s.n_shared, psz = k.xy_proof();   // nk: references to key rows; n0, a0: what an open batch holds already
   const size_t L = s.wire ? (size_t)point_len_of(c->suite) : 0, plen = k.wire_proof(L);
   const size_t w_pks = shared ? ns * L : k.pk ? n * L : 0, w_ios = shared ? a * L : 2 * a * L, w_pr = n * plen;   // the wire bytes in d_misc
   uint8_t *dw = nullptr; uint32_t *d_flag = nullptr, *h_flag = c->h_flags.as<uint32_t>() + 2, *plan = nullptr;
@@ -407,10 +414,12 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
     HIP_TRY(c->d_table_rows.ensure(ns * sizeof(te_pre_raw))); HIP_TRY(c->d_table_plan.ensure(shared_plan_words(ns, nc) * 4));
     plan = c->d_table_plan.as<uint32_t>();
   }
-  if (shared || s.wire) { HIP_TRY(c->d_proofs.ensure(n * psz)); if (k.pk) HIP_TRY(c->d_pks.ensure(n * 64)); }
+  if (shared || s.wire) { HIP_TRY(c->d_proofs.ensure((n0 + n) * psz)); if (k.pk) HIP_TRY(c->d_pks.ensure((n0 + n) * 64)); }
   if (s.wire) {
     HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
-    dw = c->d_misc.as<uint8_t>(); d_flag = c->d_status.as<uint32_t>();
+    // the decode flag: d_status word 0, cleared per staging; a chunk of an open batch ORs into the BATCH's flag instead, d_flags word 2,
+    // cleared at open alone -- d_status is reused for the per-item statuses of a segmented run's attribution pass (seg_collect)
+    dw = c->d_misc.as<uint8_t>(); d_flag = s.append ? c->d_flags.as<uint32_t>() + 2 : c->d_status.as<uint32_t>();
   }
   auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
   if (shared && s.wire) {
@@ -429,11 +438,11 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
     if (w_ios) HIP_TRY(up(dw + w_pks, s.ios, w_ios));
     HIP_TRY(up(dw + w_pks + w_ios, s.proofs, w_pr));
   } else {
-    if (s.pks) { HIP_TRY(c->d_pks.ensure(n * 64)); HIP_TRY(up(c->d_pks.p, s.pks, n * 64)); }
+    if (s.pks) { HIP_TRY(c->d_pks.ensure((n0 + n) * 64)); HIP_TRY(up(c->d_pks.as<uint8_t>() + 64 * n0, s.pks, n * 64)); }
     if (s.sks) { HIP_TRY(c->d_sks.ensure(n * 32)); HIP_TRY(up(c->d_sks.p, s.sks, n * 32)); }
-    if (s.proofs) { HIP_TRY(c->d_proofs.ensure(n * psz)); HIP_TRY(up(c->d_proofs.p, s.proofs, n * psz)); }
+    if (s.proofs) { HIP_TRY(c->d_proofs.ensure((n0 + n) * psz)); HIP_TRY(up(c->d_proofs.as<uint8_t>() + psz * n0, s.proofs, n * psz)); }
   }
-  if (s.wire) HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
+  if (s.wire && !s.append) HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
   if (shared) HIP_TRY(hipMemsetAsync(shared_plan_flag(plan, ns, nc), 0, 4, c->stream));
   if (s.wire) {
     const uint8_t *dpr = dw + w_pks + w_ios;
@@ -444,11 +453,12 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
       HIP_TRY(AVRF_SINGLE(c->suite, decode_shared_wire(dw, (uint32_t)ns, (uint32_t)a, (uint32_t)n, c->d_table.as<uint8_t>(), c->d_table_rows.as<te_pre_raw>(),
                                                        c->d_table_outs.as<uint8_t>(), c->d_proofs.as<uint8_t>(), s.validate, d_flag, c->stream)));
     else {
-      if (k.pk) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>(), 64, s.validate, d_flag, c->stream));
-      AVRF_SINGLE(c->suite, decompress_strided(dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>(), 64, s.validate, d_flag, c->stream));
+      uint8_t *d_pr = c->d_proofs.as<uint8_t>() + psz * n0;
+      if (k.pk) AVRF_SINGLE(c->suite, decompress_strided(dw, (uint32_t)L, (uint32_t)n, c->d_pks.as<uint8_t>() + 64 * n0, 64, s.validate, d_flag, c->stream));
+      AVRF_SINGLE(c->suite, decompress_strided(dw + w_pks, (uint32_t)L, (uint32_t)(2 * a), c->d_ios.as<uint8_t>() + 128 * a0, 64, s.validate, d_flag, c->stream));
       for (size_t p = 0; p < k.points; p++)
-        AVRF_SINGLE(c->suite, decompress_strided(dpr + L * p, (uint32_t)plen, (uint32_t)n, c->d_proofs.as<uint8_t>() + 64 * p, (uint32_t)psz, s.validate, d_flag, c->stream));
-      HIP_TRY(hipMemcpy2DAsync(c->d_proofs.as<uint8_t>() + 64 * k.points, psz, dpr + L * k.points, plen, k.tail, n, hipMemcpyDeviceToDevice, c->stream));
+        AVRF_SINGLE(c->suite, decompress_strided(dpr + L * p, (uint32_t)plen, (uint32_t)n, d_pr + 64 * p, (uint32_t)psz, s.validate, d_flag, c->stream));
+      HIP_TRY(hipMemcpy2DAsync(d_pr + 64 * k.points, psz, dpr + L * k.points, plen, k.tail, n, hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   }
@@ -459,7 +469,7 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
     c->n_shared = ns; c->n_contrib = nc;
   }
   if (s.proofs && s.kind != Tiny)                                      // (Tiny has no batch verifier, and a prover stages no proofs)
-    if (int e = stage_verifier(c, s.kind, s.proofs + (s.wire ? k.resp_at_wire(L) : k.resp_at_xy()), s.wire ? plen : psz)) return e;
+    if (int e = stage_verifier(c, s.kind, s.proofs + (s.wire ? k.resp_at_wire(L) : k.resp_at_xy()), s.wire ? plen : psz, s.append, n0)) return e;
   if (s.wire && !wait) { c->wire_pending = true; return AVRF_OK; }
   if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
   if (s.wire) { HIP_TRY(hipGetLastError()); if (*h_flag) return AVRF_INVALID_DATA; }
@@ -644,12 +654,46 @@ static void launch_terms(avrf_ctx *c, int kind, const BatchDev &b, const Seed64 
                                       c->L->d_pre.as<te_pre_raw>(), c->L->d_gpart.as<uint32_t>(), (uint32_t)c->n_terms, c->stream));
 }
 
+// ---- open batches (include/avrf.h avrf_*_batch_open / _push / avrf_batch_flush): what the run phases need of them
+// open: BatchVerifier::new was called on the context and nothing has staged on it, or dropped what is staged, since
+static bool ctx_open(const avrf_ctx *c) { return c->open.kind && c->open.gen == c->stage_gen && c->staged_kind == c->open.kind; }
+// The batch's decode flag (h_flags[2], cleared at open, copied back behind every wire chunk): a point that did not decode or failed
+// `validate`.  The batch is then gone, as a failed avrf_*_batch_stage_wire leaves the context.
+static int open_wire_failed(avrf_ctx *c) {
+  if (!c->h_flags.as<uint32_t>()[2]) return AVRF_OK;
+  c->staged_kind = 0; c->wire_pending = false;
+  return AVRF_INVALID_DATA;
+}
+// The running weight transcript takes the records of the chunks whose copy back has completed, oldest first: found with an event
+// query, never a wait (all: the caller has waited for c->stream, every chunk is complete).
+static int open_poll(avrf_ctx *c, bool all) {
+  avrf_ctx::OpenBatch &o = c->open;
+  const KindFacts &k = kind_facts(o.kind);
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+  const bool host_weights = suite_host_weights(c->suite);
+  while (!o.chunks.empty()) {
+    const avrf_ctx::OpenBatch::Chunk &ch = o.chunks.front();
+    if (!all) {
+      const hipError_t e = hipEventQuery(ch.done);
+      if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }    // (not an error: the slot later calls poll must stay clear)
+      HIP_TRY(e);
+    }
+    if (host_weights) o.ws.absorb_parts(c->h_c.as<uint8_t>() + 16 * ch.n0, c->h_resp.data() + k.resp * ch.n0, ch.n, k.resp);
+    else o.ws.absorb(c->h_msg.as<uint8_t>() + pl + k.record() * ch.n0, ch.n, k.record());
+    o.absorbed = ch.n0 + ch.n;
+    o.chunks.pop_front();
+  }
+  return open_wire_failed(c);
+}
+
 int batch_begin(avrf_ctx *c, int kind, bool segmented) {
   if (!c || c->staged_kind != kind || c->run_phase != 0) return AVRF_ERR_BAD_ARG;
   if (c->n == 0) { c->run_phase = 1; return AVRF_OK; }                 // src/thin.rs:262-264, src/pedersen.rs:343-345
   if (!c->n_terms) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
   c->run_t0 = now_us();
+  // an open batch: every push has enqueued its chunk's validation, prepare kernel and copies back already
+  if (ctx_open(c)) { c->run_begin_us = 0; c->run_phase = 1; return AVRF_OK; }
   const size_t n = c->n;
   BatchDev b = batch_of(c);
   HIP_TRY(reset_flags(c, segmented));
@@ -677,6 +721,7 @@ int batch_begin(avrf_ctx *c, int kind, bool segmented) {
 // the prepare kernel and the copies back have completed (the caller waited for c->stream or for an event behind them)
 int batch_collect(avrf_ctx *c, int kind) {
   if (!c || c->staged_kind != kind || c->run_phase != 1) return AVRF_ERR_BAD_ARG;
+  if (c->n && ctx_open(c)) if (int e = open_wire_failed(c)) { c->run_phase = 0; return e; }   // (before the checks of items that never decoded)
   if (c->n && *c->h_flags.as<uint32_t>()) { c->run_phase = 0; return AVRF_INVALID_DATA; }   // src/thin.rs:266-271, src/pedersen.rs:348-353
   if (c->wire_pending) {                                               // staged from wire bytes without waiting (ctx_stage): a point that failed to decode / validate
     c->wire_pending = false;
@@ -705,6 +750,15 @@ int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]) {
   const size_t n = c->n;
   memset(digest, 0, 64);
   if (!n) return AVRF_OK;
+  if (ctx_open(c)) {
+    // (the caller has waited for c->stream) what no push has absorbed yet, then a CLONE finalised: verify(&self) borrows, the batch
+    // stays open and its transcript goes on (src/thin.rs:257)
+    if (int e = open_poll(c, /*all=*/true)) return e;
+    const WeightStream fin = c->open.ws.clone();
+    if (suite_host_weights(c->suite)) { c->h_weights.resize(n * kind_facts(kind).weight); fin.squeeze(c->h_weights.data(), c->h_weights.size()); }
+    else fin.digest(digest);
+    return AVRF_OK;
+  }
   if (suite_host_weights(c->suite)) {
     c->h_weights.resize(n * kind_facts(kind).weight);
     squeeze_weights(c, kind, 0, n);
@@ -761,6 +815,210 @@ int batch_end(avrf_ctx *c, int kind) {
   return st;
 }
 }  // namespace avrf
+
+// ---------------------------------------------------------------- open batches: BatchVerifier::new / push (src/thin.rs:199-243, src/pedersen.rs:316-326)
+// A push copies its chunk to page-locked memory, restates stage_open for an append (checks, prefix sums continued from the totals,
+// only the chunk's offsets up), hands the chunk to stage_payload as a source with a base, and enqueues the chunk's validation, the
+// prepare kernel over [n0, n0 + n) and the copy back of that range's records -- all on c->stream, nothing waited for.  The run
+// phases above find that work done (batch_begin), read the accumulated flags (batch_collect) and finalise a clone of the running
+// transcript (batch_seed).
+
+// One buffer of the open batch at `bytes` or more with its first `used` bytes kept: device memory copied on c->stream, the old buffer
+// handed to `old` (the caller waits ONCE for all the copies before the old buffers go), page-locked host memory copied here.
+static int open_keep(avrf_ctx *c, DevBuf &buf, size_t used, size_t bytes, std::vector<DevBuf> &old) {
+  if (buf.p && bytes <= buf.cap) return AVRF_OK;
+  DevBuf nb;
+  HIP_TRY(nb.ensure(bytes));
+  if (buf.p && used) HIP_TRY(hipMemcpyAsync(nb.p, buf.p, used < buf.cap ? used : buf.cap, hipMemcpyDeviceToDevice, c->stream));
+  old.push_back(std::move(buf));                                       // (kept until the copy out of it has completed)
+  buf = std::move(nb);
+  return AVRF_OK;
+}
+static int open_keep(PinBuf &buf, size_t used, size_t bytes) {
+  if (buf.p && bytes <= buf.cap) return AVRF_OK;
+  PinBuf nb;
+  HIP_TRY(nb.ensure(bytes));
+  if (buf.p && used) memcpy(nb.p, buf.p, used < buf.cap ? used : buf.cap);
+  buf = std::move(nb);
+  return AVRF_OK;
+}
+// Room for `items` items, `pairs` pairs and `ad` bytes of additional data in every buffer a push writes, what was pushed kept.  Within
+// the capacities nothing happens; beyond them they double, and the call WAITS for c->stream once first: copies back into the
+// page-locked record buffer and copies up from the offsets may be in flight, and the buffers they use are about to move.
+static int open_grow(avrf_ctx *c, size_t items, size_t pairs, size_t ad) {
+  avrf_ctx::OpenBatch &o = c->open;
+  const bool fresh = !c->h_msg.p || !c->h_io.p || !o.h_ad_off.p;      // (the first open on a context: even an empty batch has a prefix and offsets [0])
+  if (items <= o.cap_items && pairs <= o.cap_pairs && ad <= o.cap_ad && !fresh) return AVRF_OK;
+  auto grown = [](size_t need, size_t cap, size_t least) { return need <= cap ? cap : need > 2 * cap ? (need > least ? need : least) : 2 * cap; };
+  const size_t ci = grown(items, o.cap_items, 256), cp = grown(pairs, o.cap_pairs, 256), ca = grown(ad, o.cap_ad, 1024);
+  const KindFacts &k = kind_facts(o.kind);
+  const size_t n = c->n, a = c->tot_io, recsz = k.record();
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+  std::vector<DevBuf> old;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (k.pk) if (int e = open_keep(c, c->d_pks, n * 64, ci * 64, old)) return e;
+  if (int e = open_keep(c, c->d_proofs, n * k.xy_proof(), ci * k.xy_proof(), old)) return e;
+  if (int e = open_keep(c, c->d_ios, a * 128, cp * 128 + 16, old)) return e;
+  if (int e = open_keep(c, c->d_ads, o.ad_bytes, ca + 16, old)) return e;
+  if (int e = open_keep(c, c->d_io_off, (n + 1) * 4, (ci + 1) * 4, old)) return e;
+  if (int e = open_keep(c, c->d_ad_off, (n + 1) * 4, (ci + 1) * 4, old)) return e;
+  if (int e = open_keep(c, c->d_c, n * 16, ci * 16, old)) return e;
+  if (int e = open_keep(c, c->d_z, z_bytes(o.kind, n, a), z_bytes(o.kind, ci, cp), old)) return e;
+  if (int e = open_keep(c, c->d_rec, n * recsz, ci * recsz + 16, old)) return e;
+  if (!old.empty()) HIP_TRY(hipStreamSynchronize(c->stream));          // the device-to-device copies: one wait for all of them
+  old.clear();
+  if (int e = open_keep(c->h_io, (n + 1) * 4, (ci + 1) * 4)) return e;
+  if (int e = open_keep(o.h_ad_off, (n + 1) * 4, (ci + 1) * 4)) return e;
+  if (int e = open_keep(c->h_msg, pl + n * recsz, pl + ci * recsz)) return e;
+  if (int e = open_keep(c->h_c, n * 16, ci * 16 + 16)) return e;
+  o.cap_items = ci; o.cap_pairs = cp; o.cap_ad = ca;
+  return AVRF_OK;
+}
+// `bytes` of page-locked memory for a chunk's copy: from the current block, or from a new one twice as large -- a block never moves or
+// goes while the batch is open, so the copies up that read it stay valid
+static uint8_t *open_arena_take(avrf_ctx *c, size_t bytes) {
+  avrf_ctx::OpenBatch &o = c->open;
+  if (o.arena.empty() || o.arena_used + bytes > o.arena.back().cap) {
+    size_t want = o.arena.empty() ? (size_t)1 << 20 : 2 * o.arena.back().cap;
+    if (want < bytes) want = bytes;
+    PinBuf nb;
+    if (nb.ensure(want) != hipSuccess) return nullptr;
+    o.arena.push_back(std::move(nb)); o.arena_used = 0;
+  }
+  uint8_t *p = o.arena.back().as<uint8_t>() + o.arena_used;
+  o.arena_used += bytes;
+  return p;
+}
+static bool open_limits_ok(size_t items, size_t pairs, size_t ad) { return items <= 0x0fffffffULL && pairs <= 0x1fffffffULL && ad <= 0x7fffffffULL; }   // stage_open's
+
+static int batch_open(avrf_ctx *c, int kind, size_t items_hint, size_t pairs_hint, size_t ad_hint) {
+  if (!c || ctx_busy(c) || !c->lane_owner || !open_limits_ok(items_hint, pairs_hint, ad_hint)) return AVRF_ERR_BAD_ARG;
+  avrf_ctx::OpenBatch &o = c->open;
+  // the reset every staging makes (n == 0: the empty batch of `kind` is staged)
+  if (int e = stage_open(c, kind, 0, true, nullptr, false, nullptr, nullptr, nullptr)) return e;     // (waits for the chunks of an open batch it replaces)
+  c->staged_kind = 0;                                                  // (until everything below has succeeded)
+  o.kind = kind; o.ad_bytes = 0; o.absorbed = 0; o.cap_items = o.cap_pairs = o.cap_ad = 0;
+  if (o.arena.size() > 1) { HIP_TRY(hipStreamSynchronize(c->stream)); o.arena.erase(o.arena.begin(), o.arena.end() - 1); }   // (the largest block stays)
+  o.arena_used = 0;
+  if (int e = open_grow(c, items_hint, pairs_hint, ad_hint)) return e;
+  // (the chunks are packed without padding, so hints that are exact for the batch are exact for the arena however many pushes bring it;
+  // x || y chunks: wire ones are smaller)
+  const size_t hint_bytes = items_hint * ((kind_facts(kind).pk ? 64 : 0) + kind_facts(kind).xy_proof()) + pairs_hint * 128 + ad_hint;
+  if (hint_bytes && (o.arena.empty() || o.arena.back().cap < hint_bytes)) {
+    if (!o.arena.empty()) { HIP_TRY(hipStreamSynchronize(c->stream)); o.arena.clear(); }
+    if (!open_arena_take(c, hint_bytes)) return AVRF_ERR_NO_DEVICE;
+    o.arena_used = 0;
+  }
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+  with_suite(c->suite, [&](auto tag_) { using S = typename decltype(tag_)::type;
+    o.ws.begin(S::XOF_SHAKE ? WeightStream::SHAKE128 : S::TR_SHA256 ? WeightStream::SHA256 : WeightStream::SHA512, prefix, pl); });
+  memcpy(c->h_msg.p, prefix, pl); c->h_msg_len = pl;
+  c->h_io.as<uint32_t>()[0] = 0; o.h_ad_off.as<uint32_t>()[0] = 0;
+  c->h_resp.clear();
+  c->h_flags.as<uint32_t>()[0] = 0; c->h_flags.as<uint32_t>()[2] = 0;
+  // the flag word (d_flags word 0) is the batch's: OR-ed across the chunks, cleared here alone; so is the decode flag of its wire chunks, word 2
+  HIP_TRY(hipMemsetAsync(c->d_flags.p, 0, 12, c->stream));
+  o.gen = c->stage_gen; c->staged_kind = kind;
+  return AVRF_OK;
+}
+
+// s: the caller's arrays of the chunk (plain_source / wire_source)
+static int batch_push(avrf_ctx *c, BatchSource s) {
+  if (!c || ctx_busy(c) || !ctx_open(c) || c->open.kind != s.kind) return AVRF_ERR_BAD_ARG;
+  const size_t n = s.n;
+  if (!n) return AVRF_OK;
+  if (!s.io_counts || !s.ad_lens || !s.proofs || (s.kind == Thin && !s.pks)) return AVRF_ERR_BAD_ARG;
+  avrf_ctx::OpenBatch &o = c->open;
+  const KindFacts &k = kind_facts(s.kind);
+  const size_t n0 = c->n, a0 = c->tot_io, b0 = o.ad_bytes;
+  if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
+  uint64_t a = 0, b = 0;
+  for (size_t j = 0; j < n; j++) { a += s.io_counts[j]; b += s.ad_lens[j]; }
+  if (!open_limits_ok(n0 + n, a0 + a, b0 + b) || (a && !s.ios) || (b && !s.ads)) return AVRF_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  // the records of earlier chunks that have come back meanwhile go into the transcript now; a wire chunk that failed ends the batch
+  if (int e = open_poll(c, /*all=*/false)) return e;
+  if (int e = open_grow(c, n0 + n, a0 + a, b0 + b)) { c->staged_kind = 0; return e; }
+  // the page-locked copy: keys | I/O points | proofs | additional data, back to back (the copies up need no alignment)
+  const size_t L = s.wire ? (size_t)point_len_of(c->suite) : 0, plen = s.wire ? k.wire_proof(L) : k.xy_proof();
+  const size_t sz_pks = k.pk ? n * (s.wire ? L : 64) : 0, sz_ios = s.wire ? 2 * a * L : a * 128, sz_pr = n * plen;
+  uint8_t *pin = open_arena_take(c, sz_pks + sz_ios + sz_pr + b);
+  if (!pin) { c->staged_kind = 0; return AVRF_ERR_NO_DEVICE; }
+  uint8_t *p_pks = pin, *p_ios = p_pks + sz_pks, *p_pr = p_ios + sz_ios, *p_ads = p_pr + sz_pr;
+  if (sz_pks) memcpy(p_pks, s.pks, sz_pks);
+  if (sz_ios) memcpy(p_ios, s.ios, sz_ios);
+  if (b) memcpy(p_ads, s.ads, b);
+  memcpy(p_pr, s.proofs, sz_pr);
+  uint32_t *io_off = c->h_io.as<uint32_t>() + n0, *ad_off = o.h_ad_off.as<uint32_t>() + n0;
+  uint64_t ta = a0, tb = b0;
+  for (size_t j = 0; j < n; j++) { io_off[j] = (uint32_t)ta; ad_off[j] = (uint32_t)tb; ta += s.io_counts[j]; tb += s.ad_lens[j]; }
+  io_off[n] = (uint32_t)ta; ad_off[n] = (uint32_t)tb;
+  // from here on a failure leaves nothing open or staged
+  c->staged_kind = 0;
+  auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
+  HIP_TRY(up(c->d_io_off.as<uint32_t>() + n0, io_off, (n + 1) * 4));
+  HIP_TRY(up(c->d_ad_off.as<uint32_t>() + n0, ad_off, (n + 1) * 4));
+  if (!s.wire && a) HIP_TRY(up(c->d_ios.as<uint8_t>() + 128 * a0, p_ios, a * 128));
+  if (b) HIP_TRY(up(c->d_ads.as<uint8_t>() + b0, p_ads, b));
+  c->n = n0 + n; c->tot_io = a0 + (size_t)a; o.ad_bytes = b0 + (size_t)b;
+  s.pks = k.pk ? p_pks : nullptr; s.ios = p_ios; s.ads = p_ads; s.proofs = p_pr;
+  s.append = true; s.n0 = n0; s.a0 = a0;
+  if (int e = stage_payload(c, s, /*wait=*/false)) return e;
+  validate_staged(c, s.kind, nullptr, n0, a0);
+  const bool host_weights = suite_host_weights(c->suite);
+  const size_t recsz = k.record();
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
+  BatchDev bd = batch_of(c);
+  bd.first = (uint32_t)n0;
+  if (!host_weights) bd.records = c->d_rec.as<uint8_t>();
+  launch_prepare(c, s.kind, bd, false);
+  if (!host_weights) {
+    HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl + n0 * recsz, c->d_rec.as<uint8_t>() + n0 * recsz, n * recsz, hipMemcpyDeviceToHost, c->stream));
+    c->h_msg_len = pl + (n0 + n) * recsz;
+  } else HIP_TRY(hipMemcpyAsync(c->h_c.as<uint8_t>() + 16 * n0, c->d_c.as<uint8_t>() + 16 * n0, n * 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+  avrf_ctx::OpenBatch::Chunk ch; ch.n0 = n0; ch.n = n;
+  HIP_TRY(ch.done.create(hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ch.done, c->stream));
+  o.chunks.push_back(std::move(ch));
+  c->staged_kind = s.kind;
+  return AVRF_OK;
+}
+
+extern "C" {
+
+int avrf_thin_batch_open(avrf_ctx *c, size_t items_hint, size_t pairs_hint, size_t ad_bytes_hint) { return batch_open(c, Thin, items_hint, pairs_hint, ad_bytes_hint); }
+int avrf_pedersen_batch_open(avrf_ctx *c, size_t items_hint, size_t pairs_hint, size_t ad_bytes_hint) { return batch_open(c, Pedersen, items_hint, pairs_hint, ad_bytes_hint); }
+int avrf_thin_batch_push(avrf_ctx *c, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
+                         const uint32_t *ad_lens, const uint8_t *proofs) {
+  return batch_push(c, plain_source(Thin, n, pks_xy, ios_xy, io_counts, ads, ad_lens, proofs));
+}
+int avrf_thin_batch_push_wire(avrf_ctx *c, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                              const uint32_t *ad_lens, const uint8_t *proofs, int validate) {
+  return batch_push(c, wire_source(plain_source(Thin, n, pks, ios, io_counts, ads, ad_lens, proofs), validate));
+}
+int avrf_pedersen_batch_push(avrf_ctx *c, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                             const uint8_t *proofs) {
+  return batch_push(c, plain_source(Pedersen, n, nullptr, ios_xy, io_counts, ads, ad_lens, proofs));
+}
+int avrf_pedersen_batch_push_wire(avrf_ctx *c, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads, const uint32_t *ad_lens,
+                                  const uint8_t *proofs, int validate) {
+  return batch_push(c, wire_source(plain_source(Pedersen, n, nullptr, ios, io_counts, ads, ad_lens, proofs), validate));
+}
+// waits for everything pushed, absorbs it, and reports what a wire chunk left: AVRF_INVALID_DATA, the batch gone
+int avrf_batch_flush(avrf_ctx *c) {
+  if (!c || ctx_busy(c) || !ctx_open(c)) return AVRF_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) { (void)hipGetLastError(); c->staged_kind = 0; return AVRF_ERR_NO_DEVICE; }
+  return open_poll(c, /*all=*/true);
+}
+size_t avrf_batch_pushed(const avrf_ctx *c, size_t out[3]) {
+  const bool open = c && ctx_open(c);
+  if (out) { out[0] = open ? c->n : 0; out[1] = open ? c->tot_io : 0; out[2] = open ? c->open.ad_bytes : 0; }
+  return open ? c->n : 0;
+}
+
+}  // extern "C"
 extern "C" {
 
 // the second of the three calls: wait for the prepare kernel, hash on the calling thread, enqueue terms + MSM
@@ -982,6 +1240,7 @@ int seg_collect(avrf_ctx *c, int kind) {
   if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
   if (seg_nothing(c)) return AVRF_OK;
   c->run_phase = 0;                                                    // an error below leaves the context idle
+  if (ctx_open(c)) if (int e = open_wire_failed(c)) return e;          // an open batch's sticky decode flag, as batch_collect
   if (c->wire_pending) {                                               // as batch_collect: a wire point that failed to decode / validate is the whole job's status
     c->wire_pending = false;
     if (c->h_flags.as<uint32_t>()[2]) { c->staged_kind = 0; return AVRF_INVALID_DATA; }

@@ -6,8 +6,10 @@
 #include "host_te.h"
 #include "msm.h"
 #include "proof_kind.h"
+#include "host_weight_stream.h"
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <deque>
 #include <new>
 #include <vector>
 
@@ -95,8 +97,24 @@ struct avrf_ctx {
   // (n_seg + 1 words, padded to 64 bytes) followed by the n_seg weight seeds and, for the merged layout, the n_seg terms row0
   struct SegRun { size_t n_seg = 0, L = 0, padded = 0; bool merged = false; std::vector<uint32_t> off, row0; std::vector<int32_t> item_status; } seg;
   avrf::PinBuf h_seg_up;
+  // An OPEN batch (include/avrf.h avrf_*_batch_open / _push / _flush; BatchVerifier::new / push, src/thin.rs:199-243): staged_kind == kind
+  // and gen == stage_gen while it is open, so whatever stages on the context, or drops what is staged, closes it.  n / tot_io / n_terms
+  // above are its totals so far; the staged buffers hold `cap_*` and grow with their used prefix kept (capi.hip open_grow).  Each push
+  // leaves a chunk: its item range and an event behind the copy back of its records (sponge / SHA-256 suites: its challenges).  `ws` has
+  // absorbed the records of items [0, absorbed); a run finalises a clone of it.  `arena`: the page-locked copies of the pushed chunks,
+  // in blocks that never move while copies up from them are in flight.  io_off stays in h_io; ad_off has a buffer of its own here
+  // (stage_open keeps it behind io_off at n + 1, which an append would have to move).
+  struct OpenBatch {
+    struct Chunk { size_t n0 = 0, n = 0; avrf::DevEvent done; };
+    int kind = 0; uint64_t gen = 0;
+    size_t ad_bytes = 0, cap_items = 0, cap_pairs = 0, cap_ad = 0, absorbed = 0;
+    std::deque<Chunk> chunks;                 // pushed and not yet absorbed, oldest first
+    avrf::WeightStream ws;
+    avrf::PinBuf h_ad_off;
+    std::vector<avrf::PinBuf> arena; size_t arena_used = 0;   // bytes used of arena.back()
+  } open;
   double timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int run_phase = 0;              // batch_begin / batch_hash / batch_end: 1, 2; a segmented run (seg_begin .. seg_end): 3, 4
+  int run_phase = 0;             // batch_begin / batch_hash / batch_end: 1, 2; a segmented run (seg_begin .. seg_end): 3, 4
   bool unit_weights = false;      // batch_launch: every item's weight is 1 (avrf_thin_verify runs ONE item as its own equation through the MSM path)
   double run_t0 = 0, run_begin_us = 0, run_msm_us = 0;
   // The order a context goes in: its device made current and its own stream drained; then the members, last first -- the staging
@@ -117,6 +135,9 @@ struct BatchSource {
   const uint8_t *sks = nullptr, *pks = nullptr, *ios = nullptr; const uint32_t *io_counts = nullptr;
   const uint8_t *ads = nullptr; const uint32_t *ad_lens = nullptr; const uint8_t *proofs = nullptr;   // proofs / pks / sks may be NULL for provers
   size_t n_shared = 0; const uint8_t *table = nullptr; const uint32_t *pk_index = nullptr, *input_index = nullptr; const uint8_t *outputs = nullptr;
+  // append: a chunk pushed to an open batch (plain or wire, never over a table) -- its n items go behind the n0 items and a0 pairs that
+  // are already there, and the decode flag is the batch's (cleared at open, not per chunk)
+  bool append = false; size_t n0 = 0, a0 = 0;
 };
 // how the entry points fill one from their argument lists: x || y arrays, a table with indices, and either as wire bytes
 inline BatchSource plain_source(int kind, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,

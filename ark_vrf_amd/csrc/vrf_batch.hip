@@ -71,7 +71,7 @@ template <class S>
 __global__ void __launch_bounds__(128)
 k_thin_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint32_t *__restrict__ z_out, uint32_t *__restrict__ flags) {
   using Fr = typename S::Fr;
-  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t j = b.first + blockIdx.x * blockDim.x + threadIdx.x;                // the range [b.first, b.n): a whole batch, or one pushed chunk of an open one
   if (j >= b.n) return;
   uint32_t io0 = b.io_off[j], io1 = b.io_off[j + 1], m = io1 - io0;
   uint32_t ad0 = b.ad_off[j], adl = b.ad_off[j + 1] - ad0;
@@ -191,7 +191,7 @@ template <class S, bool SHARED>
 __global__ void __launch_bounds__(128)
 k_ped_prepare(BatchDev b, uint32_t *__restrict__ c_out, uint8_t *__restrict__ merged_xy, uint32_t *__restrict__ flags) {
   using Fr = typename S::Fr;
-  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t j = b.first + blockIdx.x * blockDim.x + threadIdx.x;                // the range [b.first, b.n): a whole batch, or one pushed chunk of an open one
   if (j >= b.n) return;
   uint32_t io0 = b.io_off[j], m = b.io_off[j + 1] - io0, ad0 = b.ad_off[j], adl = b.ad_off[j + 1] - ad0;
   const uint8_t *ios = b.ios_xy + 128 * (size_t)io0, *pr = b.proofs + 256 * (size_t)j;
@@ -298,8 +298,8 @@ k_ped_terms(BatchDev b, Seed64 seed, uint64_t j0, const uint32_t *__restrict__ c
 }
 
 template <class S> void BatchOps<S>::ped_prepare(const BatchDev &b, uint32_t *d_c, uint8_t *d_merged, uint32_t *d_flags, bool shared, hipStream_t st) {
-  if (!b.n) return;
-  dim3 g((b.n + 127) / 128), blk(128);
+  if (b.n <= b.first) return;
+  dim3 g((b.n - b.first + 127) / 128), blk(128);                                // every output is indexed by the absolute item / pair: a range writes what the whole would
   if (shared) hipLaunchKernelGGL((k_ped_prepare<S, true>), g, blk, 0, st, b, d_c, d_merged, d_flags);
   else hipLaunchKernelGGL((k_ped_prepare<S, false>), g, blk, 0, st, b, d_c, d_merged, d_flags);
 }
@@ -313,8 +313,8 @@ template <class S> void BatchOps<S>::ped_terms(const BatchDev &b, const Seed64 &
   hipLaunchKernelGGL(k_g_final<S>, dim3(1), dim3(256), 0, st, bp, g.x, d_scalars, (te_pre *)d_pre, n_terms - 1, 1);
 }
 template <class S> void BatchOps<S>::thin_prepare(const BatchDev &b, uint32_t *d_c, uint32_t *d_z, uint32_t *d_flags, hipStream_t st) {
-  if (!b.n) return;
-  dim3 g((b.n + 127) / 128), blk(128);
+  if (b.n <= b.first) return;
+  dim3 g((b.n - b.first + 127) / 128), blk(128);                                // every output is indexed by the absolute item / pair: a range writes what the whole would
   hipLaunchKernelGGL(k_thin_prepare<S>, g, blk, 0, st, b, d_c, d_z, d_flags);
 }
 template <class S> void BatchOps<S>::thin_terms(const BatchDev &b, const Seed64 &seed, uint64_t j0, const uint32_t *d_c, const uint32_t *d_z,

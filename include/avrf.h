@@ -937,6 +937,61 @@ int avrf_pedersen_batch_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios,
 int avrf_pedersen_verify_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
                               const uint32_t *ad_lens, const uint8_t *proofs, int validate, int32_t *status_out);
 
+/* ---- OPEN batches: BatchVerifier::new, push as items arrive, verify (src/thin.rs:188-326, src/pedersen.rs:303-426).
+ * The reference's batch verifiers are incremental: `prepare` is "hashing only, no EC ops", so a caller pays for it when an item
+ * arrives and leaves the MSM for `verify`.  An open batch is that on the device: every push enqueues its chunk's copies up, wire
+ * decoding, validation, the prepare kernel over the chunk's items alone and the copy back of their transcript records, and the
+ * host absorbs the records of EARLIER chunks into a running weight transcript -- so that by the time the last item is pushed,
+ * `verify` has the last chunk's prepare, the terms kernel and the MSM left to do.
+ *
+ * verify is the existing calls, which accept an open batch of their kind exactly as a staged one: avrf_thin_batch_run /
+ * avrf_pedersen_batch_run, avrf_batch_run_begin / _hash / _end, avrf_*_batch_run_segments, and afterwards avrf_batch_last_terms,
+ * avrf_*_segment_terms, avrf_last_timing (the hash phase, out[2], is what was left to absorb).  An open batch into which items
+ * 0 .. n-1 were pushed in ANY chunking is indistinguishable from avrf_*_batch_stage of the same items in the same order: same
+ * terms bit for bit, same MSM point, same verdict -- AVRF_INVALID_DATA for an identity key / input / output, an out-of-range
+ * coordinate or s >= r is found at verify, not at push, as in the reference (src/thin.rs:265-271) -- same segment statuses.  An
+ * empty open batch verifies (AVRF_OK).  verify does not consume (verify(&self) borrows): more may be pushed and the batch run
+ * again, and that run equals a staging of all items so far.
+ *
+ * Ownership: a push makes its own page-locked copy of the chunk before it returns, whatever memory the caller's arrays are in
+ * (buffers of avrf_host_alloc / avrf_host_register included: they are copied too, not read in place); the caller may reuse them at
+ * once.  Apart from that copy a push does NOT wait: everything is enqueued on the context's own stream.  The exception is
+ * growth: pushing beyond the hints given to open grows the buffers with what was pushed kept, and that waits for the stream (twice
+ * per doubling: before the buffers move and behind the copies that move them), and a page-locked block for the chunk copies is
+ * allocated when the current one is full.  Hints that cover the batch avoid both, however many pushes bring it: the chunk copies are
+ * packed without padding, so items x (64 + 96) + pairs x 128 + additional data bytes (Pedersen: items x 256 + ..) are enough.
+ *
+ * Refusals, decided before anything is touched (AVRF_ERR_BAD_ARG, the batch unchanged): no open batch of that kind; a NULL array
+ * where the counts need one; the cumulative limits of a staging exceeded (items <= 0x0fffffff, pairs <= 0x1fffffff, additional data
+ * <= 0x7fffffff bytes); the context is a slot of a pool; and, for open, push and flush alike, a run in flight on the context
+ * (between avrf_batch_run_begin and avrf_batch_run_end).
+ * Wire failures are sticky: whether a point of a wire chunk decodes (and passes `validate`) is known only when the chunk's kernels
+ * have run; the next push, flush or run then returns AVRF_INVALID_DATA and the batch is gone -- nothing is open or staged, as a
+ * failed avrf_*_batch_stage_wire leaves the context -- until a new open.  avrf_batch_flush is how a caller learns it before pushing more.
+ * Implicit close: whatever stages on the context, or drops what is staged, ends the open batch (avrf_*_batch_stage*,
+ * avrf_*_batch_verify*, the per-item provers and verifiers, the point-wise calls, avrf_msm_*).  A staging call (and a new open) that
+ * ends an open batch whose chunks are still queued WAITS for the context's stream first: it is about to rewrite the page-locked
+ * offsets and record buffers those chunks read and write.
+ * Not covered: open batches over a shared table or through a pool; push_prepared with the caller's challenges; ring batches. */
+/* BatchVerifier::new (src/thin.rs:199-202, src/pedersen.rs:316-318) on the context: an OPEN batch, empty.  The hints size the buffers
+ * (0 = grow on demand).  Whatever was staged or open on the context before is dropped, as by a *_batch_stage call. */
+int avrf_thin_batch_open(avrf_ctx *ctx, size_t items_hint, size_t pairs_hint, size_t ad_bytes_hint);
+int avrf_pedersen_batch_open(avrf_ctx *ctx, size_t items_hint, size_t pairs_hint, size_t ad_bytes_hint);
+/* BatchVerifier::push for n more items (src/thin.rs:234-243, src/pedersen.rs:324-326; n == 0 is a no-op): the arguments of
+ * avrf_thin_batch_stage / avrf_pedersen_batch_stage (x || y) and of avrf_*_batch_stage_wire (serialize_compressed bytes, validate). */
+int avrf_thin_batch_push(avrf_ctx *ctx, size_t n, const uint8_t *pks_xy, const uint8_t *ios_xy, const uint32_t *io_counts,
+                         const uint8_t *ads, const uint32_t *ad_lens, const uint8_t *proofs);
+int avrf_thin_batch_push_wire(avrf_ctx *ctx, size_t n, const uint8_t *pks, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                              const uint32_t *ad_lens, const uint8_t *proofs, int validate);
+int avrf_pedersen_batch_push(avrf_ctx *ctx, size_t n, const uint8_t *ios_xy, const uint32_t *io_counts, const uint8_t *ads,
+                             const uint32_t *ad_lens, const uint8_t *proofs);
+int avrf_pedersen_batch_push_wire(avrf_ctx *ctx, size_t n, const uint8_t *ios, const uint32_t *io_counts, const uint8_t *ads,
+                                  const uint32_t *ad_lens, const uint8_t *proofs, int validate);
+/* waits for everything pushed, absorbs it into the running transcript, and reports a sticky wire failure (AVRF_INVALID_DATA) */
+int avrf_batch_flush(avrf_ctx *ctx);
+/* BatchVerifier::len: the items pushed so far; out (may be NULL) = { items, pairs, bytes of additional data }.  0 when nothing is open. */
+size_t avrf_batch_pushed(const avrf_ctx *ctx, size_t out[3]);
+
 /* ring::Prover::prove (src/ring.rs:211-226) as ONE call for n provers of the ring behind `key` (avrf_pedersen_prove +
  * avrf_ring_prove + serialisation): sks n x 32, key_index[i] = position of prover i's key in the ring, ios_xy as for
  * avrf_pedersen_prove; proofs_out: n x (160 + ring_proof_len) bytes, ring::Proof's compressed serialisation.

@@ -200,6 +200,43 @@ class BatchVerifier {
   std::vector<uint8_t> pks_, proofs_; detail::Packed packed_;
   friend class VerifierPool;
 };
+// thin::BatchVerifier as the reference's incremental interface (src/thin.rs:188-326) on the device: new opens a batch on the context
+// (avrf_thin_batch_open), push / push_many hand the items over as they arrive (avrf_thin_batch_push: copied, prepared and their
+// transcript records absorbed while later items are still on their way), verify is the MSM that is left (avrf_thin_batch_run).
+// verify borrows: more may be pushed afterwards and the batch verified again.  One open batch per Suite; whatever else stages on the
+// Suite's context ends it (include/avrf.h, open batches), after which push and verify throw.  The hints size the buffers (0: grow on demand).
+class OpenBatchVerifier {
+ public:
+  explicit OpenBatchVerifier(const Suite &su, size_t items_hint = 0, size_t pairs_hint = 0, size_t ad_bytes_hint = 0) : su_(su) {   // :199-202
+    if (avrf_thin_batch_open(su_.ctx(), items_hint, pairs_hint, ad_bytes_hint) != AVRF_OK) throw std::invalid_argument("avrf: thin batch open");
+  }
+  struct Item { Public pk; std::vector<VrfIo> ios; std::string ad; Proof proof; };
+  void push(const Public &pk, const std::vector<VrfIo> &ios, const std::string &ad, const Proof &proof) {   // :234-243
+    push_many({Item{pk, ios, ad, proof}});
+  }
+  // several items, in their order, as ONE chunk: one set of copies and one prepare launch
+  void push_many(const std::vector<Item> &items) {
+    std::vector<uint8_t> pks, proofs; detail::Packed p;
+    for (const Item &it : items) {
+      pks.insert(pks.end(), it.pk.point.begin(), it.pk.point.end());
+      p.push(it.ios, it.ad);
+      proofs.insert(proofs.end(), it.proof.r.begin(), it.proof.r.end()); proofs.insert(proofs.end(), it.proof.s.begin(), it.proof.s.end());
+    }
+    if (avrf_thin_batch_push(su_.ctx(), items.size(), pks.data(), p.ios.data(), p.io_counts.data(), p.ads.data(), p.ad_lens.data(), proofs.data()) != AVRF_OK)
+      throw std::invalid_argument("avrf: thin batch push");
+  }
+  Status verify() const { return avrf_thin_batch_run(su_.ctx()); }                                           // :257-325
+  size_t len() const { return avrf_batch_pushed(su_.ctx(), nullptr); }
+  // One verdict per segment of what was pushed so far (avrf_thin_batch_run_segments): seg_items[v] consecutive items each, summing to len()
+  std::vector<Status> verify_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_thin_batch_run_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: thin open verify segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+
+ private:
+  const Suite &su_;
+};
 // { L, padded terms, total terms, window bits } of a segmented run (avrf_thin_segments_layout; host arithmetic): throws beyond the limits
 inline std::array<uint64_t, 4> segments_layout(const std::vector<uint32_t> &seg_items, const std::vector<uint32_t> &io_counts) {
   std::array<uint64_t, 4> out{};
@@ -338,6 +375,35 @@ class BatchVerifier {
  private:
   const Suite &su_; size_t n_ = 0;
   std::vector<uint8_t> proofs_; detail::Packed packed_;
+};
+// pedersen::BatchVerifier as the reference's incremental interface (src/pedersen.rs:303-426) on the device, as thin::OpenBatchVerifier:
+// new opens (avrf_pedersen_batch_open), push / push_many hand items over as they arrive (avrf_pedersen_batch_push), verify is the MSM
+// that is left (avrf_pedersen_batch_run) and borrows.
+class OpenBatchVerifier {
+ public:
+  explicit OpenBatchVerifier(const Suite &su, size_t items_hint = 0, size_t pairs_hint = 0, size_t ad_bytes_hint = 0) : su_(su) {   // :316-318
+    if (avrf_pedersen_batch_open(su_.ctx(), items_hint, pairs_hint, ad_bytes_hint) != AVRF_OK) throw std::invalid_argument("avrf: pedersen batch open");
+  }
+  struct Item { std::vector<VrfIo> ios; std::string ad; Proof proof; };
+  void push(const std::vector<VrfIo> &ios, const std::string &ad, const Proof &proof) { push_many({Item{ios, ad, proof}}); }   // :324-326
+  // several items, in their order, as ONE chunk: one set of copies and one prepare launch
+  void push_many(const std::vector<Item> &items) {
+    std::vector<uint8_t> proofs; detail::Packed p;
+    for (const Item &it : items) { p.push(it.ios, it.ad); uint8_t pr[256]; to_wire(it.proof, pr); proofs.insert(proofs.end(), pr, pr + 256); }
+    if (avrf_pedersen_batch_push(su_.ctx(), items.size(), p.ios.data(), p.io_counts.data(), p.ads.data(), p.ad_lens.data(), proofs.data()) != AVRF_OK)
+      throw std::invalid_argument("avrf: pedersen batch push");
+  }
+  Status verify() const { return avrf_pedersen_batch_run(su_.ctx()); }                                       // :341-426
+  size_t len() const { return avrf_batch_pushed(su_.ctx(), nullptr); }
+  // One verdict per segment of what was pushed so far (avrf_pedersen_batch_run_segments): seg_items[v] consecutive items each, summing to len()
+  std::vector<Status> verify_segments(const std::vector<uint32_t> &seg_items) const {
+    std::vector<int32_t> st(seg_items.size() + 1);
+    if (avrf_pedersen_batch_run_segments(su_.ctx(), seg_items.size(), seg_items.data(), st.data()) != AVRF_OK) throw std::invalid_argument("avrf: pedersen open verify segments");
+    return std::vector<Status>(st.begin(), st.begin() + seg_items.size());
+  }
+
+ private:
+  const Suite &su_;
 };
 // pedersen::BatchVerifier over a table of shared inputs (avrf_pedersen_batch_stage_shared): push() keeps one row per byte-wise distinct
 // input and an index per I/O pair, so that an MSM of 4 n + T + 2 terms (shared_n_terms) answers what BatchVerifier::verify answers for
