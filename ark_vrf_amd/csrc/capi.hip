@@ -33,8 +33,8 @@ double now_us() {
 }  // namespace avrf
 
 // A run opened by avrf_batch_run_begin owns the context's stream, staged buffers and MSM workspace until avrf_batch_run_end
-// (or an error) closes it: every other entry point that touches them refuses with AVRF_ERR_BAD_ARG meanwhile (include/avrf.h).
-static inline bool ctx_busy(const avrf_ctx *c) { return c->run_phase != 0; }
+// (or an error) closes it: every other entry point that touches them refuses with AVRF_ERR_BAD_ARG meanwhile (include/avrf.h;
+// ctx_busy, capi_internal.h).
 
 // fixed-base tables for the provers: built once per context, on the context's stream
 static int ensure_fixed(avrf_ctx *c) {
@@ -286,7 +286,7 @@ int avrf_g1_msm_segments(avrf_ctx *c, size_t n_seg, size_t L, const uint8_t *bas
 
 }  // extern "C"
 namespace avrf {
-// HOST_WEIGHTS is exactly "the transcript is not the counter-mode SHA-512 one" (batch_seed squeezes a sponge's or SHA-256's stream)
+// HOST_WEIGHTS is exactly "the transcript is not the counter-mode SHA-512 one" (run_hash squeezes a sponge's or SHA-256's stream)
 template <class... S> constexpr bool host_weights_defined = ((S::HOST_WEIGHTS == (S::XOF_SHAKE || S::TR_SHA256)) && ...);
 static_assert(host_weights_defined<SuiteBandersnatch, SuiteBabyJubJub, SuiteJubJub, SuiteEd25519, SuiteBandersnatchSW, SuiteBandersnatchShake, SuiteTesting, SuiteSecp256r1>);
 bool suite_host_weights(int suite) { return with_suite(suite, [&](auto tag) { using S = typename decltype(tag)::type; return (bool)S::HOST_WEIGHTS; }); }
@@ -335,7 +335,7 @@ static bool prefix_sums(const uint32_t *counts, size_t n, uint32_t *off, uint64_
 // with their limits, offsets and `ads` copied -- and between them the I/O pairs when they come as x || y.  n == 0 stages the empty batch.
 static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8_t *ios, bool ios_xy, const uint32_t *io_counts,
                       const uint8_t *ads, const uint32_t *ad_lens) {
-  if (!c || c->run_phase || !args_ok) return AVRF_ERR_BAD_ARG;   // (a run in flight owns the staged buffers)
+  if (!c || ctx_busy(c) || !args_ok) return AVRF_ERR_BAD_ARG;    // (a run in flight owns the staged buffers)
   if (n && (!io_counts || !ad_lens)) return AVRF_ERR_BAD_ARG;
   if (n > 0x0fffffffULL) return AVRF_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
@@ -362,7 +362,7 @@ static int stage_open(avrf_ctx *c, int kind, size_t n, bool args_ok, const uint8
 // The close every flavour shares for a batch VERIFIER: the host copy of the responses (item 0's at `resp`, `stride` apart) for a sponge
 // transcript, which absorbs them on the host (counter-mode ones hash the device's records); the term count; the buffers the run writes.
 // n0 (a chunk appended to an open batch): `resp` is item n0's; the buffers are the open batch's, grown before (open_grow), and the
-// lane's term arrays are left to the run (batch_launch), which knows the final count.
+// lane's term arrays are left to the run (run_launch), which knows the final count.
 static int stage_verifier(avrf_ctx *c, int kind, const uint8_t *resp, size_t stride, bool append = false, size_t n0 = 0) {
   const size_t n = c->n, rsz = kind_facts(kind).resp;
   if (suite_host_weights(c->suite)) {
@@ -400,7 +400,7 @@ bool shared_indices_ok(const BatchSource &s) {
 //                 What decodes is canonical, so the plan's range flag stays clear.
 //   A Pedersen source over a table has no keys: its references are the tot_io inputs alone (nk = 0 below; thin_shared.h "Pedersen").
 // A wire point that fails raises the decode flag (d_status -> h_flags[2]): AVRF_INVALID_DATA here, before any equation (as the
-// reference's deserialisation would), or from batch_collect when nothing was waited for (wire_pending).  What a shared staging
+// reference's deserialisation would), or from run_collect when nothing was waited for (wire_pending).  What a shared staging
 // leaves is reused by every run of it (resident reruns, the pool's resubmission without host sources).
 static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
   const KindFacts &k = kind_facts(s.kind);
@@ -418,7 +418,7 @@ static int stage_payload(avrf_ctx *c, const BatchSource &s, bool wait) {
   if (s.wire) {
     HIP_TRY(c->d_misc.ensure(w_pks + w_ios + w_pr + 64)); HIP_TRY(c->d_status.ensure(64));
     // the decode flag: d_status word 0, cleared per staging; a chunk of an open batch ORs into the BATCH's flag instead, d_flags word 2,
-    // cleared at open alone -- d_status is reused for the per-item statuses of a segmented run's attribution pass (seg_collect)
+    // cleared at open alone -- d_status is reused for the per-item statuses of a segmented run's attribution pass (run_collect)
     dw = c->d_misc.as<uint8_t>(); d_flag = s.append ? c->d_flags.as<uint32_t>() + 2 : c->d_status.as<uint32_t>();
   }
   auto up = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
@@ -614,11 +614,11 @@ class WeightHashService {
 };
 }  // namespace
 
-// shared tail of both batch verifiers in three phases (run_phase): 1 = validation + prepare kernel + copies back enqueued,
-// 2 = weight transcript hashed on the host and terms + MSM enqueued, 0 = idle.  batch_run walks all three; the
-// avrf_batch_run_begin / _hash / _end entry points let one host thread keep several contexts in flight (hash one context's
-// transcript while the others' kernels run) instead of parking a thread per context; the pool's workers (pool.hip) call the
-// pieces themselves (batch_collect / batch_seed / batch_launch) and hash several contexts' transcripts together.
+// The run of a staged batch, for both batch verifiers and both shapes -- the whole batch under one verdict, or n_seg groups with a
+// verdict each (capi_internal.h: the record c->run and the phases run_begin .. run_end).  The run calls of the C ABI walk the phases:
+// batch_run and run_segments wait between them; avrf_batch_run_begin / _hash / _end let one host thread keep several contexts in
+// flight (hash one context's transcript while the others' kernels run) instead of parking a thread per context; the pool's workers
+// (pool.hip) call the phases themselves and hash several contexts' transcripts together (run_messages / run_job / run_seed).
 }  // extern "C"
 namespace avrf {
 static Seed64 seed_of(const uint8_t digest[64]) {
@@ -686,56 +686,43 @@ static int open_poll(avrf_ctx *c, bool all) {
   return open_wire_failed(c);
 }
 
-int batch_begin(avrf_ctx *c, int kind, bool segmented) {
-  if (!c || c->staged_kind != kind || c->run_phase != 0) return AVRF_ERR_BAD_ARG;
-  if (c->n == 0) { c->run_phase = 1; return AVRF_OK; }                 // src/thin.rs:262-264, src/pedersen.rs:343-345
-  if (!c->n_terms) return AVRF_ERR_BAD_ARG;
-  HIP_TRY(hipSetDevice(c->device));
-  c->run_t0 = now_us();
-  // an open batch: every push has enqueued its chunk's validation, prepare kernel and copies back already
-  if (ctx_open(c)) { c->run_begin_us = 0; c->run_phase = 1; return AVRF_OK; }
-  const size_t n = c->n;
+// a run with nothing to do -- no items, or no segments: every verdict is Ok and there is no device work at all
+static bool run_nothing(const avrf_ctx *c) { return !c->n || (c->run.shape.segmented && !c->run.shape.n_seg); }
+
+// The ONE place the prepare step is enqueued: over the staged items from `first` on (their pairs from a0 on) on c->stream, nothing
+// waited for and no run opened.  The flag word restarts (reset; items_only as reset_flags) or keeps what an open batch's earlier chunks
+// raised; validation; the kind's prepare kernel, which writes the transcript's records where the suite hashes them; the copies back:
+// records into h_msg behind the prefix (sponge / SHA-256 suites: challenges into h_c) -- or, for avrf_*_batch_challenges, the challenges
+// to challenges_out and no records at all -- and the flag word.
+struct Prepare { bool reset = true, items_only = false, rows_stay = false; uint8_t *challenges_out = nullptr; };
+static int enqueue_prepare(avrf_ctx *c, int kind, size_t first, size_t a0, const Prepare &p) {
+  const size_t n = c->n, count = n - first, recsz = kind_facts(kind).record();
+  const bool records = !p.challenges_out && !suite_host_weights(c->suite);
   BatchDev b = batch_of(c);
-  HIP_TRY(reset_flags(c, segmented));
-  validate_staged(c, kind, nullptr);
-  const bool host_weights = suite_host_weights(c->suite);
+  b.first = (uint32_t)first;
+  if (p.reset) HIP_TRY(reset_flags(c, p.items_only));
+  validate_staged(c, kind, nullptr, first, a0);
   // the weight transcript's message, prefix || records: the prepare kernel writes the records, one copy brings them back
-  const size_t recsz = kind_facts(kind).record();
   uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
-  if (!host_weights) {
-    HIP_TRY(c->d_rec.ensure(n * recsz)); HIP_TRY(c->h_msg.ensure(pl + n * recsz));
+  if (records) {
+    HIP_TRY(c->d_rec.ensure(n * recsz)); HIP_TRY(c->h_msg.ensure(pl + n * recsz));   // (an open batch's have grown before: open_grow)
     b.records = c->d_rec.as<uint8_t>();
   }
-  launch_prepare(c, kind, b, c->n_shared && !(segmented && !c->seg.merged));
-  if (!host_weights) {
+  launch_prepare(c, kind, b, p.rows_stay);
+  if (records) {
     memcpy(c->h_msg.p, prefix, pl);
-    HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl, c->d_rec.p, n * recsz, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl + first * recsz, c->d_rec.as<uint8_t>() + first * recsz, count * recsz, hipMemcpyDeviceToHost, c->stream));
     c->h_msg_len = pl + n * recsz;
-  } else HIP_TRY(hipMemcpyAsync(c->h_c.p, c->d_c.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+  } else
+    HIP_TRY(hipMemcpyAsync(p.challenges_out ? p.challenges_out : c->h_c.as<uint8_t>() + 16 * first, c->d_c.as<uint8_t>() + 16 * first, count * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
-  c->run_begin_us = now_us() - c->run_t0;
-  c->run_phase = 1;
   return AVRF_OK;
 }
 
-// the prepare kernel and the copies back have completed (the caller waited for c->stream or for an event behind them)
-int batch_collect(avrf_ctx *c, int kind) {
-  if (!c || c->staged_kind != kind || c->run_phase != 1) return AVRF_ERR_BAD_ARG;
-  if (c->n && ctx_open(c)) if (int e = open_wire_failed(c)) { c->run_phase = 0; return e; }   // (before the checks of items that never decoded)
-  if (c->n && *c->h_flags.as<uint32_t>()) { c->run_phase = 0; return AVRF_INVALID_DATA; }   // src/thin.rs:266-271, src/pedersen.rs:348-353
-  if (c->wire_pending) {                                               // staged from wire bytes without waiting (ctx_stage): a point that failed to decode / validate
-    c->wire_pending = false;
-    if (c->n && c->h_flags.as<uint32_t>()[2]) { c->run_phase = 0; c->staged_kind = 0; return AVRF_INVALID_DATA; }
-  }
-  return AVRF_OK;
-}
-
-// The weight transcript of the staged batch on the calling thread.  Counter-mode transcripts: SHA-512 of prefix || records ->
-// digest.  Sponge / SHA-256 transcripts (Shake128Transcript: the weights are the sponge's OUTPUT STREAM, 16 bytes per item, 32 for
-// Pedersen -- sequential, so the host squeezes it and the terms kernel reads it from HBM instead of deriving block j / 4 from a
-// seed; HashTranscript<Sha256> of the test suite takes the same route): the stream goes to c->h_weights and the digest is not used.
-// squeeze_weights is that transcript over `items` staged items from `first` -- one BatchVerifier's: absorbed from h_c / h_resp at `first`,
-// squeezed into h_weights (sized by the caller) at `first`; the segmented run calls it once per segment.
+// The weight transcript of a sponge / SHA-256 suite (Shake128Transcript: the weights are the sponge's OUTPUT STREAM, 16 bytes per item,
+// 32 for Pedersen -- sequential, so the host squeezes it and the terms kernel reads it from HBM instead of deriving block j / 4 from a
+// seed; HashTranscript<Sha256> of the test suite takes the same route) over `items` staged items from `first` -- one BatchVerifier's:
+// absorbed from h_c / h_resp at `first`, squeezed into h_weights (sized by run_collect) at `first`; a segmented run calls it once per group.
 static void squeeze_weights(avrf_ctx *c, int kind, size_t first, size_t items) {
   const KindFacts &k = kind_facts(kind);
   uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
@@ -746,82 +733,14 @@ static void squeeze_weights(avrf_ctx *c, int kind, size_t first, size_t items) {
     h.squeeze_copy(c->h_weights.data() + k.weight * first, items * k.weight);
   });
 }
-int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]) {
-  const size_t n = c->n;
-  memset(digest, 0, 64);
-  if (!n) return AVRF_OK;
-  if (ctx_open(c)) {
-    // (the caller has waited for c->stream) what no push has absorbed yet, then a CLONE finalised: verify(&self) borrows, the batch
-    // stays open and its transcript goes on (src/thin.rs:257)
-    if (int e = open_poll(c, /*all=*/true)) return e;
-    const WeightStream fin = c->open.ws.clone();
-    if (suite_host_weights(c->suite)) { c->h_weights.resize(n * kind_facts(kind).weight); fin.squeeze(c->h_weights.data(), c->h_weights.size()); }
-    else fin.digest(digest);
-    return AVRF_OK;
-  }
-  if (suite_host_weights(c->suite)) {
-    c->h_weights.resize(n * kind_facts(kind).weight);
-    squeeze_weights(c, kind, 0, n);
-    return AVRF_OK;
-  }
-  WeightJob job = WeightJob::whole(c->h_msg.as<uint8_t>(), c->h_msg_len);
-  WeightHashService &svc = WeightHashService::get();
-  if (svc.enabled()) svc.run(job); else weight_digest_scalar(job);
-  memcpy(digest, job.digest, 64);
-  return AVRF_OK;
-}
-
-int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]) {
-  if (!c || c->staged_kind != kind || c->run_phase != 1) return AVRF_ERR_BAD_ARG;
-  if (c->n == 0) { c->run_phase = 2; return AVRF_OK; }
-  c->run_phase = 0;                                                    // an error below leaves the context idle
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = c->n;
-  BatchDev b = batch_of(c);
-  if (c->unit_weights) {                                               // (Thin only) w_j = 1: the sum IS the item's own equation
-    c->h_weights.assign(n * 16, 0);
-    for (size_t j = 0; j < n; j++) c->h_weights[16 * j] = 1;
-  }
-  if (c->unit_weights || suite_host_weights(c->suite)) {               // the weights as a stream in HBM; else the terms kernel derives them from the seed
-    const size_t wbytes = n * kind_facts(kind).weight;
-    HIP_TRY(c->d_weights.ensure(wbytes));
-    HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), wbytes, hipMemcpyHostToDevice, c->stream));
-    b.weights = c->d_weights.as<uint8_t>();
-  } else b.records = c->d_rec.as<uint8_t>();
-  if (int e = ensure_terms(c)) return e;
-  const double t2 = now_us();
-  launch_terms(c, kind, b, seed_of(digest), 0, c->L->d_scalars.as<uint32_t>());
-  const double t3 = now_us();
-  if (int e = msm_guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->chain(), c->stream); })) return e;
-  c->timing[3] = t3 - t2;
-  c->run_msm_us = now_us() - t3;
-  c->run_phase = 2;
-  return AVRF_OK;
-}
-
-int batch_end(avrf_ctx *c, int kind) {
-  if (!c || c->staged_kind != kind || c->run_phase != 2) return AVRF_ERR_BAD_ARG;
-  c->run_phase = 0;
-  if (c->n == 0) return AVRF_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const double t3 = now_us();
-  HostExt r;
-  if (int e = msm_guarded([&] { return msm_te_finish(c->suite, c->L->ws, c->chain(), c->stream, &r); })) return e;
-  double t4 = now_us();
-  int st = point_is_identity(c, r) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
-  double t5 = now_us();
-  c->timing[4] = c->run_msm_us + (t4 - t3); c->timing[5] = t5 - t4;
-  c->timing[0] = c->timing[1] + c->timing[2] + c->timing[3] + c->timing[4] + c->timing[5];   // time spent IN the three calls
-  return st;
-}
 }  // namespace avrf
 
 // ---------------------------------------------------------------- open batches: BatchVerifier::new / push (src/thin.rs:199-243, src/pedersen.rs:316-326)
 // A push copies its chunk to page-locked memory, restates stage_open for an append (checks, prefix sums continued from the totals,
 // only the chunk's offsets up), hands the chunk to stage_payload as a source with a base, and enqueues the chunk's validation, the
-// prepare kernel over [n0, n0 + n) and the copy back of that range's records -- all on c->stream, nothing waited for.  The run
-// phases above find that work done (batch_begin), read the accumulated flags (batch_collect) and finalise a clone of the running
-// transcript (batch_seed).
+// prepare kernel over [n0, n0 + n) and the copy back of that range's records (enqueue_prepare) -- all on c->stream, nothing waited
+// for.  The run phases find that work done (run_begin), read the accumulated flags (run_collect) and finalise a clone of the running
+// transcript (run_hash).
 
 // One buffer of the open batch at `bytes` or more with its first `used` bytes kept: device memory copied on c->stream, the old buffer
 // handed to `old` (the caller waits ONCE for all the copies before the old buffers go), page-locked host memory copied here.
@@ -964,19 +883,8 @@ static int batch_push(avrf_ctx *c, BatchSource s) {
   s.pks = k.pk ? p_pks : nullptr; s.ios = p_ios; s.ads = p_ads; s.proofs = p_pr;
   s.append = true; s.n0 = n0; s.a0 = a0;
   if (int e = stage_payload(c, s, /*wait=*/false)) return e;
-  validate_staged(c, s.kind, nullptr, n0, a0);
-  const bool host_weights = suite_host_weights(c->suite);
-  const size_t recsz = k.record();
-  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
-  BatchDev bd = batch_of(c);
-  bd.first = (uint32_t)n0;
-  if (!host_weights) bd.records = c->d_rec.as<uint8_t>();
-  launch_prepare(c, s.kind, bd, false);
-  if (!host_weights) {
-    HIP_TRY(hipMemcpyAsync(c->h_msg.as<uint8_t>() + pl + n0 * recsz, c->d_rec.as<uint8_t>() + n0 * recsz, n * recsz, hipMemcpyDeviceToHost, c->stream));
-    c->h_msg_len = pl + (n0 + n) * recsz;
-  } else HIP_TRY(hipMemcpyAsync(c->h_c.as<uint8_t>() + 16 * n0, c->d_c.as<uint8_t>() + 16 * n0, n * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+  Prepare chunk; chunk.reset = false;                                   // (the flag word is the batch's, OR-ed across its chunks)
+  if (int e = enqueue_prepare(c, s.kind, n0, a0, chunk)) return e;
   avrf_ctx::OpenBatch::Chunk ch; ch.n0 = n0; ch.n = n;
   HIP_TRY(ch.done.create(hipEventDisableTiming));
   HIP_TRY(hipEventRecord(ch.done, c->stream));
@@ -1021,41 +929,54 @@ size_t avrf_batch_pushed(const avrf_ctx *c, size_t out[3]) {
 }  // extern "C"
 extern "C" {
 
+// between run_begin and run_collect: c->stream has drained (and_last_error: and nothing enqueued on it failed); a failure closes the run
+static int run_wait(avrf_ctx *c, bool and_last_error) {
+  if (hipStreamSynchronize(c->stream) == hipSuccess && (!and_last_error || hipGetLastError() == hipSuccess)) return AVRF_OK;
+  (void)hipGetLastError(); run_close(c);
+  return AVRF_ERR_NO_DEVICE;
+}
+
 // the second of the three calls: wait for the prepare kernel, hash on the calling thread, enqueue terms + MSM
 static int batch_hash(avrf_ctx *c, int kind) {
-  if (!c || c->staged_kind != kind || c->run_phase != 1) return AVRF_ERR_BAD_ARG;
-  if (c->n == 0) { c->run_phase = 2; return AVRF_OK; }
-  HIP_TRY(hipSetDevice(c->device));
-  const double tw = now_us();
-  if (hipStreamSynchronize(c->stream) != hipSuccess) { c->run_phase = 0; (void)hipGetLastError(); return AVRF_ERR_NO_DEVICE; }
-  const double t1 = now_us();
-  if (int e = batch_collect(c, kind)) return e;
-  uint8_t digest[64];
-  if (int e = batch_seed(c, kind, digest)) { c->run_phase = 0; return e; }
-  const double t2 = now_us();
-  c->timing[1] = c->run_begin_us + (t1 - tw); c->timing[2] = t2 - t1;
-  return batch_launch(c, kind, digest);
+  if (!c || c->staged_kind != kind || c->run.phase != RunPhase::Begun) return AVRF_ERR_BAD_ARG;
+  double tw = 0, t1 = 0;
+  if (!run_nothing(c)) {
+    HIP_TRY(hipSetDevice(c->device));
+    tw = now_us();
+    if (int e = run_wait(c, false)) return e;
+    t1 = now_us();
+  }
+  if (int e = run_collect(c, kind)) return e;
+  if (int e = run_hash(c, kind, /*spread=*/false)) return e;
+  if (!run_nothing(c)) { c->timing[1] = c->run.begin_us + (t1 - tw); c->timing[2] = now_us() - t1; }
+  return run_launch(c, kind);
+}
+// the third: the run's one status is the call's
+static int batch_end(avrf_ctx *c, int kind) {
+  int32_t st = AVRF_OK;
+  const int e = run_end(c, kind, &st);
+  return e ? e : (int)st;
 }
 
 static int batch_run(avrf_ctx *c, int kind) {
-  if (int e = batch_begin(c, kind)) return e;
+  if (int e = run_begin(c, kind)) return e;
   if (int e = batch_hash(c, kind)) return e;
   return batch_end(c, kind);
 }
 
 int avrf_thin_batch_run(avrf_ctx *c) { return batch_run(c, Thin); }
 int avrf_pedersen_batch_run(avrf_ctx *c) { return batch_run(c, Pedersen); }
-// (defensive: a run can only be open on a staged batch -- every entry point that would un-stage it is refused while
-// run_phase != 0 -- but should the two ever disagree the run is closed rather than leaving the context refusing every call)
+// (defensive: a run can only be open on a staged batch -- every entry point that would un-stage it is refused while the context is
+// busy -- but should the two ever disagree the run is closed rather than leaving the context refusing every call)
 static int run_call(avrf_ctx *c, int (*phase)(avrf_ctx *, int)) {
   if (!c) return AVRF_ERR_BAD_ARG;
   if (!c->staged_kind) {
-    if (c->run_phase) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); c->run_phase = 0; c->chain().disarm(); }
+    if (ctx_busy(c)) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); run_close(c); c->chain().disarm(); }
     return AVRF_ERR_BAD_ARG;
   }
   return phase(c, c->staged_kind);
 }
-int avrf_batch_run_begin(avrf_ctx *c) { return run_call(c, [](avrf_ctx *ctx, int kind) { return batch_begin(ctx, kind); }); }
+int avrf_batch_run_begin(avrf_ctx *c) { return run_call(c, [](avrf_ctx *ctx, int kind) { return run_begin(ctx, kind); }); }
 int avrf_batch_run_hash(avrf_ctx *c) { return run_call(c, batch_hash); }
 int avrf_batch_run_end(avrf_ctx *c) { return run_call(c, batch_end); }
 
@@ -1178,7 +1099,7 @@ int avrf_pedersen_shared_segments_layout(size_t n, size_t n_shared, size_t n_seg
 struct SegArrays { DevBuf &scalars, &pre; };
 static SegArrays seg_arrays(avrf_ctx *c) { return c->lane_owner ? SegArrays{c->d_seg_scalars, c->d_seg_pre} : SegArrays{c->L->d_scalars, c->L->d_pre}; }
 static int seg_ensure(avrf_ctx *c, int kind) {
-  const avrf_ctx::SegRun &r = c->seg; const SegArrays a = seg_arrays(c);
+  const RunShape &r = c->run.shape; const SegArrays a = seg_arrays(c);
   // (scratch per item: Thin's w s z0, Pedersen's u s and u sb)
   HIP_TRY(a.scalars.ensure(r.padded * 32)); HIP_TRY(a.pre.ensure(r.padded * sizeof(te_pre_raw))); HIP_TRY(c->L->d_seg_wsz.ensure(c->n * (kind == Thin ? 32 : 64)));
   HIP_TRY(c->L->d_seg_off.ensure((r.n_seg + 1) * 4)); HIP_TRY(c->L->d_seg_seeds.ensure(r.n_seg * sizeof(Seed64)));
@@ -1190,7 +1111,7 @@ static int seg_ensure(avrf_ctx *c, int kind) {
 }
 static void launch_seg_terms(avrf_ctx *c, int kind, const BatchDev &b, size_t n_seg, size_t L) {
   const uint32_t *off = c->L->d_seg_off.as<uint32_t>(); const Seed64 *seeds = c->L->d_seg_seeds.as<Seed64>(); const SegArrays a = seg_arrays(c);
-  if (c->seg.merged) {
+  if (c->run.shape.merged) {
     const SharedPlan p = shared_seg_plan_view(c->d_seg_plan.as<uint32_t>(), c->d_table_rows.as<te_pre_raw>(), n_seg, c->n_shared, c->n_contrib);
     if (kind == Thin) AVRF_SHARED(c->suite, thin_seg_terms(b, off, (uint32_t)n_seg, (uint32_t)L, seeds, c->d_c.as<uint32_t>(), c->d_z.as<uint32_t>(), p, c->L->d_shared.as<uint32_t>(),
                                                            c->L->d_seg_wsz.as<uint32_t>(), a.scalars.as<uint32_t>(), a.pre.as<te_pre_raw>(), c->stream));
@@ -1209,185 +1130,250 @@ static void launch_seg_item_flags(avrf_ctx *c, int kind, const BatchDev &b) {
 }
 
 namespace avrf {
-// h_seg_up: the item offsets, then (64-byte aligned) the seeds, then (the merged layout) each segment's row0
+// BatchRun::h_up: the item offsets, then (64-byte aligned) the seeds, then (the merged layout) each segment's row0
 static size_t seg_up_seeds_at(size_t n_seg) { return ((n_seg + 1) * 4 + 63) / 64 * 64; }
 static size_t seg_up_row0_at(size_t n_seg) { return seg_up_seeds_at(n_seg) + n_seg * sizeof(Seed64); }
-static bool seg_nothing(const avrf_ctx *c) { return !c->seg.n_seg || !c->n; }   // every (empty) segment is Ok: no device work at all
 
-int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, bool shared_ok) {
-  if (!c || c->run_phase != 0 || c->staged_kind != kind || (c->n_shared && !(shared_ok && c->lane_owner))) return AVRF_ERR_BAD_ARG;
-  // (the layout goes to locals first: a refusal leaves the last run's description, and the context, as they were)
-  std::vector<uint32_t> off, row0; uint64_t lay[5];
-  if (int e = seg_layout(kind, c->n, c->n_shared, n_seg, seg_items, c->h_io.as<uint32_t>(), &off, &row0, lay)) return e;
-  avrf_ctx::SegRun &r = c->seg;
-  r.off.swap(off); r.row0.swap(row0);
-  r.n_seg = n_seg; r.L = (size_t)lay[0]; r.padded = (size_t)lay[1]; r.merged = lay[4] != 0; r.item_status.clear();
-  if (seg_nothing(c)) { c->run_phase = 3; return AVRF_OK; }
+int run_begin(avrf_ctx *c, int kind, const RunRequest &rq) {
+  if (!c || c->staged_kind != kind || ctx_busy(c)) return AVRF_ERR_BAD_ARG;
+  if (rq.segmented && c->n_shared && !(rq.shared_ok && c->lane_owner)) return AVRF_ERR_BAD_ARG;
+  // (the layout goes to a local first: a refusal leaves the last segmented run's description, and the context, as they were)
+  RunShape sh; sh.segmented = rq.segmented;
+  if (rq.segmented) {
+    uint64_t lay[5];
+    if (int e = seg_layout(kind, c->n, c->n_shared, rq.n_seg, rq.seg_items, c->h_io.as<uint32_t>(), &sh.off, &sh.row0, lay)) return e;
+    sh.n_seg = rq.n_seg; sh.L = (size_t)lay[0]; sh.padded = (size_t)lay[1]; sh.merged = lay[4] != 0;
+  }
+  if (c->n && !c->n_terms) return AVRF_ERR_BAD_ARG;
+  BatchRun &r = c->run;
+  r.shape = std::move(sh); r.item_status.clear(); r.unit_weights = rq.unit_weights; memset(r.digest, 0, 64);
+  if (run_nothing(c)) { r.phase = RunPhase::Begun; return AVRF_OK; }   // src/thin.rs:262-264, src/pedersen.rs:343-345
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(c->h_seg_up.ensure(seg_up_row0_at(n_seg) + n_seg * 4));
-  memcpy(c->h_seg_up.p, r.off.data(), (n_seg + 1) * 4);
-  if (r.merged) memcpy(c->h_seg_up.as<uint8_t>() + seg_up_row0_at(n_seg), r.row0.data(), n_seg * 4);
-  if (c->lane_owner) if (int e = seg_ensure(c, kind)) return e;        // (a pool slot has no lane yet: seg_launch sizes the lane's arrays)
-  if (c->n_shared) c->chal_gen = 0;                                    // (what avrf_*_batch_challenges left in d_c / d_z is overwritten, for Pedersen in another form)
-  // prepare once, for all segments: the prepare kernels know nothing about batches, and their records are contiguous per item
-  if (int e = batch_begin(c, kind, /*segmented=*/true)) return e;
-  c->run_phase = 3;
+  if (rq.segmented) {
+    const size_t n_seg = r.shape.n_seg;
+    HIP_TRY(r.h_up.ensure(seg_up_row0_at(n_seg) + n_seg * 4));
+    memcpy(r.h_up.p, r.shape.off.data(), (n_seg + 1) * 4);
+    if (r.shape.merged) memcpy(r.h_up.as<uint8_t>() + seg_up_row0_at(n_seg), r.shape.row0.data(), n_seg * 4);
+    if (c->lane_owner) if (int e = seg_ensure(c, kind)) return e;      // (a pool slot has no lane yet: run_launch sizes the lane's arrays)
+    if (c->n_shared) c->chal_gen = 0;                                  // (what avrf_*_batch_challenges left in d_c / d_z is overwritten, for Pedersen in another form)
+  }
+  const double t0 = now_us();
+  r.begin_us = 0;
+  // prepare once, for all segments: the prepare kernels know nothing about batches, and their records are contiguous per item.
+  // An open batch: every push has enqueued its chunk's validation, prepare kernel and copies back already
+  if (!ctx_open(c)) {
+    Prepare whole; whole.items_only = rq.segmented; whole.rows_stay = c->n_shared && !(rq.segmented && !r.shape.merged);
+    if (int e = enqueue_prepare(c, kind, 0, 0, whole)) return e;
+    r.begin_us = now_us() - t0;
+  }
+  r.phase = RunPhase::Begun;
   return AVRF_OK;
 }
 
 // the prepare kernel and the copies back have completed (the caller waited for c->stream or for an event behind them)
-int seg_collect(avrf_ctx *c, int kind) {
-  if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
-  if (seg_nothing(c)) return AVRF_OK;
-  c->run_phase = 0;                                                    // an error below leaves the context idle
-  if (ctx_open(c)) if (int e = open_wire_failed(c)) return e;          // an open batch's sticky decode flag, as batch_collect
-  if (c->wire_pending) {                                               // as batch_collect: a wire point that failed to decode / validate is the whole job's status
+int run_collect(avrf_ctx *c, int kind) {
+  if (!c || c->staged_kind != kind || c->run.phase != RunPhase::Begun) return AVRF_ERR_BAD_ARG;
+  if (run_nothing(c)) return AVRF_OK;
+  BatchRun &r = c->run;
+  r.phase = RunPhase::Idle;                                            // an error below leaves the context idle
+  // a wire point that failed to decode / validate is the whole run's status, before the checks of items that never decoded: the
+  // sticky flag of an open batch's chunks, or of a staging that was not waited for (ctx_stage); the batch is then gone
+  if (ctx_open(c)) if (int e = open_wire_failed(c)) return e;
+  if (c->wire_pending) {
     c->wire_pending = false;
     if (c->h_flags.as<uint32_t>()[2]) { c->staged_kind = 0; return AVRF_INVALID_DATA; }
   }
-  // The flag word is the batch's.  Only when it is set: which items raised it -- the prepare kernel's checks again, per item, and
-  // the validation with a status per item (the clean case pays nothing).  This rare path WAITS for the stream it runs on, c->stream:
-  // a pool worker sits here for one prepare-sized kernel on its ingest stream, where only its own stagings queue.
+  // The flag word is the batch's: a refused item refuses a whole-batch run (src/thin.rs:266-271, src/pedersen.rs:348-353).  A segmented
+  // run finds out which items raised it -- the prepare kernel's checks again, per item, and the validation with a status per item
+  // (the clean case pays nothing).  This rare path WAITS for the stream it runs on, c->stream: a pool worker sits here for one
+  // prepare-sized kernel on its ingest stream, where only its own stagings queue.
   if (*c->h_flags.as<uint32_t>()) {
+    if (!r.shape.segmented) return AVRF_INVALID_DATA;
     const size_t n = c->n;
     HIP_TRY(hipSetDevice(c->device));
-    c->seg.item_status.resize(n);
+    r.item_status.resize(n);
     HIP_TRY(c->d_status.ensure(n * 4));
     HIP_TRY(hipMemsetAsync(c->d_status.p, 0, n * 4, c->stream));
     launch_seg_item_flags(c, kind, batch_of(c));
     validate_staged(c, kind, c->d_status.as<int32_t>());
-    HIP_TRY(hipMemcpyAsync(c->seg.item_status.data(), c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.item_status.data(), c->d_status.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipGetLastError());
   }
-  if (!suite_host_weights(c->suite)) {
+  // room for what the hash writes: the weight stream of a sponge / SHA-256 suite, the groups' messages of a counter-mode one
+  if (suite_host_weights(c->suite)) c->h_weights.resize(c->n * kind_facts(kind).weight);
+  else if (r.shape.segmented) {
     uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix);
-    c->h_seg_msg.resize(c->seg.n_seg * pl + c->n * kind_facts(kind).record());
-  } else c->h_weights.resize(c->n * kind_facts(kind).weight);
-  c->run_phase = 3;
+    r.h_msg.resize(r.shape.n_seg * pl + c->n * kind_facts(kind).record());
+  }
+  r.phase = RunPhase::Begun;
   return AVRF_OK;
 }
 
-// The weight transcript of segment v, SUITE_ID || 0x50 || its own records (src/thin.rs:274-279, src/pedersen.rs:361-367), built in
-// h_seg_msg at a place of its own (distinct v may be built from different threads) and described for sha512_many; seg_seed takes its digest.
-void seg_job(avrf_ctx *c, int kind, size_t v, WeightJob *job) {
-  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix), recsz = kind_facts(kind).record();
-  const size_t first = c->seg.off[v], items = c->seg.off[v + 1] - first;
-  uint8_t *m = c->h_seg_msg.data() + v * pl + first * recsz;
+size_t run_messages(const avrf_ctx *c) {
+  if (suite_host_weights(c->suite) || run_nothing(c)) return 0;
+  return c->run.shape.segmented ? c->run.shape.n_seg : 1;
+}
+// The weight transcript v of the run, SUITE_ID || 0x50 || its items' records (src/thin.rs:274-279, src/pedersen.rs:361-367), described
+// for sha512_many: the whole batch's where it is, in h_msg; a group's built in BatchRun::h_msg at a place of its own.
+void run_job(avrf_ctx *c, size_t v, WeightJob *job) {
+  BatchRun &r = c->run;
+  if (!r.shape.segmented) { *job = WeightJob::whole(c->h_msg.as<uint8_t>(), c->h_msg_len); return; }
+  uint8_t prefix[64]; const size_t pl = batch_prefix(c->suite, prefix), recsz = kind_facts(c->staged_kind).record();
+  const size_t first = r.shape.off[v], items = r.shape.off[v + 1] - first;
+  uint8_t *m = r.h_msg.data() + v * pl + first * recsz;
   memcpy(m, prefix, pl); memcpy(m + pl, c->h_msg.as<uint8_t>() + pl + first * recsz, items * recsz);
   *job = WeightJob::whole(m, pl + items * recsz);
 }
-void seg_seed(avrf_ctx *c, size_t v, const uint8_t digest[64]) {
-  ((Seed64 *)(c->h_seg_up.as<uint8_t>() + seg_up_seeds_at(c->seg.n_seg)))[v] = seed_of(digest);
+void run_seed(avrf_ctx *c, size_t v, const uint8_t digest[64]) {
+  BatchRun &r = c->run;
+  if (!r.shape.segmented) memcpy(r.digest, digest, 64);
+  else ((Seed64 *)(r.h_up.as<uint8_t>() + seg_up_seeds_at(r.shape.n_seg)))[v] = seed_of(digest);
 }
-int seg_hash(avrf_ctx *c, int kind, bool spread) {
-  if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
-  if (seg_nothing(c)) return AVRF_OK;
-  const size_t n_seg = c->seg.n_seg; const std::vector<uint32_t> &off = c->seg.off;
+int run_hash(avrf_ctx *c, int kind, bool spread) {
+  if (!c || c->staged_kind != kind || c->run.phase != RunPhase::Begun) return AVRF_ERR_BAD_ARG;
+  if (run_nothing(c)) return AVRF_OK;
+  const RunShape &sh = c->run.shape;
+  const bool host_weights = suite_host_weights(c->suite);
   auto each = [&](size_t count, auto fn) { if (spread) parallel_for(count, fn); else for (size_t i = 0; i < count; i++) fn(i); };
-  if (!suite_host_weights(c->suite))
+  if (!sh.segmented && ctx_open(c)) {
+    // (the caller has waited for c->stream) what no push has absorbed yet, then a CLONE finalised: verify(&self) borrows, the batch
+    // stays open and its transcript goes on (src/thin.rs:257)
+    if (int e = open_poll(c, /*all=*/true)) { c->run.phase = RunPhase::Idle; return e; }
+    const WeightStream fin = c->open.ws.clone();
+    if (host_weights) fin.squeeze(c->h_weights.data(), c->h_weights.size()); else fin.digest(c->run.digest);
+  } else if (host_weights) {
+    // sponge / SHA-256 transcripts: the weight stream of the batch, or of every group, squeezed on the host: item j's 16 (Pedersen: 32) bytes at 16 (32) j
+    if (!sh.segmented) squeeze_weights(c, kind, 0, c->n);
+    else each(sh.n_seg, [&](size_t v) { if (sh.off[v + 1] != sh.off[v]) squeeze_weights(c, kind, sh.off[v], sh.off[v + 1] - sh.off[v]); });
+  } else if (!sh.segmented) {
+    // the context's own whole-batch transcript: through the hash service when AVRF_HASH_THREADS enables it
+    WeightJob job; run_job(c, 0, &job);
+    WeightHashService &svc = WeightHashService::get();
+    if (svc.enabled()) svc.run(job); else weight_digest_scalar(job);
+    run_seed(c, 0, job.digest);
+  } else
     // counter-mode transcripts: sixteen messages at a time through the multi-buffer hash; a group builds its messages itself
-    each((n_seg + 15) / 16, [&](size_t g) {
+    each((sh.n_seg + 15) / 16, [&](size_t g) {
       WeightJob jobs[16]; WeightJob *pj[16]; int cnt = 0;
-      for (size_t v = 16 * g; v < n_seg && v < 16 * g + 16; v++, cnt++) { seg_job(c, kind, v, &jobs[cnt]); pj[cnt] = &jobs[cnt]; }
+      for (size_t v = 16 * g; v < sh.n_seg && v < 16 * g + 16; v++, cnt++) { run_job(c, v, &jobs[cnt]); pj[cnt] = &jobs[cnt]; }
       sha512_many(pj, cnt);
-      for (int i = 0; i < cnt; i++) seg_seed(c, 16 * g + i, jobs[i].digest);
+      for (int i = 0; i < cnt; i++) run_seed(c, 16 * g + i, jobs[i].digest);
     });
-  else
-    // sponge / SHA-256 transcripts: every segment's weight stream squeezed on the host, item j's 16 (Pedersen: 32) bytes at 16 (32) j
-    each(n_seg, [&](size_t v) { if (off[v + 1] != off[v]) squeeze_weights(c, kind, off[v], off[v + 1] - off[v]); });
   return AVRF_OK;
 }
 
-int seg_launch(avrf_ctx *c, int kind) {
-  if (!c || c->staged_kind != kind || c->run_phase != 3) return AVRF_ERR_BAD_ARG;
-  if (seg_nothing(c)) { c->run_phase = 4; return AVRF_OK; }
-  c->run_phase = 0;                                                    // an error below leaves the context idle
+int run_launch(avrf_ctx *c, int kind) {
+  if (!c || c->staged_kind != kind || c->run.phase != RunPhase::Begun) return AVRF_ERR_BAD_ARG;
+  BatchRun &r = c->run;
+  if (run_nothing(c)) { r.phase = RunPhase::Launched; return AVRF_OK; }
+  r.phase = RunPhase::Idle;                                            // an error below leaves the context idle
   HIP_TRY(hipSetDevice(c->device));
-  const size_t n_seg = c->seg.n_seg, L = c->seg.L, padded = c->seg.padded;
-  if (int e = seg_ensure(c, kind)) return e;
+  const RunShape &sh = r.shape;
+  const size_t n = c->n, n_seg = sh.n_seg;
+  if (int e = sh.segmented ? seg_ensure(c, kind) : ensure_terms(c)) return e;
   BatchDev b = batch_of(c);
-  if (!suite_host_weights(c->suite))
-    HIP_TRY(hipMemcpyAsync(c->L->d_seg_seeds.p, c->h_seg_up.as<uint8_t>() + seg_up_seeds_at(n_seg), n_seg * sizeof(Seed64), hipMemcpyHostToDevice, c->stream));
-  else {
-    const size_t wbytes = c->n * kind_facts(kind).weight;
+  if (r.unit_weights) {                                                // (Thin only) w_j = 1: the sum IS the item's own equation
+    c->h_weights.assign(n * 16, 0);
+    for (size_t j = 0; j < n; j++) c->h_weights[16 * j] = 1;
+  }
+  if (r.unit_weights || suite_host_weights(c->suite)) {                // the weights as a stream in HBM; else the terms kernel derives them from the seed(s)
+    const size_t wbytes = n * kind_facts(kind).weight;
     HIP_TRY(c->d_weights.ensure(wbytes));
     HIP_TRY(hipMemcpyAsync(c->d_weights.p, c->h_weights.data(), wbytes, hipMemcpyHostToDevice, c->stream));
     b.weights = c->d_weights.as<uint8_t>();
-  }
-  // terms into the padded layout (the padding scalars are zeroed on every run), then all segments' MSMs in ONE chain
-  const SegArrays a = seg_arrays(c);
+  } else if (sh.segmented)
+    HIP_TRY(hipMemcpyAsync(c->L->d_seg_seeds.p, r.h_up.as<uint8_t>() + seg_up_seeds_at(n_seg), n_seg * sizeof(Seed64), hipMemcpyHostToDevice, c->stream));
+  else b.records = c->d_rec.as<uint8_t>();
   const double t2 = now_us();
-  HIP_TRY(hipMemcpyAsync(c->L->d_seg_off.p, c->h_seg_up.p, (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(a.scalars.p, 0, padded * 32, c->stream));
-  if (c->seg.merged) {                                                 // this run's plan: the references sorted by (segment, row)
-    uint32_t *plan = c->d_seg_plan.as<uint32_t>();
-    HIP_TRY(hipMemcpyAsync(shared_seg_plan_row0(plan, n_seg, c->n_shared, c->n_contrib), c->h_seg_up.as<uint8_t>() + seg_up_row0_at(n_seg), n_seg * 4,
-                           hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(shared_seg_plan(c->d_table_idx.as<uint32_t>(), c->d_io_off.as<uint32_t>(), c->L->d_seg_off.as<uint32_t>(), (uint32_t)n_seg, (uint32_t)c->n_shared,
-                            (uint32_t)c->n, (uint32_t)(c->n_contrib - c->tot_io), (uint32_t)c->tot_io, plan, c->stream));
-  }
-  launch_seg_terms(c, kind, b, n_seg, L);
+  if (sh.segmented) {
+    // terms into the padded layout (the padding scalars are zeroed on every run)
+    HIP_TRY(hipMemcpyAsync(c->L->d_seg_off.p, r.h_up.p, (n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(seg_arrays(c).scalars.p, 0, sh.padded * 32, c->stream));
+    if (sh.merged) {                                                   // this run's plan: the references sorted by (segment, row)
+      uint32_t *plan = c->d_seg_plan.as<uint32_t>();
+      HIP_TRY(hipMemcpyAsync(shared_seg_plan_row0(plan, n_seg, c->n_shared, c->n_contrib), r.h_up.as<uint8_t>() + seg_up_row0_at(n_seg), n_seg * 4,
+                             hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(shared_seg_plan(c->d_table_idx.as<uint32_t>(), c->d_io_off.as<uint32_t>(), c->L->d_seg_off.as<uint32_t>(), (uint32_t)n_seg, (uint32_t)c->n_shared,
+                              (uint32_t)c->n, (uint32_t)(c->n_contrib - c->tot_io), (uint32_t)c->tot_io, plan, c->stream));
+    }
+    launch_seg_terms(c, kind, b, n_seg, sh.L);
+  } else launch_terms(c, kind, b, seed_of(r.digest), 0, c->L->d_scalars.as<uint32_t>());
   const double t3 = now_us();
   c->timing[3] = t3 - t2;
-  // a context's own call keeps msm_te_segments' choice (fewer than eight segments: one MSM each, waited for) in seg_end; a chain
-  // that others queue behind -- a pool slot's -- is enqueued here, one chain whatever n_seg is
-  if (!c->lane_owner)
-    if (int e = msm_guarded([&] { return msm_te_segments_enqueue(c->suite, a.pre.as<te_pre_raw>(), a.scalars.as<uint32_t>(), L, n_seg, c->L->ws, c->chain(), c->stream); })) return e;
-  c->run_msm_us = now_us() - t3;
-  c->run_phase = 4;
+  // The MSMs as ONE chain on the lane.  Not for a segmented run of a context of its own lane: that keeps msm_te_segments' choice (fewer
+  // than eight segments: one MSM each, waited for) in run_end; a chain that others queue behind -- a pool slot's -- is enqueued here
+  if (!sh.segmented) {
+    if (int e = msm_guarded([&] { return msm_te_enqueue(c->suite, c->L->d_pre.as<te_pre_raw>(), c->L->d_scalars.as<uint32_t>(), c->n_terms, c->L->ws, c->chain(), c->stream); })) return e;
+  } else if (!c->lane_owner) {
+    const SegArrays a = seg_arrays(c);
+    if (int e = msm_guarded([&] { return msm_te_segments_enqueue(c->suite, a.pre.as<te_pre_raw>(), a.scalars.as<uint32_t>(), sh.L, n_seg, c->L->ws, c->chain(), c->stream); })) return e;
+  }
+  r.msm_us = now_us() - t3;
+  r.phase = RunPhase::Launched;
   return AVRF_OK;
 }
 
-int seg_end(avrf_ctx *c, int kind, int32_t *status_out) {
-  if (!c || c->staged_kind != kind || c->run_phase != 4 || (c->seg.n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
-  c->run_phase = 0;
-  avrf_ctx::SegRun &r = c->seg;
-  for (size_t v = 0; v < r.n_seg; v++) status_out[v] = AVRF_OK;        // what an empty segment keeps (src/thin.rs:262-264, src/pedersen.rs:343-345)
-  if (seg_nothing(c)) return AVRF_OK;
+int run_end(avrf_ctx *c, int kind, int32_t *status_out) {
+  if (!c || c->staged_kind != kind || c->run.phase != RunPhase::Launched) return AVRF_ERR_BAD_ARG;
+  BatchRun &r = c->run;
+  const RunShape &sh = r.shape;
+  const size_t n_out = sh.segmented ? sh.n_seg : 1;
+  if (n_out && !status_out) return AVRF_ERR_BAD_ARG;
+  r.phase = RunPhase::Idle;
+  for (size_t v = 0; v < n_out; v++) status_out[v] = AVRF_OK;          // what an empty batch or segment keeps (src/thin.rs:262-264, src/pedersen.rs:343-345)
+  if (run_nothing(c)) return AVRF_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<HostExt> sums(r.n_seg);
-  const SegArrays a = seg_arrays(c);
-  if (c->lane_owner) { if (int e = lane_msm_segments(c, a.pre, a.scalars, r.L, r.n_seg, sums.data())) return e; }
+  const double t3 = now_us();
+  std::vector<HostExt> sums(n_out);
+  if (!sh.segmented) { if (int e = msm_guarded([&] { return msm_te_finish(c->suite, c->L->ws, c->chain(), c->stream, sums.data()); })) return e; }
+  else if (c->lane_owner) { const SegArrays a = seg_arrays(c); if (int e = lane_msm_segments(c, a.pre, a.scalars, sh.L, sh.n_seg, sums.data())) return e; }
   else if (int e = msm_guarded([&] { return msm_te_segments_finish(c->suite, c->L->ws, c->chain(), c->stream, sums.data()); })) return e;
-  for (size_t v = 0; v < r.n_seg; v++) {
-    if (r.off[v] == r.off[v + 1]) continue;
+  const double t4 = now_us();
+  for (size_t v = 0; v < n_out; v++) {
+    if (sh.segmented && sh.off[v] == sh.off[v + 1]) continue;
     status_out[v] = point_is_identity(c, sums[v]) ? AVRF_OK : AVRF_VERIFICATION_FAILURE;   // src/thin.rs:319-322, src/pedersen.rs:420-423
-    for (size_t j = r.off[v]; !r.item_status.empty() && j < r.off[v + 1]; j++) if (r.item_status[j]) status_out[v] = AVRF_INVALID_DATA;   // src/thin.rs:266-271, src/pedersen.rs:348-353
+    if (!r.item_status.empty())                                        // (a segmented run's attribution pass) src/thin.rs:266-271, src/pedersen.rs:348-353
+      for (size_t j = sh.off[v]; j < sh.off[v + 1]; j++) if (r.item_status[j]) status_out[v] = AVRF_INVALID_DATA;
   }
-  if (c->lane_owner) { c->seg_gen = c->stage_gen; c->seg_L = r.L; c->seg_off = r.off; c->seg_row0 = r.row0; }   // what avrf_*_segment_terms describes
+  const double t5 = now_us();
+  // avrf_last_timing after a whole-batch run: time spent IN its calls (a segmented run's caller states wall time instead, run_segments)
+  c->timing[4] = r.msm_us + (t4 - t3); c->timing[5] = t5 - t4;
+  c->timing[0] = c->timing[1] + c->timing[2] + c->timing[3] + c->timing[4] + c->timing[5];
+  if (sh.segmented && c->lane_owner) { c->last_seg.shape = sh; c->last_seg.gen = c->stage_gen; }   // what avrf_*_segment_terms describes
   return AVRF_OK;
 }
 }  // namespace avrf
 
-// the context's call: the phases one after the other, waiting for the stream between them
+// the context's segmented call: the phases one after the other, waiting for the stream between them
 static int run_segments(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, int32_t *status_out, bool shared_ok = false) {
   if (!c || ctx_busy(c) || (n_seg && !status_out)) return AVRF_ERR_BAD_ARG;
   const double t0 = now_us();
-  if (int e = seg_begin(c, kind, n_seg, seg_items, shared_ok)) return e;
-  for (size_t v = 0; v < n_seg; v++) status_out[v] = AVRF_OK;
-  if (!n_seg || !c->n) { c->run_phase = 0; return AVRF_OK; }
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) { c->run_phase = 0; (void)hipGetLastError(); return AVRF_ERR_NO_DEVICE; }
-  if (int e = seg_collect(c, kind)) return e;
+  RunRequest rq; rq.segmented = true; rq.n_seg = n_seg; rq.seg_items = seg_items; rq.shared_ok = shared_ok;
+  if (int e = run_begin(c, kind, rq)) return e;
+  const bool device_work = !run_nothing(c);
+  if (device_work) if (int e = run_wait(c, /*and_last_error=*/true)) return e;
+  if (int e = run_collect(c, kind)) return e;
   const double t1 = now_us();
-  if (int e = seg_hash(c, kind, /*spread=*/true)) { c->run_phase = 0; return e; }
+  if (int e = run_hash(c, kind, /*spread=*/true)) return e;
   const double t2 = now_us();
-  if (int e = seg_launch(c, kind)) return e;
-  if (int e = seg_end(c, kind, status_out)) return e;
+  if (int e = run_launch(c, kind)) return e;
+  if (int e = run_end(c, kind, status_out)) return e;
   // avrf_last_timing: prepare + its wait (and the attribution pass), the transcripts, the terms launches, the MSM chain with its wait
   const double t4 = now_us();
-  c->timing[1] = t1 - t0; c->timing[2] = t2 - t1; c->timing[4] = t4 - t2 - c->timing[3]; c->timing[5] = 0; c->timing[0] = t4 - t0;
+  if (device_work) { c->timing[1] = t1 - t0; c->timing[2] = t2 - t1; c->timing[4] = t4 - t2 - c->timing[3]; c->timing[5] = 0; c->timing[0] = t4 - t0; }
   return AVRF_OK;
 }
 // the terms of one segment of the last segmented run, as avrf_batch_last_terms gives the plain run's
 static size_t segment_terms(avrf_ctx *c, int kind, size_t seg, uint8_t *bases_xy, uint8_t *scalars) {
-  if (!c || ctx_busy(c) || c->staged_kind != kind || c->seg_gen != c->stage_gen || seg + 1 >= c->seg_off.size()) return 0;
+  const RunShape &sh = c ? c->last_seg.shape : RunShape();
+  if (!c || ctx_busy(c) || c->staged_kind != kind || c->last_seg.gen != c->stage_gen || seg + 1 >= sh.off.size()) return 0;
   if (hipSetDevice(c->device) != hipSuccess) return 0;
   const uint32_t *io_off = c->h_io.as<uint32_t>();
-  const size_t first = c->seg_off[seg], items = c->seg_off[seg + 1] - first;
+  const size_t first = sh.off[seg], items = sh.off[seg + 1] - first;
   if (!items) return 0;
-  const size_t t0 = seg * c->seg_L;
+  const size_t t0 = seg * sh.L;
   // the merged layout of a shared-table staging: item terms up to the segment's row 0, the rows, the base term(s)
-  const size_t count = !c->seg_row0.empty() ? (c->seg_row0[seg] - t0) + c->n_shared + (kind == Thin ? 1 : 2)
+  const size_t count = !sh.row0.empty() ? (sh.row0[seg] - t0) + c->n_shared + (kind == Thin ? 1 : 2)
                                             : n_terms(kind, items, kind == Thin ? io_off[first + items] - io_off[first] : 0);
   return terms_to_host(c, c->d_seg_pre.as<te_pre_raw>() + t0, c->d_seg_scalars.as<uint8_t>() + 32 * t0, count, bases_xy, scalars);
 }
@@ -1547,11 +1533,8 @@ static int batch_challenges(avrf_ctx *c, int kind, uint8_t *c_out) {
   if (ctx_busy(c)) return AVRF_ERR_BAD_ARG;
   if (c->n == 0) return AVRF_OK;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(reset_flags(c));
-  validate_staged(c, kind, nullptr);
-  launch_prepare(c, kind, batch_of(c), c->n_shared != 0);
-  HIP_TRY(hipMemcpyAsync(c_out, c->d_c.p, c->n * 16, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_flags.p, c->d_flags.p, 4, hipMemcpyDeviceToHost, c->stream));
+  Prepare p; p.rows_stay = c->n_shared != 0; p.challenges_out = c_out;
+  if (int e = enqueue_prepare(c, kind, 0, 0, p)) return e;
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (*c->h_flags.as<uint32_t>()) return AVRF_INVALID_DATA;
   c->chal_gen = c->stage_gen;                                         // the challenges in d_c / d_z belong to THIS staging
@@ -1699,17 +1682,16 @@ static Route prove_ped_one_as_msm(avrf_ctx *c, bool have_pk, uint8_t *proofs_out
 // expanded, the BatchVerifier's sum with the weight w = 1) through the prepare / terms kernels and the single-launch MSM
 // (msm.hip k_msm_tiny_bits): the doubling chain runs on the host's Horner instead of a lone wave -- 0.54 -> 0.28 ms.  Same
 // statuses as the per-item kernels: the flags of the prepare kernel and of the validation are InvalidData, a non-zero sum is
-// VerificationFailure.  Everything is enqueued back to back; the one wait is in batch_end.
+// VerificationFailure.  Everything is enqueued back to back; the one wait is in run_end.
 static Route verify_one_as_msm(avrf_ctx *c, int32_t *status_out) {
   if (!c->n_terms || c->n_terms > 2048) return {};
-  uint8_t zero[64] = {0};
-  c->unit_weights = true;
-  int st = batch_begin(c, Thin);
-  if (st == AVRF_OK) st = batch_launch(c, Thin, zero);
-  if (st == AVRF_OK) st = batch_end(c, Thin);
-  c->unit_weights = false;
-  if (st != AVRF_OK && st != AVRF_VERIFICATION_FAILURE) { c->run_phase = 0; return st; }
-  status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : st;
+  RunRequest rq; rq.unit_weights = true;
+  int32_t verdict = AVRF_OK;
+  int st = run_begin(c, Thin, rq);
+  if (st == AVRF_OK) st = run_launch(c, Thin);
+  if (st == AVRF_OK) st = run_end(c, Thin, &verdict);
+  if (st != AVRF_OK) return st;
+  status_out[0] = *c->h_flags.as<uint32_t>() ? AVRF_INVALID_DATA : verdict;
   return AVRF_OK;
 }
 
@@ -1718,9 +1700,8 @@ static Route verify_one_as_msm(avrf_ctx *c, int32_t *status_out) {
 // Horners side by side (see verify_one_as_msm): both sums must be the identity, exactly the reference's two checks.  0.52 -> ~0.33 ms.
 static Route verify_ped_one_as_msm(avrf_ctx *c, int32_t *status_out) {
   if (!c->n_terms || c->n_terms > 2048) return {};
-  int st = batch_begin(c, Pedersen);                                        // validation + prepare kernel (challenge, merged pair) + flags copy
-  c->run_phase = 0;
-  if (st != AVRF_OK) return st;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int e = enqueue_prepare(c, Pedersen, 0, 0, Prepare())) return e;     // validation + prepare kernel (challenge, merged pair) + flags copy: no run is opened
   const size_t nt = c->n_terms;
   HIP_TRY(c->L->d_scalars.ensure(2 * nt * 32)); HIP_TRY(c->L->d_pre.ensure(nt * sizeof(te_pre_raw))); HIP_TRY(c->L->d_gpart.ensure(2 * 64 + 64));
   c->h_weights.assign(64, 0); c->h_weights[0] = 1; c->h_weights[32 + 16] = 1;                     // (t, u) = (1, 0) | (0, 1)

@@ -1,5 +1,6 @@
 // capi_internal.h -- what the translation units of libavrf.so share about a context (capi.hip, pool.hip): buffers, the
-// execution lane (stream + MSM workspace) and the phases of BatchVerifier::verify (src/thin.rs:257-325, src/pedersen.rs:341-426).
+// execution lane (stream + MSM workspace), the record of the run in flight and the ONE family of phases that walks a staged batch
+// through BatchVerifier::verify (src/thin.rs:257-325, src/pedersen.rs:341-426), as a whole batch or as n_seg groups of items.
 // Not part of the C ABI (include/avrf.h).
 #pragma once
 #include "../../include/avrf.h"
@@ -50,11 +51,28 @@ struct Lane : LaneStream {
   MsmWorkspace ws;
   DevBuf d_scalars, d_pre, d_gpart;
   DevBuf d_shared;                // a shared-table batch: the row scalars' contributions and partial sums of the chain being built (thin_shared.h)
-  // a segmented run (seg_launch below): the terms kernel's per-item scratch (Thin w s z0, n x 32 bytes; Pedersen u s and u sb, n x 64),
+  // a segmented run (run_launch below): the terms kernel's per-item scratch (Thin w s z0, n x 32 bytes; Pedersen u s and u sb, n x 64),
   // the n_seg + 1 item offsets and the n_seg weight seeds of the chain being built
   DevBuf d_seg_wsz, d_seg_off, d_seg_seeds;
 };
 
+// The shape of a run of the staged batch: the whole batch under one verdict, or (segmented) n_seg groups of consecutive items with a
+// verdict each (thin_seg.h): group v is the items [off[v], off[v + 1]) and has L of the n_seg L = `padded` term slots.  merged: the
+// merged layout of a shared-table staging (thin_shared.h "Segments"), row0[v] the term of group v's row 0.
+struct RunShape { bool segmented = false, merged = false; size_t n_seg = 0, L = 0, padded = 0; std::vector<uint32_t> off, row0; };
+enum class RunPhase { Idle, Begun, Launched };
+// Everything about the run in flight (run_begin .. run_end below); the phase is written by those functions and by run_close alone
+struct BatchRun {
+  RunPhase phase = RunPhase::Idle;
+  RunShape shape;
+  std::vector<int32_t> item_status;   // a segmented run's attribution pass: a status per item (empty unless the batch's flag word was set)
+  uint8_t digest[64] = {0};           // a whole-batch run: the digest of its weight transcript (counter-mode suites)
+  bool unit_weights = false;          // every item's weight is 1 (avrf_thin_verify runs ONE item as its own equation through the MSM path)
+  double begin_us = 0, msm_us = 0;    // avrf_last_timing: what enqueueing the prepare step took, and the chain
+  // a segmented run: page-locked, so that the copies up never wait for the lane, the item offsets (n_seg + 1 words, padded to 64 bytes),
+  // the n_seg weight seeds and, for the merged layout, the n_seg terms row0; and the groups' transcript messages, prefix || records each
+  PinBuf h_up; std::vector<uint8_t> h_msg;
+};
 }  // namespace avrf
 
 struct avrf_ctx {
@@ -66,7 +84,7 @@ struct avrf_ctx {
   bool lane_owner = true;         // false: a pool slot -- no stream or workspace of its own (L and stream are set by the pool)
   // staged batch
   int validate = 0;               // avrf_ctx_set_validation: 0 unchecked (typed-point callers), 1 on-curve, 2 + subgroup
-  bool wire_pending = false;              // staged from wire bytes without waiting: batch_collect reads the decode flag (h_flags[2])
+  bool wire_pending = false;              // staged from wire bytes without waiting: run_collect reads the decode flag (h_flags[2])
   uint64_t stage_gen = 0, chal_gen = 0;   // challenges of *_batch_challenges belong to staging generation chal_gen
   int staged_kind = 0;            // 0 none, else the ProofKind staged (proof_kind.h)
   size_t n = 0, tot_io = 0, n_terms = 0;
@@ -84,19 +102,13 @@ struct avrf_ctx {
   avrf::DevBuf d_tabs;                               // per-item window tables of the independent prove / verify kernels
   avrf::DevBuf d_fixed; bool fixed_ready = false;   // fixed-base tables of G and BLINDING_BASE (provers, scalar_mul_base), built on first use
   avrf::PinBuf h_c, h_flags, h_io;
-  // the last segmented run of the staged batch (avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments; thin_seg.h): terms of its
-  // own, n_seg * seg_L of them, so that the plain run's terms stay what they were; seg_off (n_seg + 1 item offsets) describes them while
-  // seg_gen == stage_gen.  (A pool slot has neither: its segmented terms go to the arrays of the lane it borrows, seg_launch.)
-  // seg_row0: non-empty exactly when that run took the merged layout of a shared-table staging (thin_shared.h "Segments"): the term of each
-  // segment's row 0.  d_seg_plan: the per-run plan of such a run (shared_seg_plan).
-  uint64_t seg_gen = 0; size_t seg_L = 0; std::vector<uint32_t> seg_off, seg_row0;
+  // The run in flight, and what the last segmented run of the staged batch left for avrf_*_segment_terms: terms of its own, n_seg * L of
+  // them in d_seg_scalars / d_seg_pre, so that the plain run's terms stay what they were, described by last_seg.shape while last_seg.gen
+  // == stage_gen.  (A pool slot has neither: its segmented terms go to the arrays of the lane it borrows, run_launch.)
+  // d_seg_plan: the per-run plan of a run in the merged layout (shared_seg_plan).
+  avrf::BatchRun run;
+  struct { avrf::RunShape shape; uint64_t gen = 0; } last_seg;
   avrf::DevBuf d_seg_scalars, d_seg_pre, d_seg_plan;
-  std::vector<uint8_t> h_seg_msg;   // the segments' weight-transcript messages, prefix || records each
-  // the segmented run in flight (seg_begin .. seg_end, run_phase 3 and 4): its layout, the per-item statuses of the attribution pass
-  // (empty unless the batch's flag word was set) and, page-locked so that the copies up never wait for the lane, the item offsets
-  // (n_seg + 1 words, padded to 64 bytes) followed by the n_seg weight seeds and, for the merged layout, the n_seg terms row0
-  struct SegRun { size_t n_seg = 0, L = 0, padded = 0; bool merged = false; std::vector<uint32_t> off, row0; std::vector<int32_t> item_status; } seg;
-  avrf::PinBuf h_seg_up;
   // An OPEN batch (include/avrf.h avrf_*_batch_open / _push / _flush; BatchVerifier::new / push, src/thin.rs:199-243): staged_kind == kind
   // and gen == stage_gen while it is open, so whatever stages on the context, or drops what is staged, closes it.  n / tot_io / n_terms
   // above are its totals so far; the staged buffers hold `cap_*` and grow with their used prefix kept (capi.hip open_grow).  Each push
@@ -114,9 +126,6 @@ struct avrf_ctx {
     std::vector<avrf::PinBuf> arena; size_t arena_used = 0;   // bytes used of arena.back()
   } open;
   double timing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int run_phase = 0;             // batch_begin / batch_hash / batch_end: 1, 2; a segmented run (seg_begin .. seg_end): 3, 4
-  bool unit_weights = false;      // batch_launch: every item's weight is 1 (avrf_thin_verify runs ONE item as its own equation through the MSM path)
-  double run_t0 = 0, run_begin_us = 0, run_msm_us = 0;
   // The order a context goes in: its device made current and its own stream drained; then the members, last first -- the staging
   // buffers, then `own`: workspace and term arrays, the stream last.  (A pool slot's context has no stream or workspace of its own; the
   // pool detaches it from the lane it borrowed before it dies, pool.hip ~Slot.)
@@ -153,45 +162,52 @@ inline BatchSource shared_source(int kind, size_t n, size_t n_shared, const uint
   return s;
 }
 inline BatchSource wire_source(BatchSource s, int validate) { s.wire = true; s.validate = validate; return s; }
-// Staging, then the phases of a staged batch's run, shared by the three-call ABI (capi.hip) and the pool's workers (pool.hip).  One stager
-// over a source: opening and close are shared, the payload (what is copied, what decodes it) is the flavour's.  wait = false (pool.hip):
-// nothing is waited for, and a wire source's decode flag is read by batch_collect.
+// Staging, then the phases of a staged batch's run, shared by the C ABI's run calls (capi.hip) and the pool's workers (pool.hip).  One
+// stager over a source: opening and close are shared, the payload (what is copied, what decodes it) is the flavour's.  wait = false
+// (pool.hip): nothing is waited for, and a wire source's decode flag is read by run_collect.
 int ctx_create(int suite, int device, bool lane_owner, avrf_ctx **out);
 int ctx_stage(avrf_ctx *c, const BatchSource &src, bool wait);
 // the host's check of a shared-table source (every index < n_shared; outputs present), which ctx_stage makes itself and the pool makes on
 // the submitting thread as well
 bool shared_indices_ok(const BatchSource &src);
-// validation + prepare kernel + copies back enqueued on c->stream.  segmented (seg_begin): over a shared table the checks are those of the
-// items alone -- the table's range flag is not taken over -- and Pedersen's prepare merges the pairs as the run's layout (c->seg) wants them
-int batch_begin(avrf_ctx *c, int kind, bool segmented = false);
-int batch_collect(avrf_ctx *c, int kind);                             // (c->stream's work has completed) AVRF_INVALID_DATA for a refused item
-bool suite_host_weights(int suite);                                   // sponge / SHA-256 transcript: batch_seed squeezes the weight stream itself (no seed)
-int batch_seed(avrf_ctx *c, int kind, uint8_t digest[64]);            // the weight transcript on the calling thread
+bool suite_host_weights(int suite);                                   // sponge / SHA-256 transcript: the host squeezes the weight stream itself (no seed)
 void sha512_many(WeightJob *const *jobs, int k);                      // k <= 16 transcripts hashed together: scalar, eight or sixteen lanes, as the host CPU allows
-int batch_launch(avrf_ctx *c, int kind, const uint8_t digest[64]);    // terms kernel + MSM chain enqueued on c->stream / c->L
-int batch_end(avrf_ctx *c, int kind);                                 // waits for the chain, folds, verdict
-// The segmented run of a staged Thin or Pedersen batch (include/avrf.h avrf_thin_batch_run_segments, avrf_pedersen_batch_run_segments) in
-// phases of the same discipline: each refuses out of order, an error leaves the context idle.  run_phase 3 from seg_begin, 4 from seg_launch.
-//   seg_begin    layout check (counts, limits), buffer sizing, batch_begin: validation + prepare kernel + copies back on c->stream.
-//                A shared-table staging is refused unless shared_ok (avrf_*_batch_run_shared_segments, a context of its own lane): the
-//                layout is then the shorter of merged and expanded (include/avrf.h)
-//   seg_collect  (c->stream's work has completed) a wire batch's decode flag; only when the batch's flag word is set, the per-item
-//                attribution pass, which waits for c->stream
-//   seg_hash     the n_seg weight transcripts on the calling thread (spread: and the process's host pool): counter-mode suites hash
-//                prefix || the segment's records, sponge / SHA-256 suites squeeze every segment's weight stream.  A caller that hashes
-//                several contexts' transcripts together (pool.hip) takes the counter-mode messages one by one instead: seg_job builds
-//                message v and describes it, seg_seed stores its digest
-//   seg_launch   seeds and offsets up, padding scalars zeroed, terms kernel; a pool slot: ONE chain enqueued on c->stream / c->L with
-//                c->chain(), whatever n_seg is
-//   seg_end      a pool slot: collects the chain (waits for the stream only with the lane's own record).  A context of its own lane
-//                runs msm_te_segments here instead, which keeps that call's loop of single MSMs below eight segments.  Then
-//                status_out[0 .. n_seg), the per-item statuses folded in
-int seg_begin(avrf_ctx *c, int kind, size_t n_seg, const uint32_t *seg_items, bool shared_ok = false);
-int seg_collect(avrf_ctx *c, int kind);
-int seg_hash(avrf_ctx *c, int kind, bool spread);
-void seg_job(avrf_ctx *c, int kind, size_t v, WeightJob *job);
-void seg_seed(avrf_ctx *c, size_t v, const uint8_t digest[64]);
-int seg_launch(avrf_ctx *c, int kind);
-int seg_end(avrf_ctx *c, int kind, int32_t *status_out);
+
+// The run of a staged Thin or Pedersen batch in phases, whole or segmented (include/avrf.h avrf_*_batch_run, avrf_*_batch_run_segments).
+// Each refuses out of order, an error leaves the context idle, and a run with nothing to do (no items, or no segments) passes through
+// every phase without device work.  What a run asks for: the whole batch, or n_seg groups of seg_items[v] consecutive items; a shared-
+// table staging runs segmented only with shared_ok (avrf_*_batch_run_shared_segments, a context of its own lane), in the shorter of
+// the merged and the expanded layout.
+struct RunRequest { bool segmented = false; size_t n_seg = 0; const uint32_t *seg_items = nullptr; bool shared_ok = false, unit_weights = false; };
+inline bool ctx_busy(const avrf_ctx *c) { return c->run.phase != RunPhase::Idle; }
+//   run_begin     a segmented run's layout (in locals first: a refusal changes nothing) and buffer sizing; then validation + prepare
+//                 kernel + copies back on c->stream, once for all groups -- an open batch's pushes have enqueued that already.
+//                 Segmented over a shared table the checks are those of the items alone (the table's range flag is not taken over)
+//                 and Pedersen's prepare merges the pairs as the run's layout wants them
+//   run_collect   (c->stream's work has completed) the decode flag of a wire staging or of an open batch's chunks, then the batch's
+//                 flag word: AVRF_INVALID_DATA for a whole-batch run; a segmented run finds the items that raised it in the per-item
+//                 attribution pass, which waits for c->stream
+//   run_messages  how many counter-mode transcripts a caller that hashes several contexts' together (pool.hip) takes one by one: 0 for a
+//                 sponge / SHA-256 suite or a run with nothing to do (run_hash does what there is to do), 1 for a whole-batch run, n_seg
+//                 for a segmented one.  run_job describes message v (the whole batch's in place, a group's built at a place of its own:
+//                 distinct v may be built from different threads), run_seed stores its digest
+//   run_hash      everything on the calling thread (spread: and the process's host pool): counter-mode suites hash prefix || records,
+//                 sponge / SHA-256 suites squeeze the weight stream of the batch or of every group, an open batch finalises a clone
+//   run_launch    weight stream or seeds up, the terms kernel (segmented: offsets up and padding scalars zeroed first), then ONE MSM
+//                 chain on c->stream / c->L with c->chain(), whatever n_seg is -- but none for a segmented run of a context of its own lane
+//   run_end       collects the chain (waits for the stream only with the lane's own record); a segmented run of a context of its own lane
+//                 runs msm_te_segments here instead, which keeps that call's loop of single MSMs below eight segments.  Then a status
+//                 from every sum: status_out[0], or status_out[0 .. n_seg) with the per-item statuses folded in
+int run_begin(avrf_ctx *c, int kind, const RunRequest &rq = RunRequest());
+int run_collect(avrf_ctx *c, int kind);
+size_t run_messages(const avrf_ctx *c);
+void run_job(avrf_ctx *c, size_t v, WeightJob *job);
+void run_seed(avrf_ctx *c, size_t v, const uint8_t digest[64]);
+int run_hash(avrf_ctx *c, int kind, bool spread);
+int run_launch(avrf_ctx *c, int kind);
+int run_end(avrf_ctx *c, int kind, int32_t *status_out);
+inline bool run_chain_enqueued(const avrf_ctx *c) { return c->run.phase == RunPhase::Launched; }   // run_launch came through: a chain may be in flight on c->L
+// closes a run from outside its phases (the pool when a slot's run is over or the slot dies; the caller deals with stream and chain record)
+inline void run_close(avrf_ctx *c) { c->run.phase = RunPhase::Idle; }
 double now_us();
 }  // namespace avrf

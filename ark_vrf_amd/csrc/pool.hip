@@ -14,13 +14,14 @@
 //   * inputs are read where the caller put them: from buffers of avrf_host_alloc the staging copies are DMA transfers that
 //     overlap the other batches' kernels and cost no host time (include/avrf.h "Ownership").
 // Verdicts are those of avrf_thin_batch_run / avrf_pedersen_batch_run: a slot keeps the BatchSource it was submitted with, and the
-// workers call the same stager and phases (capi_internal.h: ctx_stage over that source, whatever its flavour; batch_begin / _collect /
-// _seed / _launch / _end; grouped hashing through sha512_many), each under `guarded` -- a failed HIP call or allocation inside a
-// worker becomes the batch's status, never an exception off the thread.
-// A SEGMENTED job (avrf_pool_submit_segments: one verdict per run of consecutive items, include/avrf.h) walks the same states through the
-// segmented phases (seg_begin / _collect / seg_job + seg_seed or seg_hash / seg_launch / seg_end): its n_seg transcripts go through the
-// same grouped hash, so a slot with many segments fills groups by itself and segments of different slots share a group, and its MSMs are
-// ONE chain on the lane.  Plain and segmented jobs share slots, lanes and workers.
+// workers call the same stager and the same phases as the context's own run calls (capi_internal.h: ctx_stage over that source,
+// whatever its flavour; run_begin / _collect / _job + _seed or _hash / _launch / _end; grouped hashing through sha512_many), each
+// under `guarded` -- a failed HIP call or allocation inside a worker becomes the batch's status, never an exception off the thread.
+// A SEGMENTED job (avrf_pool_submit_segments: one verdict per run of consecutive items, include/avrf.h) is the same walk over another
+// shape: what a slot knows of it is the shape it hands to run_begin and the statuses it hands out.  A run has run_messages
+// transcripts -- one, or n_seg -- and they all go through the same grouped hash, so a slot with many segments fills groups by itself
+// and segments of different slots share a group; its MSMs are ONE chain on the lane either way.  Plain and segmented jobs share
+// slots, lanes and workers.
 #include "capi_internal.h"
 #include "suite_dispatch.h"
 #include "host_sha512_mb.h"
@@ -52,15 +53,15 @@ struct Slot {
   MsmChain pend;                  // the record of the slot's MSM chain (several chains queue on one lane)
   uint64_t seq = 0;               // order in which the worker enqueued the slot's current phase (oldest is waited for first)
   BatchSource src;                // the host sources, as submitted (the caller keeps them alive while the slot may stage from them)
-  uint8_t digest[64];
-  // a segmented job: the items per segment (copied at submission, kept for resubmission and the cycle), the statuses of the last run
-  // (seg_have: that run reached its verdicts) and how many of the run's transcripts have been hashed
+  size_t hashed = 0;              // how many of the run's transcripts (run_messages) have been hashed
+  // a segmented job: the items per segment (copied at submission, kept for resubmission and the cycle); the statuses run_end wrote --
+  // a plain job's one, a segmented job's n_seg (seg_have: the run reached its verdicts) -- for avrf_pool_wait_segments
   bool segmented = false, seg_have = false;
-  std::vector<uint32_t> seg_items; std::vector<int32_t> seg_status; size_t seg_hashed = 0;
+  std::vector<uint32_t> seg_items; std::vector<int32_t> seg_status;
   // the event, the record, then the context: it has no stream or workspace of its own and is detached from the pool's lane before it dies
   ~Slot() {
     ev.destroy(); pend.release();
-    if (c) { c->pend = nullptr; c->L = &c->own; c->stream = nullptr; c->run_phase = 0; avrf_ctx_destroy(c); }
+    if (c) { c->pend = nullptr; c->L = &c->own; c->stream = nullptr; run_close(c); avrf_ctx_destroy(c); }
   }
 };
 
@@ -111,7 +112,7 @@ struct Run {
 
   void done(Slot &S, int status) {                                     // the slot's run is over (verdict or error)
     if (S.lane) { S.lane->queued--; S.lane = nullptr; }
-    S.c->run_phase = 0; S.c->L = &S.c->own; S.c->stream = nullptr;
+    run_close(S.c); S.c->L = &S.c->own; S.c->stream = nullptr;
     std::lock_guard<std::mutex> lk(P->m);
     if (P->cycling) {
       P->cyc_done++; P->cyc_t_last = now_us();
@@ -122,7 +123,7 @@ struct Run {
     } else { S.status = status; S.state = S_DONE; }
     P->cv_done.notify_all();
   }
-  // (a wire batch whose points did not decode leaves no usable staged state -- batch_collect drops it -- but the slot still "holds" that
+  // (a wire batch whose points did not decode leaves no usable staged state -- run_collect drops it -- but the slot still "holds" that
   // batch: resubmission and cycle mode from the resident state must give the same verdict, not a bad-argument error)
   static void latch(Slot &S, int status) { if (S.src.wire && status == AVRF_INVALID_DATA) S.resident_invalid = true; }
 
@@ -138,19 +139,20 @@ struct Run {
       st = guarded([&] { return ctx_stage(c, S.src, /*wait=*/false); });
       S.has_batch = st == AVRF_OK;
     }
-    S.seg_have = false; S.seg_hashed = 0;
-    if (st == AVRF_OK) st = guarded([&] { return S.segmented ? seg_begin(c, P->kind, S.seg_items.size(), S.seg_items.data()) : batch_begin(c, P->kind); });
+    S.seg_have = false; S.hashed = 0;
+    RunRequest rq; rq.segmented = S.segmented; rq.n_seg = S.seg_items.size(); rq.seg_items = S.seg_items.data();
+    if (st == AVRF_OK) st = guarded([&] { return run_begin(c, P->kind, rq); });
     if (st == AVRF_OK && hipEventRecord(S.ev, c->stream) != hipSuccess) { (void)hipGetLastError(); st = AVRF_ERR_NO_DEVICE; }
     W.cpu_us[0] += thread_cpu_us() - t0;
     if (st != AVRF_OK) { done(S, st); return; }
     S.seq = ++seq; S.state = S_BEGUN;
   }
 
-  // transcripts waiting in `ready`: one per plain slot, the segments not hashed yet of a segmented one
-  static bool own_stream(avrf_pool *P, const Slot &S) { return suite_host_weights(P->suite) || S.c->n == 0 || (S.segmented && S.seg_items.empty()); }
+  // transcripts waiting in `ready`: those of each slot's run that are not hashed yet; a slot whose run has none for the group -- a
+  // sponge suite squeezes its own stream, an empty run has no transcript -- counts as one
   size_t waiting(const std::vector<int> &ready) const {
     size_t k = 0;
-    for (int si : ready) { const Slot &S = P->slots[si]; k += S.segmented && !own_stream(P, S) ? S.seg_items.size() - S.seg_hashed : 1; }
+    for (int si : ready) { const Slot &S = P->slots[si]; const size_t m = run_messages(S.c); k += m ? m - S.hashed : 1; }
     return k;
   }
   // up to `count` <= 16 transcripts from the front of `ready`, hashed together; a slot leaves `ready` with its last transcript
@@ -160,22 +162,21 @@ struct Run {
     size_t taken = 0, used = 0;
     for (; taken < ready.size() && used < count; taken++) {
       Slot &S = P->slots[ready[taken]];
-      if (own_stream(P, S)) {                                          // sponge transcripts squeeze their own stream; empty batches have no transcript
+      const size_t m = run_messages(S.c);
+      if (!m) {                                                        // sponge transcripts squeeze their own stream; empty runs have no transcript
         used++;
-        int st = guarded([&] { return S.segmented ? seg_hash(S.c, P->kind, /*spread=*/false) : batch_seed(S.c, P->kind, S.digest); });
+        int st = guarded([&] { return run_hash(S.c, P->kind, /*spread=*/false); });
         if (st != AVRF_OK) { done(S, st); continue; }
         S.state = S_HASHED;
         continue;
       }
-      if (!S.segmented) { jobs[k] = WeightJob::whole(S.c->h_msg.as<uint8_t>(), S.c->h_msg_len); pj[k] = &jobs[k]; ss[k] = &S; seg[k] = 0; k++; used++; continue; }
-      for (; S.seg_hashed < S.seg_items.size() && used < count; S.seg_hashed++, k++, used++) { seg_job(S.c, P->kind, S.seg_hashed, &jobs[k]); pj[k] = &jobs[k]; ss[k] = &S; seg[k] = S.seg_hashed; }
-      if (S.seg_hashed < S.seg_items.size()) break;                    // the group is full: the slot stays at the front of `ready`
+      for (; S.hashed < m && used < count; S.hashed++, k++, used++) { run_job(S.c, S.hashed, &jobs[k]); pj[k] = &jobs[k]; ss[k] = &S; seg[k] = S.hashed; }
+      if (S.hashed < m) break;                                         // the group is full: the slot stays at the front of `ready`
     }
     if (k) sha512_many(pj, k);
     for (int i = 0; i < k; i++) {
-      if (!ss[i]->segmented) { memcpy(ss[i]->digest, jobs[i].digest, 64); ss[i]->state = S_HASHED; continue; }
-      seg_seed(ss[i]->c, seg[i], jobs[i].digest);
-      if (seg[i] + 1 == ss[i]->seg_items.size()) ss[i]->state = S_HASHED;
+      run_seed(ss[i]->c, seg[i], jobs[i].digest);
+      if (seg[i] + 1 == run_messages(ss[i]->c)) ss[i]->state = S_HASHED;
     }
     ready.erase(ready.begin(), ready.begin() + taken);
     if (k) { W.hash_groups++; W.hash_msgs += k; }
@@ -192,23 +193,19 @@ struct Run {
     const double t0 = thread_cpu_us();
     S.lane = pick_lane(); S.lane->queued++;
     S.c->L = S.lane; S.c->stream = S.lane->stream;
-    int st = guarded([&] { return S.segmented ? seg_launch(S.c, P->kind) : batch_launch(S.c, P->kind, S.digest); });
+    int st = guarded([&] { return run_launch(S.c, P->kind); });
     if (st == AVRF_OK && hipEventRecord(S.ev, S.lane->stream) != hipSuccess) { (void)hipGetLastError(); st = AVRF_ERR_NO_DEVICE; }
     W.cpu_us[3] += thread_cpu_us() - t0;
-    // (run_phase 2, a segmented run's 4: the chain was enqueued and only the event failed -- it is waited for and given up)
-    if (st != AVRF_OK) { if (S.c->run_phase == 2 || S.c->run_phase == 4) { (void)hipStreamSynchronize(S.lane->stream); S.c->chain().disarm(); } done(S, st); return; }
+    // (the chain was enqueued and only the event failed: it is waited for and given up)
+    if (st != AVRF_OK) { if (run_chain_enqueued(S.c)) { (void)hipStreamSynchronize(S.lane->stream); S.c->chain().disarm(); } done(S, st); return; }
     S.seq = ++seq; S.state = S_MSM;
   }
 
   void finish(Slot &S) {
     const double t0 = thread_cpu_us();
-    int st;
-    if (!S.segmented) st = guarded([&] { return batch_end(S.c, P->kind); });
-    else {
-      S.seg_status.assign(S.seg_items.size(), AVRF_OK);
-      st = guarded([&] { return seg_end(S.c, P->kind, S.seg_status.data()); });
-      if (st == AVRF_OK) { S.seg_have = true; for (int32_t v : S.seg_status) if (v > st) st = v; }   // the job's status: the largest of its segments'
-    }
+    S.seg_status.assign(S.segmented ? S.seg_items.size() : 1, AVRF_OK);
+    int st = guarded([&] { return run_end(S.c, P->kind, S.seg_status.data()); });
+    if (st == AVRF_OK) { S.seg_have = true; for (int32_t v : S.seg_status) if (v > st) st = v; }   // the job's status: the largest that run_end wrote
     W.cpu_us[4] += thread_cpu_us() - t0;
     done(S, st);
   }
@@ -244,7 +241,7 @@ struct Run {
         if (S.state != S_BEGUN) continue;
         if (hipEventQuery(S.ev) == hipSuccess) {
           const double t0 = thread_cpu_us();
-          const int st = guarded([&] { return S.segmented ? seg_collect(S.c, P->kind) : batch_collect(S.c, P->kind); });
+          const int st = guarded([&] { return run_collect(S.c, P->kind); });
           W.cpu_us[1] += thread_cpu_us() - t0;
           if (st != AVRF_OK) { latch(S, st); done(S, st); } else { S.state = S_READY; ready.push_back(si); }
           progress = true;
